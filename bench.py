@@ -12,9 +12,13 @@ the newest-frame poses over RCCL (the global_fusion input). Frames are independe
 collective => weak scaling. `value` counts the window solver's iterations only; the LiDAR stage is inside the timed region.
 
   python bench.py --gpus 1 --steps 10 --warmup 2
+  python bench.py --gpus 1 --steps 10 --warmup 2 --full        # + the side legs: CPU baseline, overlapped stages, ragged / converging / PCIe-inclusive /
+                                                                #   estimate_td batches, single-frame latency, the compact configs[4] leg
+  python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the steps (with the per-kernel spans that the roofline is read from) and prints the line; everything
+else it measures runs only with --full. Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -120,6 +124,93 @@ def lidar_search_statistics(cases, opts):
             tot_c += float(cnt.sum()); tot_r += float((b_[:, 1] - a[:, 1] + 1).sum()); tot_q += len(q)
         cells.append(ncell)
     return dict(candidates_per_query=tot_c / max(tot_q, 1), rows_per_query=tot_r / max(tot_q, 1), map_cells=float(np.mean(cells)))
+
+
+def host_cpus():
+    """CPUs this process may use: its affinity mask, capped by a cgroup CPU quota and by OMP_NUM_THREADS where either is set (os.cpu_count() counts the whole machine)"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
+DUMP_MAX_WINDOWS = 4096          # --dump-outputs: per-window arrays of at most this many windows (a seeded sample beyond it)
+DUMP_PRIORS = 64                 # new priors of a seeded sample of this many windows (one prior is up to 75 x 75 doubles)
+DUMP_MAPS = 4                    # local maps (edge + surf, ~0.1 M points each) of a seeded sample of this many LiDAR streams
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, solver, s2m, B, marginalized, table=None, seed=2024):
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, one DIR/<name>.npy each (float64; the local maps float32, as the library
+    returns them). Windows are slots of the batch, in slot order (window_index: which slots, when B exceeds DUMP_MAX_WINDOWS):
+      window_para_pose (S, 11, 7), window_para_speed_bias (S, 11, 9), window_para_feature (S, Fmax; zero past window_n_features), window_Ps / Rs / Vs / Bas / Bgs,
+      window_summary (S, 7): num_iterations, num_successful_steps, num_linear_solves, termination, initial_cost, final_cost, final_radius (no timings);
+      prior_index / prior_valid / prior_n / prior_residuals (P, nmax) / prior_jacobians (P, nmax, nmax): the marginalization's new priors of a seeded sample of slots;
+      lidar_pose_qt (S, 7), lidar_rel_q (S, 4), lidar_rel_t (S, 3), lidar_final_cost (S, 2), lidar_counts (S, 10): n_edge_ds, n_surf_ds, n_edge_factors[2],
+      n_surf_factors[2], iterations[2], map_edge_size, map_surf_size; lidar_map_index, lidar_map_{edge,surf}_<slot> (n, 4) of a seeded sample of streams;
+      gathered_poses (world * B, 8): the pose table of the gather (N > 1).
+    Returns the bytes written."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    idx = np.arange(B) if B <= DUMP_MAX_WINDOWS else np.sort(rng.choice(B, DUMP_MAX_WINDOWS, replace=False))
+    out = {"window_index": idx.astype(np.float64)}
+    res = solver.batch_download()
+    sm = solver.batch_summaries()
+    nf = np.array([len(res[i].para_feature) for i in idx])
+    feat = np.zeros((len(idx), max(int(nf.max()), 1)))
+    for r, i in enumerate(idx):
+        feat[r, :nf[r]] = res[i].para_feature
+    out.update(window_para_pose=np.stack([res[i].para_pose for i in idx]), window_para_speed_bias=np.stack([res[i].para_speed_bias for i in idx]),
+               window_para_feature=feat, window_n_features=nf.astype(np.float64))
+    for k in ("Ps", "Rs", "Vs", "Bas", "Bgs"):
+        out["window_" + k] = np.stack([getattr(res[i], k) for i in idx])
+    out["window_summary"] = np.array([[sm[i].num_iterations, sm[i].num_successful_steps, sm[i].num_linear_solves, sm[i].termination,
+                                       sm[i].initial_cost, sm[i].final_cost, sm[i].final_radius] for i in idx], dtype=np.float64)
+    if marginalized:
+        pidx = np.sort(rng.choice(B, min(B, DUMP_PRIORS), replace=False))
+        pri = [solver.get_prior(int(i)) for i in pidx]
+        pn = np.array([p.n if p.valid else 0 for p in pri])
+        nmax = max(int(pn.max()), 1)
+        pr = np.zeros((len(pidx), nmax)); pj = np.zeros((len(pidx), nmax, nmax))
+        for r, p in enumerate(pri):
+            n = int(pn[r])
+            pr[r, :n] = np.frombuffer(p.linearized_residuals, dtype=np.float64, count=n)
+            pj[r, :n, :n] = np.frombuffer(p.linearized_jacobians, dtype=np.float64, count=n * n).reshape(n, n)
+        out.update(prior_index=pidx.astype(np.float64), prior_valid=np.array([p.valid for p in pri], dtype=np.float64), prior_n=pn.astype(np.float64),
+                   prior_residuals=pr, prior_jacobians=pj)
+    if s2m is not None:
+        rs = s2m.results()
+        out.update(lidar_pose_qt=np.array([rs[i].pose_qt[:] for i in idx]), lidar_rel_q=np.array([rs[i].rel_q[:] for i in idx]),
+                   lidar_rel_t=np.array([rs[i].rel_t[:] for i in idx]), lidar_final_cost=np.array([rs[i].final_cost[:] for i in idx]),
+                   lidar_counts=np.array([[rs[i].n_edge_ds, rs[i].n_surf_ds, *rs[i].n_edge_factors, *rs[i].n_surf_factors, *rs[i].iterations,
+                                           rs[i].map_edge_size, rs[i].map_surf_size] for i in idx], dtype=np.float64))
+        midx = np.sort(rng.choice(B, min(B, DUMP_MAPS), replace=False))
+        out["lidar_map_index"] = midx.astype(np.float64)
+        for i in midx:
+            out[f"lidar_map_edge_{i}"] = s2m.getMapCloud(int(i), 0)
+            out[f"lidar_map_surf_{i}"] = s2m.getMapCloud(int(i), 1)
+    if table is not None:
+        out["gathered_poses"] = np.asarray(table, dtype=np.float64)
+    return write_dump(path, out)
+
+
+def write_dump(path, arrays):
+    """DIR/<name>.npy for every array (at most DUMP_MAX_BYTES in all); returns the bytes written"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total / 2**20:.1f} MB of outputs exceed the {DUMP_MAX_BYTES >> 20} MB budget")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return total
 
 
 def _profile_order(path):
@@ -290,6 +381,12 @@ def stress_main(args):
         res = solver.optimization(win); its += res.summary["num_iterations"]
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:               # the last timed solve of this rank's stress window, as vilf_window_solve returned it
+        sm = res.summary
+        write_dump(args.dump_outputs, {"window_para_pose": res.para_pose, "window_para_speed_bias": res.para_speed_bias, "window_para_feature": res.para_feature,
+                                       "window_Ps": res.Ps, "window_Rs": res.Rs, "window_Vs": res.Vs, "window_Bas": res.Bas, "window_Bgs": res.Bgs,
+                                       "window_summary": np.array([sm[k] for k in ("num_iterations", "num_successful_steps", "num_linear_solves", "termination",
+                                                                                   "initial_cost", "final_cost", "final_radius")], dtype=np.float64)})
     prof = solver.get_profile_large_window()
     t = torch.tensor([dt, float(its)], dtype=torch.float64, device="cpu" if rehearse else "cuda")
     if world > 1:
@@ -441,7 +538,16 @@ def main():
     ap.add_argument("--stress-windows", default="1,8,32", help="--stress: numbers of independent stress windows solved side by side (one handle / stream / host thread each)")
     ap.add_argument("--no-stress-leg", dest="stress_leg", action="store_false", help="skip the compact configs[4] leg (one group of 8 stress windows, 3 solves) of the default run")
     ap.add_argument("--stress", action="store_true", help="BASELINE configs[4] instead of the headline workload: one synthetic 51-frame / ~46 k-factor window per step and GPU")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline (CPU baseline, overlapped stages, ragged / converging / PCIe-inclusive / "
+                    "estimate_td batches, single-frame latency, the compact configs[4] leg; the --no-* options and the window counts above select among them). "
+                    "Without it a run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (solved windows, new priors, scan-to-map results, "
+                    "gathered poses; a seeded sample where larger than 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:                                  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_pcie = True
+        args.latency = args.stress_leg = False
+        args.ragged_windows = args.converging_windows = args.td_windows = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus)                # `python bench.py --gpus N`: this process only starts the N ranks and relays rank 0's line (it never touches the GPU)
     if os.environ.get("VILF_BENCH_DRYRUN") == "1":
@@ -457,7 +563,7 @@ def main():
     if not args.no_lidar_stage:                    # the distinct synthetic scenes (ray casting in numpy, ~6 s each): on the host cores, in child processes forked BEFORE
         from vil_fusion_amd import synth as _synth  # anything initialises the GPU
         seeds = [7000 + 31 * rank + k for k in range(args.distinct_lidar)]
-        nproc = max(1, min(len(seeds), (os.cpu_count() or 1) // max(1, min(world, 8))))
+        nproc = max(1, min(len(seeds), host_cpus() // max(1, min(world, 8))))
         try:
             if len(seeds) <= 4:                    # few scenes (profile runs: a counter-collecting profiler has initialised the GPU before python starts — no fork then)
                 raise RuntimeError("serial")
@@ -625,6 +731,12 @@ def main():
         its_local += sum(s.num_iterations for s in solver.batch_summaries())     # waits for the solver's stream (frame k done)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:               # before anything else runs on these handles: the state is the last timed step's
+        solver.synchronize()
+        tab = None
+        if world > 1:
+            tab = (gathered if gather is not None else gather_state["table"]).cpu().numpy()
+        dump_outputs(args.dump_outputs, solver, s2m, B, not args.no_marginalize, tab)
     prof = solver.get_profile()
     if not args.no_marginalize:
         prof.update(solver.get_profile_marginalize())

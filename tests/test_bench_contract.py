@@ -1,4 +1,4 @@
-"""bench.py's one JSON line: the keys the driver and the judge read (a small batch, one step; the CPU leg and the side legs are switched off — the default run has them)."""
+"""bench.py's one JSON line: the keys the driver and the judge read (a small batch, one step; the CPU leg and the side legs are switched off — a --full run has them)."""
 import json
 import os
 import subprocess
@@ -30,6 +30,37 @@ def test_bench_line_carries_the_contract_keys():
     assert rf["avg_launch_ms"] > 0 and all(v >= 0 for v in rf["kernels_ms_per_step"].values())
     # the step is the sum of its launch groups (nothing of the frame runs outside a timed group; profiling waits add a little)
     assert 0.5 * d["ms_per_step"] < sum(rf["kernels_ms_per_step"].values()) < 1.5 * d["ms_per_step"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """a plain run (no --full) times the steps and prints the line, with none of the side legs; --dump-outputs writes the last timed step's results as float64 /
+    float32 .npy files within 64 MB: the solved windows of every slot, a sample of the new priors, the scan-to-map results and a sample of the local maps"""
+    B = 128
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--windows", str(B), "--distinct", "8", "--distinct-lidar", "2",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _one_json_line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["cpu_baseline"] is None
+    for k in ("stages_overlapped", "ragged_batch", "converging_batch", "pcie_inclusive", "estimate_td_batch", "single_frame_latency", "stress"):
+        assert k not in d, k
+    import numpy as np
+    arrs = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path) if f.endswith(".npy")}
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+    assert arrs["window_para_pose"].shape == (B, 11, 7) and arrs["window_summary"].shape == (B, 7) and arrs["lidar_pose_qt"].shape == (B, 7)
+    sm = arrs["window_summary"]
+    assert (sm[:, 0] >= 1).all() and (sm[:, 5] <= sm[:, 4]).all()                 # iterations run, final cost <= initial cost
+    # the batch tiles 8 distinct windows: slot i and slot i + 8 solve the same input
+    np.testing.assert_allclose(arrs["window_para_pose"][8:16], arrs["window_para_pose"][:8], rtol=0, atol=1e-9)
+    assert np.abs(np.linalg.norm(arrs["window_para_pose"][..., 3:7], axis=-1) - 1).max() < 1e-9
+    assert np.abs(np.linalg.norm(arrs["lidar_pose_qt"][:, :4], axis=-1) - 1).max() < 1e-6
+    assert (arrs["prior_valid"] == 1).all() and (arrs["prior_n"] > 0).all()
+    for i in arrs["lidar_map_index"].astype(int):
+        assert arrs[f"lidar_map_edge_{i}"].shape[1] == 4 and len(arrs[f"lidar_map_surf_{i}"]) > 1000
 
 
 def _one_json_line(stdout):

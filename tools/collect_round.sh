@@ -1,6 +1,6 @@
-# copy what tools/gpu_round.sh TAG left under gpurun_out/TAG into profiles/ under PREFIX (e.g. r05_v2). Usage: bash tools/collect_round.sh TAG PREFIX [WINDOWS]
+# copy what tools/gpu_round.sh TAG left under runs/TAG (or $OUT/TAG) into profiles/ under PREFIX (e.g. r05_v2). Usage: bash tools/collect_round.sh TAG PREFIX [WINDOWS]
 set -e
-T=$1; P=profiles/$2; B=${3:-4096}; G=gpurun_out/$T
+T=$1; P=profiles/$2; B=${3:-4096}; G=${OUT:-runs}/$T
 ks=$(find $G/prof -name '*kernel_stats.csv' | head -1); cp "$ks" ${P}_kernel_stats.csv
 ks=$(find $G/prof_stress -name '*kernel_stats.csv' | head -1); [ -n "$ks" ] && cp "$ks" ${P}_stress_kernel_stats.csv
 grep '^{' $G/bench.json | tail -1 > ${P}_bench.json
