@@ -1,4 +1,4 @@
-"""solve time of a resident batch under the current environment (VILF_SO / VILF_NO_FUSED / ...): python tools/dev_solve_time.py [B] [label]"""
+"""solve time of a resident batch under the current environment (VILF_SO / ...): python tools/dev_solve_time.py [B] [label]"""
 import os, sys, time
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 from vil_fusion_amd import synth

@@ -37,7 +37,6 @@ __global__ void k_mf_tridiag(VbBatch b, VbMarg g, int n_lo, int n_hi);
 __global__ void k_mf_chol(VbBatch b, VbMarg g, int n_lo, int n_hi, int disable);
 __global__ void k_mf_chol_tiles(VbBatch b, VbMarg g, int disable);
 __global__ void k_linearize_split(VbBatch b, int iteration_zero);
-__global__ void k_iter(VbBatch b, int iteration_zero, unsigned *slot_bm, int *err);
 __global__ void k_sb_table(int *tab);
 __global__ void k_mf_ql(VbBatch b, VbMarg g, int force_overflow);
 __global__ void k_mf_apply(VbBatch b, VbMarg g, int n_lo, int n_hi);
@@ -174,12 +173,8 @@ extern "C" int vilf_create(const vilf_options *opts, int device, void *hip_strea
     else { if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return VILF_ERR_DEVICE; } h->own_stream = true; }
     hipEventCreate(&h->ev0); hipEventCreate(&h->ev1);
     h->solve_lds = (size_t)(66 * 256 + 6 * VB_NPAD + 512 + VILF_MAX_FEATURES) * sizeof(double) + (size_t)VILF_MAX_FEATURES * sizeof(int);
-    h->lin_lds = (size_t)VB_LIN_LDS_BYTES;                        // factor chunk + the tables behind it (all dynamic: k_iter overlays the solve's plan on it)
-    { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0) ncu = 256; h->iter_slots = 2 * ncu; }
+    h->lin_lds = (size_t)VB_LIN_LDS_BYTES;                        // factor chunk + the tables behind it (all dynamic)
     h->solve_sb_lds = (size_t)SB_LDS_DOUBLES * sizeof(double);
-    // occupancy experiment (tools/dev_window_occ.sh): unused extra dynamic LDS leaves ONE workgroup per CU instead of two
-    if (const char *e = std::getenv("VILF_LIN_LDS_EXTRA")) h->lin_lds += (size_t)std::atoi(e);
-    if (const char *e = std::getenv("VILF_SB_LDS_EXTRA")) h->solve_sb_lds += (size_t)std::atoi(e);
     static_assert(VB_LIN_LDS_DOUBLES >= 10 * 512, "IMU staging area");
     h->marg_lds_schur = (size_t)MG_MLDS * MG_MLDS * sizeof(double);
     h->marg_lds_finish = (size_t)(MG_NK + 2) * (MG_NK + 2) * sizeof(double);
@@ -193,7 +188,6 @@ extern "C" int vilf_create(const vilf_options *opts, int device, void *hip_strea
     if (hipFuncSetAttribute((const void *)k_linearize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lin_lds) != hipSuccess ||
         hipFuncSetAttribute((const void *)k_linearize_last, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lin_lds) != hipSuccess ||
         hipFuncSetAttribute((const void *)k_linearize_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lin_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_iter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(h->lin_lds, h->solve_sb_lds)) != hipSuccess ||
         hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->solve_lds) != hipSuccess ||
         hipFuncSetAttribute((const void *)k_solve_sb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->solve_sb_lds) != hipSuccess) {
         delete h; return VILF_ERR_DEVICE;
@@ -223,8 +217,6 @@ extern "C" void vilf_destroy(vilf_handle *h) {
     for (hipEvent_t e : h->prof_free) hipEventDestroy(e);
     if (h->wait_ev) hipEventDestroy(h->wait_ev);
     if (h->stamp_ev) hipEventDestroy(h->stamp_ev);
-    if (h->split_ev) hipEventDestroy(h->split_ev);
-    for (hipStream_t st : h->split_streams) if (st) hipStreamDestroy(st);
     if (h->stamp_pinned) (void)hipHostFree(h->stamp_pinned);
     h->s2m_ev.clear(); h->prof_used.clear(); h->prof_free.clear(); h->prof_pending.clear();
     if (h->own_stream) hipStreamDestroy(h->stream);
@@ -741,8 +733,8 @@ extern "C" int vilf_debug_sort_pairs(vilf_handle *h, const void *keys, const int
     hipFree(dk); hipFree(dk2); hipFree(dv); hipFree(dv2); hipFree(dt);
     return rc;
 }
-// dynamic LDS the window kernels are launched with (bytes): [0] k_linearize / k_linearize_split / k_linearize_last, [1] k_solve_sb, [2] k_iter. Diagnostic (bench.py
-// quotes them beside the registers it reads from the code objects); not part of include/vilfusion.h.
+// dynamic LDS the window kernels are launched with (bytes): [0] k_linearize / k_linearize_split / k_linearize_last, [1] k_solve_sb; [2], the larger of the two, is
+// kept for callers that read three values. Diagnostic (bench.py quotes them beside the registers it reads from the code objects); not part of include/vilfusion.h.
 extern "C" int vilf_debug_lds_bytes(vilf_handle *h, int out3[3]) {
     if (!h || !out3) return VILF_ERR_INVALID_ARGUMENT;
     out3[0] = (int)h->lin_lds; out3[1] = (int)h->solve_sb_lds; out3[2] = (int)std::max(h->lin_lds, h->solve_sb_lds);
@@ -782,7 +774,6 @@ static void solve_time_resolve(vilf_handle *h) {
     if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->last_solve_usec = ms * 1000.0;
     h->solve_time_pending = false;
 }
-static bool tlim_disabled(vilf_handle *h) { return !(h->opts.max_solver_time > 0); }
 extern "C" int vilf_batch_solve(vilf_handle *h, int sync) {
     if (!h || !h->resident) return VILF_ERR_INVALID_ARGUMENT;
     HIPCHECK(h, hipSetDevice(h->device));
@@ -832,40 +823,6 @@ extern "C" int vilf_batch_solve(vilf_handle *h, int sync) {
     auto mark = [&](int kind) { if (prof) { pev.push_back(vilf_prof_event(h)); ne++; kinds.push_back(kind); } };
     hipEventRecord(h->ev0, h->stream);
     h->batch.w0 = 0;
-    // Experiment (VILF_SOLVE_SPLIT=n): the batch as n parts on n streams, each part running its own chain of launches. The two kernels of an iteration then meet on the
-    // chip (one part's k_solve_sb beside another part's k_linearize) instead of the whole chip running one kernel at a time.
-    if (const char *es = std::getenv("VILF_SOLVE_SPLIT")) {
-        const int np = std::max(2, std::min(8, std::atoi(es)));
-        if (!dense && tlim_disabled(h) && h->B >= 2 * np) {
-            if ((int)h->split_streams.size() < np) { h->split_streams.resize(np, nullptr); for (auto &st : h->split_streams) if (!st) HIPCHECK(h, hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); }
-            if (!h->split_ev) HIPCHECK(h, hipEventCreateWithFlags(&h->split_ev, hipEventDisableTiming));
-            HIPCHECK(h, hipEventRecord(h->split_ev, h->stream));
-            for (int p = 0; p < np; p++) {
-                hipStream_t st = h->split_streams[p];
-                HIPCHECK(h, hipStreamWaitEvent(st, h->split_ev, 0));
-                VbBatch bb = h->batch;
-                bb.w0 = (int)((long long)h->B * p / np);
-                const dim3 g2((unsigned)((long long)h->B * (p + 1) / np - bb.w0));
-                hipLaunchKernelGGL(k_reset, g2, block, 0, st, bb, 0);
-                hipLaunchKernelGGL(k_linearize, g2, block, h->lin_lds, st, bb, 1);
-                for (int it = 0; it < h->opts.max_num_iterations; it++) {
-                    hipLaunchKernelGGL(k_solve_sb, g2, dim3(256), h->solve_sb_lds, st, bb);
-                    if (it + 1 == h->opts.max_num_iterations) hipLaunchKernelGGL(k_linearize_last, g2, block, h->lin_lds, st, bb);
-                    else hipLaunchKernelGGL(k_linearize, g2, block, h->lin_lds, st, bb, 0);
-                }
-                hipLaunchKernelGGL(k_finalize, g2, dim3(64), 0, st, bb);
-            }
-            for (int p = 0; p < np; p++) {                       // join: the handle's stream continues after every part
-                HIPCHECK(h, hipEventRecord(h->split_ev, h->split_streams[p]));
-                HIPCHECK(h, hipStreamWaitEvent(h->stream, h->split_ev, 0));
-            }
-            hipEventRecord(h->ev1, h->stream);
-            HIPCHECK(h, hipGetLastError());
-            h->solve_time_pending = true;
-            if (sync) { HIPCHECK(h, hipStreamSynchronize(h->stream)); solve_time_resolve(h); }
-            return VILF_OK;
-        }
-    }
     // live-window lists (vilf_batch.hpp): the launches of iteration i address their windows through the list k_linearize of iteration i - 1 left, once something has stopped
     const int max_it = h->opts.max_num_iterations;
     const bool use_live = !std::getenv("VILF_NO_LIVE_LIST") && max_it + 2 <= 64 && h->d[D_LIVE].ensure(((size_t)2 * h->B + 128) * sizeof(int));
@@ -889,48 +846,6 @@ extern "C" int vilf_batch_solve(vilf_handle *h, int sync) {
             hipLaunchKernelGGL(k_linearize_split, dim3((unsigned)(h->B * (nch + 2))), block, h->lin_lds, h->stream, bb, iteration_zero);
         } else hipLaunchKernelGGL(k_linearize, grid, block, h->lin_lds, h->stream, bb0, iteration_zero);
     };
-    // One launch per iteration (k_iter: step + linearisation at the candidate + accept / reject + reduce + solve in the same persistent workgroup, the hand-over in the
-    // workgroup's own scratch slot): whenever the speed-bias-first solve applies, the batch is not split over workgroups and no host clock runs between the iterations.
-    // (tests compare it with the two-kernel sequence to the bit)
-    // MEASURED (round 5, same box, 4096 windows, ms per 8-iteration solve): two kernels 15.6, k_iter on the windows' own workspaces 16.2, k_iter on slots 17.8 — the
-    // hand-over through HBM is not what the iteration waits for (HISTORY.md). k_iter therefore stays an experiment: VILF_FUSED=1 selects it, VILF_NO_SLOTS=1 its
-    // per-window-workspace form; the default is the two-kernel sequence.
-    const bool fused = !dense && !split && !(h->opts.max_solver_time > 0) && std::getenv("VILF_FUSED") && !std::getenv("VILF_NO_FUSED") && h->d[D_ITERQ].ensure(128 * sizeof(int));
-    if (fused) {
-        const size_t iter_lds = std::max(h->lin_lds, h->solve_sb_lds);
-        // batches of more than 1024 windows work in 1024 scratch slots (the first 1024 workspaces of set 0) handed out per XCD by a bitmap: [0..31] free bits, [32] error
-        const bool slots = h->B > 1024 && !std::getenv("VILF_NO_SLOTS");
-        unsigned *bm = slots ? h->d[D_ITERQ].as<unsigned>() : nullptr;
-        if (slots) { HIPCHECK(h, hipMemsetAsync(h->d[D_ITERQ].p, 0xff, 32 * sizeof(int), h->stream)); HIPCHECK(h, hipMemsetAsync(h->d[D_ITERQ].as<int>() + 32, 0, 4 * sizeof(int), h->stream)); }
-        mark(3);
-        hipLaunchKernelGGL(k_reset, grid, block, 0, h->stream, h->batch, 0);
-        for (int it = 0; it < max_it; it++) {
-            mark(1);             // kind 1 with no kind-0 launches beside it = the iteration kernel (bench.py names it k_iter)
-            hipLaunchKernelGGL(k_iter, grid, block, iter_lds, h->stream, h->batch, it == 0 ? 1 : 0, bm, h->d[D_ITERQ].as<int>() + 32);
-        }
-        mark(2);
-        hipLaunchKernelGGL(k_linearize_last, grid, block, h->lin_lds, h->stream, h->batch);
-        mark(3);
-        hipLaunchKernelGGL(k_finalize, grid, dim3(64), 0, h->stream, h->batch);
-        if (prof) {
-            pev.push_back(vilf_prof_event(h)); ne++;
-            for (size_t i = 0; i < kinds.size(); i++) vilf_prof_span(h, pev[i], pev[i + 1], &h->kernel_ms[kinds[i]], &h->kernel_launches[kinds[i]]);
-        }
-        hipEventRecord(h->ev1, h->stream);
-        HIPCHECK(h, hipGetLastError());
-        h->solve_time_pending = true;
-        if (sync) {
-            HIPCHECK(h, hipStreamSynchronize(h->stream));
-            solve_time_resolve(h);
-            if (prof) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-            if (slots) {                                 // a workgroup that found no free slot left its window untouched and said so
-                int e = 0;
-                HIPCHECK(h, hipMemcpy(&e, h->d[D_ITERQ].as<int>() + 32, sizeof(int), hipMemcpyDeviceToHost));
-                if (e) { h->err = "k_iter: more workgroups resident than workspace slots"; return VILF_ERR_DEVICE; }
-            }
-        }
-        return VILF_OK;
-    }
     mark(3);
     hipLaunchKernelGGL(k_reset, grid, block, 0, h->stream, with_lists(0), 0);
     mark(0);
@@ -1263,10 +1178,9 @@ extern "C" int vilf_batch_marginalize(vilf_handle *h, int sync) {
     {
         const int no_chol = std::getenv("VILF_MARG_NO_CHOL") ? 1 : 0;         // test hook: the eigen-solver for every window
         // n <= 75 (every prior the reference produces without td): the augmented factorisation on the matrix cores (k_mf_chol_tiles, 34 KB of LDS); wider kept blocks:
-        // the column-by-column kernel. VILF_MARG_CHOL_COLUMNS=1: the column kernel for every size (tests compare the two forms).
-        const bool tiles = !std::getenv("VILF_MARG_CHOL_COLUMNS");
-        const int lo = tiles ? SB_ND + 1 : 0;
-        if (tiles) hipLaunchKernelGGL(k_mf_chol_tiles, grid, block, (size_t)(SB_NR * (SB_NR + 1) / 2 + 2 * 4 * 160 + 16) * sizeof(double), h->stream, h->batch, g, no_chol);
+        // the column-by-column kernel.
+        const int lo = SB_ND + 1;
+        hipLaunchKernelGGL(k_mf_chol_tiles, grid, block, (size_t)(SB_NR * (SB_NR + 1) / 2 + 2 * 4 * 160 + 16) * sizeof(double), h->stream, h->batch, g, no_chol);
         if (one_class) hipLaunchKernelGGL(k_mf_chol, grid, block, h->marg_lds_finish, h->stream, h->batch, g, lo, 1 << 30, no_chol);
         else {
             hipLaunchKernelGGL(k_mf_chol, grid, block, lds_small, h->stream, h->batch, g, lo, 78, no_chol);

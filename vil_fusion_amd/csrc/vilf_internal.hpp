@@ -29,7 +29,7 @@ enum {
     D_PHDR, D_PX0, D_PJ, D_PR, D_PH, D_PG, D_FACW, D_HPP, D_W, D_HF, D_GF, D_IMUH, D_IMUG, D_LIDH, D_LIDG, D_G, D_DIAGH,
     D_SCALE, D_DIAG, D_GRAD, D_GN, D_ST, D_OPS, D_ORS, D_OVS, D_OBAS, D_OBGS, D_COV, D_WORK, D_HOOK, D_DBG, D_LUTI, D_LUTL, D_LUTV,
     D_MFLAG, D_MINFO, D_MF0, D_MSTP, D_MSTS, D_MSTF, D_MSTE, D_MBUF, D_MHD, D_MGD, D_MWF, D_MHF, D_MGF, D_MAMM, D_MX, D_MROT, D_MLAM, D_MAR, D_MBR, D_QLV, D_QLD, D_QLLOG, D_QLIT, D_QLINFO,
-    D_PAIRD, D_FACREC, D_CF, D_STAMPS, D_LIVE, D_ITERQ, D_SBTAB, D_SPLITC, D_SPLITB, D_UPSTAGE, D_DNSTAGE, D_OBSV, D_OBSTD, D_OBSROW, D_TD, D_PHDR0, D_PX00, D_PJ0, D_PR0, D_PH0, D_PG0,      // priors as uploaded (restored by vilf_batch_rewind after a marginalization)
+    D_PAIRD, D_FACREC, D_CF, D_STAMPS, D_LIVE, D_SBTAB, D_SPLITC, D_SPLITB, D_UPSTAGE, D_DNSTAGE, D_OBSV, D_OBSTD, D_OBSROW, D_TD, D_PHDR0, D_PX00, D_PJ0, D_PR0, D_PH0, D_PG0,      // priors as uploaded (restored by vilf_batch_rewind after a marginalization)
     D_COUNT
 };
 
@@ -102,7 +102,6 @@ struct vilf_handle {
     struct ProfSpan { hipEvent_t a, b; double *ms; long *cnt; };
     std::vector<ProfSpan> prof_pending;
     std::vector<hipEvent_t> prof_used, prof_free;
-    std::vector<hipStream_t> split_streams; hipEvent_t split_ev = nullptr;    // VILF_SOLVE_SPLIT experiment: the batch in parts on their own streams
     hipEvent_t wait_ev = nullptr;            // vilf_wait_for
     void *stamp_pinned = nullptr; size_t stamp_cap = 0; hipEvent_t stamp_ev = nullptr;   // vilf_batch_newest_poses_device: pinned staging of the caller's stamps
     double kernel_ms[4] = {0, 0, 0, 0};      // linearize, solve, step, other (accumulated since last reset)
@@ -118,7 +117,6 @@ struct vilf_handle {
     bool solve_time_pending = false;         // the last solve was enqueued with sync == 0: ev0 / ev1 are read by the next call that waits for the stream
     size_t solve_lds = 0, lin_lds = 0, solve_sb_lds = 0;
     int split_gen = 0;      // generation counter of the k_linearize_split launches of this handle
-    int iter_slots = 512;   // resident workgroups of k_iter = workspace slots it uses (two per CU)
     bool solve_dense_fallback = false;       // a prior imported from the host holds a speed-bias block other than SpeedBias[0]: k_solve (dense) instead of k_solve_sb
     FeatCtx *feat = nullptr;                 // LiDAR feature extraction workspace (vilf_feat.hip)
     S2B *s2m = nullptr, *s2b = nullptr;      // scan-to-map state: single stream / batched streams (vilf_s2m.hip)

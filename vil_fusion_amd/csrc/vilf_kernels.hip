@@ -360,10 +360,9 @@ __device__ __forceinline__ int pair_elem(int row, int col) {   // element of the
 
 // JAC = false: the launch after the LAST solve of the iteration budget. Its linearisation would never be used (Ceres tests max_num_iterations before the gradient),
 // so it only takes the step: candidate, cost of every factor (residuals only), accept / reject — a ninth of the linearisations of a solve.
-// FUSED (k_iter): the window and its workspace slot are handed in (a persistent workgroup takes windows from a queue and keeps ONE workspace for all of them);
-// iteration_zero = 2 then means "linearise at x again" (the workspace of x is gone — it was this workgroup's scratch — and an invalid step asks for another solve from it).
 // Returns 0: linearised (a solve may follow), 1: the step was invalid (nothing linearised), 2: the window had stopped before.
-// Everything that used to be static LDS lives behind the factor chunk in the dynamic region, so that a kernel that runs the solve in the same workgroup can overlay it.
+// Everything that used to be static LDS lives behind the factor chunk in the dynamic region (it was moved there for an experiment that overlaid the solve's plan on
+// it, since removed; moving it back changes the kernel).
 struct LinShared {
     double pose[77], sb[99], R[99], ric[9], tic[3];
     double lidJ[10 * 72], lidr[64], grad[176];
@@ -375,17 +374,17 @@ struct LinShared {
     int last, defi[2];
 };
 static_assert(sizeof(LinShared) <= VB_LIN_SHARED_BYTES, "VB_LIN_SHARED_BYTES (vilf_batch.hpp) must cover LinShared");
-template <bool JAC, bool SPLIT = false, bool FUSED = false>
-__device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_zero, int w_in = 0, size_t ww_in = 0, int tid_in = 0) {
+template <bool JAC, bool SPLIT = false>
+__device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_zero) {
     // SPLIT (small batches, k_linearize_split): the window's work is dealt to NR = chunks + 2 workgroups — role s < NCH evaluates the factor slots of chunk s and forms
     // their pair products, role NCH the IMU factors, role NCH + 1 the LiDAR factors and the prior's cost; every role runs the set-up (state, candidate, tables) itself
     // and changes nothing in VbState. The workgroup that arrives last (a counter) has the same set-up in its LDS and everything else in global memory: it applies the
     // trust-region bookkeeping the others left undone and runs the phases behind the chunk loop. The result is the one of the single workgroup to the bit: a pair whose
     // factors span chunks hands its MFMA accumulators from chunk to chunk (global memory + a flag, only to a HIGHER workgroup index: the dispatcher starts workgroups in
     // order, so the writer is always running or done), and the per-thread cost sums are added up by the last workgroup in the single workgroup's order.
-    const int tid = FUSED ? tid_in : (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform (SGPR)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform (SGPR)
     const int NR = SPLIT ? b.split_nr : 1, NCH = NR - 2;
-    const int w = FUSED ? w_in : (SPLIT ? (int)blockIdx.x / NR : vb_window(b));
+    const int w = SPLIT ? (int)blockIdx.x / NR : vb_window(b);
     const int role = SPLIT ? (int)blockIdx.x - w * NR : 0;
     if (w < 0) return 2;
     const bool do_vis = !SPLIT || role < NCH, do_imu = !SPLIT || role == NCH, do_lp = !SPLIT || role == NCH + 1;
@@ -434,7 +433,7 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
     // the dogleg step from the last solve, linearise at the CANDIDATE into the set that does not belong to x — the candidate's cost falls out of the same pass over
     // the factors, so there is no separate cost-only pass — and flip st->ws when the step is accepted; a rejected step leaves x, its cost and its set untouched.
     const int wset = iteration_zero ? 0 : (st->ws ^ 1);
-    const size_t ww = FUSED ? ww_in : (size_t)wset * b.B + w;              // window index inside the written set (FUSED: the workgroup's own slot)
+    const size_t ww = (size_t)wset * b.B + w;                              // window index inside the written set
 
     double *s_X = s_dyn;
     double *s_U = s_dyn;                      // the IMU staging area (10 x 512) shares the region with the factor chunk that follows it
@@ -457,12 +456,6 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
 
     if (tid < 77) s_pose[tid] = pose_g[tid];
     if (tid < 99) s_sb[tid] = sb_g[tid];
-    if (FUSED && JAC) {
-        // the slot's W rows carry another window's feature ranges: zero the rows this window uses (coalesced 16-byte stores; the factor lanes write behind several barriers)
-        double2_t *Wz = reinterpret_cast<double2_t *>(b.W + ww * FM * VB_WLD);
-        const int nz = min((F + 3) & ~3, (int)FM) * (VB_WLD / 2);
-        for (int i = tid; i < nz; i += NT) Wz[i] = double2_t{0.0, 0.0};
-    }
     double stepsq = 0;
     if (!iteration_zero) {
         // ---- DoglegStrategy::ComputeTraditionalDoglegStep + model cost change (thread 0), then the candidate x (+) delta -----------------------------
@@ -509,14 +502,8 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
         __syncthreads();
         if (!s_flagi[0]) {
             if (SPLIT) { if (arrive()) { if (tid == 0) step_bookkeeping(); } }
-            if (!FUSED) return 1;
-            // FUSED: the invalid step raised mu and asks for another solve from the linearisation at x — which was this workgroup's scratch and is gone. x is linearised
-            // again (s_pose / s_sb still hold x, the features are read from feat_x): the same arithmetic on the same state gives the same bits.
-            if (st->done) return 2;                        // (thread 0 wrote it before the barrier above: the fifth invalid step in a row ends the window)
-            iteration_zero = 2;
-            feat = feat_x;
+            return 1;
         }
-        if (!iteration_zero) {
         const double ca = s_red[1], cb = s_red[2];
         const double *scale_g = b.scale + (size_t)w * (VB_P + FM), *diag_g = b.diag + (size_t)w * (VB_P + FM);
         const double *grad_g = b.grad + (size_t)w * (VB_P + FM), *gn_g = b.gn + (size_t)w * (VB_P + FM);
@@ -542,7 +529,6 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
             cfeat[f] = v;
         }
         __threadfence_block();                                               // cfeat is read back by other threads of this workgroup below (after the next barrier)
-        }
     }
     // pair table: lane p of every wave keeps pair p's start inside its class list and its factor count in registers, and the wave the set of its own class's pairs
     // as a bit mask — the chunk loop walks the mask and fetches a pair's entry with v_readlane (three dependent LDS reads per pair and chunk before)
@@ -684,7 +670,7 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
     const int *f_start = b.f_start + (size_t)w * FM;
     const uint8_t *f_const = b.f_const + (size_t)w * FM;
     const double *facrec = b.facrec + (size_t)w * FC * 8;
-    double *facw = b.facw + (FUSED ? ww : (size_t)w) * VB_FACW * FC;
+    double *facw = b.facw + (size_t)w * VB_FACW * FC;
     double *W = b.W + ww * FM * VB_WLD;
     long long t_eval = 0, t_sync1 = 0, t_mfma = 0, t_sync2 = 0, t_a = 0;
     int pe[4];
@@ -1015,7 +1001,7 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
     const double gm = block_max(gmax, s_red);
     const double xs = block_sum(xsq, s_red);
     if (iteration_zero) {
-        // (iteration_zero == 2, FUSED: x was linearised AGAIN for another solve — its cost and norms are what they were)
+        // (`!= 2` is dead — iteration_zero is 0 or 1 — but dropping or rewriting it changes the register allocation of k_linearize / k_linearize_split)
         if (tid == 0 && iteration_zero != 2) { st->x_cost = cost; st->gradient_max_norm = gm; st->x_norm = sqrt(xs); st->need_linearize = 0; st->reuse = 0; st->initial_cost = cost; st->ws = 0; }
         LSTAMP(9);
         return 0;
@@ -1921,9 +1907,8 @@ extern "C" __global__ __launch_bounds__(256) void k_sb_table(int *tab) {
     for (int k = 0; k < SB_TAB_ROWS; k++) for (int j = 0; j < 4; j++) tab[((size_t)k * 256 + tid) * 4 + j] = t[4 * k + j];
 }
 
-template <bool FUSED>
-__device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w, size_t ww_in, int tid_in = 0) {
-    const int tid = FUSED ? tid_in : (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+__device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (w < 0) return;
     VbState *st = b.st + w;
     extern __shared__ double s_dyn[];
@@ -1952,12 +1937,12 @@ __device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w, size_t ww
     STAMP(1, 0);
     const int F = b.n_feat[w];
     const size_t FM = b.Fmax;
-    const size_t ww = FUSED ? ww_in : (size_t)st->ws * b.B + w;            // the workspace that belongs to the current state x (k_linearize; FUSED: the workgroup's slot)
+    const size_t ww = (size_t)st->ws * b.B + w;                            // the workspace that belongs to the current state x (k_linearize)
     const double *Hpp = b.Hpp + ww * 66 * 36;
     const double *imuH = b.imuH + ww * 9000, *lidH = b.lidH + ww * 1440;
     const double *priorH = b.prior_H + (size_t)w * VB_PRIOR_LD * VB_PRIOR_LD;
     double *W = b.W + ww * FM * VB_WLD;
-    double *cf = b.cf + (FUSED ? ww : (size_t)w) * FM;
+    double *cf = b.cf + (size_t)w * FM;
     const double *hf = b.hf + ww * FM, *gf = b.gf + ww * FM;
     const uint8_t *f_const = b.f_const + (size_t)w * FM;
     double *scale_g = b.scale + (size_t)w * (VB_P + FM), *diag_g = b.diag + (size_t)w * (VB_P + FM);
@@ -2566,55 +2551,7 @@ __device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w, size_t ww
         st->num_linear_solves += tries; st->solve_failed = 0; st->reuse = 1; st->scaling_ready = 1;
     }
 }
-extern "C" __global__ __launch_bounds__(SBT, 2) void k_solve_sb(VbBatch b) { solve_sb_body<false>(b, vb_window(b), 0); }
-
-// ------------------------------------------------------------------------------------------------------------------
-// k_iter: ONE launch per iteration, one workgroup per window: the trust-region step + linearisation at the candidate + accept / reject (linearize_body) and — in the
-// same workgroup, behind a barrier — the reduce + solve of the new linearisation (solve_sb_body). What the two kernels handed over through per-window double-buffered
-// workspaces in HBM (W, facw, pairD, Hpp, imuH / imug, lidH / lidg, g, diagH, hf, gf, cf: ~0.5 MB per window and set, written by one launch, read by the next after 4096
-// other windows had gone through the caches) is now the WORKGROUP's scratch, consumed microseconds after it was written. For big batches the scratch is a SLOT, not the
-// window's own workspace: a workgroup takes a free slot of its XCD (bitmap in global memory, atomicAnd / atomicOr — a bounded search, nobody waits for anybody) and gives
-// it back when it ends, so the batch works in <= 1024 slots (the lowest free ones first: in practice two per CU, close to what the 4 MB L2 of an XCD and the 256 MB
-// memory-side cache hold) instead of 2 x B workspaces. A workgroup only ever reads what it has written itself in this launch (the W rows it uses are cleared first), so
-// neither another XCD's L2 nor a stale L1 line of the slot's previous user can be observed. A rejected step needs no solve (the old Gauss-Newton step is re-used with a
-// smaller radius); an INVALID step asks for another solve from the linearisation at x, which is gone: x is linearised again (same arithmetic, same state: same bits).
-// LDS: the larger of the two bodies' plans, overlaid. Launch sequence of a solve: k_iter(iteration_zero = 1), k_iter(0) x (max_iterations - 1), k_linearize_last.
-#define VB_SLOTS_PER_XCD 128
-#define VB_SLOTS (8 * VB_SLOTS_PER_XCD)
-extern "C" __global__ __launch_bounds__(NT, 2) void k_iter(VbBatch b, int iteration_zero, unsigned *slot_bm, int *err) {
-    const int w = blockIdx.x + b.w0;
-    __shared__ int s_slot;
-    if (slot_bm) {
-        if (!iteration_zero && b.st[w].done) return;                       // (before a slot is taken: a finished window costs one load)
-        if (threadIdx.x == 0) {
-            const int xcc = (int)(__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7);     // HW_REG_XCC_ID[3:0]: slots stay on the XCD whose L2 holds their lines
-            int slot = -1;
-            for (int attempt = 0; attempt < 8 * 4 * 64 && slot < 0; attempt++) {      // own XCD's four words first, then the others'; bounded
-                const int word = ((xcc * 4 + (attempt & 3)) + 4 * ((attempt >> 2) & 7)) & 31;
-                const unsigned v = __hip_atomic_load(slot_bm + word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (!v) continue;
-                const int bit = __builtin_ctz(v);
-                if (atomicAnd(slot_bm + word, ~(1u << bit)) & (1u << bit)) slot = 32 * word + bit;
-            }
-            if (slot < 0) atomicExch(err, 1);                              // more workgroups resident than slots: cannot happen at two per CU; reported, not waited for
-            s_slot = slot;
-        }
-        __syncthreads();
-        if (s_slot < 0) return;
-    }
-    const size_t slot = slot_bm ? (size_t)s_slot : (size_t)w;
-    const int r = linearize_body<true, false, true>(b, iteration_zero ? 1 : 0, w, slot, (int)threadIdx.x);
-    __syncthreads();
-    if (r != 2) solve_sb_body<true>(b, w, slot, (int)threadIdx.x);
-    if (slot_bm) {
-        __syncthreads();                                                   // every load of the slot has returned (the barrier waits for vmcnt(0))
-        if (threadIdx.x == 0) atomicOr(slot_bm + (s_slot >> 5), 1u << (s_slot & 31));
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// k_step (folded into k_linearize)
-// (the trust-region step — dogleg step, candidate, cost, accept / reject — is the prologue and the epilogue of k_linearize)
+extern "C" __global__ __launch_bounds__(SBT, 2) void k_solve_sb(VbBatch b) { solve_sb_body(b, vb_window(b)); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // double2vector(): yaw / position gauge fix of the whole window (estimator.cpp:549-596)

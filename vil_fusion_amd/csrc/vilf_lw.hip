@@ -2025,8 +2025,7 @@ int vilf_lw_group_solve(vilf_handle *h, int G, const vilf_window_in *const *ins,
     std::vector<LwWin> dws(G);
     // K splits of the Schur reduce: a constant — the partials are summed in split order, so a count that depended on the group would make a window's bits depend on
     // who it is solved next to. 8 keeps a single window's reduce at 120 workgroups and costs a full group little (measured: 4 / 8 / 16 splits within 4 % at 32 windows)
-    int group_nks = 8;
-    if (const char *e = std::getenv("VILF_LW_NKS")) group_nks = std::min(SY_KS, std::max(1, std::atoi(e)));
+    const int group_nks = 8;
     std::vector<size_t> imu_at(G), x_at(G);
     { size_t a = 0, b = 0; for (int g = 0; g < G; g++) { imu_at[g] = a; x_at[g] = b; a += hws[g].nimu; b += hws[g].xo + 8; } }
     auto pack = [&](int g) {
