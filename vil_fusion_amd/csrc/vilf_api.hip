@@ -13,43 +13,8 @@
 #include <thread>
 #include <atomic>
 #include "vilf_internal.hpp"
+#include "vilf_kernels.hpp"
 #include "vilf_sort.hpp"
-
-#define IMU_REC 288
-#define IMU_SQRT 62
-
-extern "C" {
-__global__ void k_imu_prep(int n, const double *cov, double *work, double *imu_rec);
-__global__ void k_prior_prep(VbBatch b, double *prior_H, double *prior_g, unsigned lds_bytes, const int *done4);
-#define VILF_PRIOR_PREP_LDS ((size_t)(MG_NK + 1) * (MG_NK + 1) * sizeof(double))     // the n x n prior Jacobian in LDS (n <= 96: 73.5 KB, two workgroups per CU)
-__global__ void k_linearize(VbBatch b, int iteration_zero);
-__global__ void k_linearize_last(VbBatch b);
-__global__ void k_solve(VbBatch b);
-__global__ void k_solve_sb(VbBatch b);
-__global__ void k_finalize(VbBatch b);
-__global__ void k_reset(VbBatch b, int rewind_state);
-__global__ void k_marg_prepare(VbBatch b, VbMarg g);
-__global__ void k_marg_prepare_td(VbBatch b, VbMarg g);
-__global__ void k_prior_keep(VbBatch b, VbMarg g);
-__global__ void k_marg_schur(VbBatch b, VbMarg g, int exact);
-__global__ void k_marg_finish(VbBatch b, VbMarg g, int n_lo, int n_hi, int only_flagged);
-__global__ void k_mf_tridiag(VbBatch b, VbMarg g, int n_lo, int n_hi);
-__global__ void k_mf_chol(VbBatch b, VbMarg g, int n_lo, int n_hi, int disable);
-__global__ void k_mf_chol_tiles(VbBatch b, VbMarg g, int disable);
-__global__ void k_linearize_split(VbBatch b, int iteration_zero);
-__global__ void k_sb_table(int *tab);
-__global__ void k_mf_ql(VbBatch b, VbMarg g, int force_overflow);
-__global__ void k_mf_apply(VbBatch b, VbMarg g, int n_lo, int n_hi);
-#define VILF_MFA_LDS_EXTRA (4 * 64 * 8 + QL_ICAP * 2)      // k_mf_apply behind V: two staged chunks of the rotation log (MFA_CH = 64) + the 16-bit QL iteration table
-__global__ void k_hook_projection(const double *, const double *, const double *, double, const double *, const double *, double, double *);
-__global__ void k_hook_projection_td(const double *in, double *out);
-__global__ void k_time_limit(VbBatch b, const int *mflag, int only_margin_old);
-__global__ void k_hook_imu(const double *, const double *, const double *, const double *, const double *, const double *, double *, double *);
-__global__ void k_hook_lidar(const double *, const double *, const double *, const double *, const double *, double *);
-__global__ void k_hook_edge(const double *, const double *, const double *, const double *, double *);
-__global__ void k_hook_surf(const double *, const double *, const double *, double, double *);
-__global__ void k_hook_plus(const double *, const double *, int, double *);
-}
 
 // the batch descriptor's view of the live prior set (the two sets swap: vilf_batch_marginalize / vilf_batch_rewind)
 static void bind_prior_pointers(vilf_handle *h) {
@@ -172,30 +137,17 @@ extern "C" int vilf_create(const vilf_options *opts, int device, void *hip_strea
     // separate nodes) run side by side — with a blocking stream every default-stream operation of the process (a torch tensor op, a hipMemcpy) serialised them
     else { if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return VILF_ERR_DEVICE; } h->own_stream = true; }
     hipEventCreate(&h->ev0); hipEventCreate(&h->ev1);
-    h->solve_lds = (size_t)(66 * 256 + 6 * VB_NPAD + 512 + VILF_MAX_FEATURES) * sizeof(double) + (size_t)VILF_MAX_FEATURES * sizeof(int);
-    h->lin_lds = (size_t)VB_LIN_LDS_BYTES;                        // factor chunk + the tables behind it (all dynamic)
-    h->solve_sb_lds = (size_t)SB_LDS_DOUBLES * sizeof(double);
-    static_assert(VB_LIN_LDS_DOUBLES >= 10 * 512, "IMU staging area");
-    h->marg_lds_schur = (size_t)MG_MLDS * MG_MLDS * sizeof(double);
-    h->marg_lds_finish = (size_t)(MG_NK + 2) * (MG_NK + 2) * sizeof(double);
-    if (hipFuncSetAttribute((const void *)k_marg_schur, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->marg_lds_schur) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_marg_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->marg_lds_finish) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_prior_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VILF_PRIOR_PREP_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_mf_tridiag, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->marg_lds_finish) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_mf_chol, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->marg_lds_finish) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_mf_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(h->marg_lds_finish + VILF_MFA_LDS_EXTRA)) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_mf_ql, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * (MG_NK + 2) * QL_LPW * sizeof(double))) != hipSuccess) { delete h; return VILF_ERR_DEVICE; }
-    if (hipFuncSetAttribute((const void *)k_linearize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lin_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_linearize_last, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lin_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_linearize_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lin_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->solve_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_solve_sb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->solve_sb_lds) != hipSuccess) {
-        delete h; return VILF_ERR_DEVICE;
-    }
+    const struct { const void *kernel; int bytes; } dyn_lds[] = {      // the kernels that take more than the default 64 KB of dynamic LDS, or may (totals: vilf_kernels.hpp)
+        {(const void *)k_marg_schur, MGS_EXACT_LDS_BYTES}, {(const void *)k_marg_finish, MGF_LDS_BYTES}, {(const void *)k_prior_prep, PRIOR_PREP_LDS_BYTES},
+        {(const void *)k_mf_tridiag, MGF_LDS_BYTES}, {(const void *)k_mf_chol, MGF_LDS_BYTES}, {(const void *)k_mf_apply, MGF_LDS_BYTES + MFA_LDS_EXTRA_BYTES},
+        {(const void *)k_mf_ql, QL_LDS_BYTES}, {(const void *)k_linearize, VB_LIN_LDS_BYTES}, {(const void *)k_linearize_last, VB_LIN_LDS_BYTES},
+        {(const void *)k_linearize_split, VB_LIN_LDS_BYTES}, {(const void *)k_solve, SOLVE_LDS_BYTES}, {(const void *)k_solve_sb, SB_LDS_BYTES}};
+    for (const auto &k : dyn_lds)
+        if (hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes) != hipSuccess) { delete h; return VILF_ERR_DEVICE; }
     std::memset(&h->batch, 0, sizeof(h->batch));
     // k_solve_sb's gather index table: decoded once on the device (the same arithmetic the kernel used to run per launch), read by every solve
-    if (!h->d[D_SBTAB].ensure((size_t)23 * 256 * 16)) { delete h; return VILF_ERR_DEVICE; }
-    hipLaunchKernelGGL(k_sb_table, dim3(1), dim3(256), 0, h->stream, h->d[D_SBTAB].as<int>());
+    if (!h->d[D_SBTAB].ensure((size_t)SB_TAB_ROWS * SBT * 16)) { delete h; return VILF_ERR_DEVICE; }
+    hipLaunchKernelGGL(k_sb_table, dim3(1), dim3(SBT), 0, h->stream, h->d[D_SBTAB].as<int>());
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) { delete h; return VILF_ERR_DEVICE; }
     *out = h;
     return VILF_OK;
@@ -357,7 +309,7 @@ static int upload_priors(vilf_handle *h) {
             HIPCHECK(h, hipStreamSynchronize(h->stream));   // hd / x0 are stack buffers
         }
     }
-    hipLaunchKernelGGL(k_prior_prep, dim3(B), dim3(VB_NT), VILF_PRIOR_PREP_LDS, h->stream, h->batch, h->d[D_PH].as<double>(), h->d[D_PG].as<double>(), (unsigned)VILF_PRIOR_PREP_LDS, (const int *)nullptr);
+    hipLaunchKernelGGL(k_prior_prep, dim3(B), dim3(VB_NT), PRIOR_PREP_LDS_BYTES, h->stream, h->batch, h->d[D_PH].as<double>(), h->d[D_PG].as<double>(), (unsigned)PRIOR_PREP_LDS_BYTES, (const int *)nullptr);
     HIPCHECK(h, hipGetLastError());
     for (int w = 0; w < B; w++) h->prior_dirty[w] = 0;
     h->prior_slots_valid = std::max(h->prior_slots_valid, B);
@@ -701,7 +653,7 @@ extern "C" int vilf_batch_upload(vilf_handle *h, int B, const vilf_window_in *wi
     h->batch.lut_imu = h->d[D_LUTI].as<int>(); h->batch.lut_lid = h->d[D_LUTL].as<int>(); h->batch.lut_vis = h->d[D_LUTV].as<int>();
     h->batch.sb_tab = h->d[D_SBTAB].as<int>();
     const int nimu = B * 10;
-    hipLaunchKernelGGL(k_imu_prep, dim3((nimu + 3) / 4), dim3(64), 0, h->stream, nimu, h->d[D_COV].as<double>(), h->d[D_WORK].as<double>(), h->d[D_IMU].as<double>());
+    hipLaunchKernelGGL(k_imu_prep, dim3((nimu + 3) / 4), dim3(IMU_PREP_NT), 0, h->stream, nimu, h->d[D_COV].as<double>(), h->d[D_WORK].as<double>(), h->d[D_IMU].as<double>());
     HIPCHECK(h, hipGetLastError());
     int rc = upload_priors(h);
     if (rc != VILF_OK) return rc;
@@ -737,7 +689,7 @@ extern "C" int vilf_debug_sort_pairs(vilf_handle *h, const void *keys, const int
 // kept for callers that read three values. Diagnostic (bench.py quotes them beside the registers it reads from the code objects); not part of include/vilfusion.h.
 extern "C" int vilf_debug_lds_bytes(vilf_handle *h, int out3[3]) {
     if (!h || !out3) return VILF_ERR_INVALID_ARGUMENT;
-    out3[0] = (int)h->lin_lds; out3[1] = (int)h->solve_sb_lds; out3[2] = (int)std::max(h->lin_lds, h->solve_sb_lds);
+    out3[0] = VB_LIN_LDS_BYTES; out3[1] = SB_LDS_BYTES; out3[2] = std::max(VB_LIN_LDS_BYTES, SB_LDS_BYTES);
     return VILF_OK;
 }
 extern "C" int vilf_debug_stamps(vilf_handle *h, long long *out96) {
@@ -843,8 +795,8 @@ extern "C" int vilf_batch_solve(vilf_handle *h, int sync) {
             if (++h->split_gen <= 0) h->split_gen = 1;            // the launch's generation: what its hand-over flags carry (never 0 = the cleared state)
             bb.split_gen = h->split_gen;
             bb.split_fault = std::getenv("VILF_SPLIT_FAULT") != nullptr;
-            hipLaunchKernelGGL(k_linearize_split, dim3((unsigned)(h->B * (nch + 2))), block, h->lin_lds, h->stream, bb, iteration_zero);
-        } else hipLaunchKernelGGL(k_linearize, grid, block, h->lin_lds, h->stream, bb0, iteration_zero);
+            hipLaunchKernelGGL(k_linearize_split, dim3((unsigned)(h->B * (nch + 2))), block, VB_LIN_LDS_BYTES, h->stream, bb, iteration_zero);
+        } else hipLaunchKernelGGL(k_linearize, grid, block, VB_LIN_LDS_BYTES, h->stream, bb0, iteration_zero);
     };
     mark(3);
     hipLaunchKernelGGL(k_reset, grid, block, 0, h->stream, with_lists(0), 0);
@@ -860,21 +812,21 @@ extern "C" int vilf_batch_solve(vilf_handle *h, int sync) {
         if (tlim > 0) {
             HIPCHECK(h, hipStreamSynchronize(h->stream));
             const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-            if (el >= tlim) { hipLaunchKernelGGL(k_time_limit, grid, dim3(64), 0, h->stream, h->batch, h->d[D_MFLAG].as<int>(), 0); break; }
-            if (el >= tlim * 4.0 / 5.0 && !stopped_old) { hipLaunchKernelGGL(k_time_limit, grid, dim3(64), 0, h->stream, h->batch, h->d[D_MFLAG].as<int>(), 1); stopped_old = true; }
+            if (el >= tlim) { hipLaunchKernelGGL(k_time_limit, grid, dim3(WIN1_NT), 0, h->stream, h->batch, h->d[D_MFLAG].as<int>(), 0); break; }
+            if (el >= tlim * 4.0 / 5.0 && !stopped_old) { hipLaunchKernelGGL(k_time_limit, grid, dim3(WIN1_NT), 0, h->stream, h->batch, h->d[D_MFLAG].as<int>(), 1); stopped_old = true; }
         }
         mark(1);
         const bool last = it + 1 == h->opts.max_num_iterations;
         const VbBatch bs = with_lists(it + 1), bl = bs;
-        if (dense) hipLaunchKernelGGL(k_solve, grid, dim3(512), h->solve_lds, h->stream, bs);
-        else hipLaunchKernelGGL(k_solve_sb, grid, dim3(256), h->solve_sb_lds, h->stream, bs);
+        if (dense) hipLaunchKernelGGL(k_solve, grid, dim3(SNT), SOLVE_LDS_BYTES, h->stream, bs);
+        else hipLaunchKernelGGL(k_solve_sb, grid, dim3(SBT), SB_LDS_BYTES, h->stream, bs);
         mark(last ? 2 : 0);      // kind 2 ("k_step" in the bench line): the step-only launch that ends a solve
         // the step of the last iteration needs no linearisation behind it (nothing solves with it): residuals only
-        if (last) hipLaunchKernelGGL(k_linearize_last, grid, block, h->lin_lds, h->stream, bl);
+        if (last) hipLaunchKernelGGL(k_linearize_last, grid, block, VB_LIN_LDS_BYTES, h->stream, bl);
         else linearize(bl, 0);
     }
     mark(3);
-    hipLaunchKernelGGL(k_finalize, grid, dim3(64), 0, h->stream, h->batch);
+    hipLaunchKernelGGL(k_finalize, grid, dim3(WIN1_NT), 0, h->stream, h->batch);
     if (prof) {
         pev.push_back(vilf_prof_event(h)); ne++;
         for (size_t i = 0; i < kinds.size(); i++) vilf_prof_span(h, pev[i], pev[i + 1], &h->kernel_ms[kinds[i]], &h->kernel_launches[kinds[i]]);
@@ -1158,12 +1110,12 @@ extern "C" int vilf_batch_marginalize(vilf_handle *h, int sync) {
     if (h->batch.est_td) hipLaunchKernelGGL(k_marg_prepare_td, grid, block, 0, h->stream, h->batch, g);
     else hipLaunchKernelGGL(k_marg_prepare, grid, block, 0, h->stream, h->batch, g);
     if (prof) mev[1] = vilf_prof_event(h);
-    hipLaunchKernelGGL(k_marg_schur, grid, block, (size_t)(MG_MD * MG_MD + MG_MD * (MG_NK + 1) + 1000 + VB_NT + MG_FCH * MG_RWP) * sizeof(double), h->stream, h->batch, g,
+    hipLaunchKernelGGL(k_marg_schur, grid, block, MGS_FAST_LDS_BYTES, h->stream, h->batch, g,
                        std::getenv("VILF_MARG_FORCE_EXACT") ? 2 : 0);      // test hook: exercise the Jacobi path on well-conditioned windows too
     g.pool = (int)sPool;
     for (int r = 0; r < (int)((sB + sPool - 1) / sPool); r++) {      // one launch unless the pool is smaller than the batch (large Mcap)
         g.pool_round = r;
-        hipLaunchKernelGGL(k_marg_schur, grid, block, h->marg_lds_schur, h->stream, h->batch, g, 1);
+        hipLaunchKernelGGL(k_marg_schur, grid, block, MGS_EXACT_LDS_BYTES, h->stream, h->batch, g, 1);
     }
     g.pool_round = 0;
     if (prof) mev[2] = vilf_prof_event(h);
@@ -1171,38 +1123,29 @@ extern "C" int vilf_batch_marginalize(vilf_handle *h, int sync) {
     // finished, the launches below skip those), otherwise the
     // eigen-solver of the kept block in three launches (tred2 per workgroup, the QL recurrence of every window one lane each, rotation replay +
     // prior output per workgroup); k_marg_finish (everything in one workgroup) only takes windows whose rotation log overflowed
-    // The kept-block kernels come in two LDS sizes by dimension class (n < 78: three workgroups per CU) — for a large batch. A small one (the single window of the real-time
-    // case) does not fill the device either way and takes ONE launch of each with the full LDS: four launches less in a chain of mostly empty ones (~5 us each).
+    // The kept-block kernels come in two LDS sizes by dimension class (n < MGF_SMALL_N: three workgroups per CU) — for a large batch. A small one (the single window of the
+    // real-time case) does not fill the device either way and takes ONE launch of each with the full LDS: four launches less in a chain of mostly empty ones (~5 us each).
     const bool one_class = h->B <= 64;
-    const size_t lds_small = (size_t)77 * 77 * sizeof(double);
+    // kernel(batch, marg, n_lo, n_hi, tail...) over the kept dimensions [lo, inf): one launch, or one per dimension class, each with its class's LDS (+ extra)
+    auto by_class = [&](auto kernel, size_t extra, int lo, auto... tail) {
+        if (one_class) hipLaunchKernelGGL(kernel, grid, block, MGF_LDS_BYTES + extra, h->stream, h->batch, g, lo, 1 << 30, tail...);
+        else {
+            hipLaunchKernelGGL(kernel, grid, block, MGF_SMALL_LDS_BYTES + extra, h->stream, h->batch, g, lo, MGF_SMALL_N, tail...);
+            hipLaunchKernelGGL(kernel, grid, block, MGF_LDS_BYTES + extra, h->stream, h->batch, g, MGF_SMALL_N, 1 << 30, tail...);
+        }
+    };
     {
         const int no_chol = std::getenv("VILF_MARG_NO_CHOL") ? 1 : 0;         // test hook: the eigen-solver for every window
         // n <= 75 (every prior the reference produces without td): the augmented factorisation on the matrix cores (k_mf_chol_tiles, 34 KB of LDS); wider kept blocks:
         // the column-by-column kernel.
-        const int lo = SB_ND + 1;
-        hipLaunchKernelGGL(k_mf_chol_tiles, grid, block, (size_t)(SB_NR * (SB_NR + 1) / 2 + 2 * 4 * 160 + 16) * sizeof(double), h->stream, h->batch, g, no_chol);
-        if (one_class) hipLaunchKernelGGL(k_mf_chol, grid, block, h->marg_lds_finish, h->stream, h->batch, g, lo, 1 << 30, no_chol);
-        else {
-            hipLaunchKernelGGL(k_mf_chol, grid, block, lds_small, h->stream, h->batch, g, lo, 78, no_chol);
-            hipLaunchKernelGGL(k_mf_chol, grid, block, h->marg_lds_finish, h->stream, h->batch, g, 78, 1 << 30, no_chol);
-        }
+        hipLaunchKernelGGL(k_mf_chol_tiles, grid, block, MFT_LDS_BYTES, h->stream, h->batch, g, no_chol);
+        by_class(k_mf_chol, 0, SB_ND + 1, no_chol);
     }
-    if (one_class) hipLaunchKernelGGL(k_mf_tridiag, grid, block, h->marg_lds_finish, h->stream, h->batch, g, 0, 1 << 30);
-    else {
-        hipLaunchKernelGGL(k_mf_tridiag, grid, block, lds_small, h->stream, h->batch, g, 0, 78);
-        hipLaunchKernelGGL(k_mf_tridiag, grid, block, h->marg_lds_finish, h->stream, h->batch, g, 78, 1 << 30);
-    }
-    hipLaunchKernelGGL(k_mf_ql, dim3((h->B + QL_LPW - 1) / QL_LPW), dim3(64), (size_t)2 * (MG_NK + 2) * QL_LPW * sizeof(double), h->stream, h->batch, g,
+    by_class(k_mf_tridiag, 0, 0);
+    hipLaunchKernelGGL(k_mf_ql, dim3((h->B + QL_LPW - 1) / QL_LPW), dim3(QL_NT), QL_LDS_BYTES, h->stream, h->batch, g,
                        std::getenv("VILF_MARG_FORCE_QL_FALLBACK") ? 1 : 0);        // test hook
-    if (one_class) {
-        hipLaunchKernelGGL(k_mf_apply, grid, block, h->marg_lds_finish + VILF_MFA_LDS_EXTRA, h->stream, h->batch, g, 0, 1 << 30);
-        hipLaunchKernelGGL(k_marg_finish, grid, block, h->marg_lds_finish, h->stream, h->batch, g, 0, 1 << 30, 1);
-    } else {
-        hipLaunchKernelGGL(k_mf_apply, grid, block, lds_small + VILF_MFA_LDS_EXTRA, h->stream, h->batch, g, 0, 78);
-        hipLaunchKernelGGL(k_mf_apply, grid, block, h->marg_lds_finish + VILF_MFA_LDS_EXTRA, h->stream, h->batch, g, 78, 1 << 30);
-        hipLaunchKernelGGL(k_marg_finish, grid, block, lds_small, h->stream, h->batch, g, 0, 78, 1);
-        hipLaunchKernelGGL(k_marg_finish, grid, block, h->marg_lds_finish, h->stream, h->batch, g, 78, 1 << 30, 1);
-    }
+    by_class(k_mf_apply, MFA_LDS_EXTRA_BYTES, 0);
+    by_class(k_marg_finish, 0, 0, 1);
     if (to_other_set) {
         hipLaunchKernelGGL(k_prior_keep, grid, block, 0, h->stream, h->batch, g);
         for (int k = 0; k < 6; k++) std::swap(h->d[live[k]], h->d[bak[k]]);
@@ -1210,7 +1153,7 @@ extern "C" int vilf_batch_marginalize(vilf_handle *h, int sync) {
         h->prior_backup_valid = true;           // the other set now holds the priors as uploaded
     }
     if (prof) mev[3] = vilf_prof_event(h);
-    hipLaunchKernelGGL(k_prior_prep, grid, block, VILF_PRIOR_PREP_LDS, h->stream, h->batch, h->d[D_PH].as<double>(), h->d[D_PG].as<double>(), (unsigned)VILF_PRIOR_PREP_LDS, (const int *)g.qlInfo);
+    hipLaunchKernelGGL(k_prior_prep, grid, block, PRIOR_PREP_LDS_BYTES, h->stream, h->batch, h->d[D_PH].as<double>(), h->d[D_PG].as<double>(), (unsigned)PRIOR_PREP_LDS_BYTES, (const int *)g.qlInfo);
     if (prof) mev[4] = vilf_prof_event(h);
     HIPCHECK(h, hipGetLastError());
     if (prof) {
@@ -1265,7 +1208,7 @@ extern "C" int vilf_eval_projection(vilf_handle *h, const double *const *p, cons
     std::memcpy(in + 21, pts_i, 24); std::memcpy(in + 24, pts_j, 24);
     double *d = h->d[D_HOOK].as<double>();
     HIPCHECK(h, hipMemcpyAsync(d, in, sizeof(in), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_hook_projection, dim3(1), dim3(64), 0, h->stream, d, d + 7, d + 14, p[3][0], d + 21, d + 24, h->opts.focal_length / 1.5, d + 32);
+    hipLaunchKernelGGL(k_hook_projection, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 7, d + 14, p[3][0], d + 21, d + 24, h->opts.focal_length / 1.5, d + 32);
     double out[28];
     HIPCHECK(h, hipMemcpyAsync(out, d + 32, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
@@ -1279,7 +1222,7 @@ extern "C" int vilf_eval_projection(vilf_handle *h, const double *const *p, cons
             std::memcpy(in2, in, 27 * 8);
             in2[31] = p[3][0]; in2[37] = 0.0; in2[38] = h->opts.focal_length / 1.5;
             HIPCHECK(h, hipMemcpyAsync(d + 64, in2, sizeof(in2), hipMemcpyHostToDevice, h->stream));
-            hipLaunchKernelGGL(k_hook_projection_td, dim3(1), dim3(64), 0, h->stream, d + 64, d + 64 + 40);
+            hipLaunchKernelGGL(k_hook_projection_td, dim3(1), dim3(HOOK_NT), 0, h->stream, d + 64, d + 64 + 40);
             double out2[42];
             HIPCHECK(h, hipMemcpyAsync(out2, d + 64 + 40, sizeof(out2), hipMemcpyDeviceToHost, h->stream));
             HIPCHECK(h, hipStreamSynchronize(h->stream));
@@ -1302,7 +1245,7 @@ extern "C" int vilf_eval_projection_td(vilf_handle *h, const double *const *p, c
     in[37] = h->opts.TR / ROW; in[38] = h->opts.focal_length / 1.5;
     double *d = h->d[D_HOOK].as<double>();
     HIPCHECK(h, hipMemcpyAsync(d, in, sizeof(in), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_hook_projection_td, dim3(1), dim3(64), 0, h->stream, d, d + 40);
+    hipLaunchKernelGGL(k_hook_projection_td, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 40);
     double out[42];
     HIPCHECK(h, hipMemcpyAsync(out, d + 40, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
@@ -1337,8 +1280,8 @@ extern "C" int vilf_eval_imu(vilf_handle *h, const double *const *p, const vilf_
     pack_imu_rec(pre, &in[40]);
     std::memcpy(&in[40 + IMU_REC], pre->covariance, 225 * 8);
     HIPCHECK(h, hipMemcpyAsync(d, in.data(), in.size() * 8, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_imu_prep, dim3(1), dim3(64), 0, h->stream, 1, d + 40 + IMU_REC, d + 1024, d + 40);
-    hipLaunchKernelGGL(k_hook_imu, dim3(1), dim3(64), 0, h->stream, d, d + 7, d + 16, d + 23, d + 40, d + 32, d + 2048, d + 3072);
+    hipLaunchKernelGGL(k_imu_prep, dim3(1), dim3(IMU_PREP_NT), 0, h->stream, 1, d + 40 + IMU_REC, d + 1024, d + 40);
+    hipLaunchKernelGGL(k_hook_imu, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 7, d + 16, d + 23, d + 40, d + 32, d + 2048, d + 3072);
     std::vector<double> out(15 + 450);
     HIPCHECK(h, hipMemcpyAsync(out.data(), d + 2048, out.size() * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
@@ -1363,8 +1306,8 @@ extern "C" int vilf_eval_imu_raw(vilf_handle *h, const double *const *p, const v
     pack_imu_rec(pre, &in[40]);
     std::memcpy(&in[40 + IMU_REC], pre->covariance, 225 * 8);
     HIPCHECK(h, hipMemcpyAsync(d, in.data(), in.size() * 8, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_imu_prep, dim3(1), dim3(64), 0, h->stream, 1, d + 40 + IMU_REC, d + 1024, d + 40);
-    hipLaunchKernelGGL(k_hook_imu, dim3(1), dim3(64), 0, h->stream, d, d + 7, d + 16, d + 23, d + 40, d + 32, d + 2048, d + 3072);
+    hipLaunchKernelGGL(k_imu_prep, dim3(1), dim3(IMU_PREP_NT), 0, h->stream, 1, d + 40 + IMU_REC, d + 1024, d + 40);
+    hipLaunchKernelGGL(k_hook_imu, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 7, d + 16, d + 23, d + 40, d + 32, d + 2048, d + 3072);
     std::vector<double> raw(450 + 15), S(225);
     HIPCHECK(h, hipMemcpyAsync(raw.data(), d + 3072, raw.size() * 8, hipMemcpyDeviceToHost, h->stream));       // scratch of k_hook_imu: J_raw [15 x 30], r_raw [15]
     HIPCHECK(h, hipMemcpyAsync(S.data(), d + 40 + IMU_SQRT, 225 * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1396,7 +1339,7 @@ extern "C" int vilf_eval_lidar_between(vilf_handle *h, const double *const *p, c
     for (int i = 0; i < 3; i++) in[25 + i] = c->t[i];
     double *d = h->d[D_HOOK].as<double>();
     HIPCHECK(h, hipMemcpyAsync(d, in, sizeof(in), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_hook_lidar, dim3(1), dim3(64), 0, h->stream, d, d + 7, d + 14, d + 18, d + 21, d + 32);
+    hipLaunchKernelGGL(k_hook_lidar, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 7, d + 14, d + 18, d + 21, d + 32);
     double out[78];
     HIPCHECK(h, hipMemcpyAsync(out, d + 32, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
@@ -1414,7 +1357,7 @@ extern "C" int vilf_eval_edge(vilf_handle *h, const double pose[7], const double
     std::memcpy(in, pose, 56); std::memcpy(in + 7, cp, 24); std::memcpy(in + 10, a, 24); std::memcpy(in + 13, bb, 24);
     double *d = h->d[D_HOOK].as<double>();
     HIPCHECK(h, hipMemcpyAsync(d, in, sizeof(in), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_hook_edge, dim3(1), dim3(64), 0, h->stream, d, d + 7, d + 10, d + 13, d + 16);
+    hipLaunchKernelGGL(k_hook_edge, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 7, d + 10, d + 13, d + 16);
     double out[21];
     HIPCHECK(h, hipMemcpyAsync(out, d + 16, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
@@ -1430,7 +1373,7 @@ extern "C" int vilf_eval_surf(vilf_handle *h, const double pose[7], const double
     std::memcpy(in, pose, 56); std::memcpy(in + 7, cp, 24); std::memcpy(in + 10, n, 24);
     double *d = h->d[D_HOOK].as<double>();
     HIPCHECK(h, hipMemcpyAsync(d, in, sizeof(in), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_hook_surf, dim3(1), dim3(64), 0, h->stream, d, d + 7, d + 10, dd, d + 16);
+    hipLaunchKernelGGL(k_hook_surf, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 7, d + 10, dd, d + 16);
     double out[7];
     HIPCHECK(h, hipMemcpyAsync(out, d + 16, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
@@ -1446,7 +1389,7 @@ static int plus_hook(vilf_handle *h, const double x[7], const double dl[6], doub
     std::memcpy(in, x, 56); std::memcpy(in + 7, dl, 48);
     double *d = h->d[D_HOOK].as<double>();
     HIPCHECK(h, hipMemcpyAsync(d, in, sizeof(in), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_hook_plus, dim3(1), dim3(64), 0, h->stream, d, d + 7, kind, d + 16);
+    hipLaunchKernelGGL(k_hook_plus, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 7, kind, d + 16);
     HIPCHECK(h, hipMemcpyAsync(xp, d + 16, 56, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
     return VILF_OK;
@@ -1454,7 +1397,6 @@ static int plus_hook(vilf_handle *h, const double x[7], const double dl[6], doub
 extern "C" int vilf_pose_plus(vilf_handle *h, const double x[7], const double d[6], double xp[7]) { return plus_hook(h, x, d, xp, 0); }
 extern "C" int vilf_se3_plus(vilf_handle *h, const double x[7], const double d[6], double xp[7]) { return plus_hook(h, x, d, xp, 1); }
 
-extern "C" __global__ void k_hook_prior(const int *hdr, const double *x0, const double *x, const double *J0, const double *r0, double *out);
 extern "C" int vilf_eval_prior(vilf_handle *h, const vilf_prior *p, const double *const *params, double *residuals, double **jac) {
     if (!h || !p || !params || !residuals || !p->valid || p->n < 1 || p->n > VILF_PRIOR_MAX_DIM || p->n_blocks < 1 || p->n_blocks > VILF_PRIOR_MAX_BLOCKS) return VILF_ERR_INVALID_ARGUMENT;
     const int n = p->n, nb = p->n_blocks;
@@ -1473,7 +1415,7 @@ extern "C" int vilf_eval_prior(vilf_handle *h, const vilf_prior *p, const double
     double *d = h->d[D_HOOK].as<double>();
     HIPCHECK(h, hipMemcpyAsync(d, in.data(), in.size() * 8, hipMemcpyHostToDevice, h->stream));
     double *d_out = d + in.size();
-    hipLaunchKernelGGL(k_hook_prior, dim3(1), dim3(256), 0, h->stream, reinterpret_cast<const int *>(d), d + 32, d + 32 + 216, d + 32 + 432, d + 32 + 432 + (size_t)n * n, d_out);
+    hipLaunchKernelGGL(k_hook_prior, dim3(1), dim3(HOOK_PRIOR_NT), 0, h->stream, reinterpret_cast<const int *>(d), d + 32, d + 32 + 216, d + 32 + 432, d + 32 + 432 + (size_t)n * n, d_out);
     HIPCHECK(h, hipMemcpyAsync(residuals, d_out, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
     if (jac)                                                   // jacobians[i] = J0[:, idx : idx + local] in global size (pose: 7th column 0), :364-376

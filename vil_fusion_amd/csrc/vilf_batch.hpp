@@ -41,6 +41,8 @@
 #define VB_NPAD 176
 #define VB_PRIOR_HDR 80     // valid, n, nblocks, ids[24], sizes[24], idx[24]
 #define VB_PRIOR_LD 160
+#define IMU_REC 288         // doubles per IMU factor record (layout: vilf_device.hpp, IMUFactor raw part)
+#define IMU_SQRT 62         // sqrt_info (15 x 15) inside the record
 
 // ---- k_solve_sb: speed-bias-first elimination (vilf_kernels.hip) -------------------------------------------------------
 // After the feature Schur complement the speed-bias part of the reduced system is block tridiagonal (an IMU factor couples consecutive frames only,
@@ -88,7 +90,7 @@ struct VbState {            // per-window trust-region state (ceres TrustRegionM
 
 // ---- marginalization workspace (vilf_marg.hip) ---------------------------------------------------------------------
 #define MG_RWP 113          // staged row length: 7 tiles of 16 columns (+ 1: odd stride, no bank conflicts between the four k of an operand read)
-#define MG_FCH 16           // arrow rows staged per chunk in the fast path of k_marg_schur (16 x 118 doubles of LDS)
+#define MG_FCH 16           // arrow rows staged per chunk in the fast path of k_marg_schur (16 x MG_RWP doubles of LDS)
 #define MG_MD 21            // dropped non-feature variables: Pose[0] 6 + Pose[1] 6 (USE_LIDAR_CONST, estimator.cpp:891) + SpeedBias[0] 9
 #define MG_NK 96            // kept (prior) dimension capacity; the reference's prior never exceeds 75 + td
 #define MG_ND (MG_MD + MG_NK)

@@ -431,8 +431,7 @@ VD void lidar_between_eval(const double *posei, const double *posej, const Q &qi
 // ---- IMUFactor raw part (imu_factor.h:19-179): residual and jacobians BEFORE the sqrt_info multiplication --------
 // imu record layout (288 doubles): [0] sum_dt, [1..3] dp, [4..7] dq(xyzw), [8..10] dv, [11..13] lin_ba, [14..16] lin_bg,
 // [17..25] dp_dba, [26..34] dp_dbg, [35..43] dq_dbg, [44..52] dv_dba, [53..61] dv_dbg, [62..286] sqrt_info 15x15, [287] valid
-#define IMU_REC 288
-#define IMU_SQRT 62
+// (IMU_REC = 288, IMU_SQRT = 62: vilf_batch.hpp)
 // Jraw: 15 x LD row-major (LD >= 30), columns [pose_i 6 | sb_i 9 | pose_j 6 | sb_j 9]; ZERO: clear the 15 x 30 block first
 template <bool JAC, int LD = 30, bool ZERO = true>
 VD void imu_raw_eval(const double *posei, const double *sbi, const double *posej, const double *sbj, const double *rec, const double *G,

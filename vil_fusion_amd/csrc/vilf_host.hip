@@ -8,6 +8,7 @@
 #include <cstring>
 #include <cmath>
 #include "vilf_internal.hpp"
+#include "vilf_kernels.hpp"
 
 #define VPI __host__ __device__ inline
 namespace {
@@ -137,7 +138,7 @@ extern "C" int vilf_imu_preintegrate_batch(vilf_handle *h, int n, const vilf_imu
     HIPCHECK(h, up(off_dt, dt, 8 * (size_t)n * max_samples)); HIPCHECK(h, up(off_acc, acc, 24 * (size_t)n * max_samples)); HIPCHECK(h, up(off_gyr, gyr, 24 * (size_t)n * max_samples));
     HIPCHECK(h, up(off_ns, n_samples, 4 * sn));
     vilf_imu_preint *d_out = reinterpret_cast<vilf_imu_preint *>(d + in_doubles);
-    hipLaunchKernelGGL(k_preintegrate, dim3((n + 63) / 64), dim3(64), 0, h->stream, n, *nz, d + off_a0, d + off_g0, d + off_ba, d + off_bg, reinterpret_cast<const int *>(d + off_ns), max_samples,
+    hipLaunchKernelGGL(k_preintegrate, dim3((n + PREINT_NT - 1) / PREINT_NT), dim3(PREINT_NT), 0, h->stream, n, *nz, d + off_a0, d + off_g0, d + off_ba, d + off_bg, reinterpret_cast<const int *>(d + off_ns), max_samples,
                        d + off_dt, d + off_acc, d + off_gyr, d_out);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipMemcpyAsync(out, d_out, sn * sizeof(vilf_imu_preint), hipMemcpyDeviceToHost, h->stream));

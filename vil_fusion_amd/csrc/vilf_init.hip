@@ -13,10 +13,8 @@
 #include <algorithm>
 #include <cmath>
 #include "vilf_internal.hpp"
+#include "vilf_kernels.hpp"
 #include "vilf_device.hpp"
-
-__global__ void k_preintegrate(int n, vilf_imu_noise nz, const double *acc0, const double *gyr0, const double *ba, const double *bg, const int *n_samples, int max_samples,
-                               const double *dt, const double *acc, const double *gyr, vilf_imu_preint *out);
 
 namespace {
 using namespace vd;
@@ -327,9 +325,9 @@ extern "C" int vilf_visual_imu_alignment(vilf_handle *h, int n, const double *fr
     for (int i = 0; i < 3; i++) a.TIC[i] = h->opts.TIC[i];
     a.Gnorm = std::sqrt(h->opts.G[0] * h->opts.G[0] + h->opts.G[1] * h->opts.G[1] + h->opts.G[2] * h->opts.G[2]);
     a.gy = d + o_gy; a.ba2 = d + o_ba2; a.bg2 = d + o_bg2; a.T = d + o_Tb; a.RA = d + o_RA; a.A = d + o_A; a.b = d + o_b; a.Wg = d + o_W; a.out = d + o_out;
-    hipLaunchKernelGGL(k_preintegrate, dim3((m + 63) / 64), dim3(64), 0, h->stream, m, *nz, d + o_a0, d + o_g0, d + o_ba, d + o_bg, d_ns, max_samples, d + o_dt, d + o_acc, d + o_gyr, d_pre);
+    hipLaunchKernelGGL(k_preintegrate, dim3((m + PREINT_NT - 1) / PREINT_NT), dim3(PREINT_NT), 0, h->stream, m, *nz, d + o_a0, d + o_g0, d + o_ba, d + o_bg, d_ns, max_samples, d + o_dt, d + o_acc, d + o_gyr, d_pre);
     hipLaunchKernelGGL(k_align_gyro, dim3(1), dim3(64), 0, h->stream, a);
-    hipLaunchKernelGGL(k_preintegrate, dim3((m + 63) / 64), dim3(64), 0, h->stream, m, *nz, d + o_a0, d + o_g0, d + o_ba2, d + o_bg2, d_ns, max_samples, d + o_dt, d + o_acc, d + o_gyr, d_pre);
+    hipLaunchKernelGGL(k_preintegrate, dim3((m + PREINT_NT - 1) / PREINT_NT), dim3(PREINT_NT), 0, h->stream, m, *nz, d + o_a0, d + o_g0, d + o_ba2, d + o_bg2, d_ns, max_samples, d + o_dt, d + o_acc, d + o_gyr, d_pre);
     const size_t small = (3 * ns) * 8 + 32 + 12 * 8;
     if (n <= AL_LDS_FRAMES) {
         const size_t lds = small + ns * (ns | 1) * 8;

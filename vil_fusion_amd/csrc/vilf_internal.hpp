@@ -89,7 +89,6 @@ struct vilf_handle {
     bool prior_restore_needed = false;       // a marginalization has overwritten the device priors since that backup
     int mg_Mcap = 0;
     VbMarg marg;
-    size_t marg_lds_schur = 0, marg_lds_finish = 0;
     std::vector<int> h_nfeat, h_nframes;
     std::vector<double> h_ex, h_td;
     std::vector<OwnedWindow> own;            // only with estimate_extrinsic / estimate_td
@@ -115,7 +114,6 @@ struct vilf_handle {
     std::vector<WindowPlan> plans;
     double last_solve_usec = 0;
     bool solve_time_pending = false;         // the last solve was enqueued with sync == 0: ev0 / ev1 are read by the next call that waits for the stream
-    size_t solve_lds = 0, lin_lds = 0, solve_sb_lds = 0;
     int split_gen = 0;      // generation counter of the k_linearize_split launches of this handle
     bool solve_dense_fallback = false;       // a prior imported from the host holds a speed-bias block other than SpeedBias[0]: k_solve (dense) instead of k_solve_sb
     FeatCtx *feat = nullptr;                 // LiDAR feature extraction workspace (vilf_feat.hip)

@@ -15,7 +15,7 @@
 //
 // All arithmetic is fp64 (the reference is double throughout). MFMA: v_mfma_f64_16x16x4_f64.
 #include "vilf_device.hpp"
-#include "vilf_batch.hpp"
+#include "vilf_kernels.hpp"
 
 using namespace vd;
 
@@ -23,7 +23,6 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
 #define NT VB_NT
-#define VILF_MAX_FEATURES_DEV 1000
 // In-kernel phase stamps are a diagnostic build only (make DEFS=-DVILF_STAMPS): the production kernels carry no clock reads.
 #ifdef VILF_STAMPS
 #define STAMP(kid, i) do { if (b.dbg && blockIdx.x == 0 && threadIdx.x == 0) b.dbg[(kid) * 32 + (i)] = __builtin_readcyclecounter(); } while (0)
@@ -77,7 +76,7 @@ __device__ __forceinline__ double block_max(double v, double *s_red) {
 // cov: [n][225] in, out: rec + IMU_SQRT of each factor: sqrt_info = LLT(cov^-1).L^T (imu_factor.h:64), once per upload.
 // 16 lanes per factor (lane = matrix row, 4 factors per 64-thread block), matrices in LDS; every element sees the same sequence
 // of operations as the row-serial algorithm (Gauss-Jordan with partial pivoting = Eigen PartialPivLU inverse, left-looking LLT).
-extern "C" __global__ __launch_bounds__(64) void k_imu_prep(int n, const double *cov, double *work, double *imu_rec) {
+extern "C" __global__ __launch_bounds__(IMU_PREP_NT) void k_imu_prep(int n, const double *cov, double *work, double *imu_rec) {
     __shared__ double sA[4][15][16], sI[4][15][16], s_piv[4];
     const int grp = threadIdx.x >> 4, r = threadIdx.x & 15, id = blockIdx.x * 4 + grp;
     const bool row = id < n && r < 15;
@@ -1098,7 +1097,6 @@ __device__ __forceinline__ void tile_add(double *s_T, int r, int c, double v) {
     if (tr >= tc) s_T[tile_index(tr, tc) * 256 + TIX(r & 15, c & 15)] += v;
 }
 
-#define SNT 512
 #define SNW (SNT / 64)
 // wave butterflies, then the eight wave sums added in wave order by every thread: three barriers instead of eleven (k_solve owns its CU:
 // nothing hides a barrier chain), fixed summation order
@@ -1122,7 +1120,6 @@ __device__ __forceinline__ double block_sum_s(double v, double *s_red) {
 // indices are compile-time, so operands are plain register picks. Loads are unconditional, coalesced (zero-padded 80-wide rows,
 // rows >= F are zero) and prefetched three k-steps ahead with no arithmetic on them until they are consumed. Group results are
 // subtracted in fixed group order (bit-reproducible).
-#define SOLVE_RED_OFF (66 * 256 + 6 * VB_NPAD)   // LDS layout of k_solve: 66 tiles, then g, diag, scale, y, invd, v (VB_NPAD each), then s_red
 template <int HALF>
 __device__ __forceinline__ void schur_mfma(const double *W, int F, const double *s_cf, const double *s_scale, double *s_T, double *s_y, int lane, int wave) {
     constexpr int TA[15] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 4};
@@ -1130,7 +1127,7 @@ __device__ __forceinline__ void schur_mfma(const double *W, int F, const double 
     constexpr int NP = HALF ? 7 : 8, PB = HALF ? 8 : 0;
     const int c16 = lane & 15, grp = wave >> 1, g4 = lane >> 4;
     const int nsteps = ((F + 3) & ~3) / 4;
-    double *s_t = s_T + SOLVE_RED_OFF;            // s_red of k_solve (free between its block sums): row 67 of the reduce
+    double *s_t = s_T + SOLVE_OFF_RED;            // s_red of k_solve (free between its block sums): row 67 of the reduce
     double sc5[5];
 #pragma unroll
     for (int t5 = 0; t5 < 5; t5++) { const int col = 16 * t5 + c16; sc5[t5] = (col < VB_NPOSE) ? s_scale[col] : (col <= VB_NPOSE + 1 ? 1.0 : 0.0); }       // 66: rhs, 67: the Cauchy-point column (see k_solve)
@@ -1240,16 +1237,10 @@ extern "C" __global__ __launch_bounds__(SNT) void k_solve(VbBatch b) {
     if (w < 0) return;
     VbState *st = b.st + w;
     extern __shared__ double s_dyn[];
-    double *s_T = s_dyn;                      // 66 tiles * 256
-    double *s_g = s_T + 66 * 256;             // g~ (permuted, padded to 176)
-    double *s_diag = s_g + VB_NPAD;
-    double *s_scale = s_diag + VB_NPAD;
-    double *s_y = s_scale + VB_NPAD;          // rhs -> solution
-    double *s_invd = s_y + VB_NPAD;           // 1 / L_jj
-    double *s_v = s_invd + VB_NPAD;           // v = g~ ./ diagonal_^2
-    double *s_red = s_v + VB_NPAD;            // NT
-    double *s_cf = s_red + SNT;                // per feature: s_f / sqrt(h~')   (0 for constant features)   [<= 1000]
-    int *s_rng = (int *)(s_cf + VILF_MAX_FEATURES_DEV);   // per feature: 6*start | (6*(start+nobs)) << 16
+    double *s_T = s_dyn + SOLVE_OFF_T, *s_g = s_dyn + SOLVE_OFF_G, *s_diag = s_dyn + SOLVE_OFF_DIAG, *s_scale = s_dyn + SOLVE_OFF_SCALE;   // layout: vilf_kernels.hpp
+    double *s_y = s_dyn + SOLVE_OFF_Y, *s_invd = s_dyn + SOLVE_OFF_INVD, *s_v = s_dyn + SOLVE_OFF_V, *s_red = s_dyn + SOLVE_OFF_RED;
+    double *s_cf = s_dyn + SOLVE_OFF_CF;      // 0 for constant features
+    int *s_rng = (int *)(s_dyn + SOLVE_OFF_RNG);
     __shared__ int s_pcol[VB_P], s_pinv[VB_PRIOR_LD];
     __shared__ double s_dx[VB_PRIOR_LD];
     __shared__ int s_flag[4];
@@ -1648,7 +1639,6 @@ __device__ __forceinline__ double sb_bload(__amdgpu_buffer_rsrc_t r, int elem) {
     const uint2_t v = __builtin_amdgcn_raw_buffer_load_b64(r, elem < 0 ? 0x7ffffff0u : 8u * (unsigned)elem, 0, 0);
     return __hiloint2double((int)v.y, (int)v.x);
 }
-#define SBT 256
 #define SBW (SBT / 64)
 __device__ __forceinline__ double block_sum_sb(double v, double *s_red) {
     const int tid = threadIdx.x;
@@ -1845,9 +1835,8 @@ __device__ __forceinline__ bool sb_potrf9(double *Dp, double *linv, int lane) {
 // waves 0..2, A part: 4 x (meta, Hpp, imu0, imu1, lid0, lid1), 9 x (meta, Hpp) in rows 0..10; B part: 4 x (meta, imu), 13 x (meta, imu0, imu1) in rows 11..22;
 // wave 3 (its 64 lanes at threads 192..255): 13 x (meta, imu0, imu1), 12 x (meta, imu) in rows 0..15. meta = LDS offset | r << 14 | c << 22, bit 31 = "no such entry"
 // (r, c stay valid: the prior's column lookup is issued for every entry); a source index of -1 = absent (the buffer load returns zero).
-#define SB_TAB_ROWS 23
 #define SB_META(off, r, c, on) (((off) & 0x3fff) | ((r) << 14) | ((c) << 22) | ((on) ? 0 : (int)0x80000000))
-extern "C" __global__ __launch_bounds__(256) void k_sb_table(int *tab) {
+extern "C" __global__ __launch_bounds__(SBT) void k_sb_table(int *tab) {
     const int tid = threadIdx.x, td = tid, ln = tid & 63;
     int t[SB_TAB_ROWS * 4];
     for (int k = 0; k < SB_TAB_ROWS * 4; k++) t[k] = -1;

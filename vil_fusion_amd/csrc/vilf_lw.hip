@@ -43,9 +43,8 @@
 #include <atomic>
 #include <mutex>
 #include "vilf_internal.hpp"
+#include "vilf_kernels.hpp"
 #include "vilf_device.hpp"
-
-extern "C" __global__ void k_imu_prep(int n, const double *cov, double *work, double *imu_rec);
 
 struct LwVis { double pi[3], pj[3]; int f, i, j, cst; };     // one ProjectionFactor: feature, start frame, observing frame
 struct LwTd { double vi[2], vj[2], tdi, tdj, rowi_c, rowj_c; };     // ProjectionTdFactor constants (projection_td_factor.cpp:6-21)
@@ -2198,7 +2197,7 @@ int vilf_lw_group_solve(vilf_handle *h, int G, const vilf_window_in *const *ins,
     HIPCHECK(h, hipMemcpyAsync(dev, st, n_input, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(h, hipMemcpyAsync(c->desc.p, dws.data(), (size_t)G * sizeof(LwWin), hipMemcpyHostToDevice, h->stream));
     const LwWin *dws_dev = c->desc.as<LwWin>();
-    hipLaunchKernelGGL(k_imu_prep, dim3((unsigned)((tot_imu + 3) / 4)), dim3(64), 0, h->stream, (int)tot_imu, reinterpret_cast<const double *>(dev + o_cov), (double *)nullptr, reinterpret_cast<double *>(dev + o_imu));
+    hipLaunchKernelGGL(k_imu_prep, dim3((unsigned)((tot_imu + 3) / 4)), dim3(IMU_PREP_NT), 0, h->stream, (int)tot_imu, reinterpret_cast<const double *>(dev + o_cov), (double *)nullptr, reinterpret_cast<double *>(dev + o_imu));
 
     int rc = VILF_OK;
     const int max_it = h->opts.max_num_iterations;

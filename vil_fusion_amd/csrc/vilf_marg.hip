@@ -14,11 +14,10 @@
 // Block ordering: dropped blocks then kept blocks, both ascending in block id (the reference iterates address-keyed
 // unordered_maps; any order is a permutation of the same result — SURVEY.md §7 "address-keyed bookkeeping").
 #include "vilf_device.hpp"
-#include "vilf_batch.hpp"
+#include "vilf_kernels.hpp"
 
 using namespace vd;
 #define NT VB_NT
-#define VILF_MAX_FEATURES_DEV 1000
 __device__ __forceinline__ int pair_index_c(int i, int j) { return j * (j - 1) / 2 + i; }  // i < j
 
 __device__ __forceinline__ void rr_pair(int round, int k, int M, int &p, int &q) {   // round-robin tournament pairing
@@ -623,8 +622,7 @@ __device__ __forceinline__ void marg_prepare_body(const VbBatch &b, const VbMarg
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-#define MG_LDS_DOUBLES (MG_MLDS * MG_MLDS)
-// launched twice: exact == 0 runs the arrow fast path in ~30 KB of LDS (five workgroups per CU) and flags the windows whose guard
+// launched twice: exact == 0 runs the arrow fast path in 44 KB of LDS (three workgroups per CU) and flags the windows whose guard
 // fails (info[7] = 1); exact == 1 runs the Jacobi path, with the full-size LDS allocation, for the flagged windows only.
 extern "C" __global__ __launch_bounds__(NT, 2) void k_marg_prepare(VbBatch b, VbMarg g) { marg_prepare_body<false>(b, g); }
 extern "C" __global__ __launch_bounds__(NT) void k_marg_prepare_td(VbBatch b, VbMarg g) { marg_prepare_body<true>(b, g); }
@@ -667,7 +665,7 @@ extern "C" __global__ __launch_bounds__(NT, 3) void k_marg_schur(VbBatch b, VbMa
     // Guard: D > 0, S > 0 (Cholesky pivots) and trace(Amm^-1) < 1e8 (the trace bounds the largest eigenvalue of the inverse, i.e.
     // lambda_min(Amm) > 1e-8: nothing would be truncated). Otherwise fall through to the Jacobi path below.
     if (!exact) {
-        double *s_S = s_dyn, *s_Y = s_S + MG_MD * MG_MD, *s_ih = s_Y + MG_MD * (MG_NK + 1), *s_red = s_ih + VILF_MAX_FEATURES_DEV;   // [md][md], [md][XL], [mf], [NT]
+        double *s_S = s_dyn + MGS_OFF_S, *s_Y = s_dyn + MGS_OFF_Y, *s_ih = s_dyn + MGS_OFF_IH, *s_red = s_dyn + MGS_OFF_RED;   // [md][md], [md][XL], [mf], [NT] (vilf_kernels.hpp)
         __shared__ int s_ok;
         __shared__ double s_linv[MG_MD + 3];                       // 1 / L_jj of the arrow Cholesky
         MG_STAMP(2, 0);
@@ -688,7 +686,7 @@ extern "C" __global__ __launch_bounds__(NT, 3) void k_marg_schur(VbBatch b, VbMa
             T[t] = mg_double4{0.0, 0.0, 0.0, 0.0};
         }
         const int RW = md + n + 1, lane = tid & 63, l16 = lane & 15, l4 = lane >> 4;
-        double *s_w = s_red + NT;                                   // [MG_FCH][MG_RWP]
+        double *s_w = s_dyn + MGS_OFF_W;                             // [MG_FCH][MG_RWP]
         // (round 5) the rows of chunk t + 1 are requested before the products of chunk t and go to LDS behind them; the loop's barriers order LDS only. Until then
         // every chunk of sixteen rows was a full memory round trip in front of 28 MFMAs: fifteen trips per window, the larger part of the launch.
         constexpr int NLD = (MG_FCH * MG_RWP + NT - 1) / NT;
@@ -910,7 +908,7 @@ extern "C" __global__ __launch_bounds__(NT, 3) void k_marg_schur(VbBatch b, VbMa
     for (int i = tid; i < M; i += NT) lam[i] = A[i * M + i];
     __syncthreads();
     // replay the rotations on X (X' = V^T X); X lives in LDS when it fits
-    double *X = (M * XL <= MG_LDS_DOUBLES) ? s_dyn : Xg;
+    double *X = (M * XL <= MGS_EXACT_LDS_DOUBLES) ? s_dyn : Xg;
     if (X != Xg) { for (int e = tid; e < M * XL; e += NT) X[e] = Xg[e]; }
     __syncthreads();
     for (int sw = 0; sw < sweeps; sw++)
@@ -1323,9 +1321,7 @@ extern "C" __global__ __launch_bounds__(NT) void k_mf_chol(VbBatch b, VbMarg g, 
 // identity rows 80 + c as row c of L^-T — their squares are summed where the row threads produce them: |L^-1|_F^2 without ever storing L^-1. n < 75 is padded with an
 // identity block (pivots 1, no coupling). Same guard, same outputs as k_mf_chol (J0 = L^T, r0, H0 = A, g0 = b, block table); a window that fails the guard is left to the
 // eigen-solver launches exactly as before. ~34 KB of LDS: four workgroups per CU.
-#define MFT_ROWS 160                                      // 80 (A, b, padding) + 80 (identity rows, padding)
 #define MFT_NT10 10                                       // tiles per wave: 40 = 15 (rows 0..79, lower) + 25 (rows 80..159, all five column tiles)
-#define MFT_LDS_DOUBLES (SB_NR * (SB_NR + 1) / 2 + 2 * 4 * MFT_ROWS + 16)
 extern "C" __global__ __launch_bounds__(NT, 2) void k_mf_chol_tiles(VbBatch b, VbMarg g, int disable) {
     const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int *info = g.info + (size_t)w * MG_INFO;
@@ -1334,7 +1330,7 @@ extern "C" __global__ __launch_bounds__(NT, 2) void k_mf_chol_tiles(VbBatch b, V
     if (info[3] > SB_ND) return;                                  // wider kept blocks: k_mf_chol
     if (disable) { if (tid == 0) qi[3] = 0; return; }             // test hook: every window through the eigen-solver
     extern __shared__ double s_dyn[];
-    double *s_P = s_dyn, *s_pan = s_P + SB_NR * (SB_NR + 1) / 2, *s_lp = s_pan + 4 * MFT_ROWS;      // packed lower rows 0..75; the panel's columns [row][4]; the panel's factor rows [row][4]
+    double *s_P = s_dyn + MFT_OFF_P, *s_pan = s_dyn + MFT_OFF_PAN, *s_lp = s_dyn + MFT_OFF_LP;      // packed lower rows 0..75; the panel's columns [row][4]; the panel's factor rows [row][4]
     __shared__ double s_red[NT / 64];
     __shared__ int s_ok;
     const int n = info[3], nb = info[5];
@@ -1512,7 +1508,7 @@ extern "C" __global__ __launch_bounds__(NT) void k_mf_tridiag(VbBatch b, VbMarg 
     if (tid < n) { dg[tid] = s_lam[tid]; dg[MG_NK + 2 + tid] = s_e[tid]; }
 }
 // one lane per window; d / e live in LDS as [i][lane]
-extern "C" __global__ __launch_bounds__(64) void k_mf_ql(VbBatch b, VbMarg g, int force_overflow) {
+extern "C" __global__ __launch_bounds__(QL_NT) void k_mf_ql(VbBatch b, VbMarg g, int force_overflow) {
     extern __shared__ double s_de[];
     // QL_LPW windows per wave: the recurrence is one serial chain per window and lanes in different sweeps diverge (the wave pays the longest
     // sweep of its lanes every time), so fewer windows per wave on more CUs is faster than full waves on a quarter of the chip
@@ -1523,7 +1519,7 @@ extern "C" __global__ __launch_bounds__(64) void k_mf_ql(VbBatch b, VbMarg g, in
     qi[0] = 0; qi[1] = 0; qi[2] = 0;
     if (info[0] != 0 || qi[3]) return;
     const int n = info[3];
-    double *d = s_de + lane, *e = s_de + (MG_NK + 2) * QL_LPW + lane;      // element i at [QL_LPW * i]: 6 KB of LDS per wave, several waves per CU
+    double *d = s_de + QL_OFF_D + lane, *e = s_de + QL_OFF_E + lane;      // element i at [QL_LPW * i]: QL_LDS_BYTES (24.5 KB) per wave, several waves per CU
     double *dg = g.qlD + (size_t)w * 2 * (MG_NK + 2);
     for (int i = 0; i < n; i++) { d[QL_LPW * i] = dg[i]; e[QL_LPW * i] = dg[MG_NK + 2 + i]; }
     double *lg = g.qlLog + (size_t)w * 2 * QL_RCAP;
@@ -1604,7 +1600,6 @@ extern "C" __global__ __launch_bounds__(64) void k_mf_ql(VbBatch b, VbMarg g, in
     for (int i = 0; i < n; i++) dg[i] = d[QL_LPW * i];                          // eigenvalues
     qi[0] = ni; qi[1] = nr; qi[2] = over ? 1 : 0;
 }
-#define MFA_CH 64            // rotations per staged chunk of k_mf_apply (two buffers of 1 KB)
 extern "C" __global__ __launch_bounds__(NT) void k_mf_apply(VbBatch b, VbMarg g, int n_lo, int n_hi) {
     const int w = blockIdx.x, tid = threadIdx.x;
     const int *info = g.info + (size_t)w * MG_INFO;
