@@ -348,6 +348,61 @@ typedef struct vilf_pg_edge {
 int vilf_posegraph_optimize(vilf_handle *h, int n_nodes, double *poses_qt /*[n][7] in/out*/, const double prior_sigma[6], int n_edges, const vilf_pg_edge *edges,
                             int max_iterations, double tol, int *iterations_out, double *final_cost);
 
+/* ---- Scan Context loop detection of global_fusion (≙ SCManager, global_fusion/include/Scancontext/Scancontext.h; device) ----
+ * A database of key-frame descriptors that lives on the device (sized at creation, one per handle) and the search over it:
+ *   descriptor   makeScancontext :42-86 + xy2theta common.h:79-92: 20 rings x 60 sectors, bin = max(z + lidar_height) as float, stored as double, empty bin 0.
+ *                Point arithmetic is float like the reference's (range = sqrtf of separately rounded products; the angle from a correctly rounded
+ *                atanf = fp64 atan of the float quotient rounded to float, scaled in double, rounded to float; ceil in double, clamped to [1, 20] / [1, 60]).
+ *                Points with a non-finite x, y or z, and points with x == 0 && y == 0, are undefined behaviour in the reference (int(ceil(NaN))): they are skipped.
+ *   keys         ring key :89-103 = row means (summed in column order, fp64, / 60, cast to float like eig2stdvec); sector key :105-119 = column means (fp64)
+ *   detection    detectLoopClosureID :210-300: nothing while fewer than num_exclude_recent + 1 descriptors exist; the searchable set is a snapshot
+ *                [0, n - num_exclude_recent) taken when the call counter is a multiple of tree_making_period and reused for the following calls; the
+ *                num_candidates snapshot entries nearest to the query's ring key (float squared L2, dimensions summed in order; nanoflann's search is exact, so
+ *                the brute-force set is the same; exact ties go to the lower index, where nanoflann's order would depend on its tree), fewer if the snapshot is smaller
+ *   distance     distanceBtnScanContext :153-190: first shift = argmin over 60 shifts of |sector-key difference| (first minimum wins), searched shifts = that one
+ *                +- round(0.5 * search_ratio * 60) in ascending order, first minimum wins; distance at a shift (distDirectSC :127-151) = 1 - mean over the columns
+ *                where both norms are non-zero of the cosine; no such column: NaN, which never wins. circshift moves column c to (c + s) % 60.
+ * Exhaustive mode (not in the reference; equation 6 of the Scan Context paper): num_candidates = 0 takes every snapshot entry (candidate order = index order),
+ * search_ratio = 1 every shift. vilf_reset leaves the database alone; vilf_sc_create resets it. */
+typedef struct vilf_sc_params {
+    int num_rings, num_sectors;      /* PC_NUM_RING 20, PC_NUM_SECTOR 60 (:308-309): the only shape the kernels are built for, anything else is VILF_ERR_UNSUPPORTED */
+    double max_radius;               /* PC_MAX_RADIUS 80 (:311, setMaximumRadius :301) */
+    double lidar_height;             /* LIDAR_HEIGHT 2.0 (:306) */
+    int num_exclude_recent;          /* NUM_EXCLUDE_RECENT 30 (:316) */
+    int num_candidates;              /* NUM_CANDIDATES_FROM_TREE 3 (:317), at most 16; 0 = every snapshot entry */
+    double search_ratio;             /* SEARCH_RATIO 0.1 (:320); 1 = all shifts */
+    double dist_thres;               /* SC_DIST_THRES 0.2 (:322, setSCdistThres :296) */
+    int tree_making_period;          /* TREE_MAKING_PERIOD_ 30 (:325) */
+    int pad_;
+} vilf_sc_params;
+void vilf_sc_default_params(vilf_sc_params *p);
+typedef struct vilf_sc_result {
+    int loop_id;                     /* nearest if min_dist < dist_thres, else -1 (:275-285) */
+    int nearest;                     /* nn_idx (what the reference prints); -1 for a query that returned early (:221-225) */
+    int shift;                       /* nn_align */
+    int n_candidates;                /* candidates searched (exhaustive mode: the snapshot size) */
+    double min_dist;                 /* 10000000 (the reference's initial value) when no candidate had a distance */
+    float yaw_diff_rad;              /* float(deg2rad(shift * 6.0)) :288 */
+    int candidates[16];              /* the first min(n_candidates, 16) candidate indices in search order, the rest -1 */
+} vilf_sc_result;
+/* a database for `capacity` key frames (an existing one of the handle is dropped, the call counter and the snapshot with it) */
+int vilf_sc_create(vilf_handle *h, const vilf_sc_params *p, int capacity);
+/* makeAndSaveScancontextAndKeys (:193-204; poseGraphOptimization.cpp:553): xyzi [n_points][4] -> descriptor + keys of key frame *index_out.
+ * A full database is VILF_ERR_UNSUPPORTED and leaves it as it was. */
+int vilf_sc_add_keyframe(vilf_handle *h, const float *xyzi, int n_points, int *index_out);
+/* the same for n clouds in one upload and one launch: cloud i = points [offsets[i], offsets[i + 1]) of xyzi */
+int vilf_sc_add_keyframes(vilf_handle *h, int n, const float *xyzi, const int *offsets /*[n + 1]*/, int *first_index_out);
+/* detectLoopClosureID (:210-300; performSCLoopDetection, poseGraphOptimization.cpp:598-614) for the newest key frame; counts the calls that get past the early return */
+int vilf_sc_detect(vilf_handle *h, vilf_sc_result *out);
+/* replay: out[i] = what vilf_sc_detect returned, or would have, right after key frame first + i was added, had it been called once per key frame from an empty
+ * database (query k >= num_exclude_recent is call c = k - num_exclude_recent, its snapshot [0, period * (c / period) + 1)). One chain of launches for all queries;
+ * does not touch the call counter of vilf_sc_detect. */
+int vilf_sc_detect_range(vilf_handle *h, int first, int n, vilf_sc_result *out);
+int vilf_sc_get(vilf_handle *h, int index, double desc[1200] /*[20][60]*/, float ring_key[20], double sector_key[60]);
+int vilf_sc_size(vilf_handle *h, int *n_out);
+/* vilf_set_profiling: sc_descriptor, sc_ringkey_topk, sc_distance, sc_reduce */
+int vilf_get_profile_sc(vilf_handle *h, double ms_out[4], long launches_out[4]);
+
 /* ---- scan-to-map (≙ EstimationMapping) -------------------------------------------------- */
 /* points are float xyzi (pcl::PointXYZI without padding): [n][4] */
 int vilf_scan2map_init(vilf_handle *h, const float *edge_xyzi, int n_edge, const float *surf_xyzi, int n_surf);   /* localMapInited, :105 */

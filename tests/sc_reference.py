@@ -1,0 +1,236 @@
+"""numpy restatement of the Scan Context semantics that include/vilfusion.h states for vilf_sc_* (≙ SCManager, global_fusion/include/Scancontext/Scancontext.h of
+the reference), written from that header's text: test infrastructure, no device code, nothing shared with vil_fusion_amd/csrc.
+
+Every sum whose order the semantics fix is a cumulative sum (numpy's cumsum adds in index order; its sum() adds pairwise), float steps stay float32 (numpy rounds
+every elementwise product and sum separately, there is no fused multiply-add), and the atan is the fp64 one rounded to float (the "correctly rounded atanf").
+"""
+import math
+import numpy as np
+
+RINGS, SECTORS = 20, 60
+NO_POINT = -1000.0
+NO_DIST = 10000000.0
+
+
+class Params:
+    def __init__(self, **over):
+        self.max_radius = 80.0
+        self.lidar_height = 2.0
+        self.num_exclude_recent = 30
+        self.num_candidates = 3          # 0: every snapshot entry
+        self.search_ratio = 0.1          # 1: every shift
+        self.dist_thres = 0.2
+        self.tree_making_period = 30
+        for k, v in over.items():
+            assert hasattr(self, k), k
+            setattr(self, k, v)
+
+
+def seq_sum(a, axis):
+    """sum along an axis in index order"""
+    return np.take(np.cumsum(a, axis=axis), -1, axis=axis)
+
+
+def point_bins(cloud, p):
+    """per point: (used, ring index 0..19, sector index 0..59, z + height as float32, range float32, angle in degrees float32). `used` is False for the points the
+    semantics skip (non-finite coordinate, x == 0 and y == 0) and for those beyond the radius."""
+    c = np.asarray(cloud, dtype=np.float32).reshape(-1, np.shape(cloud)[1] if np.ndim(cloud) == 2 else 4)
+    x, y, z = c[:, 0], c[:, 1], c[:, 2]
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(x) & np.isfinite(y) & np.isfinite(z) & ~((x == 0) & (y == 0))
+        zf = (z.astype(np.float64) + p.lidar_height).astype(np.float32)
+        rng = np.sqrt(x * x + y * y)                                     # float32 products, float32 sum, float32 sqrt
+        k = 180.0 / math.pi
+        at = lambda q: np.arctan(q.astype(np.float64)).astype(np.float32).astype(np.float64)      # q is the float32 quotient
+        theta = np.where((x >= 0) & (y >= 0), k * at(y / x),
+                np.where((x < 0) & (y >= 0), 180.0 - k * at(y / (-x)),
+                np.where((x < 0) & (y < 0), 180.0 + k * at(y / x), 360.0 - k * at((-y) / x)))).astype(np.float32)
+        ok &= ~(rng.astype(np.float64) > p.max_radius)
+        ring = np.clip(np.ceil((rng.astype(np.float64) / p.max_radius) * RINGS), 1, RINGS)
+        sector = np.clip(np.ceil((theta.astype(np.float64) / 360.0) * SECTORS), 1, SECTORS)
+    ring = np.where(ok, ring, 1).astype(np.int64) - 1
+    sector = np.where(ok, sector, 1).astype(np.int64) - 1
+    return ok, ring, sector, zf, rng, theta
+
+
+def make_descriptor(cloud, p):
+    if len(cloud) == 0:
+        return np.zeros((RINGS, SECTORS))
+    ok, ring, sector, zf, _, _ = point_bins(cloud, p)
+    desc = np.full((RINGS, SECTORS), NO_POINT)
+    np.maximum.at(desc, (ring[ok], sector[ok]), zf[ok].astype(np.float64))       # `if desc < z: desc = z` over the points = the maximum, from NO_POINT
+    desc[desc == NO_POINT] = 0.0
+    return desc
+
+
+def ring_key(desc):
+    return (seq_sum(desc, 1) / SECTORS).astype(np.float32)
+
+
+def sector_key(desc):
+    return seq_sum(desc, 0) / RINGS
+
+
+def col_norms(desc):
+    return np.sqrt(seq_sum(desc * desc, 0))
+
+
+_IDX = (np.arange(SECTORS)[None, :] - np.arange(SECTORS)[:, None]) % SECTORS          # [s][c] = (c - s) % 60: column c of circshift(., s) is column (c - s) % 60
+
+
+def align(vkey1, vkey2):
+    """fastAlignUsingVkey: first minimum of |vkey1 - circshift(vkey2, s)| over s, from 10000000"""
+    d = vkey1[None, :] - vkey2[_IDX]
+    n = np.sqrt(seq_sum(d * d, 1))
+    s = int(np.argmin(n))                 # first minimum
+    return s if n[s] < NO_DIST else 0
+
+
+def shift_distances(a, b, shifts):
+    """distDirectSC(a, circshift(b, s)) for every s of `shifts`; NaN where no column has both norms non-zero"""
+    shifts = np.asarray(shifts, dtype=np.int64)
+    na, nb = col_norms(a), col_norms(b)
+    idx = _IDX[shifts]                                                     # [S][60]
+    bs = b[:, idx]                                                         # [20][S][60]
+    dots = seq_sum(a[:, None, :] * bs, 0)
+    eff = (na != 0)[None, :] & (nb[idx] != 0)
+    with np.errstate(all="ignore"):
+        cos = np.where(eff, dots / (na[None, :] * nb[idx]), 0.0)
+        return 1.0 - seq_sum(cos, 1) / eff.sum(axis=1)
+
+
+def search_shifts(first, p):
+    radius = int(math.floor(0.5 * p.search_ratio * SECTORS + 0.5))          # round(): half away from zero
+    return sorted({first} | {(first + i) % SECTORS for i in range(1, radius + 1)} | {(first - i) % SECTORS for i in range(1, radius + 1)})
+
+
+def distance(a, b, p, all_out=None):
+    """distanceBtnScanContext -> (distance, shift); (10000000, 0) when no searched shift has a distance"""
+    shifts = search_shifts(align(sector_key(a), sector_key(b)), p)
+    d = shift_distances(a, b, shifts)
+    if all_out is not None:
+        all_out.extend(float(v) for v in d if not np.isnan(v))
+    best, arg = NO_DIST, 0
+    for s, v in zip(shifts, d):
+        if v < best:
+            best, arg = float(v), s
+    return best, arg
+
+
+def ring_key_distances(q, keys):
+    """float32 squared L2, dimensions summed in order"""
+    acc = np.zeros(len(keys), dtype=np.float32)
+    for i in range(RINGS):
+        df = q[i] - keys[:, i]
+        acc = acc + df * df
+    return acc
+
+
+class SCManager:
+    def __init__(self, params=None):
+        self.p = params or Params()
+        self.descs, self.rkeys = [], []
+        self.calls = 0
+        self.snapshot = 0             # entries [0, snapshot) are searchable
+
+    def add(self, cloud):
+        d = make_descriptor(cloud, self.p)
+        self.descs.append(d)
+        self.rkeys.append(ring_key(d))
+        return len(self.descs) - 1
+
+    def detect(self):
+        """detectLoopClosureID for the newest key frame: the record vilf_sc_result holds, plus what the tests' preconditions need
+        (ring_gap_rel: (d4 - d3) / d4 of the ring-key distances when a fourth entry exists; runner_up_gap: second smallest minus smallest distance over every
+        searched (candidate, shift))"""
+        p = self.p
+        n = len(self.descs)
+        none = dict(loop_id=-1, nearest=-1, shift=0, n_candidates=0, min_dist=NO_DIST, yaw_diff_rad=0.0, candidates=[], ring_gap_rel=np.inf, runner_up_gap=np.inf, snapshot=0)
+        if n < p.num_exclude_recent + 1:
+            return none
+        if self.calls % p.tree_making_period == 0:
+            self.snapshot = n - p.num_exclude_recent
+        self.calls += 1
+        S = self.snapshot
+        ring_gap = np.inf
+        if p.num_candidates == 0:
+            cand = list(range(S))
+        else:
+            d = ring_key_distances(self.rkeys[-1], np.array(self.rkeys[:S]))
+            order = np.argsort(d, kind="stable")                       # ties: the lower index first
+            cand = [int(v) for v in order[:min(p.num_candidates, S)]]
+            if S > p.num_candidates:
+                d3, d4 = float(d[order[p.num_candidates - 1]]), float(d[order[p.num_candidates]])
+                ring_gap = (d4 - d3) / d4 if d4 > 0 else 0.0
+        min_dist, nn_align, nn_idx = NO_DIST, 0, 0
+        every = []
+        for ci in cand:
+            dist, sh = distance(self.descs[-1], self.descs[ci], p, every)
+            if dist < min_dist:
+                min_dist, nn_align, nn_idx = dist, sh, ci
+        every.sort()
+        return dict(loop_id=nn_idx if min_dist < p.dist_thres else -1, nearest=nn_idx, shift=nn_align, n_candidates=len(cand), min_dist=min_dist,
+                    yaw_diff_rad=float(np.float32(nn_align * (360.0 / SECTORS) * math.pi / 180.0)), candidates=cand[:16], ring_gap_rel=ring_gap,
+                    runner_up_gap=every[1] - every[0] if len(every) > 1 else np.inf, snapshot=S)
+
+
+def replay(clouds, params=None):
+    """one detect() after every add(), from an empty manager: the record per key frame"""
+    m = SCManager(params)
+    out = []
+    for c in clouds:
+        m.add(c)
+        out.append(m.detect())
+    return m, out
+
+
+MOUNT_YAW = 0.0123456          # rad
+
+
+def mount(cloud, yaw=MOUNT_YAW):
+    """the cloud as a sensor mounted with a small yaw sees it. synth.LidarScene fires on a regular azimuth grid, so in its own frame every 12th return of a 720-azimuth
+    scan lies on a multiple of 6 degrees, exactly on a sector boundary; a real sensor's grid has no such relation to the sectors."""
+    c = np.asarray(cloud, dtype=np.float32).copy()
+    x, y = c[:, 0].astype(np.float64), c[:, 1].astype(np.float64)
+    c[:, 0] = (math.cos(yaw) * x - math.sin(yaw) * y).astype(np.float32)
+    c[:, 1] = (math.sin(yaw) * x + math.cos(yaw) * y).astype(np.float32)
+    return c
+
+
+def revisit_route(seed=3, n_frames=140, radius=22.0, step=2.0, yaw2=0.7, offset2=0.4, rings=16, azimuths=720, n_poles=80):
+    """the route of the replay tests: key frames `step` apart on a circle, the laps after the first yawed by yaw2 and offset by offset2 (a revisit from another heading,
+    slightly beside the first pass). The clouds are mount()ed and have their
+    boundary points dropped (drop_boundary_points). Returns (clouds, poses [x y yaw])"""
+    from vil_fusion_amd import synth
+    scene = synth.LidarScene(seed, n_poles=n_poles, rings=rings, azimuths=azimuths)
+    per_lap = 2.0 * math.pi * radius / step
+    clouds, poses = [], []
+    for k in range(n_frames):
+        lap = int(k // per_lap)
+        a = step * k / radius
+        r = radius + (offset2 if lap > 0 else 0.0)
+        yaw = a + math.pi / 2 + (yaw2 if lap > 0 else 0.0)
+        R = synth.euler_R(np.array(yaw), np.array(0.0), np.array(0.0))
+        t = np.array([r * math.cos(a), r * math.sin(a), scene.h])
+        clouds.append(drop_boundary_points(mount(scene.scan_raw(R, t)), Params())[0])
+        poses.append((t[0], t[1], yaw))
+    return clouds, np.array(poses)
+
+
+def drop_boundary_points(cloud, p, eps_deg=1e-4, eps_m=1e-4):
+    """remove every point whose fp64 angle lies within eps_deg of a sector boundary or whose range lies within eps_m of a ring boundary or of the radius: the binning of
+    what is left does not depend on the last bit of an atan. Points the semantics skip anyway (non-finite, x == y == 0) are kept: skipping them is part of what is tested.
+    Returns (kept cloud, number removed)."""
+    c = np.asarray(cloud, dtype=np.float32)
+    if len(c) == 0:
+        return c, 0
+    x, y = c[:, 0].astype(np.float64), c[:, 1].astype(np.float64)
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(x) & np.isfinite(y) & ~((x == 0) & (y == 0))
+        ang = np.degrees(np.arctan2(y, x)) % 360.0
+        rng = np.hypot(x, y)
+        sec = ang / (360.0 / SECTORS)
+        gap = p.max_radius / RINGS
+        near = (np.abs(sec - np.round(sec)) * (360.0 / SECTORS) < eps_deg) | (np.abs(rng / gap - np.round(rng / gap)) * gap < eps_m)
+    drop = finite & near
+    return np.ascontiguousarray(c[~drop]), int(drop.sum())

@@ -110,6 +110,23 @@ class Scan2MapResult(C.Structure):
     ]
 
 
+class ScParams(C.Structure):
+    """vilf_sc_params: SCManager's constants (Scancontext.h:304-327)"""
+    _fields_ = [
+        ("num_rings", C.c_int), ("num_sectors", C.c_int), ("max_radius", C.c_double), ("lidar_height", C.c_double),
+        ("num_exclude_recent", C.c_int), ("num_candidates", C.c_int), ("search_ratio", C.c_double), ("dist_thres", C.c_double),
+        ("tree_making_period", C.c_int), ("pad_", C.c_int),
+    ]
+
+
+class ScResult(C.Structure):
+    """vilf_sc_result: what detectLoopClosureID returns and what it only prints"""
+    _fields_ = [
+        ("loop_id", C.c_int), ("nearest", C.c_int), ("shift", C.c_int), ("n_candidates", C.c_int), ("min_dist", C.c_double),
+        ("yaw_diff_rad", C.c_float), ("candidates", C.c_int * 16),
+    ]
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

@@ -338,6 +338,93 @@ def posegraph_optimize(solver, poses_qt, prior_sigma, edges, max_iterations=30, 
     return x, it.value, cost[0]
 
 
+def sc_default_params(**over):
+    """vilf_sc_params with SCManager's constants (Scancontext.h:304-327); keyword arguments replace fields (dist_thres=0.4, num_candidates=0, ...)"""
+    p = abi.ScParams()
+    lib().vilf_sc_default_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"vilf_sc_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def sc_result_dict(r):
+    return dict(loop_id=r.loop_id, nearest=r.nearest, shift=r.shift, n_candidates=r.n_candidates, min_dist=r.min_dist, yaw_diff_rad=float(r.yaw_diff_rad),
+                candidates=[int(v) for v in r.candidates[:min(max(r.n_candidates, 0), 16)]])
+
+
+class ScanContext:
+    """Host mirror of SCManager (global_fusion/include/Scancontext/Scancontext.h) over the device database of a BackendSolver handle (vilf_sc_*).
+    Clouds are (n, 3) or (n, 4) arrays (xyz or xyzi). `last` holds the full record of the latest detectLoopClosureID."""
+
+    def __init__(self, solver, capacity=4096, params=None, **over):
+        self.s = solver
+        self._L = solver._L
+        self.params = params if params is not None else sc_default_params(**over)
+        self.last = None
+        self.s._check(self._L.vilf_sc_create(self.s._h, C.byref(self.params), int(capacity)), "vilf_sc_create")
+
+    @staticmethod
+    def _xyzi(cloud):
+        a = np.asarray(cloud, dtype=np.float32)
+        if a.size == 0:
+            return np.zeros((0, 4), dtype=np.float32)
+        assert a.ndim == 2 and a.shape[1] in (3, 4), a.shape
+        if a.shape[1] == 3:
+            a = np.concatenate([a, np.zeros((len(a), 1), dtype=np.float32)], axis=1)
+        return np.ascontiguousarray(a)
+
+    def __len__(self):
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_sc_size(self.s._h, C.byref(n)), "vilf_sc_size")
+        return n.value
+
+    def makeAndSaveScancontextAndKeys(self, cloud):
+        """:193-204. Returns the index of the new key frame."""
+        a = self._xyzi(cloud)
+        idx = C.c_int(-1)
+        self.s._check(self._L.vilf_sc_add_keyframe(self.s._h, a.ctypes.data_as(C.POINTER(C.c_float)), len(a), C.byref(idx)), "vilf_sc_add_keyframe")
+        return idx.value
+
+    def add_many(self, clouds):
+        """all clouds in one upload and one launch (vilf_sc_add_keyframes). Returns the index of the first."""
+        cl = [self._xyzi(c) for c in clouds]
+        off = np.zeros(len(cl) + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(c) for c in cl])
+        pts = np.ascontiguousarray(np.concatenate(cl, axis=0)) if cl else np.zeros((0, 4), dtype=np.float32)
+        first = C.c_int(-1)
+        self.s._check(self._L.vilf_sc_add_keyframes(self.s._h, len(cl), pts.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int)), C.byref(first)),
+                      "vilf_sc_add_keyframes")
+        return first.value
+
+    def detectLoopClosureID(self):
+        """:210-300 for the newest key frame -> (loop_id, yaw_diff_rad)"""
+        r = abi.ScResult()
+        self.s._check(self._L.vilf_sc_detect(self.s._h, C.byref(r)), "vilf_sc_detect")
+        self.last = sc_result_dict(r)
+        return r.loop_id, float(r.yaw_diff_rad)
+
+    def detect_range(self, first=0, n=None):
+        """the replay (vilf_sc_detect_range): one record per key frame first .. first + n - 1, as a list of dicts"""
+        n = len(self) - first if n is None else n
+        arr = (abi.ScResult * max(n, 1))()
+        self.s._check(self._L.vilf_sc_detect_range(self.s._h, int(first), int(n), arr), "vilf_sc_detect_range")
+        return [sc_result_dict(arr[i]) for i in range(n)]
+
+    def get(self, index):
+        """(descriptor (20, 60) float64, ring key (20,) float32, sector key (60,) float64) of a key frame"""
+        d, rk, sk = np.zeros((20, 60)), np.zeros(20, dtype=np.float32), np.zeros(60)
+        self.s._check(self._L.vilf_sc_get(self.s._h, int(index), abi.dptr(d), rk.ctypes.data_as(C.POINTER(C.c_float)), abi.dptr(sk)), "vilf_sc_get")
+        return d, rk, sk
+
+    def profile(self):
+        """ms and launches of sc_descriptor, sc_ringkey_topk, sc_distance, sc_reduce since vilf_set_profiling was switched on"""
+        ms, cnt = (C.c_double * 4)(), (C.c_long * 4)()
+        self.s._check(self._L.vilf_get_profile_sc(self.s._h, ms, cnt), "vilf_get_profile_sc")
+        return dict(zip(("sc_descriptor", "sc_ringkey_topk", "sc_distance", "sc_reduce"), ((ms[i], cnt[i]) for i in range(4))))
+
+
 class Scan2Map:
     """Host mirror of EstimationMapping (feature_tracker/include/EstimationMapping.hpp): localMapInited / optimation_processing /
     getMapCloud over the device path. One LiDAR stream per BackendSolver handle."""

@@ -19,6 +19,7 @@ EXPORTED = [
     "vilf_scan2map_batch_create", "vilf_scan2map_batch_init", "vilf_scan2map_batch_set_scan", "vilf_scan2map_batch_step", "vilf_scan2map_batch_snapshot",
     "vilf_scan2map_batch_rewind", "vilf_scan2map_batch_copy_stream", "vilf_scan2map_batch_results", "vilf_scan2map_batch_get_map", "vilf_get_profile_scan2map", "vilf_get_profile_marginalize", "vilf_batch_marginalize_stats", "vilf_get_profile_large_window", "vilf_lidar_extract_features", "vilf_feature_depth",
     "vilf_comm_unique_id", "vilf_comm_create", "vilf_comm_destroy", "vilf_gather_poses", "vilf_gather_poses_handle", "vilf_comm_ranks", "vilf_get_stream", "vilf_comm_last_error",
+    "vilf_sc_default_params", "vilf_sc_create", "vilf_sc_add_keyframe", "vilf_sc_add_keyframes", "vilf_sc_detect", "vilf_sc_detect_range", "vilf_sc_get", "vilf_sc_size", "vilf_get_profile_sc",
 ]
 
 
@@ -103,6 +104,17 @@ def lib():
     L.vilf_scan2map_batch_copy_stream.argtypes = [vp, C.c_int, C.c_int]
     L.vilf_scan2map_batch_results.argtypes = [vp, C.c_int, C.c_int, C.POINTER(abi.Scan2MapResult)]
     L.vilf_scan2map_batch_get_map.argtypes = [vp, C.c_int, C.c_int, fpp, C.c_int, C.POINTER(C.c_int)]
+    ip = C.POINTER(C.c_int)
+    L.vilf_sc_default_params.argtypes = [C.POINTER(abi.ScParams)]
+    L.vilf_sc_default_params.restype = None
+    L.vilf_sc_create.argtypes = [vp, C.POINTER(abi.ScParams), C.c_int]
+    L.vilf_sc_add_keyframe.argtypes = [vp, fpp, C.c_int, ip]
+    L.vilf_sc_add_keyframes.argtypes = [vp, C.c_int, fpp, ip, ip]
+    L.vilf_sc_detect.argtypes = [vp, C.POINTER(abi.ScResult)]
+    L.vilf_sc_detect_range.argtypes = [vp, C.c_int, C.c_int, C.POINTER(abi.ScResult)]
+    L.vilf_sc_get.argtypes = [vp, C.c_int, abi.c_double_p, fpp, abi.c_double_p]
+    L.vilf_sc_size.argtypes = [vp, ip]
+    L.vilf_get_profile_sc.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 

@@ -5,7 +5,9 @@ What the reference's threads do around gtsam, restated as plain host code over t
   * icpCalculation()    :376-443   an accepted ICP result -> robust loop BetweenFactor(prev, curr)
   * isamUpdate()        :349-374   isam->update(); calculateEstimate(); updatePoses()
   * saveTUMTrajOdometry :88-110    `t x y z qx qy qz qw`, precision 9 / 5
-ScanContext loop detection and the ICP itself are not part of this row: loop candidates come in as (prev, curr, ICP transform).
+  * makeAndSaveScancontextAndKeys :553, performSCLoopDetection :598-614   with a detector attached (estimator.ScanContext over the device database, vilf_sc_*):
+                                   every key frame's cloud becomes a descriptor, detect_loop() names the pair to verify
+The ICP verification itself (:376-443, pcl::IterativeClosestPoint) is not part of this row: add_loop takes its transform from the caller.
 """
 import numpy as np
 
@@ -16,6 +18,7 @@ KEYFRAME_ROT_TH = np.deg2rad(10.0)           # /keyframe_rotate_th (:648-649)
 PRIOR_SIGMA = np.sqrt(np.full(6, 1e-12))     # initNoises() :121-139, gtsam order [rot, trans]
 ODOM_SIGMA = np.sqrt(np.array([1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4]))
 LOOP_SIGMA = np.sqrt(np.full(6, 0.5))
+LOOP_MIN_KEYFRAMES = 30                      # performSCLoopDetection's own gate: scManager.NUM_EXCLUDE_RECENT (:600)
 
 
 def inverse(p):
@@ -68,15 +71,17 @@ def diff_transformation(p1, p2):
 class PoseGraph:
     """`backend(poses[n,7], prior_sigma, edges) -> poses[n,7]` runs the solve (HIP: estimator.posegraph_optimize; tests: the oracle)."""
 
-    def __init__(self, backend):
+    def __init__(self, backend, detector=None):
         self.backend = backend
+        self.detector = detector      # scManager: anything with makeAndSaveScancontextAndKeys(cloud) and detectLoopClosureID() -> (loop_id, yaw_diff_rad)
         self.translate_acc, self.rotation_acc = 1000000.0, 100000.0          # :50-51
         self.prev = np.zeros(6); self.curr = np.zeros(6)
         self.nodes = []               # key frames: dict(stamp, pose6d, updated6d)
         self.edges = []               # (i, j, q, t, sigma, robust)
 
-    def add_odometry(self, stamp, pose_qt):
-        """one synchronised odometry message (:483-587). Returns True if it became a key frame."""
+    def add_odometry(self, stamp, pose_qt, cloud=None):
+        """one synchronised odometry message (:483-587) with its down-sampled cloud (thisKeyFrameDS; used only with a detector attached, and then needed for every
+        message that becomes a key frame: detector index = key-frame index). Returns True if it became a key frame."""
         pose_qt = np.asarray(pose_qt, dtype=np.float64)
         cur = np.concatenate([pose_qt[4:], rpy_from_q(pose_qt[:4])])
         self.prev, self.curr = self.curr, cur
@@ -85,13 +90,24 @@ class PoseGraph:
         self.rotation_acc += rel[3] + rel[4] + rel[5]
         if not (self.translate_acc > KEYFRAME_TRANS_TH or self.rotation_acc > KEYFRAME_ROT_TH):
             return False
+        if self.detector is not None and cloud is None:
+            raise ValueError("a loop detector is attached: the message that becomes key frame %d needs its cloud" % len(self.nodes))
         self.translate_acc = self.rotation_acc = 0.0
+        if self.detector is not None:
+            self.detector.makeAndSaveScancontextAndKeys(cloud)              # :553
         self.nodes.append(dict(stamp=float(stamp), pose=cur.copy(), updated=cur.copy()))
         k = len(self.nodes) - 1
         if k > 0:                                                           # BetweenFactor(prev, curr, poseFrom.between(poseTo), odomNoise) :577-584
             rel_qt = between(self._qt(self.nodes[k - 1]["pose"]), self._qt(cur))
             self.edges.append((k - 1, k, rel_qt[:4], rel_qt[4:], ODOM_SIGMA, 0))
         return True
+
+    def detect_loop(self):
+        """performSCLoopDetection (:598-614): (prev, curr, yaw_diff_rad) for the newest key frame, the pair the reference queues for ICP, or None"""
+        if self.detector is None or len(self.nodes) < LOOP_MIN_KEYFRAMES:
+            return None
+        loop_id, yaw = self.detector.detectLoopClosureID()
+        return None if loop_id == -1 else (int(loop_id), len(self.nodes) - 1, float(yaw))
 
     def add_loop(self, prev, curr, icp_qt):
         """an accepted ICP alignment of key frame `curr` onto `prev` (:420-436): measured = poseFrom.between(identity) = poseFrom^-1"""
