@@ -403,6 +403,85 @@ int vilf_sc_size(vilf_handle *h, int *n_out);
 /* vilf_set_profiling: sc_descriptor, sc_ringkey_topk, sc_distance, sc_reduce */
 int vilf_get_profile_sc(vilf_handle *h, double ms_out[4], long launches_out[4]);
 
+/* ---- ICP verification of a loop candidate (≙ icpCalculation, global_fusion/poseGraphOptimization.cpp:376-443; device) ----
+ * PCL 1.7.2 is not available, so this is a restatement from PCL's documented behaviour: parity unpinned. Every choice PCL leaves to Eigen or FLANN internals is
+ * pinned here; tests/icp_reference.py restates the same text in numpy.
+ *   store        key-frame clouds (thisKeyFrameDS :541-551, float xyzi, finite) resident on the device, one store per handle, sized at creation (key frames and
+ *                total points). Poses (KeyFramePosesUpdated, x y z roll pitch yaw as doubles) come with every call: they change after every graph update.
+ *   sub-map      loopFindNearKeyframeCLoud(key, submap_size, root) :194-219: the clouds key - submap_size .. key + submap_size that exist, concatenated in that
+ *                order, every one transformed with the pose of key frame `root` (the own-pose line is commented out at :205; own_pose = 1 uses each cloud's own
+ *                pose instead). The transform is pcl::getTransformation as a float affine: the six values rounded to float, sine and cosine of an angle = the fp64
+ *                function of the float angle rounded to float, A, B = cos, sin yaw, C, D = cos, sin pitch, E, F = cos, sin roll, DE = D*E, DF = D*F,
+ *                rows [A*C, A*DF - B*E, B*F + A*DE | x], [B*C, A*E + B*DF, B*DE - A*F | y], [-D, C*F, C*E | z], every product and sum rounded on its own.
+ *                Applied as local2global :171-192: per component ((m0*x + m1*y) + m2*z) + m3 in float, no contraction; intensity copied.
+ *                Then pcl::VoxelGrid with leaf `leaf_size`: inv = 1.0f / leaf; leaf coordinates floor(p * inv) in float relative to floor(min * inv) of the
+ *                cloud's own bounding box; leaf index ix + iy * dx + iz * dx * dy; leaves in ascending leaf index; centroid of x, y, z, intensity: the points of
+ *                a leaf summed in float in concatenation order, then divided by the float count (PCL's std::sort leaves the order open; this is the order of
+ *                the oracle's voxel_grid). An empty sub-map stays empty (:210-211). A bounding box of 2^40 leaves or more is VILF_ERR_UNSUPPORTED.
+ *                Source = (curr, 0, root = prev), target = (prev, history, root = prev) :394-398.
+ *   ICP          pcl::IterativeClosestPoint as configured at :401-412. final = guess (identity in the reference) as a float 4 x 4, the source moved by it.
+ *                Each round: for every source point its nearest target point, d2 = ((dx*dx) + (dy*dy)) + (dz*dz) in float without contraction (FLANN L2_Simple),
+ *                exact ties to the lower target index; accepted if d2 <= max_correspondence_distance^2 (compared in double). No reciprocal test, no rejectors,
+ *                no RANSAC. Fewer than 3 accepted: not converged, stop (criterion 5). Step = rigid Umeyama without scale (TransformationEstimationSVD) in fp64:
+ *                n, sum s, sum t, sum s t^T over the accepted pairs accumulated in fp64 in a fixed tree (xor butterfly 32, 16, .. 1 within 64 consecutive source
+ *                points, then the 4 groups of 64 of a block of 256 in order, then the blocks in order), H = sum t s^T / n - mean_t mean_s^T, H = U D V^T by
+ *                one-sided Jacobi, R = U diag(1, 1, det U det V) V^T, t = mean_t - R mean_s; the 4 x 4 rounded to float = T_k. source <- T_k source (float,
+ *                as above, on the already moved source: incrementally, as PCL does), final <- T_k final (float, entry = ((a0*b0 + a1*b1) + a2*b2) + a3*b3).
+ *                DefaultConvergenceCriteria after every step, in this order: 1 iterations reached max_iterations; 2 cos = 0.5 (trace R_k - 1) >=
+ *                rotation_threshold and |t_k|^2 <= transformation_epsilon (fp64 of the float entries); with mse = mean of the accepted d2 of this round (fp64):
+ *                3 |mse - mse_prev| < euclidean_fitness_epsilon; 4 |mse - mse_prev| / mse_prev < mse_relative (mse_prev starts at DBL_MAX).
+ *   fitness      getFitnessScore(): one more search over the final source, mean of the nearest d2 (float each, summed in fp64 in the same tree) over all source
+ *                points, no range limit; no source or no target point: DBL_MAX. accepted = converged && fitness <= fitness_threshold (:414-423).
+ *   result       pcl::getTranslationAndEulerAngles(final): roll = atan2(m21, m22), pitch = asin(-m20), yaw = atan2(m10, m00), each the fp64 function of the float
+ *                entries rounded to float -> pose6 [x y z roll pitch yaw]; pose_qt = [qx qy qz qw tx ty tz] of Rot3::RzRyRx(roll, pitch, yaw) in fp64, qw >= 0
+ *                (:428-432). The loop edge measures its inverse (:433-436), which PoseGraph.add_loop takes.
+ * vilf_reset leaves the store alone; vilf_icp_create resets it. */
+typedef struct vilf_icp_params {
+    double max_correspondence_distance;  /* 100 (:402) */
+    int max_iterations;                  /* 100 (:403); at most 1000 */
+    int history_keyframes;               /* historyKeyframesSearchNum 25 (:394) */
+    double transformation_epsilon;       /* 1e-6 (:404) */
+    double euclidean_fitness_epsilon;    /* 1e-6 (:405) */
+    double rotation_threshold;           /* DefaultConvergenceCriteria: 0.99999 */
+    double mse_relative;                 /* DefaultConvergenceCriteria: 1e-5 */
+    double fitness_threshold;            /* loopFitnessScoreThreshold 0.3 (:414) */
+    double leaf_size;                    /* MapLeafSize 0.4 (:646-647) */
+    int own_pose;                        /* 0 (:206); 1: every cloud of a sub-map under its own pose (:205) */
+    int pad_;
+} vilf_icp_params;
+void vilf_icp_default_params(vilf_icp_params *p);
+enum { VILF_ICP_NONE = 0, VILF_ICP_ITERATIONS = 1, VILF_ICP_TRANSFORM = 2, VILF_ICP_ABS_MSE = 3, VILF_ICP_REL_MSE = 4, VILF_ICP_NO_CORRESPONDENCES = 5 };
+typedef struct vilf_icp_result {
+    int converged, accepted, criterion /* VILF_ICP_*: the rule that ended the rounds */, iterations;
+    int n_source, n_target, n_correspondences /* of the last round */, pad_;
+    double fitness, final_mse;
+    float transform[16];             /* final, row-major */
+    double pose6[6], pose_qt[7];
+} vilf_icp_result;
+typedef struct vilf_icp_iter {
+    int n_correspondences, criterion /* VILF_ICP_NONE while the rounds go on */;
+    double mse, cos_angle, translation_sqr;
+} vilf_icp_iter;
+/* a store for cap_keyframes clouds of cap_points points in all (an existing one of the handle is dropped) */
+int vilf_icp_create(vilf_handle *h, const vilf_icp_params *p, int cap_keyframes, long cap_points);
+/* cloud of the next key frame (xyzi [n][4]). A full store is VILF_ERR_UNSUPPORTED, a value that is not finite invalid-argument; both leave the store as it was.
+ * Poses and guesses that are not finite are invalid-argument too, before any work is enqueued. */
+int vilf_icp_add_cloud(vilf_handle *h, const float *xyzi, int n, int *index_out);
+int vilf_icp_add_clouds(vilf_handle *h, int n, const float *xyzi, const int *offsets /*[n + 1]*/, int *first_index_out);
+int vilf_icp_size(vilf_handle *h, int *n_out);
+/* the sub-map as ICP sees it; poses6 = [size][6]. n_out is always complete, xyzi_out truncated to cap points. A key or root outside the store: invalid argument. */
+int vilf_icp_submap(vilf_handle *h, int key, int submap_size, int root, const double *poses6, float *xyzi_out, int cap, int *n_out);
+/* icpCalculation for the pair (prev, curr); guess_qt = [qx qy qz qw tx ty tz] or NULL for identity */
+int vilf_icp_align(vilf_handle *h, int prev, int curr, const double *poses6, const double *guess_qt, vilf_icp_result *out);
+/* n pairs in one chain of launches (grid dimension = pair); out[i] is bit-identical to the single call. guess_qt = [n][7] or NULL */
+int vilf_icp_align_pairs(vilf_handle *h, int n, const int *prev, const int *curr, const double *poses6, const double *guess_qt, vilf_icp_result *out);
+/* the rounds of pair `pair` of the last align call */
+int vilf_icp_get_history(vilf_handle *h, int pair, vilf_icp_iter *out, int cap, int *n_out);
+/* diagnostic (what lets a test compare the search point by point): nearest target index (into the target sub-map, -1: none) and d2 of every source point of pair `pair` of the last align call: which = 0 the first round, 1 the fitness pass */
+int vilf_icp_get_search(vilf_handle *h, int pair, int which, int *index_out, float *d2_out, int cap, int *n_out);
+/* vilf_set_profiling: icp_bbox, icp_leaf_keys, radix sorts, icp_voxel, icp_cell_keys + icp_cell_table, icp_search, icp_step, (unused) */
+int vilf_get_profile_icp(vilf_handle *h, double ms_out[8], long launches_out[8]);
+
 /* ---- scan-to-map (≙ EstimationMapping) -------------------------------------------------- */
 /* points are float xyzi (pcl::PointXYZI without padding): [n][4] */
 int vilf_scan2map_init(vilf_handle *h, const float *edge_xyzi, int n_edge, const float *surf_xyzi, int n_surf);   /* localMapInited, :105 */

@@ -1,0 +1,300 @@
+"""numpy restatement of the loop-candidate ICP (icpCalculation, global_fusion/poseGraphOptimization.cpp:376-443), written from the statement of the semantics in
+include/vilfusion.h: sub-map assembly + voxel filter, pcl::IterativeClosestPoint with DefaultConvergenceCriteria, getFitnessScore. Parity with PCL 1.7.2 is unpinned;
+what is pinned is the text of the header. Nearest neighbours: scipy's cKDTree proposes candidates in fp64, the float d2 formula and the index tie-break decide.
+align() also returns what the GPU tests need to know how far its own answer can be trusted: the margin of every convergence comparison it made, |fitness - threshold|,
+and (align_both) a second run whose sums are accumulated in reversed order."""
+import math
+
+import numpy as np
+from scipy.spatial import cKDTree
+
+NONE, ITERATIONS, TRANSFORM, ABS_MSE, REL_MSE, NO_CORRESPONDENCES = 0, 1, 2, 3, 4, 5
+DBL_MAX = float(np.finfo(np.float64).max)
+F = np.float32
+
+
+class Params:
+    max_correspondence_distance = 100.0
+    max_iterations = 100
+    history_keyframes = 25
+    transformation_epsilon = 1e-6
+    euclidean_fitness_epsilon = 1e-6
+    rotation_threshold = 0.99999
+    mse_relative = 1e-5
+    fitness_threshold = 0.3
+    leaf_size = 0.4
+    own_pose = 0
+
+    def __init__(self, **over):
+        for k, v in over.items():
+            assert hasattr(Params, k), k
+            setattr(self, k, v)
+
+
+def pose_matrix(p6):
+    """pcl::getTransformation(x, y, z, roll, pitch, yaw) as float rows [R | t]: sine / cosine = fp64 function of the float angle rounded to float"""
+    x, y, z, roll, pitch, yaw = [F(v) for v in p6]
+    cs = lambda a: (F(math.cos(float(a))), F(math.sin(float(a))))
+    (A, B), (C, D), (E, Fs) = cs(yaw), cs(pitch), cs(roll)
+    DE, DF = D * E, D * Fs
+    return np.array([[A * C, A * DF - B * E, B * Fs + A * DE, x],
+                     [B * C, A * E + B * DF, B * DE - A * Fs, y],
+                     [-D, C * Fs, C * E, z]], dtype=F)
+
+
+def transform(M, cloud):
+    """local2global: ((m0 x + m1 y) + m2 z) + m3 per component in float; further columns (intensity) copied"""
+    c = np.asarray(cloud, dtype=F)
+    out = c.copy()
+    M = np.asarray(M, dtype=F)
+    for r in range(3):
+        out[:, r] = ((M[r, 0] * c[:, 0] + M[r, 1] * c[:, 1]) + M[r, 2] * c[:, 2]) + M[r, 3]
+    return out
+
+
+def voxel_grid(cloud, leaf):
+    """pcl::VoxelGrid: ascending leaf index, centroid = float sum in input order / float count"""
+    c = np.asarray(cloud, dtype=F)
+    if len(c) == 0:
+        return c.reshape(0, 4)
+    inv = F(1.0) / F(leaf)
+    ijk = np.floor(c[:, :3] * inv).astype(np.int64)
+    minb = np.floor(c[:, :3].min(0) * inv).astype(np.int64)
+    maxb = np.floor(c[:, :3].max(0) * inv).astype(np.int64)
+    div = maxb - minb + 1
+    ijk -= minb
+    key = ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * div[0] * div[1]
+    order = np.argsort(key, kind="stable")
+    ks = key[order]
+    heads = np.flatnonzero(np.r_[True, ks[1:] != ks[:-1]])
+    counts = np.diff(np.r_[heads, len(ks)])
+    acc = np.zeros((len(heads), 4), dtype=F)
+    for j in range(int(counts.max())):              # the j-th point of every leaf that has one: sequential float sums, vectorised over the leaves
+        m = counts > j
+        acc[m] = acc[m] + c[order[heads[m] + j]]
+    return acc / counts.astype(F)[:, None]
+
+
+def submap(clouds, poses6, key, submap_size, root, p=None):
+    """loopFindNearKeyframeCLoud(key, submap_size, root)"""
+    p = p or Params()
+    parts = []
+    for k in range(key - submap_size, key + submap_size + 1):
+        if 0 <= k < len(clouds):
+            parts.append(transform(pose_matrix(poses6[k if p.own_pose else root]), xyzi(clouds[k])))
+    if not parts or sum(len(q) for q in parts) == 0:
+        return np.zeros((0, 4), dtype=F)
+    return voxel_grid(np.concatenate(parts), p.leaf_size)
+
+
+def xyzi(cloud):
+    a = np.asarray(cloud, dtype=F)
+    if a.size == 0:
+        return np.zeros((0, 4), dtype=F)
+    return a if a.shape[1] == 4 else np.concatenate([a, np.zeros((len(a), 1), dtype=F)], axis=1)
+
+
+def d2_float(q, t):
+    d = q.astype(F) - t.astype(F)
+    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+
+class Target:
+    def __init__(self, pts):
+        self.p = np.ascontiguousarray(np.asarray(pts, dtype=F)[:, :3])
+        self.tree = cKDTree(self.p.astype(np.float64)) if len(self.p) else None
+
+    def nearest(self, q, k=8):
+        """(index, float d2) of the nearest target point of every query: smallest (d2, index). Candidates from the tree; where the k-th candidate is not clearly
+        farther than the best one (many near ties), all target points are tried."""
+        q = np.asarray(q, dtype=F)[:, :3]
+        n = len(q)
+        if self.tree is None or n == 0:
+            return np.full(n, -1, dtype=np.int64), np.full(n, np.inf, dtype=F)
+        k = min(k, len(self.p))
+        dd, ii = self.tree.query(q.astype(np.float64), k=k)
+        dd, ii = dd.reshape(n, k), ii.reshape(n, k)
+        d2 = d2_float(q[:, None, :], self.p[ii])
+        best = d2.min(1)
+        cand = np.where(d2 == best[:, None], ii, np.iinfo(np.int64).max)
+        idx = cand.min(1)
+        if k < len(self.p):
+            unsure = np.flatnonzero(dd[:, -1] <= dd[:, 0] * (1 + 1e-5) + 1e-12)
+            for u in unsure:
+                da = d2_float(q[u][None, :], self.p)
+                best[u] = da.min()
+                idx[u] = int(np.flatnonzero(da == best[u])[0])
+        return idx, best
+
+
+def umeyama(S, T, reverse=False):
+    """rigid, no scale, from the raw fp64 sums n, sum s, sum t, sum s t^T (the header's formula); reverse: the sums in reversed order"""
+    S, T = S.astype(np.float64), T.astype(np.float64)
+    if reverse:
+        S, T = S[::-1], T[::-1]
+    n = float(len(S))
+    seq = lambda a: np.cumsum(a, axis=0)[-1]          # one element after the other
+    ms, mt = seq(S) / n, seq(T) / n
+    H = seq(T[:, :, None] * S[:, None, :]) / n - np.outer(mt, ms)
+    U, _, Vt = np.linalg.svd(H)
+    R = U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U) * np.linalg.det(Vt)) or 1.0]) @ Vt
+    M = np.eye(4, dtype=F)
+    M[:3, :3] = R.astype(F)
+    M[:3, 3] = (mt - R @ ms).astype(F)
+    return M
+
+
+def mat4_mul(A, B):
+    """float 4 x 4 product, entry = ((a0 b0 + a1 b1) + a2 b2) + a3 b3"""
+    A, B = A.astype(F), B.astype(F)
+    out = np.zeros((4, 4), dtype=F)
+    for i in range(4):
+        for j in range(4):
+            out[i, j] = ((A[i, 0] * B[0, j] + A[i, 1] * B[1, j]) + A[i, 2] * B[2, j]) + A[i, 3] * B[3, j]
+    return out
+
+
+def guess_matrix(qt):
+    M = np.eye(4, dtype=F)
+    if qt is None:
+        return M
+    qt = np.asarray(qt, dtype=np.float64)
+    x, y, z, w = qt[:4] / np.linalg.norm(qt[:4])
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    M[:3, :3] = R.astype(F)
+    M[:3, 3] = qt[4:].astype(F)
+    return M
+
+
+def result_pose(M):
+    """getTranslationAndEulerAngles + Rot3::RzRyRx -> (pose6, [qx qy qz qw tx ty tz] with qw >= 0)"""
+    roll = float(F(math.atan2(float(M[2, 1]), float(M[2, 2]))))
+    pitch = float(F(math.asin(max(-1.0, min(1.0, -float(M[2, 0]))))))
+    yaw = float(F(math.atan2(float(M[1, 0]), float(M[0, 0]))))
+    cr, sr, cp, sp, cy, sy = math.cos(roll / 2), math.sin(roll / 2), math.cos(pitch / 2), math.sin(pitch / 2), math.cos(yaw / 2), math.sin(yaw / 2)
+    q = np.array([sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy])
+    if q[3] < 0:
+        q = -q
+    t = [float(M[0, 3]), float(M[1, 3]), float(M[2, 3])]
+    return np.array(t + [roll, pitch, yaw]), np.concatenate([q, t])
+
+
+def align(source, target, p=None, guess_qt=None, reverse=False):
+    """pcl::IterativeClosestPoint::align + getFitnessScore on two sub-maps. Returns a dict; `rounds` holds a record per round, `margin` the smallest relative
+    margin of the convergence comparisons that decided a round (inf if none was evaluated), `first_search` / `fitness_search` the (index, d2) arrays."""
+    p = p or Params()
+    src = np.asarray(source, dtype=F)[:, :3].copy() if len(source) else np.zeros((0, 3), dtype=F)
+    tg = Target(target if len(target) else np.zeros((0, 3), dtype=F))
+    final = guess_matrix(guess_qt)
+    pend = final.copy()
+    rounds, margin = [], np.inf
+    converged, criterion, iterations, mse_prev, mse, ncorr = False, NONE, 0, DBL_MAX, 0.0, 0
+    first_search = None
+    rel = lambda v, thr, scale: abs(v - thr) / scale
+    for r in range(p.max_iterations):
+        src = transform(pend[:3], src)
+        idx, d2 = tg.nearest(src)
+        if r == 0:
+            first_search = (idx.copy(), d2.copy())
+        ok = (idx >= 0) & (d2.astype(np.float64) <= p.max_correspondence_distance ** 2)
+        ncorr = int(ok.sum())
+        if ncorr < 3:
+            rounds.append(dict(n_correspondences=ncorr, criterion=NO_CORRESPONDENCES, mse=0.0, cos_angle=0.0, translation_sqr=0.0))
+            criterion = NO_CORRESPONDENCES
+            pend = np.eye(4, dtype=F)
+            break
+        S, T = src[ok], tg.p[idx[ok]]
+        M = umeyama(S, T, reverse)
+        final, pend = mat4_mul(M, final), M
+        iterations += 1
+        dsel = d2[ok].astype(np.float64)
+        mse = float(np.cumsum(dsel[::-1] if reverse else dsel)[-1] / ncorr)
+        cosa = 0.5 * (((float(M[0, 0]) + float(M[1, 1])) + float(M[2, 2])) - 1.0)
+        tsq = (float(M[0, 3]) ** 2 + float(M[1, 3]) ** 2) + float(M[2, 3]) ** 2
+        dm = abs(mse - mse_prev)
+        crit = NONE
+        if iterations >= p.max_iterations:
+            crit = ITERATIONS
+        else:
+            mc, mt = rel(cosa, p.rotation_threshold, 1.0 - p.rotation_threshold), rel(tsq, p.transformation_epsilon, p.transformation_epsilon)
+            pc, pt = cosa >= p.rotation_threshold, tsq <= p.transformation_epsilon
+            if pc and pt:
+                crit = TRANSFORM
+                margin = min(margin, mc, mt)
+            else:
+                margin = min(margin, max(mc if not pc else 0.0, mt if not pt else 0.0))
+                m3 = rel(dm, p.euclidean_fitness_epsilon, p.euclidean_fitness_epsilon)
+                margin = min(margin, m3)
+                if dm < p.euclidean_fitness_epsilon:
+                    crit = ABS_MSE
+                else:
+                    m4 = rel(dm / mse_prev, p.mse_relative, p.mse_relative)
+                    margin = min(margin, m4)
+                    if dm / mse_prev < p.mse_relative:
+                        crit = REL_MSE
+        mse_prev = mse
+        rounds.append(dict(n_correspondences=ncorr, criterion=crit, mse=mse, cos_angle=cosa, translation_sqr=tsq))
+        if crit != NONE:
+            converged, criterion = True, crit
+            break
+    src = transform(pend[:3], src)
+    fidx, fd2 = tg.nearest(src)
+    got = fidx >= 0
+    fsel = fd2[got].astype(np.float64)
+    fitness = float(np.cumsum(fsel[::-1] if reverse else fsel)[-1] / got.sum()) if got.any() else DBL_MAX
+    pose6, pose_qt = result_pose(final)
+    return dict(converged=converged, accepted=bool(converged and fitness <= p.fitness_threshold), criterion=criterion, iterations=iterations, n_source=len(src),
+                n_target=len(tg.p), n_correspondences=ncorr, fitness=fitness, final_mse=mse, transform=final, pose6=pose6, pose_qt=pose_qt, rounds=rounds,
+                margin=float(margin), fitness_margin=abs(fitness - p.fitness_threshold), first_search=first_search, fitness_search=(fidx, fd2), final_source=src)
+
+
+def rotation_angle(M):
+    return math.acos(max(-1.0, min(1.0, 0.5 * (float(M[0, 0]) + float(M[1, 1]) + float(M[2, 2]) - 1.0))))
+
+
+def align_both(source, target, p=None, guess_qt=None):
+    """align() in both summation orders + `order_diff`: the restatement's own sensitivity to the order (translation, angle, fitness, per-round mse) and `stable`:
+    the two runs agree in iterations, criterion and verdict"""
+    a, b = align(source, target, p, guess_qt, False), align(source, target, p, guess_qt, True)
+    stable = a["iterations"] == b["iterations"] and a["criterion"] == b["criterion"] and a["accepted"] == b["accepted"] and a["converged"] == b["converged"]
+    nr = min(len(a["rounds"]), len(b["rounds"]))
+    a["order_diff"] = dict(translation=float(np.abs(a["transform"][:3, 3].astype(np.float64) - b["transform"][:3, 3]).max()),
+                           angle=abs(rotation_angle(a["transform"]) - rotation_angle(b["transform"])),
+                           fitness=abs(a["fitness"] - b["fitness"]),
+                           mse=max([abs(a["rounds"][i]["mse"] - b["rounds"][i]["mse"]) for i in range(nr)] or [0.0]))
+    a["stable"] = bool(stable)
+    return a
+
+
+def align_pair(clouds, poses6, prev, curr, p=None, guess_qt=None, both=True):
+    """icpCalculation for the pair: source = (curr, 0, prev), target = (prev, history, prev)"""
+    p = p or Params()
+    src, tgt = submap(clouds, poses6, curr, 0, prev, p), submap(clouds, poses6, prev, p.history_keyframes, prev, p)
+    return (align_both if both else align)(src, tgt, p, guess_qt)
+
+
+def loop_route(seed=5, n_first=48, step=2.0, radius=30.0, small=((4, 0.03, 0.15), (8, -0.04, -0.2), (12, 0.05, 0.1), (16, 0.02, -0.1), (20, -0.03, 0.2), (10, 0.04, 0.05), (14, -0.02, 0.12), (18, 0.035, -0.17)),
+               large=((6, 2.2, 0.2), (9, -2.6, -0.15), (13, 3.0, 0.1), (17, 1.9, -0.2)), rings=16, azimuths=360, n_poles=60):
+    """key frames `step` apart on an arc, then two kinds of revisit: `small` (place, yaw change, lateral offset) with a heading close to the first pass, so that the
+    identity guess succeeds, and `large` with a heading far from it. Every place is more than history_keyframes before the first revisit, so no target holds a revisit. Returns (clouds, poses6 [x y z roll pitch yaw], pairs [(prev, curr, kind)])."""
+    from vil_fusion_amd import synth
+    import sc_reference
+    scene = synth.LidarScene(seed, n_poles=n_poles, rings=rings, azimuths=azimuths)
+    spots = []
+    for k in range(n_first):
+        a = step * k / radius
+        spots.append((radius * math.cos(a), radius * math.sin(a), a + math.pi / 2))
+    pairs = []
+    for kind, lst in (("small", small), ("large", large)):
+        for place, dyaw, off in lst:
+            x, y, yaw = spots[place]
+            a = step * place / radius
+            pairs.append((place, len(spots), kind))
+            spots.append(((radius + off) * math.cos(a), (radius + off) * math.sin(a), yaw + dyaw))
+    clouds, poses = [], []
+    for x, y, yaw in spots:
+        R = synth.euler_R(np.array(yaw), np.array(0.0), np.array(0.0))
+        clouds.append(sc_reference.mount(scene.scan_raw(R, np.array([x, y, scene.h])), 0.0)[:, :4])
+        poses.append([x, y, scene.h, 0.0, 0.0, math.atan2(math.sin(yaw), math.cos(yaw))])
+    return clouds, np.array(poses), pairs

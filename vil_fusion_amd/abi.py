@@ -127,6 +127,29 @@ class ScResult(C.Structure):
     ]
 
 
+class IcpParams(C.Structure):
+    """vilf_icp_params: the constants of icpCalculation (poseGraphOptimization.cpp:394-414, :646-647) and of DefaultConvergenceCriteria"""
+    _fields_ = [
+        ("max_correspondence_distance", C.c_double), ("max_iterations", C.c_int), ("history_keyframes", C.c_int), ("transformation_epsilon", C.c_double),
+        ("euclidean_fitness_epsilon", C.c_double), ("rotation_threshold", C.c_double), ("mse_relative", C.c_double), ("fitness_threshold", C.c_double),
+        ("leaf_size", C.c_double), ("own_pose", C.c_int), ("pad_", C.c_int),
+    ]
+
+
+class IcpResult(C.Structure):
+    """vilf_icp_result"""
+    _fields_ = [
+        ("converged", C.c_int), ("accepted", C.c_int), ("criterion", C.c_int), ("iterations", C.c_int),
+        ("n_source", C.c_int), ("n_target", C.c_int), ("n_correspondences", C.c_int), ("pad_", C.c_int),
+        ("fitness", C.c_double), ("final_mse", C.c_double), ("transform", C.c_float * 16), ("pose6", C.c_double * 6), ("pose_qt", C.c_double * 7),
+    ]
+
+
+class IcpIter(C.Structure):
+    """vilf_icp_iter: one round"""
+    _fields_ = [("n_correspondences", C.c_int), ("criterion", C.c_int), ("mse", C.c_double), ("cos_angle", C.c_double), ("translation_sqr", C.c_double)]
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

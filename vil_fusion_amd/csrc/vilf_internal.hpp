@@ -54,6 +54,7 @@ struct FeatCtx;
 struct PgCtx;
 struct LwCtx;
 struct ScCtx;
+struct IcpCtx;
 
 // deep copy of a window snapshot (estimate_extrinsic / estimate_td: the batched entry points run the general single-window solve per slot and need the inputs again)
 struct OwnedWindow {
@@ -122,6 +123,7 @@ struct vilf_handle {
     PgCtx *pg = nullptr;                     // pose-graph workspace (vilf_pg.hip)
     LwCtx *lw = nullptr;                     // large-window solve workspace (vilf_lw.hip)
     ScCtx *sc = nullptr;                     // Scan Context descriptor database and search workspace (vilf_sc.hip)
+    IcpCtx *icp = nullptr;                   // key-frame cloud store and ICP workspace of the loop verification (vilf_icp.hip)
 };
 
 // a copy ordered on the handle's stream and waited for: the library's streams are non-blocking (they do not synchronise with the legacy default stream), so a plain
@@ -148,6 +150,8 @@ void vilf_feat_release(vilf_handle *h);
 void vilf_pg_release(vilf_handle *h);
 void vilf_lw_release(vilf_handle *h);
 void vilf_sc_release(vilf_handle *h);
+void vilf_icp_release(vilf_handle *h);
+void vilf_icp_profile_reset(vilf_handle *h);
 void vilf_sc_profile_reset(vilf_handle *h);                                 // vilf_set_profiling: the Scan Context spans start from zero
 int vilf_lw_chol_max_n();                                                      // largest n vilf_lw_chol_solve takes (its back substitution keeps the solution in LDS)
 int vilf_lw_chol_solve(vilf_handle *h, int n, double *S, double *y, int *info);   // blocked Cholesky solve on the handle's stream (vilf_lw.hip): S = [(n + 1) x n] row-major, row n = rhs

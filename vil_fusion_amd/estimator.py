@@ -425,6 +425,117 @@ class ScanContext:
         return dict(zip(("sc_descriptor", "sc_ringkey_topk", "sc_distance", "sc_reduce"), ((ms[i], cnt[i]) for i in range(4))))
 
 
+ICP_KERNELS = ("icp_bbox", "icp_leaf_keys", "radix_sort", "icp_voxel", "icp_cell_table", "icp_search", "icp_step", "unused")
+
+
+def icp_default_params(**over):
+    """vilf_icp_params with the reference's constants (poseGraphOptimization.cpp:394-414); keyword arguments replace fields (own_pose=1, max_iterations=30, ...)"""
+    p = abi.IcpParams()
+    lib().vilf_icp_default_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"vilf_icp_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def icp_result_dict(r):
+    return dict(converged=bool(r.converged), accepted=bool(r.accepted), criterion=r.criterion, iterations=r.iterations, n_source=r.n_source, n_target=r.n_target,
+                n_correspondences=r.n_correspondences, fitness=r.fitness, final_mse=r.final_mse, transform=np.array(r.transform, dtype=np.float32).reshape(4, 4),
+                pose6=np.array(r.pose6), pose_qt=np.array(r.pose_qt))
+
+
+class LoopICP:
+    """Host mirror of icpCalculation (global_fusion/poseGraphOptimization.cpp:376-443) over the key-frame cloud store of a BackendSolver handle (vilf_icp_*).
+    Clouds are (n, 3) or (n, 4) arrays; poses6 is (size, 6) [x y z roll pitch yaw], the KeyFramePosesUpdated of every stored key frame."""
+
+    def __init__(self, solver, cap_keyframes=4096, cap_points=1 << 24, params=None, **over):
+        self.s = solver
+        self._L = solver._L
+        self.params = params if params is not None else icp_default_params(**over)
+        self.s._check(self._L.vilf_icp_create(self.s._h, C.byref(self.params), int(cap_keyframes), int(cap_points)), "vilf_icp_create")
+
+    def __len__(self):
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_icp_size(self.s._h, C.byref(n)), "vilf_icp_size")
+        return n.value
+
+    def add_cloud(self, cloud):
+        """the cloud of the next key frame (thisKeyFrameDS). Returns its index."""
+        a = ScanContext._xyzi(cloud)
+        idx = C.c_int(-1)
+        self.s._check(self._L.vilf_icp_add_cloud(self.s._h, a.ctypes.data_as(C.POINTER(C.c_float)), len(a), C.byref(idx)), "vilf_icp_add_cloud")
+        return idx.value
+
+    def add_many(self, clouds):
+        """all clouds in one upload (vilf_icp_add_clouds). Returns the index of the first."""
+        cl = [ScanContext._xyzi(c) for c in clouds]
+        off = np.zeros(len(cl) + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(c) for c in cl])
+        pts = np.ascontiguousarray(np.concatenate(cl, axis=0)) if cl else np.zeros((0, 4), dtype=np.float32)
+        first = C.c_int(-1)
+        self.s._check(self._L.vilf_icp_add_clouds(self.s._h, len(cl), pts.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int)), C.byref(first)),
+                      "vilf_icp_add_clouds")
+        return first.value
+
+    def _poses(self, poses6):
+        p = np.ascontiguousarray(np.asarray(poses6, dtype=np.float64).reshape(-1, 6))
+        if len(p) < len(self):
+            raise ValueError(f"{len(p)} poses for {len(self)} stored key frames")
+        return p
+
+    def submap(self, key, submap_size, root, poses6):
+        """loopFindNearKeyframeCLoud(key, submap_size, root) :194-219 -> (n, 4) float32"""
+        p = self._poses(poses6)
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_icp_submap(self.s._h, int(key), int(submap_size), int(root), abi.dptr(p), None, 0, C.byref(n)), "vilf_icp_submap")
+        out = np.zeros((max(n.value, 1), 4), dtype=np.float32)
+        self.s._check(self._L.vilf_icp_submap(self.s._h, int(key), int(submap_size), int(root), abi.dptr(p), out.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)), "vilf_icp_submap")
+        return out[:n.value]
+
+    def align(self, prev, curr, poses6, guess_qt=None):
+        """the ICP of the pair (prev, curr) -> result dict (pose_qt is what PoseGraph.add_loop takes)"""
+        p = self._poses(poses6)
+        g = None if guess_qt is None else np.ascontiguousarray(np.asarray(guess_qt, dtype=np.float64).reshape(7))
+        r = abi.IcpResult()
+        self.s._check(self._L.vilf_icp_align(self.s._h, int(prev), int(curr), abi.dptr(p), abi.dptr(g), C.byref(r)), "vilf_icp_align")
+        return icp_result_dict(r)
+
+    def align_pairs(self, pairs, poses6, guesses_qt=None):
+        """all (prev, curr) pairs in one chain of launches -> list of result dicts, each identical to the single call"""
+        p = self._poses(poses6)
+        pr = np.ascontiguousarray(np.array([a for a, _ in pairs], dtype=np.int32))
+        cu = np.ascontiguousarray(np.array([b for _, b in pairs], dtype=np.int32))
+        g = None if guesses_qt is None else np.ascontiguousarray(np.asarray(guesses_qt, dtype=np.float64).reshape(len(pairs), 7))
+        arr = (abi.IcpResult * max(len(pairs), 1))()
+        ipt = C.POINTER(C.c_int)
+        self.s._check(self._L.vilf_icp_align_pairs(self.s._h, len(pairs), pr.ctypes.data_as(ipt), cu.ctypes.data_as(ipt), abi.dptr(p), abi.dptr(g), arr), "vilf_icp_align_pairs")
+        return [icp_result_dict(arr[i]) for i in range(len(pairs))]
+
+    def history(self, pair=0):
+        """the rounds of pair `pair` of the last align call, as a list of dicts"""
+        n = C.c_int(0)
+        arr = (abi.IcpIter * self.params.max_iterations)()
+        self.s._check(self._L.vilf_icp_get_history(self.s._h, int(pair), arr, self.params.max_iterations, C.byref(n)), "vilf_icp_get_history")
+        return [dict(n_correspondences=arr[i].n_correspondences, criterion=arr[i].criterion, mse=arr[i].mse, cos_angle=arr[i].cos_angle, translation_sqr=arr[i].translation_sqr)
+                for i in range(min(n.value, self.params.max_iterations))]
+
+    def search(self, pair=0, which=0):
+        """(nearest target index, d2) of every source point of pair `pair` of the last align call: which = 0 the first round, 1 the fitness pass"""
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_icp_get_search(self.s._h, int(pair), int(which), None, None, 0, C.byref(n)), "vilf_icp_get_search")
+        idx, d2 = np.zeros(max(n.value, 1), dtype=np.int32), np.zeros(max(n.value, 1), dtype=np.float32)
+        self.s._check(self._L.vilf_icp_get_search(self.s._h, int(pair), int(which), idx.ctypes.data_as(C.POINTER(C.c_int)), d2.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)),
+                      "vilf_icp_get_search")
+        return idx[:n.value], d2[:n.value]
+
+    def profile(self):
+        """ms and launches of the ICP kernels since vilf_set_profiling was switched on"""
+        ms, cnt = (C.c_double * 8)(), (C.c_long * 8)()
+        self.s._check(self._L.vilf_get_profile_icp(self.s._h, ms, cnt), "vilf_get_profile_icp")
+        return dict(zip(ICP_KERNELS[:7], ((ms[i], cnt[i]) for i in range(7))))
+
+
 class Scan2Map:
     """Host mirror of EstimationMapping (feature_tracker/include/EstimationMapping.hpp): localMapInited / optimation_processing /
     getMapCloud over the device path. One LiDAR stream per BackendSolver handle."""

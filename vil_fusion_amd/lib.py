@@ -20,6 +20,8 @@ EXPORTED = [
     "vilf_scan2map_batch_rewind", "vilf_scan2map_batch_copy_stream", "vilf_scan2map_batch_results", "vilf_scan2map_batch_get_map", "vilf_get_profile_scan2map", "vilf_get_profile_marginalize", "vilf_batch_marginalize_stats", "vilf_get_profile_large_window", "vilf_lidar_extract_features", "vilf_feature_depth",
     "vilf_comm_unique_id", "vilf_comm_create", "vilf_comm_destroy", "vilf_gather_poses", "vilf_gather_poses_handle", "vilf_comm_ranks", "vilf_get_stream", "vilf_comm_last_error",
     "vilf_sc_default_params", "vilf_sc_create", "vilf_sc_add_keyframe", "vilf_sc_add_keyframes", "vilf_sc_detect", "vilf_sc_detect_range", "vilf_sc_get", "vilf_sc_size", "vilf_get_profile_sc",
+    "vilf_icp_default_params", "vilf_icp_create", "vilf_icp_add_cloud", "vilf_icp_add_clouds", "vilf_icp_size", "vilf_icp_submap", "vilf_icp_align", "vilf_icp_align_pairs",
+    "vilf_icp_get_history", "vilf_icp_get_search", "vilf_get_profile_icp",
 ]
 
 
@@ -115,6 +117,18 @@ def lib():
     L.vilf_sc_get.argtypes = [vp, C.c_int, abi.c_double_p, fpp, abi.c_double_p]
     L.vilf_sc_size.argtypes = [vp, ip]
     L.vilf_get_profile_sc.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_icp_default_params.argtypes = [C.POINTER(abi.IcpParams)]
+    L.vilf_icp_default_params.restype = None
+    L.vilf_icp_create.argtypes = [vp, C.POINTER(abi.IcpParams), C.c_int, C.c_long]
+    L.vilf_icp_add_cloud.argtypes = [vp, fpp, C.c_int, ip]
+    L.vilf_icp_add_clouds.argtypes = [vp, C.c_int, fpp, ip, ip]
+    L.vilf_icp_size.argtypes = [vp, ip]
+    L.vilf_icp_submap.argtypes = [vp, C.c_int, C.c_int, C.c_int, abi.c_double_p, fpp, C.c_int, ip]
+    L.vilf_icp_align.argtypes = [vp, C.c_int, C.c_int, abi.c_double_p, abi.c_double_p, C.POINTER(abi.IcpResult)]
+    L.vilf_icp_align_pairs.argtypes = [vp, C.c_int, ip, ip, abi.c_double_p, abi.c_double_p, C.POINTER(abi.IcpResult)]
+    L.vilf_icp_get_history.argtypes = [vp, C.c_int, C.POINTER(abi.IcpIter), C.c_int, ip]
+    L.vilf_icp_get_search.argtypes = [vp, C.c_int, C.c_int, ip, fpp, C.c_int, ip]
+    L.vilf_get_profile_icp.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 

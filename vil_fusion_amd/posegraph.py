@@ -7,7 +7,9 @@ What the reference's threads do around gtsam, restated as plain host code over t
   * saveTUMTrajOdometry :88-110    `t x y z qx qy qz qw`, precision 9 / 5
   * makeAndSaveScancontextAndKeys :553, performSCLoopDetection :598-614   with a detector attached (estimator.ScanContext over the device database, vilf_sc_*):
                                    every key frame's cloud becomes a descriptor, detect_loop() names the pair to verify
-The ICP verification itself (:376-443, pcl::IterativeClosestPoint) is not part of this row: add_loop takes its transform from the caller.
+  * icpCalculation :376-443         with a verifier attached too (estimator.LoopICP over the device cloud store, vilf_icp_*): every key frame's cloud is stored,
+                                   verify_loop(prev, curr) aligns the pair under the current poses and adds the loop edge when the result is accepted;
+                                   close_loops() = detect_loop() + verify_loop(). Without a verifier add_loop takes its transform from the caller, as before.
 """
 import numpy as np
 
@@ -71,8 +73,9 @@ def diff_transformation(p1, p2):
 class PoseGraph:
     """`backend(poses[n,7], prior_sigma, edges) -> poses[n,7]` runs the solve (HIP: estimator.posegraph_optimize; tests: the oracle)."""
 
-    def __init__(self, backend, detector=None):
+    def __init__(self, backend, detector=None, verifier=None):
         self.backend = backend
+        self.verifier = verifier      # icpCalculation: anything with add_cloud(cloud) and align(prev, curr, poses6) -> dict(accepted, pose_qt, ...)
         self.detector = detector      # scManager: anything with makeAndSaveScancontextAndKeys(cloud) and detectLoopClosureID() -> (loop_id, yaw_diff_rad)
         self.translate_acc, self.rotation_acc = 1000000.0, 100000.0          # :50-51
         self.prev = np.zeros(6); self.curr = np.zeros(6)
@@ -80,8 +83,8 @@ class PoseGraph:
         self.edges = []               # (i, j, q, t, sigma, robust)
 
     def add_odometry(self, stamp, pose_qt, cloud=None):
-        """one synchronised odometry message (:483-587) with its down-sampled cloud (thisKeyFrameDS; used only with a detector attached, and then needed for every
-        message that becomes a key frame: detector index = key-frame index). Returns True if it became a key frame."""
+        """one synchronised odometry message (:483-587) with its down-sampled cloud (thisKeyFrameDS; used only with a detector or a verifier attached, and then needed
+        for every message that becomes a key frame: detector / store index = key-frame index). Returns True if it became a key frame."""
         pose_qt = np.asarray(pose_qt, dtype=np.float64)
         cur = np.concatenate([pose_qt[4:], rpy_from_q(pose_qt[:4])])
         self.prev, self.curr = self.curr, cur
@@ -92,9 +95,13 @@ class PoseGraph:
             return False
         if self.detector is not None and cloud is None:
             raise ValueError("a loop detector is attached: the message that becomes key frame %d needs its cloud" % len(self.nodes))
+        if self.verifier is not None and cloud is None:
+            raise ValueError("a loop verifier is attached: the message that becomes key frame %d needs its cloud" % len(self.nodes))
         self.translate_acc = self.rotation_acc = 0.0
         if self.detector is not None:
             self.detector.makeAndSaveScancontextAndKeys(cloud)              # :553
+        if self.verifier is not None:
+            self.verifier.add_cloud(cloud)                                  # KeyFrameClouds.push_back :551
         self.nodes.append(dict(stamp=float(stamp), pose=cur.copy(), updated=cur.copy()))
         k = len(self.nodes) - 1
         if k > 0:                                                           # BetweenFactor(prev, curr, poseFrom.between(poseTo), odomNoise) :577-584
@@ -113,6 +120,22 @@ class PoseGraph:
         """an accepted ICP alignment of key frame `curr` onto `prev` (:420-436): measured = poseFrom.between(identity) = poseFrom^-1"""
         m = inverse(np.asarray(icp_qt, dtype=np.float64))
         self.edges.append((int(prev), int(curr), m[:4], m[4:], LOOP_SIGMA, 1))
+
+    def verify_loop(self, prev, curr):
+        """icpCalculation (:390-437) for one queued pair under the current KeyFramePosesUpdated: the alignment's result; an accepted one becomes a loop edge"""
+        if self.verifier is None:
+            raise ValueError("no loop verifier attached")
+        res = self.verifier.align(int(prev), int(curr), np.array([n["updated"] for n in self.nodes]))
+        if res["accepted"]:
+            self.add_loop(prev, curr, res["pose_qt"])
+        return res
+
+    def close_loops(self):
+        """performSCLoopDetection + icpCalculation for the newest key frame: None without a candidate, else (prev, curr, result)"""
+        hit = self.detect_loop()
+        if hit is None:
+            return None
+        return hit[0], hit[1], self.verify_loop(hit[0], hit[1])
 
     @staticmethod
     def _qt(p6):
