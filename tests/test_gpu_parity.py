@@ -354,6 +354,45 @@ def test_asynchronous_upload_over_two_handles_gives_the_same_results(opts):
         h.close()
 
 
+def test_every_upload_path_puts_the_same_batch_on_the_device(opts, monkeypatch):
+    """The four ways an upload reaches the device — (a) B = 8: one host image + the span copy kernel, (b) B = 8 with VILF_NO_STAGED_UPLOAD=1: one packing pass + a copy per
+    array (the download takes its per-array arm too), (c) 96 slots: packed by the host threads, (d) 300 slots: packers overlapped with the copies of four chunks — each
+    with and without vilf_set_async_upload. Eight distinct windows (different feature counts: the padding up to Fmax / FACmax differs per window) with priors are uploaded,
+    solved, marginalized and downloaded; every slot i must return, to the bit, the state, the summary counts and the new prior that (a) returns for window i % 8."""
+    from vil_fusion_amd.estimator import BackendSolver
+    base = [synth.make_window(7100 + i, opts, synth.SynthConfig(n_features=40 + 23 * i, marginalization_flag=1 if i % 3 == 2 else 0)) for i in range(8)]
+    fields = ("para_pose", "para_speed_bias", "para_feature", "Ps", "Rs", "Vs", "Bas", "Bgs", "tic", "ric")
+
+    def run(s, n, no_staged):
+        if no_staged: monkeypatch.setenv("VILF_NO_STAGED_UPLOAD", "1")
+        try:
+            s.batch_upload([base[i % 8][0] for i in range(n)], [base[i % 8][1] for i in range(n)])
+            s.batch_solve(); s.batch_marginalize()
+            res, sums = s.batch_download(), s.batch_summaries()
+        finally:
+            if no_staged: monkeypatch.delenv("VILF_NO_STAGED_UPLOAD")
+        out = []
+        for i in range(n):
+            state = np.concatenate([np.asarray(getattr(res[i], k), dtype=np.float64).ravel() for k in fields] + [[res[i].td]])
+            counts = np.array([sums[i].num_iterations, sums[i].num_successful_steps, sums[i].num_linear_solves, sums[i].termination])
+            out.append((state, counts, np.frombuffer(bytes(s.get_prior(i)), dtype=np.uint8)))
+        return out
+
+    s = BackendSolver(opts)
+    try:
+        want = run(s, 8, False)
+        assert any(not np.array_equal(want[0][0][:77], want[i][0][:77]) for i in range(1, 8)), "the eight windows must differ"
+        for asynchronous in (False, True):
+            s.set_async_upload(asynchronous)
+            for arm, (n, no_staged) in dict(staged=(8, False), one_pass=(8, True), threaded=(96, False), chunked=(300, False)).items():
+                got = run(s, n, no_staged)
+                for i in range(n):
+                    for part, g, w in zip(("state", "summary counts", "prior"), got[i], want[i % 8]):
+                        assert np.array_equal(g, w), (arm, asynchronous, i, part)
+    finally:
+        s.close()
+
+
 def test_prior_factor_hook(solver, oracle, opts):
     """MarginalizationFactor::Evaluate on the device vs the oracle: residual r0 + J0 dx (quaternion sign flip) and J0 column blocks."""
     rng = np.random.default_rng(12)

@@ -12,16 +12,10 @@
 #include <cstdlib>
 #include <thread>
 #include <atomic>
+#include <type_traits>
 #include "vilf_internal.hpp"
 #include "vilf_kernels.hpp"
 #include "vilf_sort.hpp"
-
-// the batch descriptor's view of the live prior set (the two sets swap: vilf_batch_marginalize / vilf_batch_rewind)
-static void bind_prior_pointers(vilf_handle *h) {
-    VbBatch &b = h->batch;
-    b.prior_hdr = h->d[D_PHDR].as<int>(); b.prior_x0 = h->d[D_PX0].as<double>(); b.prior_J = h->d[D_PJ].as<double>(); b.prior_r = h->d[D_PR].as<double>();
-    b.prior_H = h->d[D_PH].as<double>(); b.prior_g = h->d[D_PG].as<double>();
-}
 
 namespace {
 
@@ -42,9 +36,6 @@ int class_plan(const vilf_window_in &in, int *cls, int *cstart, int *ccount) {
     const int longest = std::max(std::max(pos[0], pos[1]), std::max(pos[2], pos[3]));
     return VB_CHUNK * std::max(1, (longest + VB_CLS - 1) / VB_CLS);
 }
-
-// typed spans out of one (pinned) staging allocation, 64-byte aligned
-struct Carve { char *base; size_t off = 0; template <typename T> T *take(size_t n) { off = (off + 63) & ~(size_t)63; T *r = reinterpret_cast<T *>(base + off); off += n * sizeof(T); return r; } };
 
 void quat_from_R(const double *m, double *q /*xyzw*/) {   // Eigen Quaterniond(Matrix3d)
     double t = m[0] + m[4] + m[8];
@@ -240,8 +231,8 @@ static int pull_device_priors(vilf_handle *h) {
         HIPCHECK(h, vilf_copy_sync(h, hdr, h->d[D_PHDR].as<int>() + (size_t)w * VB_PRIOR_HDR, sizeof(hdr), hipMemcpyDeviceToHost));
         p.valid = hdr[0]; p.n = hdr[1]; p.n_blocks = hdr[2]; p.m = hdr[75];
         if (p.valid) {
-            std::vector<double> x0(24 * 9);
-            HIPCHECK(h, vilf_copy_sync(h, x0.data(), h->d[D_PX0].as<double>() + (size_t)w * 24 * 9, x0.size() * 8, hipMemcpyDeviceToHost));
+            std::vector<double> x0(VB_PRIOR_X0_LD);
+            HIPCHECK(h, vilf_copy_sync(h, x0.data(), h->d[D_PX0].as<double>() + (size_t)w * VB_PRIOR_X0_LD, x0.size() * 8, hipMemcpyDeviceToHost));
             for (int i = 0; i < p.n_blocks; i++) { p.block_id[i] = hdr[3 + i]; p.block_size[i] = hdr[27 + i]; p.block_idx[i] = hdr[51 + i]; for (int k = 0; k < 9; k++) p.block_x0[i][k] = x0[i * 9 + k]; }
             HIPCHECK(h, vilf_copy_sync(h, p.linearized_jacobians, h->d[D_PJ].as<double>() + (size_t)w * VB_PRIOR_LD * VB_PRIOR_LD, sizeof(double) * p.n * p.n, hipMemcpyDeviceToHost));
             HIPCHECK(h, vilf_copy_sync(h, p.linearized_residuals, h->d[D_PR].as<double>() + (size_t)w * VB_PRIOR_LD, sizeof(double) * p.n, hipMemcpyDeviceToHost));
@@ -270,7 +261,7 @@ static int upload_priors(vilf_handle *h) {
     }
     h->solve_dense_fallback = h->prior_dense_count > 0;      // recomputed with every upload: a later prior without such a block returns the handle to k_solve_sb
     auto fill = [&](const vilf_prior &p, int *hd, double *x0) {
-        std::memset(hd, 0, VB_PRIOR_HDR * sizeof(int)); std::memset(x0, 0, 24 * 9 * sizeof(double));
+        std::memset(hd, 0, VB_PRIOR_HDR * sizeof(int)); std::memset(x0, 0, VB_PRIOR_X0_LD * sizeof(double));
         if (!p.valid) return;
         hd[0] = 1; hd[1] = p.n; hd[2] = p.n_blocks; hd[75] = p.m;
         for (int i = 0; i < p.n_blocks; i++) {
@@ -280,14 +271,14 @@ static int upload_priors(vilf_handle *h) {
     };
     if ((int)dirty.size() * 4 > B) {          // most slots: one bulk copy per array
         std::vector<int> hdr((size_t)B * VB_PRIOR_HDR, 0);
-        std::vector<double> x0((size_t)B * 24 * 9, 0.0), J((size_t)B * VB_PRIOR_LD * VB_PRIOR_LD, 0.0), r((size_t)B * VB_PRIOR_LD, 0.0);
+        std::vector<double> x0((size_t)B * VB_PRIOR_X0_LD, 0.0), J((size_t)B * VB_PRIOR_LD * VB_PRIOR_LD, 0.0), r((size_t)B * VB_PRIOR_LD, 0.0);
         if ((int)dirty.size() < B) {           // keep what the other slots hold on the device
             { int rcp = pull_device_priors(h); if (rcp != VILF_OK) return rcp; }
             for (int w = 0; w < B; w++) h->prior_dirty[w] = 1;
         }
         for (int w = 0; w < B; w++) {
             const vilf_prior &p = h->priors[w];
-            fill(p, &hdr[(size_t)w * VB_PRIOR_HDR], &x0[(size_t)w * 24 * 9]);
+            fill(p, &hdr[(size_t)w * VB_PRIOR_HDR], &x0[(size_t)w * VB_PRIOR_X0_LD]);
             if (!p.valid) continue;
             std::memcpy(&J[(size_t)w * VB_PRIOR_LD * VB_PRIOR_LD], p.linearized_jacobians, sizeof(double) * p.n * p.n);
             std::memcpy(&r[(size_t)w * VB_PRIOR_LD], p.linearized_residuals, sizeof(double) * p.n);
@@ -300,10 +291,10 @@ static int upload_priors(vilf_handle *h) {
     } else {                                   // a few slots: per-slot copies
         for (int w : dirty) {
             const vilf_prior &p = h->priors[w];
-            int hd[VB_PRIOR_HDR]; double x0[24 * 9];
+            int hd[VB_PRIOR_HDR]; double x0[VB_PRIOR_X0_LD];
             fill(p, hd, x0);
             HIPCHECK(h, hipMemcpyAsync(h->d[D_PHDR].as<int>() + (size_t)w * VB_PRIOR_HDR, hd, sizeof(hd), hipMemcpyHostToDevice, h->stream));
-            HIPCHECK(h, hipMemcpyAsync(h->d[D_PX0].as<double>() + (size_t)w * 24 * 9, x0, sizeof(x0), hipMemcpyHostToDevice, h->stream));
+            HIPCHECK(h, hipMemcpyAsync(h->d[D_PX0].as<double>() + (size_t)w * VB_PRIOR_X0_LD, x0, sizeof(x0), hipMemcpyHostToDevice, h->stream));
             if (p.valid) {
                 HIPCHECK(h, hipMemcpyAsync(h->d[D_PJ].as<double>() + (size_t)w * VB_PRIOR_LD * VB_PRIOR_LD, p.linearized_jacobians, sizeof(double) * p.n * p.n, hipMemcpyHostToDevice, h->stream));
                 HIPCHECK(h, hipMemcpyAsync(h->d[D_PR].as<double>() + (size_t)w * VB_PRIOR_LD, p.linearized_residuals, sizeof(double) * p.n, hipMemcpyHostToDevice, h->stream));
@@ -318,347 +309,379 @@ static int upload_priors(vilf_handle *h) {
     return VILF_OK;
 }
 
+// ---- the window batch's device arrays ---------------------------------------------------------------------------------
+// One row per per-window array. Everything vilf_batch_upload does with an array — the device allocation, its span of the pinned staging, the per-window-range
+// copies, the job list of the staged copy kernel, the whole-batch copies of the small arrays — is derived from this table; bind_batch_arrays is the one other place
+// that lists the arrays (it names the VbBatch fields). A new uploaded array is an enum entry (vilf_internal.hpp), a row here, a line in bind_batch_arrays and
+// the packer's writes (pack_window).
+enum ArrayUse : uint8_t {
+    A_WINDOW,      // packed per window, copied per range of windows (large batches: the copies of a quarter overlap the packing of the next)
+    A_WINDOW_TD,   // the same with estimate_td; without it an 8-byte placeholder that nothing reads
+    A_SMALL,       // packed per window, copied as one whole-batch array once every window is packed
+    A_PRIOR,       // written by upload_priors / the marginalization; twin = the same array of the second prior set (allocated by the first marginalization)
+    A_WORK,        // not uploaded: trial point, workspace, results
+};
+struct BatchDims { size_t B, F, O, C; bool est_td; };      // windows, Fmax, Omax, FACmax of an upload
+struct ArrayRow {
+    int id; size_t elem;          // buffer; bytes per element
+    int k, f, o, c;               // elements per window = k + f Fmax + o Omax + c FACmax
+    ArrayUse use;
+    int twin = -1;                // a second buffer of the same size: of an uploaded array the *_init copy the same host span also seeds; of a prior array see A_PRIOR
+    int copies = 1;               // 2: one per linearisation workspace (VbState::ws)
+    size_t per_window(const BatchDims &d) const { return elem * (k + f * d.F + o * d.O + c * d.C); }
+    size_t bytes(const BatchDims &d) const { return use == A_WINDOW_TD && !d.est_td ? 8 : copies * d.B * per_window(d); }
+    bool by_range(const BatchDims &d) const { return use == A_WINDOW || (use == A_WINDOW_TD && d.est_td); }
+    bool uploaded(const BatchDims &d) const { return by_range(d) || use == A_SMALL; }
+};
+constexpr ArrayRow kBatchArrays[] = {
+    // uploaded per window, in the order their copies are enqueued
+    {D_POSE, 8, VB_POSE_LD, 0, 0, 0, A_WINDOW, D_POSE0}, {D_SB, 8, VB_SB_LD, 0, 0, 0, A_WINDOW, D_SB0}, {D_FEAT, 8, 0, 1, 0, 0, A_WINDOW, D_FEAT0},
+    {D_FSTART, 4, 0, 1, 0, 0, A_WINDOW}, {D_FNOBS, 4, 0, 1, 0, 0, A_WINDOW}, {D_FFAC0, 4, 0, 1, 0, 0, A_WINDOW}, {D_FCONST, 1, 0, 1, 0, 0, A_WINDOW}, {D_PSSLOT, 4, 0, 0, 0, 1, A_WINDOW},
+    {D_FOBS0, 4, 0, 1, 0, 0, A_WINDOW_TD}, {D_PSOBS, 4, 0, 0, 0, 1, A_WINDOW_TD},      // observation indices: only the td factors of k_marg_prepare look an observation up
+    {D_FACREC, 8, 0, 0, 0, 8, A_WINDOW}, {D_IMU, 8, VB_IMU_LD, 0, 0, 0, A_WINDOW}, {D_LIDAR, 8, VB_LIDAR_LD, 0, 0, 0, A_WINDOW}, {D_COV, 8, VB_COV_LD, 0, 0, 0, A_WINDOW},
+    {D_OBSV, 8, 0, 0, 2, 0, A_WINDOW_TD}, {D_OBSTD, 8, 0, 0, 1, 0, A_WINDOW_TD}, {D_OBSROW, 8, 0, 0, 1, 0, A_WINDOW_TD},
+    // uploaded whole, in that order
+    {D_NFEAT, 4, 1, 0, 0, 0, A_SMALL}, {D_NFAC, 4, 1, 0, 0, 0, A_SMALL}, {D_EX, 8, VB_EX_LD, 0, 0, 0, A_SMALL}, {D_GR0, 8, 9, 0, 0, 0, A_SMALL}, {D_GP0, 8, 3, 0, 0, 0, A_SMALL},
+    {D_PAIROFF, 4, VB_PTAB, 0, 0, 0, A_SMALL}, {D_MFLAG, 4, 1, 0, 0, 0, A_SMALL}, {D_TD, 8, 1, 0, 0, 0, A_SMALL},
+    // the two prior sets: live, and as uploaded (restored by vilf_batch_rewind after a marginalization)
+    {D_PHDR, 4, VB_PRIOR_HDR, 0, 0, 0, A_PRIOR, D_PHDR0}, {D_PX0, 8, VB_PRIOR_X0_LD, 0, 0, 0, A_PRIOR, D_PX00}, {D_PJ, 8, VB_PRIOR_LD * VB_PRIOR_LD, 0, 0, 0, A_PRIOR, D_PJ0},
+    {D_PR, 8, VB_PRIOR_LD, 0, 0, 0, A_PRIOR, D_PR0}, {D_PH, 8, VB_PRIOR_LD * VB_PRIOR_LD, 0, 0, 0, A_PRIOR, D_PH0}, {D_PG, 8, VB_PRIOR_LD, 0, 0, 0, A_PRIOR, D_PG0},
+    // trial point, workspace, results
+    {D_CPOSE, 8, VB_POSE_LD, 0, 0, 0, A_WORK}, {D_CSB, 8, VB_SB_LD, 0, 0, 0, A_WORK}, {D_CFEAT, 8, 0, 1, 0, 0, A_WORK}, {D_CF, 8, 0, 1, 0, 0, A_WORK},
+    {D_FACW, 8, 0, 0, 0, VB_FACW, A_WORK}, {D_HPP, 8, 66 * 36, 0, 0, 0, A_WORK, -1, 2}, {D_W, 8, 0, VB_WLD, 0, 0, A_WORK, -1, 2}, {D_HF, 8, 0, 1, 0, 0, A_WORK, -1, 2},
+    {D_GF, 8, 0, 1, 0, 0, A_WORK, -1, 2}, {D_IMUH, 8, 9000, 0, 0, 0, A_WORK, -1, 2}, {D_IMUG, 8, 300, 0, 0, 0, A_WORK, -1, 2}, {D_LIDH, 8, 1440, 0, 0, 0, A_WORK, -1, 2},
+    {D_LIDG, 8, 120, 0, 0, 0, A_WORK, -1, 2}, {D_G, 8, VB_P, 0, 0, 0, A_WORK, -1, 2}, {D_DIAGH, 8, VB_P, 0, 0, 0, A_WORK, -1, 2}, {D_PAIRD, 8, VB_NPAIR * VB_PAIRD, 0, 0, 0, A_WORK, -1, 2},
+    {D_SCALE, 8, VB_P, 1, 0, 0, A_WORK}, {D_DIAG, 8, VB_P, 1, 0, 0, A_WORK}, {D_GRAD, 8, VB_P, 1, 0, 0, A_WORK}, {D_GN, 8, VB_P, 1, 0, 0, A_WORK},
+    {D_ST, sizeof(VbState), 1, 0, 0, 0, A_WORK}, {D_OPS, 8, VB_OUT3_LD, 0, 0, 0, A_WORK}, {D_ORS, 8, VB_OUTR_LD, 0, 0, 0, A_WORK}, {D_OVS, 8, VB_OUT3_LD, 0, 0, 0, A_WORK},
+    {D_OBAS, 8, VB_OUT3_LD, 0, 0, 0, A_WORK}, {D_OBGS, 8, VB_OUT3_LD, 0, 0, 0, A_WORK}, {D_WORK, 8, 10 * 450, 0, 0, 0, A_WORK},
+};
+constexpr int upload_destinations() { int n = 0; for (const ArrayRow &r : kBatchArrays) if (r.use <= A_SMALL) n += 1 + (r.twin >= 0); return n; }
+static_assert(upload_destinations() <= (int)(sizeof(UpJobs::j) / sizeof(UpJob)), "the staged upload hands every destination to ONE launch of k_copy_spans");
+static size_t batch_array_bytes(int id, const BatchDims &d) { for (const ArrayRow &r : kBatchArrays) if (r.id == id) return r.bytes(d); return 0; }
+
+// the batch descriptor's view of the live prior set, and the swap of the two sets (vilf_batch_marginalize / vilf_batch_rewind: no copy)
+static void bind_prior_pointers(vilf_handle *h) {
+    VbBatch &b = h->batch;
+    b.prior_hdr = h->d[D_PHDR].as<int>(); b.prior_x0 = h->d[D_PX0].as<double>(); b.prior_J = h->d[D_PJ].as<double>(); b.prior_r = h->d[D_PR].as<double>();
+    b.prior_H = h->d[D_PH].as<double>(); b.prior_g = h->d[D_PG].as<double>();
+}
+static void swap_prior_sets(vilf_handle *h) {
+    for (const ArrayRow &r : kBatchArrays) if (r.use == A_PRIOR) std::swap(h->d[r.id], h->d[r.twin]);
+    bind_prior_pointers(h);
+}
+// qil = Quaterniond(RIC*RCL), til = RIC*TCL + TIC (lidar_factor.h:28-29)
+static void lidar_extrinsic(const vilf_options &o, VbBatch &b) {
+    double M[9];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M[3 * i + j] = o.RIC[3 * i] * o.RCL[j] + o.RIC[3 * i + 1] * o.RCL[3 + j] + o.RIC[3 * i + 2] * o.RCL[6 + j];
+    quat_from_R(M, b.qil);
+    for (int i = 0; i < 3; i++) b.til[i] = o.RIC[3 * i] * o.TCL[0] + o.RIC[3 * i + 1] * o.TCL[1] + o.RIC[3 * i + 2] * o.TCL[2] + o.TIC[i];
+}
+// the batch descriptor: options, sizes and the typed pointers into the arrays of the table
+static void bind_batch_arrays(vilf_handle *h, const BatchDims &dm) {
+    VbBatch &b = h->batch;
+    std::memset(&b, 0, sizeof(b));          // (obs, ps_feat, dbg, the live / split lists: null)
+    const vilf_options &o = h->opts;
+    b.B = (int)dm.B; b.w0 = 0; b.Fmax = (int)dm.F; b.Omax = (int)dm.O; b.FACmax = (int)dm.C;
+    b.sqrt_info = o.focal_length / 1.5; b.cauchy_b = o.cauchy_a * o.cauchy_a;
+    for (int i = 0; i < 3; i++) b.G[i] = o.G[i];
+    lidar_extrinsic(o, b);
+    b.use_lidar = o.use_lidar_const; b.max_iterations = o.max_num_iterations;
+    b.min_relative_decrease = 1e-3; b.function_tolerance = 1e-6; b.gradient_tolerance = 1e-10; b.parameter_tolerance = 1e-8;
+    b.min_radius = 1e-32; b.initial_radius = 1e4; b.min_lm_diagonal = 1e-6; b.max_lm_diagonal = 1e32;
+    b.est_td = o.estimate_td ? 1 : 0; b.tr_over_row = o.TR / o.ROW; b.row_half = o.ROW / 2;
+    DBuf *d = h->d;
+    b.n_feat = d[D_NFEAT].as<int>(); b.n_fac = d[D_NFAC].as<int>(); b.pose = d[D_POSE].as<double>(); b.sb = d[D_SB].as<double>(); b.feat = d[D_FEAT].as<double>();
+    b.cand_pose = d[D_CPOSE].as<double>(); b.cand_sb = d[D_CSB].as<double>(); b.cand_feat = d[D_CFEAT].as<double>();
+    b.pose_init = d[D_POSE0].as<double>(); b.sb_init = d[D_SB0].as<double>(); b.feat_init = d[D_FEAT0].as<double>();
+    b.ex = d[D_EX].as<double>(); b.gauge_R0 = d[D_GR0].as<double>(); b.gauge_P0 = d[D_GP0].as<double>(); b.td = d[D_TD].as<double>();
+    b.f_start = d[D_FSTART].as<int>(); b.f_nobs = d[D_FNOBS].as<int>(); b.f_obs0 = d[D_FOBS0].as<int>(); b.f_fac0 = d[D_FFAC0].as<int>(); b.f_const = d[D_FCONST].as<uint8_t>();
+    b.obs_vel = d[D_OBSV].as<double>(); b.obs_ctd = d[D_OBSTD].as<double>(); b.obs_row = d[D_OBSROW].as<double>(); b.ps_obs = d[D_PSOBS].as<int>(); b.ps_slot = d[D_PSSLOT].as<int>();
+    b.pair_off = d[D_PAIROFF].as<int>(); b.facrec = d[D_FACREC].as<double>(); b.imu = d[D_IMU].as<double>(); b.lidar = d[D_LIDAR].as<double>();
+    bind_prior_pointers(h);
+    b.facw = d[D_FACW].as<double>(); b.Hpp = d[D_HPP].as<double>(); b.W = d[D_W].as<double>(); b.hf = d[D_HF].as<double>(); b.gf = d[D_GF].as<double>(); b.cf = d[D_CF].as<double>();
+    b.imuH = d[D_IMUH].as<double>(); b.imug = d[D_IMUG].as<double>(); b.lidH = d[D_LIDH].as<double>(); b.lidg = d[D_LIDG].as<double>(); b.g = d[D_G].as<double>();
+    b.diagH = d[D_DIAGH].as<double>(); b.pairD = d[D_PAIRD].as<double>(); b.scale = d[D_SCALE].as<double>(); b.diag = d[D_DIAG].as<double>(); b.grad = d[D_GRAD].as<double>(); b.gn = d[D_GN].as<double>();
+    b.st = d[D_ST].as<VbState>(); b.out_Ps = d[D_OPS].as<double>(); b.out_Rs = d[D_ORS].as<double>(); b.out_Vs = d[D_OVS].as<double>(); b.out_Bas = d[D_OBAS].as<double>(); b.out_Bgs = d[D_OBGS].as<double>();
+    b.sb_tab = d[D_SBTAB].as<int>();
+}
+
+// ---- vilf_batch_upload, stage by stage ------------------------------------------------------------------------------------
+namespace {
+struct Lap {        // VILF_DEBUG_TIMING: host time of every phase of an upload to stderr (tools/dev_upload_timing.py)
+    const bool on = std::getenv("VILF_DEBUG_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void operator()(const char *what) { if (on) { const auto now = std::chrono::steady_clock::now(); fprintf(stderr, "[vilf_batch_upload] %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count()); t = now; } }
+};
+// what the stages of one upload share: the caller's windows, the batch maxima, and each uploaded array's span of the pinned staging
+struct Upload {
+    vilf_handle *h; const vilf_window_in *wins;
+    int nthr;                       // host threads of the validation and the packing
+    BatchDims dims;
+    bool keep_inputs;               // estimate_extrinsic / estimate_td: the batched solve runs the general path per slot and needs the inputs again (OwnedWindow)
+    char *image; size_t image_bytes;      // the pinned staging; its bytes in use, rounded up to 64
+    size_t at[D_COUNT], ld[D_COUNT];      // per buffer id: where its span starts in the image (uploaded arrays only), bytes per window
+    template <typename T> T *row(int id, int w) const { return reinterpret_cast<T *>(image + at[id] + (size_t)w * ld[id]); }
+};
+// validation of one window; nullptr = accepted. *mf: its features that start in frame 0 (the marginalization drops them with the oldest frame)
+const char *check_window(const vilf_options &o, const vilf_window_in &in, int *mf) {
+    if (in.n_frames != VB_NF) return "n_frames must be window_size + 1 = 11";
+    if (in.n_features < 0 || in.n_features > VILF_MAX_FEATURES) return "n_features out of range";
+    if (!in.para_pose || !in.para_speed_bias || !in.imu || (in.n_features && (!in.para_feature || !in.feature_const || !in.feature_start_frame || !in.feature_obs_offset || !in.obs_point)))
+        return "null input array";
+    if (o.use_lidar_const && !in.lidar) return "lidar constraints missing (use_lidar_const = 1)";
+    if (o.estimate_td && in.n_features && (!in.obs_velocity || !in.obs_cur_td || !in.obs_row)) return "estimate_td needs obs_velocity / obs_cur_td / obs_row";
+    // the observation CSR must be exactly [0 .. n_obs): the packer indexes obs_point / the factor arrays through it
+    if (in.n_obs < 0 || (in.n_features && (in.feature_obs_offset[0] != 0 || in.feature_obs_offset[in.n_features] != in.n_obs)) || (!in.n_features && in.n_obs != 0))
+        return "feature_obs_offset must start at 0 and end at n_obs";
+    *mf = 0;
+    for (int f = 0; f < in.n_features; f++) {
+        const int s = in.feature_start_frame[f], n = in.feature_obs_offset[f + 1] - in.feature_obs_offset[f];     // n >= 2 also makes the offsets increasing
+        if (s < 0 || n < 2 || s + n > VB_NF) return "feature track outside the window";
+        if (s == 0) (*mf)++;
+    }
+    return nullptr;
+}
+// Stage 1: validation, the class plan of every window (h->plans, kept for the packer) and the batch-wide maxima (u.dims, h->mg_Mcap), on the host threads: one thread
+// took 4.3 of the 16.5 ms a 2048-window upload cost
+int plan_windows(Upload &u, int B) {
+    vilf_handle *h = u.h;
+    struct Local { int F = 4, O = 4, C = 4, M = 2; const char *err = nullptr; };
+    std::vector<Local> loc(u.nthr);
+    h->plans.resize(B);
+    auto check = [&](int t) {
+        Local &L = loc[t];
+        for (int w = t; w < B; w += u.nthr) {
+            const vilf_window_in &in = u.wins[w]; int mf = 0;
+            if (const char *msg = check_window(h->opts, in, &mf)) { if (!L.err) L.err = msg; continue; }
+            WindowPlan &pl = h->plans[w];
+            pl.nslot = class_plan(in, pl.cls, pl.cstart, pl.ccount);
+            L.C = std::max(L.C, pl.nslot); L.F = std::max(L.F, in.n_features); L.O = std::max(L.O, in.n_obs); L.M = std::max(L.M, MG_MD + mf + 1);
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < u.nthr; t++) pool.emplace_back(check, t);
+    check(0);                                    // (the calling thread takes a share)
+    for (std::thread &th : pool) th.join();
+    Local m;
+    for (const Local &L : loc) {
+        if (L.err) { h->err = L.err; return VILF_ERR_INVALID_ARGUMENT; }
+        m.F = std::max(m.F, L.F); m.O = std::max(m.O, L.O); m.C = std::max(m.C, L.C); m.M = std::max(m.M, L.M);
+    }
+    u.dims = BatchDims{(size_t)B, (size_t)((m.F + 3) & ~3), (size_t)m.O, (size_t)((m.C + 63) & ~63), h->opts.estimate_td != 0};
+    h->mg_Mcap = (m.M + 1) & ~1;
+    return VILF_OK;
+}
+// Stage 2: the device buffers of the table (the second prior set is the marginalization's) and the persistent PINNED staging, one 64-byte-aligned span per
+// uploaded array: allocating and zero-filling ~250 MB of std::vectors per call was half of the upload time, and copies from pageable memory are neither fast nor
+// asynchronous. Every slice a kernel reads is rewritten by pack_window; padding is never read.
+int reserve(Upload &u, Lap &lap) {
+    vilf_handle *h = u.h;
+    size_t off = 0;
+    for (const ArrayRow &r : kBatchArrays) {
+        const size_t bytes = r.bytes(u.dims);
+        if (!h->d[r.id].ensure(bytes) || (r.twin >= 0 && r.use != A_PRIOR && !h->d[r.twin].ensure(bytes))) { h->err = "hipMalloc failed"; return VILF_ERR_DEVICE; }
+        u.ld[r.id] = r.per_window(u.dims);
+        if (!r.uploaded(u.dims)) continue;
+        u.at[r.id] = off = (off + 63) & ~(size_t)63;
+        off += u.dims.B * u.ld[r.id];
+    }
+    lap("validate + device buffers");
+    u.image_bytes = (off + 63) & ~(size_t)63;
+    if (!h->pin_up.ensure(off + 64)) { h->err = "hipHostMalloc failed (upload staging)"; return VILF_ERR_DEVICE; }
+    u.image = static_cast<char *>(h->pin_up.p);
+    // the host's own mirrors of what the read-back needs without a copy; the retained inputs
+    h->h_nfeat.assign(u.dims.B, 0); h->h_ex.assign(u.dims.B * VB_EX_LD, 0.0); h->h_td.assign(u.dims.B, 0.0);
+    h->own.clear(); h->own.resize(u.keep_inputs ? u.dims.B : 0);
+    lap("host vectors");
+    return VILF_OK;
+}
+void fill_imu_rec(const vilf_imu_preint &p, double *rec) {      // the raw part of an IMU record (layout: vilf_device.hpp); rec[287], the factor's weight, is the caller's
+    rec[0] = p.sum_dt;
+    for (int i = 0; i < 3; i++) { rec[1 + i] = p.delta_p[i]; rec[8 + i] = p.delta_v[i]; rec[11 + i] = p.linearized_ba[i]; rec[14 + i] = p.linearized_bg[i]; }
+    for (int i = 0; i < 4; i++) rec[4 + i] = p.delta_q[i];
+    auto blk = [&](int off, int r0, int c0) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) rec[off + 3 * i + j] = p.jacobian[(r0 + i) * 15 + c0 + j]; };
+    blk(17, 0, 9); blk(26, 0, 12); blk(35, 3, 12); blk(44, 6, 9); blk(53, 6, 12);
+}
+void retain_window(OwnedWindow &o, const vilf_window_in &in) {      // deep copy: the caller's arrays need not outlive the upload
+    const size_t F = in.n_features, O = in.n_obs;
+    auto keep = [](auto &v, auto *&p, size_t n) { if (p) { v.assign(p, p + n); p = v.empty() ? nullptr : v.data(); } };      // the copy's pointer follows its data
+    o.in = in;
+    keep(o.pose, o.in.para_pose, VB_POSE_LD); keep(o.sb, o.in.para_speed_bias, VB_SB_LD); keep(o.feat, o.in.para_feature, F); keep(o.fconst, o.in.feature_const, F);
+    keep(o.fstart, o.in.feature_start_frame, F); keep(o.foff, o.in.feature_obs_offset, F + 1); keep(o.obs, o.in.obs_point, 3 * O);
+    keep(o.vel, o.in.obs_velocity, 2 * O); keep(o.ctd, o.in.obs_cur_td, O); keep(o.row, o.in.obs_row, O);
+    keep(o.imu, o.in.imu, VB_NF); keep(o.lidar, o.in.lidar, VB_NF); keep(o.gR0, o.in.gauge_R0, 9); keep(o.gP0, o.in.gauge_P0, 3);
+}
+// Stage 3: one window into its slices of the staging (and of the host mirrors). A window writes its own slices only: safe from several host threads.
+void pack_window(const Upload &u, int w) {
+    vilf_handle *h = u.h;
+    const vilf_window_in &in = u.wins[w];
+    const int F = in.n_features;
+    *u.row<int>(D_NFEAT, w) = F; h->h_nfeat[w] = F; *u.row<int>(D_MFLAG, w) = in.marginalization_flag;
+    *u.row<double>(D_TD, w) = in.para_td; h->h_td[w] = in.para_td;
+    std::memcpy(u.row<double>(D_POSE, w), in.para_pose, VB_POSE_LD * 8); std::memcpy(u.row<double>(D_SB, w), in.para_speed_bias, VB_SB_LD * 8);
+    std::memcpy(u.row<double>(D_EX, w), in.para_ex_pose, VB_EX_LD * 8); std::memcpy(&h->h_ex[(size_t)w * VB_EX_LD], in.para_ex_pose, VB_EX_LD * 8);
+    if (in.gauge_R0) std::memcpy(u.row<double>(D_GR0, w), in.gauge_R0, 72); else quat_to_R(in.para_pose + 3, u.row<double>(D_GR0, w));
+    std::memcpy(u.row<double>(D_GP0, w), in.gauge_P0 ? in.gauge_P0 : in.para_pose, 24);
+    if (u.dims.est_td && in.n_obs) {
+        std::memcpy(u.row<double>(D_OBSV, w), in.obs_velocity, (size_t)in.n_obs * 16);
+        std::memcpy(u.row<double>(D_OBSTD, w), in.obs_cur_td, (size_t)in.n_obs * 8);
+        std::memcpy(u.row<double>(D_OBSROW, w), in.obs_row, (size_t)in.n_obs * 8);
+    }
+    if (u.keep_inputs) retain_window(h->own[w], in);
+    // the pair table and the factor slots: null records first (flag bit 17; the kernels sweep slots), then every factor at the next slot of its pair's class list
+    const WindowPlan &pl = h->plans[w];
+    *u.row<int>(D_NFAC, w) = pl.nslot;
+    int cur[VB_NPAIR], *po = u.row<int>(D_PAIROFF, w);
+    for (int p = 0; p < VB_NPAIR; p++) { po[2 * p] = pl.cstart[p]; po[2 * p + 1] = pl.ccount[p] | (pl.cls[p] << 24); cur[p] = pl.cstart[p]; }
+    po[2 * VB_NPAIR] = 0; po[2 * VB_NPAIR + 1] = 0;
+    double *facrec = u.row<double>(D_FACREC, w), *feat = u.row<double>(D_FEAT, w);
+    int *psslot = u.row<int>(D_PSSLOT, w), *fstart = u.row<int>(D_FSTART, w), *fnobs = u.row<int>(D_FNOBS, w), *ffac0 = u.row<int>(D_FFAC0, w);
+    int *psobs = u.dims.est_td ? u.row<int>(D_PSOBS, w) : nullptr, *fobs0 = u.dims.est_td ? u.row<int>(D_FOBS0, w) : nullptr;
+    uint8_t *fconst = u.row<uint8_t>(D_FCONST, w);
+    const unsigned long long nul = 1ULL << 17;
+    for (int g = 0; g < pl.nslot; g++) { double *rec = &facrec[(size_t)g * 8]; for (int k = 0; k < 7; k++) rec[k] = 0.0; std::memcpy(&rec[7], &nul, 8); psslot[g] = 0; if (psobs) psobs[g] = 0; }
+    int q = 0;                                            // factor index in feature-major order
+    for (int f = 0; f < F; f++) {
+        const int o0 = in.feature_obs_offset[f], o1 = in.feature_obs_offset[f + 1], s = in.feature_start_frame[f], cst = in.feature_const[f] ? 1 : 0;
+        feat[f] = in.para_feature[f]; fconst[f] = (uint8_t)cst; fstart[f] = s; fnobs[f] = o1 - o0; ffac0[f] = q;
+        if (fobs0) fobs0[f] = o0;
+        const double *pi = in.obs_point + 3 * (size_t)o0;
+        for (int t = o0 + 1; t < o1; t++, q++) {
+            const int j = s + (t - o0), p = j * (j - 1) / 2 + s, pos = VB_SLOT(pl.cls[p], cur[p]);
+            cur[p]++; psslot[pos] = q;
+            if (psobs) psobs[pos] = t;
+            double *rec = &facrec[(size_t)pos * 8]; const double *pj = in.obs_point + 3 * (size_t)t;
+            for (int k = 0; k < 3; k++) { rec[k] = pi[k]; rec[3 + k] = pj[k]; }
+            const unsigned long long a = (unsigned long long)(unsigned)f | ((unsigned long long)(unsigned)q << 32);
+            const unsigned long long b2 = (unsigned long long)s | ((unsigned long long)j << 8) | ((unsigned long long)cst << 16);
+            std::memcpy(&rec[6], &a, 8); std::memcpy(&rec[7], &b2, 8);
+        }
+    }
+    for (int k = 0; k < 10; k++) {
+        const vilf_imu_preint &p = in.imu[k + 1];
+        double *rec = u.row<double>(D_IMU, w) + (size_t)k * IMU_REC, *l = u.row<double>(D_LIDAR, w) + 7 * k;
+        fill_imu_rec(p, rec);
+        rec[287] = (p.sum_dt > 10.0) ? 0.0 : 1.0;                           // estimator.cpp:745
+        std::memcpy(u.row<double>(D_COV, w) + 225 * k, p.covariance, 225 * 8);
+        if (in.lidar) { const vilf_lidar_constraint &c = in.lidar[k + 1]; for (int i = 0; i < 4; i++) l[i] = c.q[i]; for (int i = 0; i < 3; i++) l[4 + i] = c.t[i]; }
+        else for (int i = 0; i < 7; i++) l[i] = (i == 3) ? 1.0 : 0.0;
+    }
+}
+// Stage 4: pack and copy. The per-window arrays of windows [w0, w1), every one a single copy (two where the same span also seeds the *_init copy) ...
+int copy_windows(const Upload &u, int w0, int w1) {
+    vilf_handle *h = u.h;
+    for (const ArrayRow &r : kBatchArrays) {
+        if (!r.by_range(u.dims)) continue;
+        const size_t at = (size_t)w0 * u.ld[r.id], bytes = (size_t)(w1 - w0) * u.ld[r.id];
+        const char *src = u.image + u.at[r.id] + at;
+        HIPCHECK(h, hipMemcpyAsync(h->d[r.id].as<char>() + at, src, bytes, hipMemcpyHostToDevice, h->stream));
+        if (r.twin >= 0) HIPCHECK(h, hipMemcpyAsync(h->d[r.twin].as<char>() + at, src, bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    return VILF_OK;
+}
+// ... by one of three strategies. staged (a small batch): the whole host image in ONE copy, k_copy_spans hands its spans out to the arrays (see there). One pass: pack, a
+// copy per array. Large batches: packing and copying overlap — the windows are packed in order by the host threads (an atomic cursor), and as soon as every window of a
+// quarter of the batch is done the calling thread enqueues that quarter's slices, so the DMA engine works while the threads pack the next part (pack 5.1 ms + copy 6.6 ms one
+// after the other before; eight parts: no better — 200 copy calls of the calling thread compete with the packers).
+int pack_and_copy(const Upload &u, bool staged, Lap &lap) {
+    vilf_handle *h = u.h;
+    const int B = (int)u.dims.B;
+    const int nchunk = (u.nthr > 1 && B >= 256) ? 4 : 1, csz = (B + nchunk - 1) / nchunk;
+    std::atomic<int> next(0);
+    std::vector<std::atomic<int>> done(nchunk); for (auto &d : done) d.store(0);
+    auto packer = [&]() { for (int w = next.fetch_add(1); w < B; w = next.fetch_add(1)) { pack_window(u, w); done[w / csz].fetch_add(1, std::memory_order_release); } };
+    std::vector<std::thread> pool;
+    if (u.nthr <= 1) packer();
+    else for (int t = 0; t < u.nthr; t++) pool.emplace_back(packer);
+    int rc = VILF_OK;
+    for (int c = 0; c < nchunk && !staged; c++) {
+        const int w0 = c * csz, w1 = std::min(B, w0 + csz);
+        while (done[c].load(std::memory_order_acquire) < w1 - w0) std::this_thread::yield();
+        if (rc == VILF_OK) rc = copy_windows(u, w0, w1);
+    }
+    for (std::thread &th : pool) th.join();
+    if (rc != VILF_OK) return rc;
+    lap("pack + per-window copies");
+    if (staged) {
+        UpJobs jobs; jobs.n = 0; size_t big = 0;
+        for (const ArrayRow &r : kBatchArrays) {
+            if (!r.uploaded(u.dims)) continue;
+            const size_t bytes = u.dims.B * u.ld[r.id];
+            const char *src = h->d[D_UPSTAGE].as<char>() + u.at[r.id];
+            jobs.j[jobs.n++] = UpJob{src, h->d[r.id].as<char>(), bytes};
+            if (r.twin >= 0) jobs.j[jobs.n++] = UpJob{src, h->d[r.twin].as<char>(), bytes};
+            big = std::max(big, bytes);
+        }
+        HIPCHECK(h, hipMemcpyAsync(h->d[D_UPSTAGE].p, u.image, u.image_bytes, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_copy_spans, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(64, big / 65536 + 1)), (unsigned)jobs.n), dim3(256), 0, h->stream, jobs);
+        HIPCHECK(h, hipGetLastError());
+    } else {
+        // (from the pinned image, like everything else: an asynchronous upload must not read pageable memory the next call rewrites)
+        for (const ArrayRow &r : kBatchArrays)
+            if (r.use == A_SMALL) HIPCHECK(h, hipMemcpyAsync(h->d[r.id].p, u.image + u.at[r.id], u.dims.B * u.ld[r.id], hipMemcpyHostToDevice, h->stream));
+        if (!h->async_upload) HIPCHECK(h, hipStreamSynchronize(h->stream));
+    }
+    lap("small arrays + sync");
+    return VILF_OK;
+}
+// Stage 6, once per handle: the static scatter tables of the tile assembly (same for every window): source element -> LDS offset
+int build_scatter_tables(vilf_handle *h) {
+    auto perm = [](int a, int l) { return l < 6 ? 6 * a + l : 66 + 9 * a + (l - 6); };
+    // packed entry: bits 0..14 = LDS offset + 1 (0: element not stored, upper block triangle), bits 15..22 = row, bits 23..30 = column
+    auto off1 = [](int r, int c) { const int tr = r >> 4, tc = c >> 4; if (tr < tc) return 0; return (tr * (tr + 1) / 2 + tc) * 256 + 16 * (r & 15) + ((c & 15) ^ (r & 15)) + 1; };
+    auto off = [&](int r, int c) { return off1(r, c) | (r << 15) | (c << 23); };
+    std::vector<int> li(9000), ll(1440), lv(2 * 2376);
+    for (int k = 0; k < 10; k++) {
+        for (int e = 0; e < 900; e++) { const int p = e / 30, q = e % 30; li[900 * k + e] = off(perm(k + p / 15, p % 15), perm(k + q / 15, q % 15)); }
+        for (int e = 0; e < 144; e++) { const int p = e / 12, q = e % 12; ll[144 * k + e] = off(perm(k + p / 6, p % 6), perm(k + q / 6, q % 6)); }
+    }
+    for (int t = 0; t < 2376; t++) {
+        const int blk = t / 36, e = t % 36, l = e / 6, m = e % 6;
+        int a = 0; while ((a + 1) * (a + 2) / 2 <= blk) a++;
+        const int bb = blk - a * (a + 1) / 2, r = 6 * a + l, c = 6 * bb + m;
+        lv[2 * t] = off(r, c);
+        lv[2 * t + 1] = (a != bb && (r >> 4) == (c >> 4)) ? off1(c, r) : 0;
+    }
+    if (!h->d[D_LUTI].ensure(li.size() * 4) || !h->d[D_LUTL].ensure(ll.size() * 4) || !h->d[D_LUTV].ensure(lv.size() * 4)) return VILF_ERR_DEVICE;
+    HIPCHECK(h, vilf_copy_sync(h, h->d[D_LUTI].p, li.data(), li.size() * 4, hipMemcpyHostToDevice));
+    HIPCHECK(h, vilf_copy_sync(h, h->d[D_LUTL].p, ll.data(), ll.size() * 4, hipMemcpyHostToDevice));
+    HIPCHECK(h, vilf_copy_sync(h, h->d[D_LUTV].p, lv.data(), lv.size() * 4, hipMemcpyHostToDevice));
+    h->luts_ready = true;
+    return VILF_OK;
+}
+
+}  // namespace
+
 extern "C" int vilf_batch_upload(vilf_handle *h, int B, const vilf_window_in *wins) {
     if (!h || B <= 0 || !wins) return VILF_ERR_INVALID_ARGUMENT;
-    const bool timing = std::getenv("VILF_DEBUG_TIMING") != nullptr;
-    auto tnow = []() { return std::chrono::steady_clock::now(); };
-    auto t_a = tnow();
-    auto lap = [&](const char *what) { if (timing) { auto t = tnow(); fprintf(stderr, "[vilf_batch_upload] %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_a).count()); t_a = t; } };
+    Lap lap;
     HIPCHECK(h, hipSetDevice(h->device));
     if (h->upload_inflight) { HIPCHECK(h, hipStreamSynchronize(h->stream)); h->upload_inflight = false; }      // vilf_set_async_upload: the last upload's copies may still read the staging
     // the device-resident priors of slots 0..B-1 survive this call unless the slot range grows (buffers may be re-allocated)
     const bool keep_priors = h->resident && B <= h->prior_slots_valid;
     if (!keep_priors) { int rcp = pull_device_priors(h); if (rcp != VILF_OK) return rcp; }
-    // validation, the class plan of every window (kept for the packer) and the batch-wide maxima, on the host threads: one thread took 4.3 of the 16.5 ms
-    // a 2048-window upload cost
-    int Fmax = 4, Omax = 4, FACmax = 4, Mcap = 2;
-    const int nthr = B >= 64 ? (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency())) : 1;
-    h->plans.resize(B);
-    {
-        struct Local { int Fmax = 4, Omax = 4, FACmax = 4, Mcap = 2, rc = VILF_OK; const char *err = nullptr; };
-        std::vector<Local> loc(nthr);
-        auto check = [&](int t) {
-            Local &L = loc[t];
-            auto fail = [&](const char *msg, int rc) { if (L.rc == VILF_OK) { L.rc = rc; L.err = msg; } };
-            for (int w = t; w < B; w += nthr) {
-                const vilf_window_in &in = wins[w];
-                if (in.n_frames != VB_NF) { fail("n_frames must be window_size + 1 = 11", VILF_ERR_INVALID_ARGUMENT); continue; }
-                if (in.n_features < 0 || in.n_features > VILF_MAX_FEATURES) { fail("n_features out of range", VILF_ERR_INVALID_ARGUMENT); continue; }
-                if (!in.para_pose || !in.para_speed_bias || !in.imu || (in.n_features && (!in.para_feature || !in.feature_const || !in.feature_start_frame || !in.feature_obs_offset || !in.obs_point))) {
-                    fail("null input array", VILF_ERR_INVALID_ARGUMENT); continue;
-                }
-                if (h->opts.use_lidar_const && !in.lidar) { fail("lidar constraints missing (use_lidar_const = 1)", VILF_ERR_INVALID_ARGUMENT); continue; }
-                if (h->opts.estimate_td && in.n_features && (!in.obs_velocity || !in.obs_cur_td || !in.obs_row)) { fail("estimate_td needs obs_velocity / obs_cur_td / obs_row", VILF_ERR_INVALID_ARGUMENT); continue; }
-                // the observation CSR must be exactly [0 .. n_obs): the packer indexes obs_point / the factor arrays through it
-                if (in.n_obs < 0 || (in.n_features && (in.feature_obs_offset[0] != 0 || in.feature_obs_offset[in.n_features] != in.n_obs)) || (!in.n_features && in.n_obs != 0)) {
-                    fail("feature_obs_offset must start at 0 and end at n_obs", VILF_ERR_INVALID_ARGUMENT); continue;
-                }
-                bool ok = true;
-                int mf = 0;
-                for (int f = 0; f < in.n_features; f++) {
-                    const int s = in.feature_start_frame[f], n = in.feature_obs_offset[f + 1] - in.feature_obs_offset[f];     // n >= 2 also makes the offsets increasing
-                    if (s < 0 || n < 2 || s + n > VB_NF) { ok = false; break; }
-                    if (s == 0) mf++;
-                }
-                if (!ok) { fail("feature track outside the window", VILF_ERR_INVALID_ARGUMENT); continue; }
-                WindowPlan &pl = h->plans[w];
-                pl.nslot = class_plan(in, pl.cls, pl.cstart, pl.ccount);
-                L.FACmax = std::max(L.FACmax, pl.nslot); L.Fmax = std::max(L.Fmax, in.n_features); L.Omax = std::max(L.Omax, in.n_obs); L.Mcap = std::max(L.Mcap, MG_MD + mf + 1);
-            }
-        };
-        if (nthr <= 1) check(0);
-        else {
-            std::vector<std::thread> pool;
-            for (int t = 0; t < nthr; t++) pool.emplace_back(check, t);
-            for (std::thread &th : pool) th.join();
-        }
-        for (const Local &L : loc) {
-            if (L.rc != VILF_OK) { h->err = L.err; return L.rc; }
-            Fmax = std::max(Fmax, L.Fmax); Omax = std::max(Omax, L.Omax); FACmax = std::max(FACmax, L.FACmax); Mcap = std::max(Mcap, L.Mcap);
-        }
-    }
-    Fmax = (Fmax + 3) & ~3; FACmax = (FACmax + 63) & ~63;
-    h->B = B;
-    h->resident = false;
+    Upload u{};
+    u.h = h; u.wins = wins; u.keep_inputs = h->opts.estimate_extrinsic || h->opts.estimate_td;
+    u.nthr = B >= 64 ? (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency())) : 1;
+    int rc = plan_windows(u, B);
+    if (rc != VILF_OK) return rc;
+    h->B = B; h->resident = false;
     if ((int)h->priors.size() < B) { vilf_prior z; std::memset(&z, 0, sizeof(z)); h->priors.resize(B, z); }
     if (!keep_priors) { h->prior_dirty.assign(h->priors.size(), 1); h->prior_dev_newer.assign(h->priors.size(), 0); h->prior_slots_valid = 0; }
     h->prior_dirty.resize(h->priors.size(), 1); h->prior_dev_newer.resize(h->priors.size(), 0);
-    h->h_mflag.resize(B);
-    for (int w = 0; w < B; w++) h->h_mflag[w] = wins[w].marginalization_flag;
-    Mcap = (Mcap + 1) & ~1;
-    h->mg_Mcap = Mcap;
-    const size_t sB = B, sF = Fmax, sO = Omax, sC = FACmax;
-    struct Req { int id; size_t bytes; };
-    const Req reqs[] = {
-        {D_NFEAT, sB * 4}, {D_NFAC, sB * 4}, {D_POSE, sB * 77 * 8}, {D_SB, sB * 99 * 8}, {D_FEAT, sB * sF * 8}, {D_CPOSE, sB * 77 * 8}, {D_CSB, sB * 99 * 8},
-        {D_CFEAT, sB * sF * 8}, {D_POSE0, sB * 77 * 8}, {D_SB0, sB * 99 * 8}, {D_FEAT0, sB * sF * 8}, {D_EX, sB * 7 * 8}, {D_GR0, sB * 9 * 8}, {D_GP0, sB * 3 * 8},
-        {D_FSTART, sB * sF * 4}, {D_FNOBS, sB * sF * 4}, {D_FOBS0, sB * sF * 4}, {D_FFAC0, sB * sF * 4}, {D_FCONST, sB * sF}, {D_OBS, sB * sO * 3 * 8},
-        {D_PSFEAT, sB * sC * 4}, {D_PSOBS, sB * sC * 4}, {D_PSSLOT, sB * sC * 4}, {D_PAIROFF, sB * VB_PTAB * 4}, {D_IMU, sB * 10 * IMU_REC * 8},
-        {D_LIDAR, sB * 10 * 7 * 8}, {D_PHDR, sB * VB_PRIOR_HDR * 4}, {D_PX0, sB * 24 * 9 * 8}, {D_PJ, sB * VB_PRIOR_LD * VB_PRIOR_LD * 8}, {D_PR, sB * VB_PRIOR_LD * 8},
-        {D_PH, sB * VB_PRIOR_LD * VB_PRIOR_LD * 8}, {D_PG, sB * VB_PRIOR_LD * 8}, {D_FACW, sB * VB_FACW * sC * 8}, {D_HPP, 2 * sB * 66 * 36 * 8},      // 2 x: the two linearisation workspaces (VbState::ws)
-        {D_W, 2 * sB * sF * VB_WLD * 8}, {D_HF, 2 * sB * sF * 8}, {D_GF, 2 * sB * sF * 8}, {D_IMUH, 2 * sB * 9000 * 8}, {D_IMUG, 2 * sB * 300 * 8}, {D_LIDH, 2 * sB * 1440 * 8},
-        {D_LIDG, 2 * sB * 120 * 8}, {D_G, 2 * sB * VB_P * 8}, {D_DIAGH, 2 * sB * VB_P * 8}, {D_SCALE, sB * (VB_P + sF) * 8}, {D_DIAG, sB * (VB_P + sF) * 8}, {D_GRAD, sB * (VB_P + sF) * 8},
-        {D_GN, sB * (VB_P + sF) * 8}, {D_ST, sB * sizeof(VbState)}, {D_OPS, sB * 33 * 8}, {D_ORS, sB * 99 * 8}, {D_OVS, sB * 33 * 8}, {D_OBAS, sB * 33 * 8},
-        {D_OBGS, sB * 33 * 8}, {D_PAIRD, 2 * sB * VB_NPAIR * VB_PAIRD * 8}, {D_FACREC, sB * sC * 64}, {D_CF, sB * sF * 8}, {D_TD, sB * 8},
-        {D_OBSV, h->opts.estimate_td ? sB * sO * 16 : 8}, {D_OBSTD, h->opts.estimate_td ? sB * sO * 8 : 8}, {D_OBSROW, h->opts.estimate_td ? sB * sO * 8 : 8}, {D_COV, sB * 10 * 225 * 8}, {D_WORK, sB * 10 * 450 * 8}, {D_MFLAG, sB * 4},
-    };
-    for (const Req &r : reqs) if (!h->d[r.id].ensure(r.bytes)) { h->err = "hipMalloc failed"; return VILF_ERR_DEVICE; }
-
-    lap("validate + device buffers");
-    // ---- pack on the host ---------------------------------------------------------------------------------------
-    // persistent PINNED staging carved into typed spans: allocating and zero-filling ~250 MB of std::vectors per call was half of the upload time, and copies
-    // from pageable memory are neither fast nor asynchronous. Every slice a kernel reads is rewritten by pack_one; padding is never read.
-    const bool est_td0 = h->opts.estimate_td != 0;
-    int *nfeat, *nfac, *fstart, *fnobs, *fobs0, *ffac0, *facfeat, *facobs, *pairoff, *psfeat, *psobs, *psslot;
-    uint8_t *fconst;
-    double *pose, *sb, *feat, *ex, *gR0, *gP0, *imu, *lidar, *cov, *facrec, *obsv = nullptr, *obstd = nullptr, *obsrow = nullptr, *td_img = nullptr;
-    int *mflag_img = nullptr;
-    auto carve_all = [&](Carve &cv) {          // the same sequence sizes the allocation (base = 0) and hands out the spans
-        mflag_img = cv.take<int>(sB); td_img = cv.take<double>(sB);
-        nfeat = cv.take<int>(sB); nfac = cv.take<int>(sB); fstart = cv.take<int>(sB * sF); fnobs = cv.take<int>(sB * sF); fobs0 = cv.take<int>(sB * sF); ffac0 = cv.take<int>(sB * sF);
-        facfeat = cv.take<int>(sB * sC); facobs = cv.take<int>(sB * sC); pairoff = cv.take<int>(sB * VB_PTAB); psfeat = cv.take<int>(sB * sC); psobs = cv.take<int>(sB * sC); psslot = cv.take<int>(sB * sC);
-        fconst = cv.take<uint8_t>(sB * sF);
-        pose = cv.take<double>(sB * 77); sb = cv.take<double>(sB * 99); feat = cv.take<double>(sB * sF); ex = cv.take<double>(sB * 7); gR0 = cv.take<double>(sB * 9); gP0 = cv.take<double>(sB * 3);
-        imu = cv.take<double>(sB * 10 * IMU_REC); lidar = cv.take<double>(sB * 10 * 7); cov = cv.take<double>(sB * 10 * 225); facrec = cv.take<double>(sB * sC * 8);
-        if (est_td0) { obsv = cv.take<double>(sB * sO * 2); obstd = cv.take<double>(sB * sO); obsrow = cv.take<double>(sB * sO); }
-    };
-    size_t image_bytes = 0;
-    { Carve sz{nullptr}; carve_all(sz); image_bytes = (sz.off + 63) & ~(size_t)63; if (!h->pin_up.ensure(sz.off + 64)) { h->err = "hipHostMalloc failed (upload staging)"; return VILF_ERR_DEVICE; } }
-    { Carve cv{static_cast<char *>(h->pin_up.p)}; carve_all(cv); }
-    h->h_nfeat.assign(B, 0); h->h_ex.assign(sB * 7, 0.0); h->h_td.assign(B, 0.0);
-    const bool est_any = h->opts.estimate_extrinsic || h->opts.estimate_td, est_td = est_td0;
-    h->own.clear();
-    if (est_any) h->own.resize(B);
-    lap("host vectors");
-    auto pack_one = [&](int w) {        // every window writes its own slices only: packed by several host threads below
-        const vilf_window_in &in = wins[w];
-        const int F = in.n_features;
-        nfeat[w] = F; h->h_nfeat[w] = F;
-        std::memcpy(&pose[(size_t)w * 77], in.para_pose, 77 * 8);
-        std::memcpy(&sb[(size_t)w * 99], in.para_speed_bias, 99 * 8);
-        std::memcpy(&ex[(size_t)w * 7], in.para_ex_pose, 7 * 8);
-        std::memcpy(&h->h_ex[(size_t)w * 7], in.para_ex_pose, 7 * 8);
-        h->h_td[w] = in.para_td;
-        if (in.gauge_R0) std::memcpy(&gR0[(size_t)w * 9], in.gauge_R0, 72); else quat_to_R(in.para_pose + 3, &gR0[(size_t)w * 9]);
-        if (in.gauge_P0) std::memcpy(&gP0[(size_t)w * 3], in.gauge_P0, 24); else std::memcpy(&gP0[(size_t)w * 3], in.para_pose, 24);
-        if (est_td && in.n_obs) {
-            std::memcpy(&obsv[(size_t)w * sO * 2], in.obs_velocity, (size_t)in.n_obs * 16);
-            std::memcpy(&obstd[(size_t)w * sO], in.obs_cur_td, (size_t)in.n_obs * 8);
-            std::memcpy(&obsrow[(size_t)w * sO], in.obs_row, (size_t)in.n_obs * 8);
-        }
-        if (est_any) {                  // the batched solve of these options runs the general path per slot: keep the inputs
-            OwnedWindow &o = h->own[w];
-            o.in = in;
-            o.pose.assign(in.para_pose, in.para_pose + 77); o.sb.assign(in.para_speed_bias, in.para_speed_bias + 99);
-            o.feat.assign(in.para_feature, in.para_feature + F); o.fconst.assign(in.feature_const, in.feature_const + F);
-            o.fstart.assign(in.feature_start_frame, in.feature_start_frame + F); o.foff.assign(in.feature_obs_offset, in.feature_obs_offset + F + 1);
-            o.obs.assign(in.obs_point, in.obs_point + 3 * (size_t)in.n_obs);
-            if (in.obs_velocity) o.vel.assign(in.obs_velocity, in.obs_velocity + 2 * (size_t)in.n_obs);
-            if (in.obs_cur_td) o.ctd.assign(in.obs_cur_td, in.obs_cur_td + in.n_obs);
-            if (in.obs_row) o.row.assign(in.obs_row, in.obs_row + in.n_obs);
-            o.imu.assign(in.imu, in.imu + VB_NF);
-            if (in.lidar) o.lidar.assign(in.lidar, in.lidar + VB_NF);
-            if (in.gauge_R0) o.gR0.assign(in.gauge_R0, in.gauge_R0 + 9);
-            if (in.gauge_P0) o.gP0.assign(in.gauge_P0, in.gauge_P0 + 3);
-            o.in.para_pose = o.pose.data(); o.in.para_speed_bias = o.sb.data(); o.in.para_feature = o.feat.data(); o.in.feature_const = o.fconst.data();
-            o.in.feature_start_frame = o.fstart.data(); o.in.feature_obs_offset = o.foff.data(); o.in.obs_point = o.obs.data();
-            o.in.obs_velocity = o.vel.empty() ? nullptr : o.vel.data(); o.in.obs_cur_td = o.ctd.empty() ? nullptr : o.ctd.data(); o.in.obs_row = o.row.empty() ? nullptr : o.row.data();
-            o.in.imu = o.imu.data(); o.in.lidar = o.lidar.empty() ? nullptr : o.lidar.data();
-            o.in.gauge_R0 = o.gR0.empty() ? nullptr : o.gR0.data(); o.in.gauge_P0 = o.gP0.empty() ? nullptr : o.gP0.data();
-        }
-        int fac = 0;
-        for (int f = 0; f < F; f++) {
-            const int o0 = in.feature_obs_offset[f], o1 = in.feature_obs_offset[f + 1], s = in.feature_start_frame[f];
-            feat[(size_t)w * sF + f] = in.para_feature[f];
-            fconst[(size_t)w * sF + f] = in.feature_const[f] ? 1 : 0;
-            fstart[(size_t)w * sF + f] = s; fnobs[(size_t)w * sF + f] = o1 - o0; fobs0[(size_t)w * sF + f] = o0; ffac0[(size_t)w * sF + f] = fac;
-            for (int t = o0 + 1; t < o1; t++) { facfeat[(size_t)w * sC + fac] = f; facobs[(size_t)w * sC + fac] = t; fac++; }
-        }
-        const WindowPlan &pl = h->plans[w];
-        const int *cls = pl.cls, *cstart = pl.cstart, *ccount = pl.ccount, nslot = pl.nslot;
-        int cur[VB_NPAIR];
-        nfac[w] = nslot;                                   // the kernels sweep slots; unused ones carry a null record
-        int *po = &pairoff[(size_t)w * VB_PTAB];
-        for (int p = 0; p < VB_NPAIR; p++) { po[2 * p] = cstart[p]; po[2 * p + 1] = ccount[p] | (cls[p] << 24); cur[p] = cstart[p]; }
-        po[2 * VB_NPAIR] = 0; po[2 * VB_NPAIR + 1] = 0;
-        {   // null records first (flag bit 17), then the factors at their slots
-            const unsigned long long nul = 1ULL << 17;
-            for (int g = 0; g < nslot; g++) { double *rec = &facrec[((size_t)w * sC + g) * 8]; for (int k = 0; k < 7; k++) rec[k] = 0.0; std::memcpy(&rec[7], &nul, 8); psslot[(size_t)w * sC + g] = 0; psobs[(size_t)w * sC + g] = 0; }
-        }
-        for (int q = 0; q < fac; q++) {
-            const int f = facfeat[(size_t)w * sC + q], t = facobs[(size_t)w * sC + q];
-            const int s = in.feature_start_frame[f], j = s + (t - in.feature_obs_offset[f]), p = j * (j - 1) / 2 + s;
-            const int pos = VB_SLOT(cls[p], cur[p]); cur[p]++;
-            psfeat[(size_t)w * sC + pos] = f; psobs[(size_t)w * sC + pos] = t; psslot[(size_t)w * sC + pos] = q;
-            double *rec = &facrec[((size_t)w * sC + pos) * 8];
-            const double *pi = in.obs_point + 3 * (size_t)in.feature_obs_offset[f], *pj = in.obs_point + 3 * (size_t)t;
-            for (int k = 0; k < 3; k++) { rec[k] = pi[k]; rec[3 + k] = pj[k]; }
-            const unsigned long long a = (unsigned long long)(unsigned)f | ((unsigned long long)(unsigned)q << 32);
-            const unsigned long long b2 = (unsigned long long)s | ((unsigned long long)j << 8) | ((unsigned long long)(in.feature_const[f] ? 1 : 0) << 16);
-            std::memcpy(&rec[6], &a, 8); std::memcpy(&rec[7], &b2, 8);
-        }
-        for (int k = 0; k < 10; k++) {
-            const vilf_imu_preint &p = in.imu[k + 1];
-            double *rec = &imu[((size_t)w * 10 + k) * IMU_REC];
-            rec[0] = p.sum_dt;
-            for (int i = 0; i < 3; i++) { rec[1 + i] = p.delta_p[i]; rec[8 + i] = p.delta_v[i]; rec[11 + i] = p.linearized_ba[i]; rec[14 + i] = p.linearized_bg[i]; }
-            for (int i = 0; i < 4; i++) rec[4 + i] = p.delta_q[i];
-            auto blk = [&](int off, int r0, int c0) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) rec[off + 3 * i + j] = p.jacobian[(r0 + i) * 15 + c0 + j]; };
-            blk(17, 0, 9); blk(26, 0, 12); blk(35, 3, 12); blk(44, 6, 9); blk(53, 6, 12);
-            rec[287] = (p.sum_dt > 10.0) ? 0.0 : 1.0;                           // estimator.cpp:745
-            std::memcpy(&cov[((size_t)w * 10 + k) * 225], p.covariance, 225 * 8);
-            if (in.lidar) { const vilf_lidar_constraint &c = in.lidar[k + 1]; double *l = &lidar[((size_t)w * 10 + k) * 7]; for (int i = 0; i < 4; i++) l[i] = c.q[i]; for (int i = 0; i < 3; i++) l[4 + i] = c.t[i]; }
-            else { double *l = &lidar[((size_t)w * 10 + k) * 7]; for (int i = 0; i < 7; i++) l[i] = (i == 3) ? 1.0 : 0.0; }
-        }
-    };
-    // Packing and copying overlap: the windows are packed in order by the host threads (an atomic cursor), and as soon as every window of a quarter of the batch
-    // is done the main thread enqueues that part's slices of the per-window arrays — the DMA engine works while the threads pack the next part
-    // (pack 5.1 ms + copy 6.6 ms one after the other before).
-    auto upr = [&](int id, const void *src, size_t per_window_bytes, int w0, int w1) {
-        return hipMemcpyAsync(static_cast<char *>(h->d[id].p) + (size_t)w0 * per_window_bytes, static_cast<const char *>(src) + (size_t)w0 * per_window_bytes, (size_t)(w1 - w0) * per_window_bytes, hipMemcpyHostToDevice, h->stream);
-    };
-    auto copy_range = [&](int w0, int w1) -> int {
-        HIPCHECK(h, upr(D_POSE, pose, 77 * 8, w0, w1)); HIPCHECK(h, upr(D_POSE0, pose, 77 * 8, w0, w1));
-        HIPCHECK(h, upr(D_SB, sb, 99 * 8, w0, w1)); HIPCHECK(h, upr(D_SB0, sb, 99 * 8, w0, w1));
-        HIPCHECK(h, upr(D_FEAT, feat, sF * 8, w0, w1)); HIPCHECK(h, upr(D_FEAT0, feat, sF * 8, w0, w1));
-        HIPCHECK(h, upr(D_FSTART, fstart, sF * 4, w0, w1)); HIPCHECK(h, upr(D_FNOBS, fnobs, sF * 4, w0, w1));
-        HIPCHECK(h, upr(D_FFAC0, ffac0, sF * 4, w0, w1)); HIPCHECK(h, upr(D_FCONST, fconst, sF, w0, w1));
-        HIPCHECK(h, upr(D_PSSLOT, psslot, sC * 4, w0, w1));                                   // (obs points and the factor -> feature / observation maps travel inside facrec; the
-        if (est_td) { HIPCHECK(h, upr(D_FOBS0, fobs0, sF * 4, w0, w1)); HIPCHECK(h, upr(D_PSOBS, psobs, sC * 4, w0, w1)); }   //  observation indices are only needed by the td factors)
-        HIPCHECK(h, upr(D_FACREC, facrec, sC * 64, w0, w1));
-        HIPCHECK(h, upr(D_IMU, imu, 10 * IMU_REC * 8, w0, w1)); HIPCHECK(h, upr(D_LIDAR, lidar, 10 * 7 * 8, w0, w1));
-        HIPCHECK(h, upr(D_COV, cov, 10 * 225 * 8, w0, w1));
-        if (est_td) { HIPCHECK(h, upr(D_OBSV, obsv, sO * 16, w0, w1)); HIPCHECK(h, upr(D_OBSTD, obstd, sO * 8, w0, w1)); HIPCHECK(h, upr(D_OBSROW, obsrow, sO * 8, w0, w1)); }
-        return VILF_OK;
-    };
-    // a small batch: one copy of the whole host image + k_copy_spans (see there)
-    const bool staged = nthr <= 1 && image_bytes <= ((size_t)64 << 20) && !std::getenv("VILF_NO_STAGED_UPLOAD") && h->d[D_UPSTAGE].ensure(image_bytes + 4096);
-    UpJobs jobs; jobs.n = 0;
-    auto span = [&](int id, const void *src, size_t bytes) {          // a span of the image -> the whole of a library array
-        UpJob &jb = jobs.j[jobs.n++];
-        jb.src = h->d[D_UPSTAGE].as<char>() + (static_cast<const char *>(src) - static_cast<const char *>(h->pin_up.p)); jb.dst = static_cast<char *>(h->d[id].p); jb.bytes = bytes;
-    };
-    {
-        const int nchunk = (nthr > 1 && B >= 256) ? 4 : 1, csz = (B + nchunk - 1) / nchunk;      // (eight parts: no better — 200 copy calls of the main thread compete with the packers)
-        if (staged) {
-            for (int w = 0; w < B; w++) pack_one(w);
-            span(D_POSE, pose, sB * 77 * 8); span(D_POSE0, pose, sB * 77 * 8); span(D_SB, sb, sB * 99 * 8); span(D_SB0, sb, sB * 99 * 8);
-            span(D_FEAT, feat, sB * sF * 8); span(D_FEAT0, feat, sB * sF * 8);
-            span(D_FSTART, fstart, sB * sF * 4); span(D_FNOBS, fnobs, sB * sF * 4); span(D_FFAC0, ffac0, sB * sF * 4); span(D_FCONST, fconst, sB * sF);
-            span(D_PSSLOT, psslot, sB * sC * 4);
-            if (est_td) { span(D_FOBS0, fobs0, sB * sF * 4); span(D_PSOBS, psobs, sB * sC * 4); }
-            span(D_FACREC, facrec, sB * sC * 64);
-            span(D_IMU, imu, sB * 10 * IMU_REC * 8); span(D_LIDAR, lidar, sB * 10 * 7 * 8); span(D_COV, cov, sB * 10 * 225 * 8);
-            if (est_td) { span(D_OBSV, obsv, sB * sO * 16); span(D_OBSTD, obstd, sB * sO * 8); span(D_OBSROW, obsrow, sB * sO * 8); }
-        }
-        else if (nthr <= 1) { for (int w = 0; w < B; w++) pack_one(w); const int rcc = copy_range(0, B); if (rcc != VILF_OK) return rcc; }
-        else {
-            std::atomic<int> next(0);
-            std::vector<std::atomic<int>> done(nchunk);
-            for (auto &d : done) d.store(0);
-            std::vector<std::thread> pool;
-            for (int t = 0; t < nthr; t++) pool.emplace_back([&]() { for (int w = next.fetch_add(1); w < B; w = next.fetch_add(1)) { pack_one(w); done[w / csz].fetch_add(1, std::memory_order_release); } });
-            int rcc = VILF_OK;
-            for (int c = 0; c < nchunk; c++) {
-                const int w0 = c * csz, w1 = std::min(B, w0 + csz);
-                while (done[c].load(std::memory_order_acquire) < w1 - w0) std::this_thread::yield();
-                if (rcc == VILF_OK) rcc = copy_range(w0, w1);
-            }
-            for (std::thread &th : pool) th.join();
-            if (rcc != VILF_OK) return rcc;
-        }
-    }
-    lap("pack + per-window copies");
-    auto up = [&](int id, const void *src, size_t bytes) { return hipMemcpyAsync(h->d[id].p, src, bytes, hipMemcpyHostToDevice, h->stream); };
-    if (staged) {
-        std::memcpy(mflag_img, h->h_mflag.data(), sB * 4); std::memcpy(td_img, h->h_td.data(), sB * 8);
-        span(D_NFEAT, nfeat, sB * 4); span(D_NFAC, nfac, sB * 4); span(D_EX, ex, sB * 7 * 8); span(D_GR0, gR0, sB * 9 * 8); span(D_GP0, gP0, sB * 3 * 8);
-        span(D_PAIROFF, pairoff, sB * VB_PTAB * 4); span(D_MFLAG, mflag_img, sB * 4); span(D_TD, td_img, sB * 8);
-        HIPCHECK(h, hipMemcpyAsync(h->d[D_UPSTAGE].p, h->pin_up.p, image_bytes, hipMemcpyHostToDevice, h->stream));
-        size_t big = 0; for (int k = 0; k < jobs.n; k++) big = std::max<size_t>(big, jobs.j[k].bytes);
-        hipLaunchKernelGGL(k_copy_spans, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(64, big / 65536 + 1)), (unsigned)jobs.n), dim3(256), 0, h->stream, jobs);
-        HIPCHECK(h, hipGetLastError());
-    } else {
-    HIPCHECK(h, up(D_NFEAT, nfeat, sB * 4)); HIPCHECK(h, up(D_NFAC, nfac, sB * 4));
-    HIPCHECK(h, up(D_EX, ex, sB * 7 * 8)); HIPCHECK(h, up(D_GR0, gR0, sB * 9 * 8)); HIPCHECK(h, up(D_GP0, gP0, sB * 3 * 8));
-    HIPCHECK(h, up(D_PAIROFF, pairoff, sB * VB_PTAB * 4));
-    std::memcpy(mflag_img, h->h_mflag.data(), sB * 4); std::memcpy(td_img, h->h_td.data(), sB * 8);      // (from the pinned image, like everything else: an asynchronous upload must not read pageable memory the next call rewrites)
-    HIPCHECK(h, up(D_MFLAG, mflag_img, sB * 4));
-    HIPCHECK(h, up(D_TD, td_img, sB * 8));
-    if (!h->async_upload) HIPCHECK(h, hipStreamSynchronize(h->stream));
-    }
-    lap("small arrays + sync");
-
-    // ---- batch descriptor -------------------------------------------------------------------------------------
-    VbBatch &b = h->batch;
-    std::memset(&b, 0, sizeof(b));
-    const vilf_options &o = h->opts;
-    b.B = B; b.w0 = 0; b.Fmax = Fmax; b.Omax = Omax; b.FACmax = FACmax;
-    b.sqrt_info = o.focal_length / 1.5; b.cauchy_b = o.cauchy_a * o.cauchy_a;
-    for (int i = 0; i < 3; i++) b.G[i] = o.G[i];
-    {   // qil = Quaterniond(RIC*RCL), til = RIC*TCL + TIC (lidar_factor.h:28-29)
-        double M[9];
-        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M[3 * i + j] = o.RIC[3 * i] * o.RCL[j] + o.RIC[3 * i + 1] * o.RCL[3 + j] + o.RIC[3 * i + 2] * o.RCL[6 + j];
-        quat_from_R(M, b.qil);
-        for (int i = 0; i < 3; i++) b.til[i] = o.RIC[3 * i] * o.TCL[0] + o.RIC[3 * i + 1] * o.TCL[1] + o.RIC[3 * i + 2] * o.TCL[2] + o.TIC[i];
-    }
-    b.use_lidar = o.use_lidar_const; b.max_iterations = o.max_num_iterations;
-    b.min_relative_decrease = 1e-3; b.function_tolerance = 1e-6; b.gradient_tolerance = 1e-10; b.parameter_tolerance = 1e-8;
-    b.min_radius = 1e-32; b.initial_radius = 1e4; b.min_lm_diagonal = 1e-6; b.max_lm_diagonal = 1e32;
-    b.n_feat = h->d[D_NFEAT].as<int>(); b.n_fac = h->d[D_NFAC].as<int>();
-    b.pose = h->d[D_POSE].as<double>(); b.sb = h->d[D_SB].as<double>(); b.feat = h->d[D_FEAT].as<double>();
-    b.cand_pose = h->d[D_CPOSE].as<double>(); b.cand_sb = h->d[D_CSB].as<double>(); b.cand_feat = h->d[D_CFEAT].as<double>();
-    b.pose_init = h->d[D_POSE0].as<double>(); b.sb_init = h->d[D_SB0].as<double>(); b.feat_init = h->d[D_FEAT0].as<double>();
-    b.ex = h->d[D_EX].as<double>(); b.gauge_R0 = h->d[D_GR0].as<double>(); b.gauge_P0 = h->d[D_GP0].as<double>();
-    b.f_start = h->d[D_FSTART].as<int>(); b.f_nobs = h->d[D_FNOBS].as<int>(); b.f_obs0 = h->d[D_FOBS0].as<int>(); b.f_fac0 = h->d[D_FFAC0].as<int>();
-    b.f_const = h->d[D_FCONST].as<uint8_t>(); b.obs = h->d[D_OBS].as<double>();
-    b.obs_vel = h->d[D_OBSV].as<double>(); b.obs_ctd = h->d[D_OBSTD].as<double>(); b.obs_row = h->d[D_OBSROW].as<double>(); b.td = h->d[D_TD].as<double>();
-    b.est_td = o.estimate_td ? 1 : 0; b.tr_over_row = o.TR / o.ROW; b.row_half = o.ROW / 2;
-    b.ps_feat = h->d[D_PSFEAT].as<int>(); b.ps_obs = h->d[D_PSOBS].as<int>(); b.ps_slot = h->d[D_PSSLOT].as<int>();
-    b.pair_off = h->d[D_PAIROFF].as<int>(); b.facrec = h->d[D_FACREC].as<double>();
-    b.imu = h->d[D_IMU].as<double>(); b.lidar = h->d[D_LIDAR].as<double>();
-    bind_prior_pointers(h);
-    b.facw = h->d[D_FACW].as<double>(); b.Hpp = h->d[D_HPP].as<double>(); b.W = h->d[D_W].as<double>(); b.hf = h->d[D_HF].as<double>(); b.gf = h->d[D_GF].as<double>();
-    b.imuH = h->d[D_IMUH].as<double>(); b.imug = h->d[D_IMUG].as<double>(); b.lidH = h->d[D_LIDH].as<double>(); b.lidg = h->d[D_LIDG].as<double>(); b.g = h->d[D_G].as<double>(); b.diagH = h->d[D_DIAGH].as<double>(); b.pairD = h->d[D_PAIRD].as<double>();
-    b.cf = h->d[D_CF].as<double>();
-    b.scale = h->d[D_SCALE].as<double>(); b.diag = h->d[D_DIAG].as<double>(); b.grad = h->d[D_GRAD].as<double>(); b.gn = h->d[D_GN].as<double>();
-    b.st = h->d[D_ST].as<VbState>();
-    b.out_Ps = h->d[D_OPS].as<double>(); b.out_Rs = h->d[D_ORS].as<double>(); b.out_Vs = h->d[D_OVS].as<double>();
-    b.out_Bas = h->d[D_OBAS].as<double>(); b.out_Bgs = h->d[D_OBGS].as<double>();
-    b.dbg = nullptr;
-    if (getenv("VILF_DEBUG_STAMPS")) { if (!h->d[D_DBG].ensure(3 * 32 * 8)) return VILF_ERR_DEVICE; hipMemsetAsync(h->d[D_DBG].p, 0, 3 * 32 * 8, h->stream); b.dbg = h->d[D_DBG].as<long long>(); }
-
-    HIPCHECK(h, hipMemsetAsync(h->d[D_W].p, 0, 2 * sB * sF * VB_WLD * 8, h->stream));   // W rows are zero outside the rewritten ranges
-    if (!h->luts_ready) {   // static scatter tables of the tile assembly (same for every window): source element -> LDS offset, -1 = not stored
-        auto perm = [](int a, int l) { return l < 6 ? 6 * a + l : 66 + 9 * a + (l - 6); };
-        // packed entry: bits 0..14 = LDS offset + 1 (0: element not stored, upper block triangle), bits 15..22 = row, bits 23..30 = column
-        auto off1 = [](int r, int c) { const int tr = r >> 4, tc = c >> 4; if (tr < tc) return 0; return (tr * (tr + 1) / 2 + tc) * 256 + 16 * (r & 15) + ((c & 15) ^ (r & 15)) + 1; };
-        auto off = [&](int r, int c) { return off1(r, c) | (r << 15) | (c << 23); };
-        std::vector<int> li(9000), ll(1440), lv(2 * 2376);
-        for (int k = 0; k < 10; k++) {
-            for (int e = 0; e < 900; e++) { const int p = e / 30, q = e % 30; li[900 * k + e] = off(perm(k + p / 15, p % 15), perm(k + q / 15, q % 15)); }
-            for (int e = 0; e < 144; e++) { const int p = e / 12, q = e % 12; ll[144 * k + e] = off(perm(k + p / 6, p % 6), perm(k + q / 6, q % 6)); }
-        }
-        for (int t = 0; t < 2376; t++) {
-            const int blk = t / 36, e = t % 36, l = e / 6, m = e % 6;
-            int a = 0; while ((a + 1) * (a + 2) / 2 <= blk) a++;
-            const int bb = blk - a * (a + 1) / 2, r = 6 * a + l, c = 6 * bb + m;
-            lv[2 * t] = off(r, c);
-            lv[2 * t + 1] = (a != bb && (r >> 4) == (c >> 4)) ? off1(c, r) : 0;
-        }
-        if (!h->d[D_LUTI].ensure(li.size() * 4) || !h->d[D_LUTL].ensure(ll.size() * 4) || !h->d[D_LUTV].ensure(lv.size() * 4)) return VILF_ERR_DEVICE;
-        HIPCHECK(h, vilf_copy_sync(h, h->d[D_LUTI].p, li.data(), li.size() * 4, hipMemcpyHostToDevice));
-        HIPCHECK(h, vilf_copy_sync(h, h->d[D_LUTL].p, ll.data(), ll.size() * 4, hipMemcpyHostToDevice));
-        HIPCHECK(h, vilf_copy_sync(h, h->d[D_LUTV].p, lv.data(), lv.size() * 4, hipMemcpyHostToDevice));
-        h->luts_ready = true;
-    }
+    if ((rc = reserve(u, lap)) != VILF_OK) return rc;
+    // a small batch takes the staged copy: one copy of the whole host image + k_copy_spans
+    const bool staged = u.nthr <= 1 && u.image_bytes <= ((size_t)64 << 20) && !std::getenv("VILF_NO_STAGED_UPLOAD") && h->d[D_UPSTAGE].ensure(u.image_bytes + 4096);
+    if ((rc = pack_and_copy(u, staged, lap)) != VILF_OK) return rc;
+    bind_batch_arrays(h, u.dims);
+    if (getenv("VILF_DEBUG_STAMPS")) { if (!h->d[D_DBG].ensure(3 * 32 * 8)) return VILF_ERR_DEVICE; hipMemsetAsync(h->d[D_DBG].p, 0, 3 * 32 * 8, h->stream); h->batch.dbg = h->d[D_DBG].as<long long>(); }
+    HIPCHECK(h, hipMemsetAsync(h->d[D_W].p, 0, batch_array_bytes(D_W, u.dims), h->stream));   // W rows are zero outside the rewritten ranges
+    if (!h->luts_ready && (rc = build_scatter_tables(h)) != VILF_OK) return rc;
     h->batch.lut_imu = h->d[D_LUTI].as<int>(); h->batch.lut_lid = h->d[D_LUTL].as<int>(); h->batch.lut_vis = h->d[D_LUTV].as<int>();
-    h->batch.sb_tab = h->d[D_SBTAB].as<int>();
     const int nimu = B * 10;
     hipLaunchKernelGGL(k_imu_prep, dim3((nimu + 3) / 4), dim3(IMU_PREP_NT), 0, h->stream, nimu, h->d[D_COV].as<double>(), h->d[D_WORK].as<double>(), h->d[D_IMU].as<double>());
     HIPCHECK(h, hipGetLastError());
-    int rc = upload_priors(h);
-    if (rc != VILF_OK) return rc;
+    if ((rc = upload_priors(h)) != VILF_OK) return rc;
     hipLaunchKernelGGL(k_reset, dim3(B), dim3(VB_NT), 0, h->stream, h->batch, 0);
     HIPCHECK(h, hipGetLastError());
     if (h->async_upload || (h->defer_upload_sync && staged)) h->upload_inflight = true;          // the next upload of this handle waits before it touches the staging (also when
@@ -705,14 +728,12 @@ extern "C" int vilf_batch_rewind(vilf_handle *h) {
     hipLaunchKernelGGL(k_reset, dim3(h->B), dim3(VB_NT), 0, h->stream, h->batch, 1);
     HIPCHECK(h, hipGetLastError());
     if ((h->opts.estimate_extrinsic || h->opts.estimate_td) && (int)h->own.size() == h->B) {      // Ex_Pose / td are variables then: their uploaded values are part of the state
-        for (int w = 0; w < h->B; w++) { std::memcpy(&h->h_ex[(size_t)w * 7], h->own[w].in.para_ex_pose, 56); h->h_td[w] = h->own[w].in.para_td; }
-        HIPCHECK(h, hipMemcpyAsync(h->d[D_EX].p, h->h_ex.data(), (size_t)h->B * 56, hipMemcpyHostToDevice, h->stream));
+        for (int w = 0; w < h->B; w++) { std::memcpy(&h->h_ex[(size_t)w * VB_EX_LD], h->own[w].in.para_ex_pose, VB_EX_LD * 8); h->h_td[w] = h->own[w].in.para_td; }
+        HIPCHECK(h, hipMemcpyAsync(h->d[D_EX].p, h->h_ex.data(), (size_t)h->B * VB_EX_LD * 8, hipMemcpyHostToDevice, h->stream));
         HIPCHECK(h, hipMemcpyAsync(h->d[D_TD].p, h->h_td.data(), (size_t)h->B * 8, hipMemcpyHostToDevice, h->stream));
     }
     if (h->prior_restore_needed && h->prior_backup_valid) {          // a marginalization replaced the priors: the set as uploaded becomes the live one again (swap, no copy)
-        const int live[6] = {D_PHDR, D_PX0, D_PJ, D_PR, D_PH, D_PG}, bak[6] = {D_PHDR0, D_PX00, D_PJ0, D_PR0, D_PH0, D_PG0};
-        for (int k = 0; k < 6; k++) std::swap(h->d[live[k]], h->d[bak[k]]);
-        bind_prior_pointers(h);
+        swap_prior_sets(h);
         // the device now holds the authoritative priors; the host mirror may have seen the marginalized ones through an export
         for (int w = 0; w < h->B; w++) { h->prior_dev_newer[w] = 1; h->prior_dirty[w] = 0; }
         // (the restored set is the uploaded one: prior_dense / solve_dense_fallback describe exactly it)
@@ -736,13 +757,11 @@ extern "C" int vilf_batch_solve(vilf_handle *h, int sync) {
         // (vilf_lw.hip: ProjectionTdFactor / Ex_Pose Jacobians, the slot's device-resident prior), one after the other. State, gauge-fixed outputs and the
         // summary are written back to the slot, so download / summaries / marginalization continue as after the batched kernels.
         if ((int)h->own.size() != h->B) { h->err = "batch inputs not retained"; return VILF_ERR_INVALID_ARGUMENT; }
-        bool dirty0 = false;
-        for (int w = 0; w < h->B; w++) if (h->prior_dirty[w]) dirty0 = true;
-        if (dirty0) { int rc = upload_priors(h); if (rc != VILF_OK) return rc; }
+        { int rc = upload_priors(h); if (rc != VILF_OK) return rc; }      // (the slots whose host mirror changed; nothing otherwise)
         const auto t0 = std::chrono::steady_clock::now();
         // all slots as ONE group: a single chain of launches solves them side by side (vilf_lw_group_solve), priors in and states / summaries back in bulk copies
         const size_t B = h->B;
-        std::vector<double> bufP(B * 77), bufS(B * 99), bufF(B * (h->batch.Fmax + 4)), Ps(B * 33), Rs(B * 99), Vs(B * 33), Bas(B * 33), Bgs(B * 33);
+        std::vector<double> bufP(B * VB_POSE_LD), bufS(B * VB_SB_LD), bufF(B * (h->batch.Fmax + 4)), Ps(B * VB_OUT3_LD), Rs(B * VB_OUTR_LD), Vs(B * VB_OUT3_LD), Bas(B * VB_OUT3_LD), Bgs(B * VB_OUT3_LD);
         std::vector<vilf_window_out> outv(B);
         std::vector<const vilf_window_in *> inp(B);
         std::vector<vilf_window_out *> outp(B);
@@ -750,8 +769,8 @@ extern "C" int vilf_batch_solve(vilf_handle *h, int sync) {
         for (size_t w = 0; w < B; w++) {
             vilf_window_out &out = outv[w];
             std::memset(&out, 0, sizeof(out));
-            out.para_pose = &bufP[w * 77]; out.para_speed_bias = &bufS[w * 99]; out.para_feature = &bufF[w * (h->batch.Fmax + 4)];
-            out.Ps = &Ps[w * 33]; out.Rs = &Rs[w * 99]; out.Vs = &Vs[w * 33]; out.Bas = &Bas[w * 33]; out.Bgs = &Bgs[w * 33];
+            out.para_pose = &bufP[w * VB_POSE_LD]; out.para_speed_bias = &bufS[w * VB_SB_LD]; out.para_feature = &bufF[w * (h->batch.Fmax + 4)];
+            out.Ps = &Ps[w * VB_OUT3_LD]; out.Rs = &Rs[w * VB_OUTR_LD]; out.Vs = &Vs[w * VB_OUT3_LD]; out.Bas = &Bas[w * VB_OUT3_LD]; out.Bgs = &Bgs[w * VB_OUT3_LD];
             inp[w] = &h->own[w].in; outp[w] = &out; slot1[w] = (int)w + 1;
         }
         const int rc = vilf_lw_group_solve(h, h->B, inp.data(), outp.data(), slot1.data());
@@ -761,9 +780,7 @@ extern "C" int vilf_batch_solve(vilf_handle *h, int sync) {
         (void)sync;                             // the general path reads its results back: always synchronous
         return VILF_OK;
     }
-    bool dirty = false;
-    for (int w = 0; w < h->B; w++) if (h->prior_dirty[w]) dirty = true;
-    if (dirty) { int rc = upload_priors(h); if (rc != VILF_OK) return rc; }
+    { int rc = upload_priors(h); if (rc != VILF_OK) return rc; }          // (the slots whose host mirror changed; nothing otherwise)
     const dim3 grid(h->B), block(VB_NT);
     // k_solve_sb eliminates SpeedBias[1..10] as a block-tridiagonal chain: valid while the priors hold no speed-bias block but SpeedBias[0] (all the
     // reference ever produces, estimator.cpp:960-971); VILF_SOLVE_DENSE=1 forces the dense-Cholesky kernel (tests compare the two)
@@ -880,6 +897,12 @@ static int vb_check_dev_error(vilf_handle *h, const VbState *st, int first, int 
     }
     return VILF_OK;
 }
+static vilf_summary summary_of(const VbState &s, double usec_solve) {
+    vilf_summary m;
+    m.num_iterations = s.iteration; m.num_successful_steps = s.num_successful; m.num_linear_solves = s.num_linear_solves; m.termination = s.termination;
+    m.initial_cost = s.initial_cost; m.final_cost = s.x_cost; m.final_radius = s.radius; m.usec_solve = usec_solve;
+    return m;
+}
 extern "C" int vilf_batch_summaries(vilf_handle *h, int first, int n, vilf_summary *sums) {
     if (!h || !h->resident || first < 0 || n < 0 || first + n > h->B || !sums) return VILF_ERR_INVALID_ARGUMENT;
     std::vector<VbState> st(n);
@@ -888,92 +911,72 @@ extern "C" int vilf_batch_summaries(vilf_handle *h, int first, int n, vilf_summa
     solve_time_resolve(h);
     { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }     // the stream is idle: pending profile spans cost nothing to read now
     { const int rce = vb_check_dev_error(h, st.data(), first, n); if (rce != VILF_OK) return rce; }
-    for (int i = 0; i < n; i++) {
-        sums[i].num_iterations = st[i].iteration;
-        sums[i].num_successful_steps = st[i].num_successful;
-        sums[i].num_linear_solves = st[i].num_linear_solves;
-        sums[i].termination = st[i].termination;
-        sums[i].initial_cost = st[i].initial_cost;
-        sums[i].final_cost = st[i].x_cost;
-        sums[i].final_radius = st[i].radius;
-        sums[i].usec_solve = h->last_solve_usec;
-    }
+    for (int i = 0; i < n; i++) sums[i] = summary_of(st[i], h->last_solve_usec);
     return VILF_OK;
+}
+
+// the eight result rows of a window in the order of vilf_window_out's pointers (para_pose, para_speed_bias, para_feature, Ps, Rs, Vs, Bas, Bgs): device array, doubles per window
+struct ResultRow { const double *dev; size_t ld; };
+static void result_rows(const vilf_handle *h, ResultRow rows[8]) {
+    const VbBatch &b = h->batch;
+    const ResultRow r[8] = {{b.pose, VB_POSE_LD}, {b.sb, VB_SB_LD}, {b.feat, (size_t)b.Fmax}, {b.out_Ps, VB_OUT3_LD}, {b.out_Rs, VB_OUTR_LD}, {b.out_Vs, VB_OUT3_LD}, {b.out_Bas, VB_OUT3_LD}, {b.out_Bgs, VB_OUT3_LD}};
+    std::copy(r, r + 8, rows);
+}
+// window w's output from host copies of its eight rows, the host mirrors of Ex_Pose / td (kept current by the general path with estimate_extrinsic / estimate_td) and its summary
+static void fill_window_out(const vilf_handle *h, int w, const ResultRow rows[8], const double *const host[8], const vilf_summary &sum, vilf_window_out &o) {
+    double *const dst[8] = {o.para_pose, o.para_speed_bias, o.para_feature, o.Ps, o.Rs, o.Vs, o.Bas, o.Bgs};
+    for (int k = 0; k < 8; k++) {
+        const size_t cnt = k == 2 ? (size_t)h->h_nfeat[w] : rows[k].ld;
+        if (dst[k] && cnt) std::memcpy(dst[k], host[k], cnt * 8);
+    }
+    const double *exw = &h->h_ex[(size_t)w * VB_EX_LD];
+    for (int k = 0; k < 3; k++) o.tic[k] = exw[k];
+    quat_to_R(exw + 3, o.ric);
+    o.td = h->h_td[w];
+    o.summary = sum;
 }
 
 extern "C" int vilf_batch_download(vilf_handle *h, int first, int n, vilf_window_out *outs) {
     if (!h || !h->resident || first < 0 || n < 0 || first + n > h->B || !outs) return VILF_ERR_INVALID_ARGUMENT;
-    const size_t sF = h->batch.Fmax;
+    ResultRow rows[8]; result_rows(h, rows);
+    size_t per = 0; const size_t sn = n;
+    for (const ResultRow &r : rows) per += r.ld;
+    const double *host[8];                    // host copy of every row, windows first .. first + n - 1
+    std::vector<double> pageable;
+    std::vector<vilf_summary> sums(n);
     // a few windows (the single-window entry point): the nine result arrays are gathered on the device (k_copy_spans) and come back in ONE copy through pinned memory
-    const size_t sn0 = n, per0 = 77 + 99 + sF + 33 + 99 + 33 + 33 + 33, img0 = ((sn0 * per0 * 8 + 63) & ~(size_t)63) + sn0 * sizeof(VbState);
+    const size_t img0 = ((sn * per * 8 + 63) & ~(size_t)63) + sn * sizeof(VbState);
     if (n <= 64 && !std::getenv("VILF_NO_STAGED_UPLOAD") && h->d[D_DNSTAGE].ensure(img0 + 256) && h->pin_down.ensure(img0 + 256)) {
         UpJobs jobs; jobs.n = 0;
         char *dst = h->d[D_DNSTAGE].as<char>();
         size_t off = 0;
-        auto gather = [&](const void *src, size_t bytes) { UpJob &jb = jobs.j[jobs.n++]; jb.src = static_cast<const char *>(src); jb.dst = dst + off; jb.bytes = bytes; const size_t at = off; off += (bytes + 15) & ~(size_t)15; return at; };
-        const size_t o_pose = gather(h->batch.pose + (size_t)first * 77, sn0 * 77 * 8), o_sb = gather(h->batch.sb + (size_t)first * 99, sn0 * 99 * 8), o_feat = gather(h->batch.feat + (size_t)first * sF, sn0 * sF * 8);
-        const size_t o_ps = gather(h->batch.out_Ps + (size_t)first * 33, sn0 * 33 * 8), o_rs = gather(h->batch.out_Rs + (size_t)first * 99, sn0 * 99 * 8), o_vs = gather(h->batch.out_Vs + (size_t)first * 33, sn0 * 33 * 8);
-        const size_t o_ba = gather(h->batch.out_Bas + (size_t)first * 33, sn0 * 33 * 8), o_bg = gather(h->batch.out_Bgs + (size_t)first * 33, sn0 * 33 * 8), o_st = gather(h->batch.st + first, sn0 * sizeof(VbState));
+        auto gather = [&](const void *src, size_t bytes) { jobs.j[jobs.n++] = UpJob{static_cast<const char *>(src), dst + off, bytes}; const size_t at = off; off += (bytes + 15) & ~(size_t)15; return at; };
+        const char *img = static_cast<const char *>(h->pin_down.p);
+        for (int k = 0; k < 8; k++) host[k] = reinterpret_cast<const double *>(img + gather(rows[k].dev + (size_t)first * rows[k].ld, sn * rows[k].ld * 8));
+        const VbState *st = reinterpret_cast<const VbState *>(img + gather(h->batch.st + first, sn * sizeof(VbState)));
         hipLaunchKernelGGL(k_copy_spans, dim3(1, (unsigned)jobs.n), dim3(256), 0, h->stream, jobs);
         HIPCHECK(h, hipGetLastError());
         HIPCHECK(h, hipMemcpyAsync(h->pin_down.p, dst, off, hipMemcpyDeviceToHost, h->stream));
         HIPCHECK(h, hipStreamSynchronize(h->stream));
         solve_time_resolve(h);
         { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-        const char *img = static_cast<const char *>(h->pin_down.p);
-        auto dd = [&](size_t at) { return reinterpret_cast<const double *>(img + at); };
-        const VbState *st = reinterpret_cast<const VbState *>(img + o_st);
         { const int rce = vb_check_dev_error(h, st, first, n); if (rce != VILF_OK) return rce; }
-        for (int i = 0; i < n; i++) {
-            vilf_window_out &o = outs[i];
-            const int F = h->h_nfeat[first + i];
-            if (o.para_pose) std::memcpy(o.para_pose, dd(o_pose) + (size_t)i * 77, 77 * 8);
-            if (o.para_speed_bias) std::memcpy(o.para_speed_bias, dd(o_sb) + (size_t)i * 99, 99 * 8);
-            if (o.para_feature && F) std::memcpy(o.para_feature, dd(o_feat) + (size_t)i * sF, (size_t)F * 8);
-            if (o.Ps) std::memcpy(o.Ps, dd(o_ps) + (size_t)i * 33, 33 * 8);
-            if (o.Rs) std::memcpy(o.Rs, dd(o_rs) + (size_t)i * 99, 99 * 8);
-            if (o.Vs) std::memcpy(o.Vs, dd(o_vs) + (size_t)i * 33, 33 * 8);
-            if (o.Bas) std::memcpy(o.Bas, dd(o_ba) + (size_t)i * 33, 33 * 8);
-            if (o.Bgs) std::memcpy(o.Bgs, dd(o_bg) + (size_t)i * 33, 33 * 8);
-            const double *exw = &h->h_ex[(size_t)(first + i) * 7];
-            for (int k = 0; k < 3; k++) o.tic[k] = exw[k];
-            quat_to_R(exw + 3, o.ric);
-            o.td = h->h_td[first + i];
-            o.summary.num_iterations = st[i].iteration; o.summary.num_successful_steps = st[i].num_successful; o.summary.num_linear_solves = st[i].num_linear_solves;
-            o.summary.termination = st[i].termination; o.summary.initial_cost = st[i].initial_cost; o.summary.final_cost = st[i].x_cost; o.summary.final_radius = st[i].radius;
-            o.summary.usec_solve = h->last_solve_usec;
+        for (int i = 0; i < n; i++) sums[i] = summary_of(st[i], h->last_solve_usec);
+    } else {
+        pageable.resize(sn * per);
+        size_t off = 0;
+        for (int k = 0; k < 8; k++) {
+            host[k] = pageable.data() + off;
+            HIPCHECK(h, hipMemcpyAsync(pageable.data() + off, rows[k].dev + (size_t)first * rows[k].ld, sn * rows[k].ld * 8, hipMemcpyDeviceToHost, h->stream));
+            off += sn * rows[k].ld;
         }
-        return VILF_OK;
+        const int rc = vilf_batch_summaries(h, first, n, sums.data());   // synchronises the stream
+        if (rc != VILF_OK) return rc;
     }
-    std::vector<double> pose((size_t)n * 77), sb((size_t)n * 99), feat((size_t)n * sF), Ps((size_t)n * 33), Rs((size_t)n * 99), Vs((size_t)n * 33), Bas((size_t)n * 33), Bgs((size_t)n * 33);
-    auto dn = [&](void *dst, const double *src, size_t cnt) { return hipMemcpyAsync(dst, src, cnt * 8, hipMemcpyDeviceToHost, h->stream); };
-    HIPCHECK(h, dn(pose.data(), h->batch.pose + (size_t)first * 77, (size_t)n * 77));
-    HIPCHECK(h, dn(sb.data(), h->batch.sb + (size_t)first * 99, (size_t)n * 99));
-    HIPCHECK(h, dn(feat.data(), h->batch.feat + (size_t)first * sF, (size_t)n * sF));
-    HIPCHECK(h, dn(Ps.data(), h->batch.out_Ps + (size_t)first * 33, (size_t)n * 33));
-    HIPCHECK(h, dn(Rs.data(), h->batch.out_Rs + (size_t)first * 99, (size_t)n * 99));
-    HIPCHECK(h, dn(Vs.data(), h->batch.out_Vs + (size_t)first * 33, (size_t)n * 33));
-    HIPCHECK(h, dn(Bas.data(), h->batch.out_Bas + (size_t)first * 33, (size_t)n * 33));
-    HIPCHECK(h, dn(Bgs.data(), h->batch.out_Bgs + (size_t)first * 33, (size_t)n * 33));
-    std::vector<vilf_summary> sums(n);
-    int rc = vilf_batch_summaries(h, first, n, sums.data());   // synchronises the stream
-    if (rc != VILF_OK) return rc;
     for (int i = 0; i < n; i++) {
-        vilf_window_out &o = outs[i];
-        const int F = h->h_nfeat[first + i];
-        if (o.para_pose) std::memcpy(o.para_pose, &pose[(size_t)i * 77], 77 * 8);
-        if (o.para_speed_bias) std::memcpy(o.para_speed_bias, &sb[(size_t)i * 99], 99 * 8);
-        if (o.para_feature && F) std::memcpy(o.para_feature, &feat[(size_t)i * sF], (size_t)F * 8);
-        if (o.Ps) std::memcpy(o.Ps, &Ps[(size_t)i * 33], 33 * 8);
-        if (o.Rs) std::memcpy(o.Rs, &Rs[(size_t)i * 99], 99 * 8);
-        if (o.Vs) std::memcpy(o.Vs, &Vs[(size_t)i * 33], 33 * 8);
-        if (o.Bas) std::memcpy(o.Bas, &Bas[(size_t)i * 33], 33 * 8);
-        if (o.Bgs) std::memcpy(o.Bgs, &Bgs[(size_t)i * 33], 33 * 8);
-        const double *exw = &h->h_ex[(size_t)(first + i) * 7];
-        for (int k = 0; k < 3; k++) o.tic[k] = exw[k];
-        quat_to_R(exw + 3, o.ric);
-        o.td = h->h_td[first + i];                      // kept current by the general path (estimate_td)
-        o.summary = sums[i];
+        const double *mine[8];
+        for (int k = 0; k < 8; k++) mine[k] = host[k] + (size_t)i * rows[k].ld;
+        fill_window_out(h, first + i, rows, mine, sums[i], outs[i]);
     }
     return VILF_OK;
 }
@@ -984,31 +987,24 @@ extern "C" int vilf_batch_download(vilf_handle *h, int first, int n, vilf_window
 extern "C" int vilf_batch_download_states(vilf_handle *h, int first, int n, double *Ps, double *Rs, double *Vs, double *Bas, double *Bgs, vilf_summary *sums) {
     if (!h || !h->resident || first < 0 || n < 0 || first + n > h->B) return VILF_ERR_INVALID_ARGUMENT;
     if (n == 0) return VILF_OK;
-    const size_t sn = n, per = 33 + 99 + 33 + 33 + 33;
+    ResultRow all[8];
+    result_rows(h, all);
+    const ResultRow *rows = all + 3;          // out_Ps ... out_Bgs
+    double *const dst[5] = {Ps, Rs, Vs, Bas, Bgs};
+    const size_t sn = n;
+    size_t per = 0;
+    for (int k = 0; k < 5; k++) per += rows[k].ld;
     if (!h->pin_down.ensure(sn * per * 8 + sn * sizeof(VbState) + 256)) { h->err = "hipHostMalloc failed (download staging)"; return VILF_ERR_DEVICE; }
-    double *st = static_cast<double *>(h->pin_down.p);
-    double *pP = st, *pR = pP + sn * 33, *pV = pR + sn * 99, *pA = pV + sn * 33, *pG = pA + sn * 33;
-    VbState *pS = reinterpret_cast<VbState *>(pG + sn * 33);
-    auto dn = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
-    if (Ps) HIPCHECK(h, dn(pP, h->batch.out_Ps + (size_t)first * 33, sn * 33 * 8));
-    if (Rs) HIPCHECK(h, dn(pR, h->batch.out_Rs + (size_t)first * 99, sn * 99 * 8));
-    if (Vs) HIPCHECK(h, dn(pV, h->batch.out_Vs + (size_t)first * 33, sn * 33 * 8));
-    if (Bas) HIPCHECK(h, dn(pA, h->batch.out_Bas + (size_t)first * 33, sn * 33 * 8));
-    if (Bgs) HIPCHECK(h, dn(pG, h->batch.out_Bgs + (size_t)first * 33, sn * 33 * 8));
-    if (sums) HIPCHECK(h, dn(pS, h->batch.st + first, sn * sizeof(VbState)));
+    double *pin[5], *end = static_cast<double *>(h->pin_down.p);
+    for (int k = 0; k < 5; k++) { pin[k] = end; end += sn * rows[k].ld; }
+    VbState *pS = reinterpret_cast<VbState *>(end);
+    for (int k = 0; k < 5; k++) if (dst[k]) HIPCHECK(h, hipMemcpyAsync(pin[k], rows[k].dev + (size_t)first * rows[k].ld, sn * rows[k].ld * 8, hipMemcpyDeviceToHost, h->stream));
+    if (sums) HIPCHECK(h, hipMemcpyAsync(pS, h->batch.st + first, sn * sizeof(VbState), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
     solve_time_resolve(h);
-    if (Ps) std::memcpy(Ps, pP, sn * 33 * 8);
-    if (Rs) std::memcpy(Rs, pR, sn * 99 * 8);
-    if (Vs) std::memcpy(Vs, pV, sn * 33 * 8);
-    if (Bas) std::memcpy(Bas, pA, sn * 33 * 8);
-    if (Bgs) std::memcpy(Bgs, pG, sn * 33 * 8);
+    for (int k = 0; k < 5; k++) if (dst[k]) std::memcpy(dst[k], pin[k], sn * rows[k].ld * 8);
     if (sums) { const int rce = vb_check_dev_error(h, pS, first, n); if (rce != VILF_OK) return rce; }
-    if (sums) for (int i = 0; i < n; i++) {
-        sums[i].num_iterations = pS[i].iteration; sums[i].num_successful_steps = pS[i].num_successful; sums[i].num_linear_solves = pS[i].num_linear_solves;
-        sums[i].termination = pS[i].termination; sums[i].initial_cost = pS[i].initial_cost; sums[i].final_cost = pS[i].x_cost; sums[i].final_radius = pS[i].radius;
-        sums[i].usec_solve = h->last_solve_usec;
-    }
+    if (sums) for (int i = 0; i < n; i++) sums[i] = summary_of(pS[i], h->last_solve_usec);
     return VILF_OK;
 }
 
@@ -1070,43 +1066,48 @@ extern "C" int vilf_prior_export(vilf_handle *h, int slot, vilf_prior *out) {
     return VILF_OK;
 }
 
+// The marginalization workspace: every array's size and its VbMarg field once, and where the new priors go. sPool: slots of the exact (Jacobi) fallback's pool.
+// Two sets of prior buffers. When the live set is still the one the windows were uploaded / rewound with, the new priors go to the other set and the sets swap
+// afterwards: the uploaded priors stay intact for vilf_batch_rewind at no cost (this used to be a 1.7 GB device copy per marginalization and another per rewind).
+// A second marginalization without a rewind in between writes in place, as before, so that the snapshot survives.
+static int reserve_marg_workspace(vilf_handle *h, size_t sPool, bool to_other_set) {
+    const BatchDims dm{(size_t)h->B, (size_t)h->batch.Fmax, (size_t)h->batch.Omax, (size_t)h->batch.FACmax, h->batch.est_td != 0};
+    const size_t sB = dm.B, sF = dm.F, sC = dm.C, M = h->mg_Mcap;
+    VbMarg &g = h->marg;
+    DBuf *d = h->d;
+    bool ok = true;
+    auto take = [&](int id, size_t bytes, auto *&field) { ok = ok && d[id].ensure(bytes); field = d[id].as<std::remove_reference_t<decltype(*field)>>(); };
+    g.Mcap = (int)M; g.init_depth = h->opts.init_depth; g.mflag = d[D_MFLAG].as<int>();
+    take(D_MINFO, sB * MG_INFO * 4, g.info); take(D_MF0, sB * sF * 4, g.f0rank);
+    take(D_MSTP, sB * VB_POSE_LD * 8, g.st_pose); take(D_MSTS, sB * VB_SB_LD * 8, g.st_sb); take(D_MSTF, sB * sF * 8, g.st_feat); take(D_MSTE, sB * VB_EX_LD * 8, g.st_ex);
+    take(D_MBUF, sB * MG_MROW * sC * 8, g.Mbuf); take(D_MHD, sB * MG_ND * MG_ND * 8, g.Hd); take(D_MGD, sB * MG_ND * 8, g.gd); take(D_MWF, sB * sF * MG_ND * 8, g.Wf);
+    take(D_MHF, sB * sF * 8, g.hfm); take(D_MGF, sB * sF * 8, g.gfm);
+    take(D_MAMM, M > MG_MLDS ? sPool * M * M * 8 : 8, g.Amm); take(D_MX, sPool * M * (MG_NK + 1) * 8, g.X); take(D_MROT, sPool * MG_SWEEPS * (M - 1) * M * 8, g.rot); take(D_MLAM, sPool * M * 8, g.lam);
+    take(D_MAR, sB * MG_NK * MG_NK * 8, g.Ar); take(D_MBR, sB * MG_NK * 8, g.br);
+    take(D_QLV, sB * MG_NK * (MG_NK + 1) * 8, g.qlV); take(D_QLD, sB * 2 * (MG_NK + 2) * 8, g.qlD); take(D_QLLOG, sB * 2 * QL_RCAP * 8, g.qlLog);
+    take(D_QLIT, sB * QL_ICAP * 4, g.qlIt); take(D_QLINFO, sB * 4 * 4, g.qlInfo);
+    if (!ok) { h->err = "hipMalloc failed (marginalization workspace)"; return VILF_ERR_DEVICE; }
+    if (to_other_set)
+        for (const ArrayRow &r : kBatchArrays) if (r.use == A_PRIOR && !d[r.twin].ensure(r.bytes(dm))) { h->err = "hipMalloc failed (second prior set)"; return VILF_ERR_DEVICE; }
+    const bool o = to_other_set;
+    g.prior_hdr_out = d[o ? D_PHDR0 : D_PHDR].as<int>(); g.prior_x0_out = d[o ? D_PX00 : D_PX0].as<double>(); g.prior_J_out = d[o ? D_PJ0 : D_PJ].as<double>();
+    g.prior_r_out = d[o ? D_PR0 : D_PR].as<double>(); g.prior_H_out = d[o ? D_PH0 : D_PH].as<double>(); g.prior_g_out = d[o ? D_PG0 : D_PG].as<double>();
+    return VILF_OK;
+}
+
 extern "C" int vilf_batch_marginalize(vilf_handle *h, int sync) {
     if (!h || !h->resident) return VILF_ERR_INVALID_ARGUMENT;
     HIPCHECK(h, hipSetDevice(h->device));
-    { bool dirty = false; for (int w = 0; w < h->B; w++) if (h->prior_dirty[w]) dirty = true; if (dirty) { int rc = upload_priors(h); if (rc != VILF_OK) return rc; } }
-    const size_t sB = h->B, sF = h->batch.Fmax, sC = h->batch.FACmax, M = h->mg_Mcap;
+    { int rc = upload_priors(h); if (rc != VILF_OK) return rc; }
+    const size_t sB = h->B, M = h->mg_Mcap;
     // the exact (Jacobi) fallback's workspace — rotation log, Amm, X, eigenvalues — is a pool of slots, not one per window: the log alone is 24 (M - 1) M doubles
     // (20 MB at 300 dropped features). The pool is as large as 8 GB allow; flagged windows beyond it are taken by further launches of the exact pass.
     const size_t slot_bytes = (MG_SWEEPS * (M - 1) * M + (M > MG_MLDS ? M * M : 0) + M * (MG_NK + 1) + M) * 8;
     size_t sPool = std::max<size_t>(1, std::min<size_t>(sB, ((size_t)8 << 30) / std::max<size_t>(slot_bytes, 1)));
     if (const char *e = std::getenv("VILF_MARG_POOL")) sPool = std::max<size_t>(1, std::min<size_t>(sB, (size_t)std::atoi(e)));      // test hook: several rounds on a small batch
-    struct Req { int id; size_t bytes; };
-    const Req reqs[] = {
-        {D_MINFO, sB * MG_INFO * 4}, {D_MF0, sB * sF * 4}, {D_MSTP, sB * 77 * 8}, {D_MSTS, sB * 99 * 8}, {D_MSTF, sB * sF * 8}, {D_MSTE, sB * 7 * 8},
-        {D_MBUF, sB * MG_MROW * sC * 8}, {D_MHD, sB * MG_ND * MG_ND * 8}, {D_MGD, sB * MG_ND * 8}, {D_MWF, sB * sF * MG_ND * 8}, {D_MHF, sB * sF * 8},
-        {D_MGF, sB * sF * 8}, {D_MAMM, (M > MG_MLDS ? sPool * M * M * 8 : 8)}, {D_MX, sPool * M * (MG_NK + 1) * 8}, {D_MROT, sPool * MG_SWEEPS * (M - 1) * M * 8},
-        {D_MLAM, sPool * M * 8}, {D_MAR, sB * MG_NK * MG_NK * 8}, {D_MBR, sB * MG_NK * 8},
-        {D_QLV, sB * MG_NK * (MG_NK + 1) * 8}, {D_QLD, sB * 2 * (MG_NK + 2) * 8}, {D_QLLOG, sB * 2 * QL_RCAP * 8}, {D_QLIT, sB * QL_ICAP * 4}, {D_QLINFO, sB * 4 * 4},
-    };
-    for (const Req &r : reqs) if (!h->d[r.id].ensure(r.bytes)) { h->err = "hipMalloc failed (marginalization workspace)"; return VILF_ERR_DEVICE; }
-    VbMarg &g = h->marg;
-    g.Mcap = (int)M; g.init_depth = h->opts.init_depth;
-    g.mflag = h->d[D_MFLAG].as<int>(); g.info = h->d[D_MINFO].as<int>(); g.f0rank = h->d[D_MF0].as<int>();
-    g.st_pose = h->d[D_MSTP].as<double>(); g.st_sb = h->d[D_MSTS].as<double>(); g.st_feat = h->d[D_MSTF].as<double>(); g.st_ex = h->d[D_MSTE].as<double>();
-    g.Mbuf = h->d[D_MBUF].as<double>(); g.Hd = h->d[D_MHD].as<double>(); g.gd = h->d[D_MGD].as<double>(); g.Wf = h->d[D_MWF].as<double>();
-    g.hfm = h->d[D_MHF].as<double>(); g.gfm = h->d[D_MGF].as<double>(); g.Amm = h->d[D_MAMM].as<double>(); g.X = h->d[D_MX].as<double>();
-    g.rot = h->d[D_MROT].as<double>(); g.lam = h->d[D_MLAM].as<double>(); g.Ar = h->d[D_MAR].as<double>(); g.br = h->d[D_MBR].as<double>();
-    g.qlV = h->d[D_QLV].as<double>(); g.qlD = h->d[D_QLD].as<double>(); g.qlLog = h->d[D_QLLOG].as<double>(); g.qlIt = h->d[D_QLIT].as<int>(); g.qlInfo = h->d[D_QLINFO].as<int>();
-    // Two sets of prior buffers. When the live set is still the one the windows were uploaded / rewound with, the new priors go to the other set and the sets swap
-    // afterwards: the uploaded priors stay intact for vilf_batch_rewind at no cost (this used to be a 1.7 GB device copy per marginalization and another per rewind).
-    // A second marginalization without a rewind in between writes in place, as before, so that the snapshot survives.
-    const int live[6] = {D_PHDR, D_PX0, D_PJ, D_PR, D_PH, D_PG}, bak[6] = {D_PHDR0, D_PX00, D_PJ0, D_PR0, D_PH0, D_PG0};
-    const size_t pbytes[6] = {sB * VB_PRIOR_HDR * 4, sB * 24 * 9 * 8, sB * VB_PRIOR_LD * VB_PRIOR_LD * 8, sB * VB_PRIOR_LD * 8, sB * VB_PRIOR_LD * VB_PRIOR_LD * 8, sB * VB_PRIOR_LD * 8};
     const bool to_other_set = !h->prior_restore_needed;
-    if (to_other_set) for (int k = 0; k < 6; k++) if (!h->d[bak[k]].ensure(pbytes[k])) { h->err = "hipMalloc failed (second prior set)"; return VILF_ERR_DEVICE; }
-    const int *oset = to_other_set ? bak : live;
-    g.prior_hdr_out = h->d[oset[0]].as<int>(); g.prior_x0_out = h->d[oset[1]].as<double>(); g.prior_J_out = h->d[oset[2]].as<double>(); g.prior_r_out = h->d[oset[3]].as<double>();
-    g.prior_H_out = h->d[oset[4]].as<double>(); g.prior_g_out = h->d[oset[5]].as<double>();
+    { const int rc = reserve_marg_workspace(h, sPool, to_other_set); if (rc != VILF_OK) return rc; }
+    VbMarg &g = h->marg;
     const dim3 grid(h->B), block(VB_NT);
     const bool prof = h->profiling != 0;
     hipEvent_t mev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1152,8 +1153,7 @@ extern "C" int vilf_batch_marginalize(vilf_handle *h, int sync) {
     by_class(k_marg_finish, 0, 0, 1);
     if (to_other_set) {
         hipLaunchKernelGGL(k_prior_keep, grid, block, 0, h->stream, h->batch, g);
-        for (int k = 0; k < 6; k++) std::swap(h->d[live[k]], h->d[bak[k]]);
-        bind_prior_pointers(h);
+        swap_prior_sets(h);
         h->prior_backup_valid = true;           // the other set now holds the priors as uploaded
     }
     if (prof) mev[3] = vilf_prof_event(h);
@@ -1266,26 +1266,28 @@ extern "C" int vilf_eval_projection_td(vilf_handle *h, const double *const *p, c
 
 static void pack_imu_rec(const vilf_imu_preint *p, double *rec) {
     std::memset(rec, 0, IMU_REC * 8);
-    rec[0] = p->sum_dt;
-    for (int i = 0; i < 3; i++) { rec[1 + i] = p->delta_p[i]; rec[8 + i] = p->delta_v[i]; rec[11 + i] = p->linearized_ba[i]; rec[14 + i] = p->linearized_bg[i]; }
-    for (int i = 0; i < 4; i++) rec[4 + i] = p->delta_q[i];
-    auto blk = [&](int off, int r0, int c0) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) rec[off + 3 * i + j] = p->jacobian[(r0 + i) * 15 + c0 + j]; };
-    blk(17, 0, 9); blk(26, 0, 12); blk(35, 3, 12); blk(44, 6, 9); blk(53, 6, 12);
+    fill_imu_rec(*p, rec);
     rec[287] = 1.0;
 }
 
-extern "C" int vilf_eval_imu(vilf_handle *h, const double *const *p, const vilf_imu_preint *pre, double *residuals, double **jac) {
-    if (!h || !p || !pre || !residuals) return VILF_ERR_INVALID_ARGUMENT;
+// IMUFactor::Evaluate on the device for one factor (k_imu_prep + k_hook_imu); *d_out: the hook buffer, results at + 2048 (weighted), + 3072 (raw), sqrt_info inside the record at + 40
+static int run_imu_hook(vilf_handle *h, const double *const *p, const vilf_imu_preint *pre, double **d_out) {
     if (hook_buf(h, 4096) != VILF_OK) return VILF_ERR_DEVICE;
-    double *d = h->d[D_HOOK].as<double>();
+    double *d = *d_out = h->d[D_HOOK].as<double>();
     std::vector<double> in(40 + IMU_REC + 225, 0.0);
     std::memcpy(&in[0], p[0], 56); std::memcpy(&in[7], p[1], 72); std::memcpy(&in[16], p[2], 56); std::memcpy(&in[23], p[3], 72);
     for (int i = 0; i < 3; i++) in[32 + i] = h->opts.G[i];
     pack_imu_rec(pre, &in[40]);
     std::memcpy(&in[40 + IMU_REC], pre->covariance, 225 * 8);
-    HIPCHECK(h, hipMemcpyAsync(d, in.data(), in.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, vilf_copy_sync(h, d, in.data(), in.size() * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_imu_prep, dim3(1), dim3(IMU_PREP_NT), 0, h->stream, 1, d + 40 + IMU_REC, d + 1024, d + 40);
     hipLaunchKernelGGL(k_hook_imu, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 7, d + 16, d + 23, d + 40, d + 32, d + 2048, d + 3072);
+    return VILF_OK;
+}
+extern "C" int vilf_eval_imu(vilf_handle *h, const double *const *p, const vilf_imu_preint *pre, double *residuals, double **jac) {
+    if (!h || !p || !pre || !residuals) return VILF_ERR_INVALID_ARGUMENT;
+    double *d;
+    { const int rc = run_imu_hook(h, p, pre, &d); if (rc != VILF_OK) return rc; }
     std::vector<double> out(15 + 450);
     HIPCHECK(h, hipMemcpyAsync(out.data(), d + 2048, out.size() * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
@@ -1302,16 +1304,8 @@ extern "C" int vilf_eval_imu(vilf_handle *h, const double *const *p, const vilf_
 // computes once per upload (k_imu_prep) — the tests compare each tightly instead of only their ill-conditioned product
 extern "C" int vilf_eval_imu_raw(vilf_handle *h, const double *const *p, const vilf_imu_preint *pre, double *residuals, double **jac, double *sqrt_info_out) {
     if (!h || !p || !pre || !residuals) return VILF_ERR_INVALID_ARGUMENT;
-    if (hook_buf(h, 4096) != VILF_OK) return VILF_ERR_DEVICE;
-    double *d = h->d[D_HOOK].as<double>();
-    std::vector<double> in(40 + IMU_REC + 225, 0.0);
-    std::memcpy(&in[0], p[0], 56); std::memcpy(&in[7], p[1], 72); std::memcpy(&in[16], p[2], 56); std::memcpy(&in[23], p[3], 72);
-    for (int i = 0; i < 3; i++) in[32 + i] = h->opts.G[i];
-    pack_imu_rec(pre, &in[40]);
-    std::memcpy(&in[40 + IMU_REC], pre->covariance, 225 * 8);
-    HIPCHECK(h, hipMemcpyAsync(d, in.data(), in.size() * 8, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_imu_prep, dim3(1), dim3(IMU_PREP_NT), 0, h->stream, 1, d + 40 + IMU_REC, d + 1024, d + 40);
-    hipLaunchKernelGGL(k_hook_imu, dim3(1), dim3(HOOK_NT), 0, h->stream, d, d + 7, d + 16, d + 23, d + 40, d + 32, d + 2048, d + 3072);
+    double *d;
+    { const int rc = run_imu_hook(h, p, pre, &d); if (rc != VILF_OK) return rc; }
     std::vector<double> raw(450 + 15), S(225);
     HIPCHECK(h, hipMemcpyAsync(raw.data(), d + 3072, raw.size() * 8, hipMemcpyDeviceToHost, h->stream));       // scratch of k_hook_imu: J_raw [15 x 30], r_raw [15]
     HIPCHECK(h, hipMemcpyAsync(S.data(), d + 40 + IMU_SQRT, 225 * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1329,13 +1323,7 @@ extern "C" int vilf_eval_imu_raw(vilf_handle *h, const double *const *p, const v
 extern "C" int vilf_eval_lidar_between(vilf_handle *h, const double *const *p, const vilf_lidar_constraint *c, double *residuals, double **jac) {
     if (!h || !p || !c || !residuals) return VILF_ERR_INVALID_ARGUMENT;
     if (hook_buf(h, 256) != VILF_OK) return VILF_ERR_DEVICE;
-    if (!h->resident) {   // qil / til are derived at upload; derive here too
-        const vilf_options &o = h->opts; VbBatch &b = h->batch;
-        double M[9];
-        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M[3 * i + j] = o.RIC[3 * i] * o.RCL[j] + o.RIC[3 * i + 1] * o.RCL[3 + j] + o.RIC[3 * i + 2] * o.RCL[6 + j];
-        quat_from_R(M, b.qil);
-        for (int i = 0; i < 3; i++) b.til[i] = o.RIC[3 * i] * o.TCL[0] + o.RIC[3 * i + 1] * o.TCL[1] + o.RIC[3 * i + 2] * o.TCL[2] + o.TIC[i];
-    }
+    if (!h->resident) lidar_extrinsic(h->opts, h->batch);   // qil / til are derived at upload; derive here too
     double in[32];
     std::memcpy(in, p[0], 56); std::memcpy(in + 7, p[1], 56);
     std::memcpy(in + 14, h->batch.qil, 32); std::memcpy(in + 18, h->batch.til, 24);

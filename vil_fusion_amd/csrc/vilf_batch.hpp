@@ -1,16 +1,18 @@
 // vilf_batch.hpp — device-resident layout of a batch of independent sliding windows (one workgroup per window).
 //
-// Memory layout in HBM (all per-window arrays are [B][stride] with strides fixed per upload):
-//   state      pose[B][11*7]  sb[B][11*9]  feat[B][Fmax]          (+ *_init copies for rewind, cand_* trial point)
-//   features   f_start/f_nobs/f_obs0/f_fac0/f_const [B][Fmax]     (CSR over observations, feature_manager order)
-//   obs        obs[B][Omax][3]                                     (feature_per_frame[k].point)
-//   factors    facrec / ps_obs / ps_slot [B][FACmax]               (one slot per (feature, later observation); the factors of a frame pair (i<j) are contiguous inside
+// Memory layout in HBM (all per-window arrays are [B][stride] with strides fixed per upload; the host's table of them, with sizes: kBatchArrays, vilf_api.hip):
+//   state      pose[B][11*7]  sb[B][11*9]  feat[B][Fmax]  ex[B][7]  td[B]   (+ *_init copies for rewind, cand_* trial point)
+//   features   f_start/f_nobs/f_fac0/f_const [B][Fmax]             (feature_manager order)
+//   factors    facrec[B][FACmax][8] / ps_slot[B][FACmax]           (one slot per (feature, later observation); the factors of a frame pair (i<j) are contiguous inside
 //                                                                   the list of the pair's wave class, the four class lists interleaved 56 slots at a time (VB_SLOT);
-//                                                                   unused slots carry a null record; ps_slot = index in feature-major order)
+//                                                                   unused slots carry a null record; ps_slot = index in feature-major order. The observation points
+//                                                                   (feature_per_frame[k].point) and the factor -> feature map travel inside facrec)
+//   td only    f_obs0[B][Fmax] ps_obs[B][FACmax] obs_vel[B][Omax][2] obs_ctd/obs_row[B][Omax]   (estimate_td: observation indices and the per-observation inputs
+//                                                                   of ProjectionTdFactor; 8-byte placeholders otherwise)
 //   pairs      pair_off[B][VB_PTAB]                                (per pair: start inside its class list, factor count, class)
 //   imu        imu[B][10][288]  (delta_*, bias jacobians, 15x15 sqrt_info precomputed once: imu_factor.h:64)
 //   lidar      lidar[B][10][7]
-//   prior      hdr[B][80] x0[B][24][9] J[B][160*160] r[B][160] H=J^T J [B][160*160] g=J^T r [B][160]
+//   prior      hdr[B][80] x0[B][24][9] J[B][160*160] r[B][160] H=J^T J [B][160*160] g=J^T r [B][160]   (two sets: live / as uploaded)
 //   workspace  facw[B][8][FACmax] (per factor: Ji^T Jf (6), Jf^T Jf, Jf^T r)  Hpp[B][66][36] (visual pose-pose blocks)
 //              W[B][Fmax][80] (H_pf rows zero-initialised at upload; the feature's frame range + column 66 = g_f are
 //              rewritten every linearization) hf gf [B][Fmax]
@@ -43,6 +45,16 @@
 #define VB_PRIOR_LD 160
 #define IMU_REC 288         // doubles per IMU factor record (layout: vilf_device.hpp, IMUFactor raw part)
 #define IMU_SQRT 62         // sqrt_info (15 x 15) inside the record
+// per-window strides (doubles unless noted) of the fixed-size arrays, for the host code that sizes, copies and reads them back
+#define VB_POSE_LD (VB_NF * 7)          // pose / cand_pose / pose_init: para_Pose
+#define VB_SB_LD (VB_NF * 9)            // sb / cand_sb / sb_init: para_SpeedBias
+#define VB_EX_LD 7                      // ex: para_Ex_Pose
+#define VB_OUT3_LD (VB_NF * 3)          // out_Ps / out_Vs / out_Bas / out_Bgs
+#define VB_OUTR_LD (VB_NF * 9)          // out_Rs
+#define VB_PRIOR_X0_LD (24 * 9)         // prior_x0: 24 blocks of up to 9 values
+#define VB_IMU_LD (10 * IMU_REC)        // imu: one record per consecutive frame pair
+#define VB_LIDAR_LD (10 * 7)            // lidar: q, t per consecutive frame pair
+#define VB_COV_LD (10 * 225)            // the 15 x 15 pre-integration covariances k_imu_prep factorises
 
 // ---- k_solve_sb: speed-bias-first elimination (vilf_kernels.hip) -------------------------------------------------------
 // After the feature Schur complement the speed-bias part of the reduced system is block tridiagonal (an IMU factor couples consecutive frames only,
@@ -172,11 +184,11 @@ struct VbBatch {
     // problem description
     const int *f_start, *f_nobs, *f_obs0, *f_fac0;
     const uint8_t *f_const;
-    const double *obs;
+    const double *obs;      // unused, NULL: nothing is resident behind it (the points travel inside facrec); kept so that the kernel-argument layout stays
     const double *obs_vel, *obs_ctd, *obs_row;   // estimate_td only: [B][Omax][2] pixel velocity, [B][Omax] td at capture, [B][Omax] image row (ProjectionTdFactor, projection_td_factor.cpp:6-21)
     double *td;             // [B] para_Td
     int est_td; double tr_over_row, row_half;
-    const int *ps_feat, *ps_obs, *ps_slot;
+    const int *ps_feat, *ps_obs, *ps_slot;   // ps_feat: unused, NULL (the feature index is part of facrec); ps_obs: estimate_td only
     const int *pair_off;
     const double *facrec;   // [B][FACmax][8]: per pair-sorted factor {pts_i[3], pts_j[3], (feature | slot << 32), (frame_i | frame_j << 8 | const << 16)} — one
                             // coalesced 64-byte record instead of five dependent gathers

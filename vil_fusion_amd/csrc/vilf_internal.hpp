@@ -25,7 +25,7 @@ struct DBuf {
 
 enum {
     D_NFEAT, D_NFAC, D_POSE, D_SB, D_FEAT, D_CPOSE, D_CSB, D_CFEAT, D_POSE0, D_SB0, D_FEAT0, D_EX, D_GR0, D_GP0,
-    D_FSTART, D_FNOBS, D_FOBS0, D_FFAC0, D_FCONST, D_OBS, D_PSFEAT, D_PSOBS, D_PSSLOT, D_PAIROFF, D_IMU, D_LIDAR,
+    D_FSTART, D_FNOBS, D_FOBS0, D_FFAC0, D_FCONST, D_PSOBS, D_PSSLOT, D_PAIROFF, D_IMU, D_LIDAR,
     D_PHDR, D_PX0, D_PJ, D_PR, D_PH, D_PG, D_FACW, D_HPP, D_W, D_HF, D_GF, D_IMUH, D_IMUG, D_LIDH, D_LIDG, D_G, D_DIAGH,
     D_SCALE, D_DIAG, D_GRAD, D_GN, D_ST, D_OPS, D_ORS, D_OVS, D_OBAS, D_OBGS, D_COV, D_WORK, D_HOOK, D_DBG, D_LUTI, D_LUTL, D_LUTV,
     D_MFLAG, D_MINFO, D_MF0, D_MSTP, D_MSTS, D_MSTF, D_MSTE, D_MBUF, D_MHD, D_MGD, D_MWF, D_MHF, D_MGF, D_MAMM, D_MX, D_MROT, D_MLAM, D_MAR, D_MBR, D_QLV, D_QLD, D_QLLOG, D_QLIT, D_QLINFO,
@@ -85,7 +85,6 @@ struct vilf_handle {
     std::vector<char> prior_dense;           // slot's live prior (imported from the host) holds a speed-bias block other than SpeedBias[0]
     int prior_dense_count = 0;
     std::vector<char> prior_dev_newer;       // slot's prior was produced on the device (marginalize) and not yet mirrored
-    std::vector<int> h_mflag;
     int prior_slots_valid = 0;               // the device prior arrays hold slots 0 .. prior_slots_valid-1 (survive a re-upload of the windows)
     bool prior_backup_valid = false;         // D_P*0 hold the priors as last uploaded
     bool prior_restore_needed = false;       // a marginalization has overwritten the device priors since that backup

@@ -1919,16 +1919,16 @@ int vilf_lw_group_solve(vilf_handle *h, int G, const vilf_window_in *const *ins,
     const size_t rF = any_slot ? (size_t)h->batch.Fmax : 0;
     if (any_slot) {
         std::vector<int> hdr_all; std::vector<double> x0_all;
-        r_pose.resize((size_t)G * 77); r_sb.resize((size_t)G * 99); r_feat.resize((size_t)G * std::max<size_t>(rF, 1)); r_ex.resize((size_t)G * 7); r_td.resize(G);
+        r_pose.resize((size_t)G * VB_POSE_LD); r_sb.resize((size_t)G * VB_SB_LD); r_feat.resize((size_t)G * std::max<size_t>(rF, 1)); r_ex.resize((size_t)G * VB_EX_LD); r_td.resize(G);
         if (contig) {
             const size_t s0 = hws[0].slot;
-            hdr_all.resize((size_t)G * VB_PRIOR_HDR); x0_all.resize((size_t)G * 24 * 9);
+            hdr_all.resize((size_t)G * VB_PRIOR_HDR); x0_all.resize((size_t)G * VB_PRIOR_X0_LD);
             // seven copies: through the pinned image of the previous group when there is one (it is idle here) — a copy into pageable memory is staged by the runtime
             // and waited for, ~25 us each; from pinned memory the seven are enqueued in ~25 us together (round 5)
             struct Seg { void *dst; const void *src; size_t bytes; };
-            const Seg segs[7] = {{hdr_all.data(), h->d[D_PHDR].as<int>() + s0 * VB_PRIOR_HDR, hdr_all.size() * 4}, {x0_all.data(), h->d[D_PX0].as<double>() + s0 * 24 * 9, x0_all.size() * 8},
-                                 {r_pose.data(), h->d[D_POSE].as<double>() + s0 * 77, r_pose.size() * 8}, {r_sb.data(), h->d[D_SB].as<double>() + s0 * 99, r_sb.size() * 8},
-                                 {r_feat.data(), h->d[D_FEAT].as<double>() + s0 * rF, (size_t)G * rF * 8}, {r_ex.data(), h->d[D_EX].as<double>() + s0 * 7, r_ex.size() * 8},
+            const Seg segs[7] = {{hdr_all.data(), h->d[D_PHDR].as<int>() + s0 * VB_PRIOR_HDR, hdr_all.size() * 4}, {x0_all.data(), h->d[D_PX0].as<double>() + s0 * VB_PRIOR_X0_LD, x0_all.size() * 8},
+                                 {r_pose.data(), h->d[D_POSE].as<double>() + s0 * VB_POSE_LD, r_pose.size() * 8}, {r_sb.data(), h->d[D_SB].as<double>() + s0 * VB_SB_LD, r_sb.size() * 8},
+                                 {r_feat.data(), h->d[D_FEAT].as<double>() + s0 * rF, (size_t)G * rF * 8}, {r_ex.data(), h->d[D_EX].as<double>() + s0 * VB_EX_LD, r_ex.size() * 8},
                                  {r_td.data(), h->d[D_TD].as<double>() + s0, r_td.size() * 8}};
             size_t tot = 0;
             for (const Seg &sg : segs) tot += (sg.bytes + 63) & ~(size_t)63;
@@ -1945,18 +1945,18 @@ int vilf_lw_group_solve(vilf_handle *h, int G, const vilf_window_in *const *ins,
                 LwHostWin &w = hws[g];
                 if (!w.resident) continue;
                 HIPCHECK(h, hipMemcpyAsync(w.phdr, h->d[D_PHDR].as<int>() + w.slot * VB_PRIOR_HDR, sizeof(w.phdr), hipMemcpyDeviceToHost, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(w.px0, h->d[D_PX0].as<double>() + w.slot * 24 * 9, sizeof(w.px0), hipMemcpyDeviceToHost, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(&r_pose[(size_t)g * 77], h->d[D_POSE].as<double>() + w.slot * 77, 77 * 8, hipMemcpyDeviceToHost, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(&r_sb[(size_t)g * 99], h->d[D_SB].as<double>() + w.slot * 99, 99 * 8, hipMemcpyDeviceToHost, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(w.px0, h->d[D_PX0].as<double>() + w.slot * VB_PRIOR_X0_LD, sizeof(w.px0), hipMemcpyDeviceToHost, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(&r_pose[(size_t)g * VB_POSE_LD], h->d[D_POSE].as<double>() + w.slot * VB_POSE_LD, VB_POSE_LD * 8, hipMemcpyDeviceToHost, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(&r_sb[(size_t)g * VB_SB_LD], h->d[D_SB].as<double>() + w.slot * VB_SB_LD, VB_SB_LD * 8, hipMemcpyDeviceToHost, h->stream));
                 if (rF) HIPCHECK(h, hipMemcpyAsync(&r_feat[(size_t)g * rF], h->d[D_FEAT].as<double>() + w.slot * rF, rF * 8, hipMemcpyDeviceToHost, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(&r_ex[(size_t)g * 7], h->d[D_EX].as<double>() + w.slot * 7, 56, hipMemcpyDeviceToHost, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(&r_ex[(size_t)g * VB_EX_LD], h->d[D_EX].as<double>() + w.slot * VB_EX_LD, VB_EX_LD * 8, hipMemcpyDeviceToHost, h->stream));
                 HIPCHECK(h, hipMemcpyAsync(&r_td[g], h->d[D_TD].as<double>() + w.slot, 8, hipMemcpyDeviceToHost, h->stream));
             }
         HIPCHECK(h, hipStreamSynchronize(h->stream));
         for (int g = 0; g < G; g++) {
             LwHostWin &w = hws[g];
             if (!w.resident) continue;
-            if (contig) { std::memcpy(w.phdr, &hdr_all[(size_t)g * VB_PRIOR_HDR], sizeof(w.phdr)); std::memcpy(w.px0, &x0_all[(size_t)g * 24 * 9], sizeof(w.px0)); }
+            if (contig) { std::memcpy(w.phdr, &hdr_all[(size_t)g * VB_PRIOR_HDR], sizeof(w.phdr)); std::memcpy(w.px0, &x0_all[(size_t)g * VB_PRIOR_X0_LD], sizeof(w.px0)); }
             if (w.phdr[0]) { w.pn = w.phdr[1]; w.pnb = w.phdr[2]; }
         }
     }
@@ -2309,37 +2309,37 @@ int vilf_lw_group_solve(vilf_handle *h, int G, const vilf_window_in *const *ins,
             stt.iteration = hc.iteration; stt.num_successful = hc.num_successful; stt.num_linear_solves = hc.num_linear_solves;
             stt.termination = hc.termination; stt.initial_cost = hc.initial_cost; stt.x_cost = hc.x_cost; stt.radius = hc.radius; stt.done = 1;
             if (contig) {
-                std::memcpy(&b_pose[(size_t)g * 77], &x[0], 77 * 8); std::memcpy(&b_sb[(size_t)g * 99], &x[77], 99 * 8);
+                std::memcpy(&b_pose[(size_t)g * VB_POSE_LD], &x[0], VB_POSE_LD * 8); std::memcpy(&b_sb[(size_t)g * VB_SB_LD], &x[VB_POSE_LD], VB_SB_LD * 8);
                 for (int f = 0; f < F; f++) b_feat[(size_t)g * sF2 + f] = x[16 * (size_t)NF + f];
-                std::memcpy(&b_ex[(size_t)g * 7], &x[xo], 56); b_td[g] = out->td;
-                std::memcpy(&b_ps[(size_t)g * 33], out->Ps, 33 * 8); std::memcpy(&b_rs[(size_t)g * 99], out->Rs, 99 * 8); std::memcpy(&b_vs[(size_t)g * 33], out->Vs, 33 * 8);
-                std::memcpy(&b_bas[(size_t)g * 33], out->Bas, 33 * 8); std::memcpy(&b_bgs[(size_t)g * 33], out->Bgs, 33 * 8);
+                std::memcpy(&b_ex[(size_t)g * VB_EX_LD], &x[xo], VB_EX_LD * 8); b_td[g] = out->td;
+                std::memcpy(&b_ps[(size_t)g * VB_OUT3_LD], out->Ps, VB_OUT3_LD * 8); std::memcpy(&b_rs[(size_t)g * VB_OUTR_LD], out->Rs, VB_OUTR_LD * 8); std::memcpy(&b_vs[(size_t)g * VB_OUT3_LD], out->Vs, VB_OUT3_LD * 8);
+                std::memcpy(&b_bas[(size_t)g * VB_OUT3_LD], out->Bas, VB_OUT3_LD * 8); std::memcpy(&b_bgs[(size_t)g * VB_OUT3_LD], out->Bgs, VB_OUT3_LD * 8);
                 b_st.push_back(stt);
             } else {
-                HIPCHECK(h, hipMemcpyAsync(h->d[D_POSE].as<double>() + s * 77, &x[0], 77 * 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(h->d[D_SB].as<double>() + s * 99, &x[77], 99 * 8, hipMemcpyHostToDevice, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(h->d[D_POSE].as<double>() + s * VB_POSE_LD, &x[0], VB_POSE_LD * 8, hipMemcpyHostToDevice, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(h->d[D_SB].as<double>() + s * VB_SB_LD, &x[VB_POSE_LD], VB_SB_LD * 8, hipMemcpyHostToDevice, h->stream));
                 if (F) HIPCHECK(h, hipMemcpyAsync(h->d[D_FEAT].as<double>() + s * sF2, &x[16 * (size_t)NF], (size_t)F * 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(h->d[D_EX].as<double>() + s * 7, &x[xo], 56, hipMemcpyHostToDevice, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(h->d[D_EX].as<double>() + s * VB_EX_LD, &x[xo], VB_EX_LD * 8, hipMemcpyHostToDevice, h->stream));
                 HIPCHECK(h, hipMemcpyAsync(h->d[D_TD].as<double>() + s, &out->td, 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(h->d[D_OPS].as<double>() + s * 33, out->Ps, 33 * 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(h->d[D_ORS].as<double>() + s * 99, out->Rs, 99 * 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(h->d[D_OVS].as<double>() + s * 33, out->Vs, 33 * 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(h->d[D_OBAS].as<double>() + s * 33, out->Bas, 33 * 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHECK(h, hipMemcpyAsync(h->d[D_OBGS].as<double>() + s * 33, out->Bgs, 33 * 8, hipMemcpyHostToDevice, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(h->d[D_OPS].as<double>() + s * VB_OUT3_LD, out->Ps, VB_OUT3_LD * 8, hipMemcpyHostToDevice, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(h->d[D_ORS].as<double>() + s * VB_OUTR_LD, out->Rs, VB_OUTR_LD * 8, hipMemcpyHostToDevice, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(h->d[D_OVS].as<double>() + s * VB_OUT3_LD, out->Vs, VB_OUT3_LD * 8, hipMemcpyHostToDevice, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(h->d[D_OBAS].as<double>() + s * VB_OUT3_LD, out->Bas, VB_OUT3_LD * 8, hipMemcpyHostToDevice, h->stream));
+                HIPCHECK(h, hipMemcpyAsync(h->d[D_OBGS].as<double>() + s * VB_OUT3_LD, out->Bgs, VB_OUT3_LD * 8, hipMemcpyHostToDevice, h->stream));
                 HIPCHECK(h, hipMemcpyAsync(h->batch.st + s, &stt, sizeof(stt), hipMemcpyHostToDevice, h->stream));
                 HIPCHECK(h, hipStreamSynchronize(h->stream));              // the sources are locals of this iteration
             }
-            std::memcpy(&h->h_ex[s * 7], &x[xo], 56); h->h_td[s] = out->td;
+            std::memcpy(&h->h_ex[s * VB_EX_LD], &x[xo], VB_EX_LD * 8); h->h_td[s] = out->td;
         }
     }
     if (contig) {
         const size_t s0 = hws[0].slot;
         struct Seg { void *dst; const void *src; size_t bytes; };
-        const Seg segs[11] = {{h->d[D_POSE].as<double>() + s0 * 77, b_pose.data(), b_pose.size() * 8}, {h->d[D_SB].as<double>() + s0 * 99, b_sb.data(), b_sb.size() * 8},
-                              {h->d[D_FEAT].as<double>() + s0 * sF2, b_feat.data(), sF2 ? b_feat.size() * 8 : 0}, {h->d[D_EX].as<double>() + s0 * 7, b_ex.data(), b_ex.size() * 8},
-                              {h->d[D_TD].as<double>() + s0, b_td.data(), b_td.size() * 8}, {h->d[D_OPS].as<double>() + s0 * 33, b_ps.data(), b_ps.size() * 8},
-                              {h->d[D_ORS].as<double>() + s0 * 99, b_rs.data(), b_rs.size() * 8}, {h->d[D_OVS].as<double>() + s0 * 33, b_vs.data(), b_vs.size() * 8},
-                              {h->d[D_OBAS].as<double>() + s0 * 33, b_bas.data(), b_bas.size() * 8}, {h->d[D_OBGS].as<double>() + s0 * 33, b_bgs.data(), b_bgs.size() * 8},
+        const Seg segs[11] = {{h->d[D_POSE].as<double>() + s0 * VB_POSE_LD, b_pose.data(), b_pose.size() * 8}, {h->d[D_SB].as<double>() + s0 * VB_SB_LD, b_sb.data(), b_sb.size() * 8},
+                              {h->d[D_FEAT].as<double>() + s0 * sF2, b_feat.data(), sF2 ? b_feat.size() * 8 : 0}, {h->d[D_EX].as<double>() + s0 * VB_EX_LD, b_ex.data(), b_ex.size() * 8},
+                              {h->d[D_TD].as<double>() + s0, b_td.data(), b_td.size() * 8}, {h->d[D_OPS].as<double>() + s0 * VB_OUT3_LD, b_ps.data(), b_ps.size() * 8},
+                              {h->d[D_ORS].as<double>() + s0 * VB_OUTR_LD, b_rs.data(), b_rs.size() * 8}, {h->d[D_OVS].as<double>() + s0 * VB_OUT3_LD, b_vs.data(), b_vs.size() * 8},
+                              {h->d[D_OBAS].as<double>() + s0 * VB_OUT3_LD, b_bas.data(), b_bas.size() * 8}, {h->d[D_OBGS].as<double>() + s0 * VB_OUT3_LD, b_bgs.data(), b_bgs.size() * 8},
                               {h->batch.st + s0, b_st.data(), b_st.size() * sizeof(VbState)}};
         size_t tot = 0;
         for (const Seg &sg : segs) tot += (sg.bytes + 63) & ~(size_t)63;
