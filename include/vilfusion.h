@@ -435,6 +435,13 @@ int vilf_get_profile_sc(vilf_handle *h, double ms_out[4], long launches_out[4]);
  *   result       pcl::getTranslationAndEulerAngles(final): roll = atan2(m21, m22), pitch = asin(-m20), yaw = atan2(m10, m00), each the fp64 function of the float
  *                entries rounded to float -> pose6 [x y z roll pitch yaw]; pose_qt = [qx qy qz qw tx ty tz] of Rot3::RzRyRx(roll, pitch, yaw) in fp64, qw >= 0
  *                (:428-432). The loop edge measures its inverse (:433-436), which PoseGraph.add_loop takes.
+ *   global map   publishGlobalMap :310-336 (driven by loopMap :338-347, topic /Map_graph): the clouds first, first + skip, ... (< first + count), each under its OWN
+ *                pose whatever own_pose says (:320), concatenated in key-frame order, then pcl::VoxelGrid with leaf `leaf_size` (:326-327): transform, voxel-filter
+ *                arithmetic and summation order are the sub-map's, above, so the map of an own_pose = 1 store equals the sub-map over the same clouds bit for bit.
+ *                Rebuilt from scratch by every call, as the reference does every 5 s: a loop closure moves every pose. The map lives in a buffer of its own until
+ *                the next build or vilf_icp_create; no align or sub-map call writes it. An empty selection is an empty map. More than 2^30 selected points, or a
+ *                bounding box of 2^40 leaves or more, is VILF_ERR_UNSUPPORTED: the store stays as it was and the previous map is dropped (size 0). This
+ *                deliberately does not mirror PCL's int32 guard, which warns and returns the input unfiltered.
  * vilf_reset leaves the store alone; vilf_icp_create resets it. */
 typedef struct vilf_icp_params {
     double max_correspondence_distance;  /* 100 (:402) */
@@ -481,6 +488,16 @@ int vilf_icp_get_history(vilf_handle *h, int pair, vilf_icp_iter *out, int cap, 
 int vilf_icp_get_search(vilf_handle *h, int pair, int which, int *index_out, float *d2_out, int cap, int *n_out);
 /* vilf_set_profiling: icp_bbox, icp_leaf_keys, radix sorts, icp_voxel, icp_cell_keys + icp_cell_table, icp_search, icp_step, (unused) */
 int vilf_get_profile_icp(vilf_handle *h, double ms_out[8], long launches_out[8]);
+/* publishGlobalMap: clouds first, first+skip, ... (< first+count) each under its OWN pose (whatever own_pose says), concatenated in key-frame order, VoxelGrid(leaf_size).
+ * One chain of launches over the whole grid, one wait. Invalid argument, nothing enqueued, the previous map kept: first < 0, count < 0, skip < 1, first + count > size,
+ * a null poses6 or n_out, a pose that is not finite. count = 0 is a valid empty map. Like vilf_icp_submap, a build invalidates vilf_icp_get_history / get_search. */
+int vilf_icp_global_map(vilf_handle *h, int first, int count, int skip, const double *poses6 /*[size][6]*/, long *n_out);
+/* points of the current map (0: none built, or the last build failed) */
+int vilf_icp_global_map_size(vilf_handle *h, long *n_out);
+/* points [offset, offset + count) of the map, ascending leaf index. Outside [0, n), or before any build: invalid argument */
+int vilf_icp_global_map_get(vilf_handle *h, long offset, long count, float *xyzi_out /*[count][4]*/);
+/* vilf_set_profiling: gmap_xf_bbox + gmap_box, gmap_leaf_keys, radix sort, gmap_count + gmap_scan + gmap_centroids */
+int vilf_get_profile_icp_map(vilf_handle *h, double ms_out[4], long launches_out[4]);
 
 /* ---- scan-to-map (≙ EstimationMapping) -------------------------------------------------- */
 /* points are float xyzi (pcl::PointXYZI without padding): [n][4] */

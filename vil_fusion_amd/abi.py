@@ -23,6 +23,7 @@ MARGIN_SECOND_NEW = 1
 TERM_NAMES = {0: "NO_CONVERGENCE", 1: "CONVERGENCE_FUNCTION", 2: "CONVERGENCE_PARAMETER", 3: "CONVERGENCE_GRADIENT", 4: "FAILURE"}
 
 c_double_p = C.POINTER(C.c_double)
+c_long_p = C.POINTER(C.c_long)      # vilf_icp_global_map*: point counts of a map are long
 
 
 class Options(C.Structure):

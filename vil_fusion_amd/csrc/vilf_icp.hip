@@ -12,6 +12,12 @@
 // One align call is ONE chain of launches (max_iterations x (icp_search, icp_step) + the fitness pass); the host waits once, at the end. A pair whose `done` flag is set
 // makes the later launches of its grid row return at once. No floating-point atomics and no result that depends on which wave finishes first: partial sums have fixed
 // places and are added in a fixed order, every minimum is lexicographic in (d2, target index).
+// The global map (≙ publishGlobalMap :310-336) is built from the same store by kernels of its own, spread over the whole grid (a sub-map runs one workgroup per segment):
+//   gmap_xf_bbox    a workgroup per chunk of one cloud (host table chunk -> cloud, first point, count, place): the points under their cloud's own pose, a min/max partial
+//   gmap_box        one workgroup: the partials -> minb, divb, the overflow flag, by icp_bbox's rules
+//   gmap_leaf_keys  a thread per point: key = leaf index, value = place in concatenation order; then the same stable radix sort
+//   gmap_count, gmap_scan, gmap_centroids   leaf heads per block of sorted keys, the scan of the block counts, a thread per head: rank = block base + ballot rank,
+//                   its run summed in sorted order (across block boundaries), the centroid written at `rank` of the map's own buffer
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cfloat>
@@ -69,6 +75,33 @@ static_assert(sizeof(IcpSearchShared) == ICP_SRCH_LDS_BYTES && ICP_SRCH_LDS_BYTE
 #define ICP_STEP_NT 64                 // icp_step: grid = pairs, one wave
 struct IcpStepShared { double s[ICP_NSUM]; };
 static_assert(sizeof(IcpStepShared) <= VILF_LDS_CU_BYTES / 8, "icp_step: 136 B");
+struct GmapHdr { int minb[3], divb[3]; int n_in, n_out; };
+struct GmapDev {
+    const float4 *pts; const float *mats; const int4 *chunks;              // the store, [size][12] pose matrices, per chunk: cloud, first store point, count, first place
+    float *part; int nchunks;                                              // [nchunks][6] min / max of a chunk
+    float4 *tp, *map;                                                      // transformed points in concatenation order; the centroids in ascending leaf index
+    unsigned long long *k1, *k2; int *v1, *v2;
+    GmapHdr *hdr; int *bcount, *bbase, *flag;                              // heads per block of GM_RUN_NT sorted keys, their exclusive scan
+    int W, nblk;
+    float leaf;
+};
+#define GM_XF_NT 256                   // gmap_xf_bbox: grid = chunks, a chunk holds at most GM_CHUNK points of one cloud
+#define GM_CHUNK 1024
+#define GM_XF_WAVES (GM_XF_NT / 64)
+struct GmapBoxShared { float mn[GM_XF_WAVES][3], mx[GM_XF_WAVES][3]; };    // gmap_box: grid = 1, the same block and LDS
+#define GM_BOX_LDS_BYTES (GM_XF_WAVES * 6 * 4)
+static_assert(sizeof(GmapBoxShared) == GM_BOX_LDS_BYTES && GM_BOX_LDS_BYTES <= VILF_LDS_CU_BYTES / 8, "gmap_xf_bbox / gmap_box: 96 B");
+#define GM_RUN_NT 1024                 // gmap_count, gmap_centroids: grid = ceil(W / 1024), a thread per sorted key; gmap_scan: grid = 1, block counts in chunks of 1024
+#define GM_RUN_WAVES (GM_RUN_NT / 64)
+struct GmapRunShared { int wave[GM_RUN_WAVES]; };
+#define GM_RUN_LDS_BYTES (GM_RUN_WAVES * 4)
+static_assert(sizeof(GmapRunShared) == GM_RUN_LDS_BYTES && GM_RUN_LDS_BYTES <= VILF_LDS_CU_BYTES / 2, "gmap_count / gmap_scan / gmap_centroids: 64 B");
+__global__ void gmap_xf_bbox(GmapDev G);                                   // gmap_leaf_keys: ICP_PT_NT, grid = ceil(W / 256), no LDS
+__global__ void gmap_box(GmapDev G);
+__global__ void gmap_leaf_keys(GmapDev G);
+__global__ void gmap_count(GmapDev G);
+__global__ void gmap_scan(GmapDev G);
+__global__ void gmap_centroids(GmapDev G);
 __global__ void icp_bbox(IcpDev D);
 __global__ void icp_leaf_keys(IcpDev D);
 __global__ void icp_voxel(IcpDev D);
@@ -89,12 +122,23 @@ struct IcpCtx {
     int last_n = 0, last_W = 0;        // pairs and work elements of the last align call (vilf_icp_get_history / get_search)
     double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long launches[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DBuf gm_chunks, gm_part, gm_hdr, gm_bcount, gm_bbase, gm_map;      // the global map: gm_map is its own, no align or sub-map call writes it
+    std::vector<int> h_chunks;
+    bool gm_built = false;
+    long gm_n = 0;
+    double gm_ms[4] = {0, 0, 0, 0};
+    long gm_launches[4] = {0, 0, 0, 0};
     void release() {
-        DBuf *all[] = {&pts, &doff, &mats, &segs, &tp, &vox, &cur, &tgs, &k1, &k2, &v1, &v2, &temp, &hdr, &st, &cells, &part, &hist, &nn_idx, &nn_d2, &flag};
+        DBuf *all[] = {&pts, &doff, &mats, &segs, &tp, &vox, &cur, &tgs, &k1, &k2, &v1, &v2, &temp, &hdr, &st, &cells, &part, &hist, &nn_idx, &nn_d2, &flag,
+                       &gm_chunks, &gm_part, &gm_hdr, &gm_bcount, &gm_bbase, &gm_map};
         for (DBuf *b : all) b->release();
     }
 };
-void vilf_icp_profile_reset(vilf_handle *h) { if (h->icp) for (int i = 0; i < 8; i++) { h->icp->ms[i] = 0; h->icp->launches[i] = 0; } }
+void vilf_icp_profile_reset(vilf_handle *h) {
+    if (!h->icp) return;
+    for (int i = 0; i < 8; i++) { h->icp->ms[i] = 0; h->icp->launches[i] = 0; }
+    for (int i = 0; i < 4; i++) { h->icp->gm_ms[i] = 0; h->icp->gm_launches[i] = 0; }
+}
 void vilf_icp_release(vilf_handle *h) { if (h->icp) { h->icp->release(); delete h->icp; h->icp = nullptr; } }
 
 namespace {
@@ -709,5 +753,200 @@ extern "C" int vilf_get_profile_icp(vilf_handle *h, double ms_out[8], long launc
     if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
     { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
     for (int i = 0; i < 8; i++) { ms_out[i] = h->icp ? h->icp->ms[i] : 0.0; launches_out[i] = h->icp ? h->icp->launches[i] : 0; }
+    return VILF_OK;
+}
+
+// ---- the global map (≙ publishGlobalMap :310-336) -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(GM_XF_NT) void gmap_xf_bbox(GmapDev G) {
+    __shared__ GmapBoxShared sh;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int4 ch = G.chunks[blockIdx.x];              // x: cloud, y: first store point, z: count (<= GM_CHUNK), w: first place
+    float m[12];
+    for (int k = 0; k < 12; k++) m[k] = G.mats[12 * (size_t)ch.x + k];
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int j = t; j < ch.z; j += GM_XF_NT) {
+        const float4 q = icp_xf(m, G.pts[(size_t)ch.y + j]);
+        G.tp[(size_t)ch.w + j] = q;
+        mn[0] = fminf(mn[0], q.x); mn[1] = fminf(mn[1], q.y); mn[2] = fminf(mn[2], q.z);
+        mx[0] = fmaxf(mx[0], q.x); mx[1] = fmaxf(mx[1], q.y); mx[2] = fmaxf(mx[2], q.z);
+    }
+    for (int o = 32; o > 0; o >>= 1) for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], o)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o)); }
+    if (lane == 0) for (int k = 0; k < 3; k++) { sh.mn[wave][k] = mn[k]; sh.mx[wave][k] = mx[k]; }
+    lds_barrier();
+    if (t < 3) {
+        float a = sh.mn[0][t], b = sh.mx[0][t];
+        for (int w = 1; w < GM_XF_WAVES; w++) { a = fminf(a, sh.mn[w][t]); b = fmaxf(b, sh.mx[w][t]); }
+        G.part[6 * (size_t)blockIdx.x + t] = a; G.part[6 * (size_t)blockIdx.x + 3 + t] = b;
+    }
+}
+
+// the chunks' partials -> the box; the tail is icp_bbox's. Minimum and maximum do not depend on the order they are taken in.
+__global__ __launch_bounds__(GM_XF_NT) void gmap_box(GmapDev G) {
+    __shared__ GmapBoxShared sh;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int c = t; c < G.nchunks; c += GM_XF_NT) for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], G.part[6 * (size_t)c + k]); mx[k] = fmaxf(mx[k], G.part[6 * (size_t)c + 3 + k]); }
+    for (int o = 32; o > 0; o >>= 1) for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], o)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o)); }
+    if (lane == 0) for (int k = 0; k < 3; k++) { sh.mn[wave][k] = mn[k]; sh.mx[wave][k] = mx[k]; }
+    lds_barrier();
+    if (t == 0) {
+        GmapHdr *H = G.hdr;
+        H->n_in = G.W; H->n_out = 0;
+        const float inv = __fdiv_rn(1.0f, G.leaf);
+        double leaves = 1.0;               // exact: a product of integers below 2^71 compared with 2^40
+        for (int k = 0; k < 3; k++) {
+            float a = sh.mn[0][k], b = sh.mx[0][k];
+            for (int w = 1; w < GM_XF_WAVES; w++) { a = fminf(a, sh.mn[w][k]); b = fmaxf(b, sh.mx[w][k]); }
+            if (G.W == 0) { a = 0.f; b = 0.f; }
+            const float fa = floorf(__fmul_rn(a, inv)), fb = floorf(__fmul_rn(b, inv));
+            const bool bad = !(fabsf(fa) < 1e9f && fabsf(fb) < 1e9f);
+            H->minb[k] = bad ? 0 : (int)fa;
+            H->divb[k] = bad ? 1 : (int)fb - (int)fa + 1;
+            if (bad || leaves * (double)H->divb[k] >= (double)(1l << ICP_LEAF_BITS)) { G.flag[0] = 1; H->divb[k] = 1; } else leaves *= (double)H->divb[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(ICP_PT_NT) void gmap_leaf_keys(GmapDev G) {
+    const int i = blockIdx.x * ICP_PT_NT + threadIdx.x;
+    if (i >= G.W) return;
+    const GmapHdr *H = G.hdr;
+    const float4 q = G.tp[i];
+    const float inv = __fdiv_rn(1.0f, G.leaf);
+    long c[3];
+    const float v[3] = {q.x, q.y, q.z};
+    for (int k = 0; k < 3; k++) { long a = (long)floorf(__fmul_rn(v[k], inv)) - H->minb[k]; c[k] = a < 0 ? 0 : (a >= H->divb[k] ? H->divb[k] - 1 : a); }   // a clamp acts only after the overflow flag
+    G.k1[i] = (unsigned long long)(c[0] + c[1] * (long)H->divb[0] + c[2] * (long)H->divb[0] * (long)H->divb[1]);
+    G.v1[i] = i;
+}
+
+__global__ __launch_bounds__(GM_RUN_NT) void gmap_count(GmapDev G) {
+    __shared__ GmapRunShared sh;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const long i = (long)blockIdx.x * GM_RUN_NT + t;
+    const bool head = i < G.W && (i == 0 || G.k2[i] != G.k2[i - 1]);
+    const unsigned long long bal = __ballot(head);
+    if (lane == 0) sh.wave[wave] = __popcll(bal);
+    lds_barrier();
+    if (t == 0) { int total = 0; for (int w = 0; w < GM_RUN_WAVES; w++) total += sh.wave[w]; G.bcount[blockIdx.x] = total; }
+}
+
+__global__ __launch_bounds__(GM_RUN_NT) void gmap_scan(GmapDev G) {
+    __shared__ GmapRunShared sh;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    int base = 0;
+    for (int c0 = 0; c0 < G.nblk; c0 += GM_RUN_NT) {
+        const int i = c0 + t, v = i < G.nblk ? G.bcount[i] : 0;
+        int inc = v;
+        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
+        if (lane == 63) sh.wave[wave] = inc;
+        lds_barrier();
+        int before = 0, total = 0;
+        for (int w = 0; w < GM_RUN_WAVES; w++) { const int c = sh.wave[w]; before += w < wave ? c : 0; total += c; }
+        if (i < G.nblk) G.bbase[i] = base + before + inc - v;
+        base += total;
+        lds_barrier();
+    }
+    if (t == 0) G.hdr->n_out = base;
+}
+
+__global__ __launch_bounds__(GM_RUN_NT) void gmap_centroids(GmapDev G) {
+    __shared__ GmapRunShared sh;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const long i = (long)blockIdx.x * GM_RUN_NT + t;
+    const unsigned long long key = i < G.W ? G.k2[i] : 0ull;
+    const bool head = i < G.W && (i == 0 || key != G.k2[i - 1]);
+    const unsigned long long bal = __ballot(head);
+    if (lane == 0) sh.wave[wave] = __popcll(bal);
+    lds_barrier();
+    if (!head) return;
+    int before = 0;
+    for (int w = 0; w < wave; w++) before += sh.wave[w];
+    const int rank = G.bbase[blockIdx.x] + before + __popcll(bal & ((1ull << lane) - 1ull));
+    float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
+    long e = i;
+    for (; e < G.W && G.k2[e] == key; e++) { const float4 p = G.tp[G.v2[e]]; sx = __fadd_rn(sx, p.x); sy = __fadd_rn(sy, p.y); sz = __fadd_rn(sz, p.z); si = __fadd_rn(si, p.w); }
+    const float cnt = (float)(e - i);
+    G.map[rank] = make_float4(__fdiv_rn(sx, cnt), __fdiv_rn(sy, cnt), __fdiv_rn(sz, cnt), __fdiv_rn(si, cnt));
+}
+
+extern "C" int vilf_icp_global_map(vilf_handle *h, int first, int count, int skip, const double *poses6, long *n_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    IcpCtx *c = h->icp;
+    if (!c || !poses6 || !n_out) { h->err = "vilf_icp_global_map: no store (vilf_icp_create) or null argument"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (first < 0 || count < 0 || skip < 1 || (long)first + count > c->size) { h->err = "vilf_icp_global_map: first >= 0, count >= 0, skip >= 1, first + count <= size"; return VILF_ERR_INVALID_ARGUMENT; }
+    for (size_t i = 0; i < 6 * (size_t)c->size; i++) if (!std::isfinite(poses6[i])) { h->err = "vilf_icp_global_map: the pose of key frame " + std::to_string(i / 6) + " is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
+    c->gm_built = false; c->gm_n = 0; c->last_n = 0;
+    std::vector<int> &hc = c->h_chunks;
+    hc.clear();
+    long W = 0;
+    for (long k = first; k < (long)first + count; k += skip) {
+        const int p0 = c->off[k], n = c->off[k + 1] - p0;
+        if (W + n > INT_MAX / 2) { h->err = "vilf_icp_global_map: more than 2^30 points selected"; return VILF_ERR_UNSUPPORTED; }
+        for (int j = 0; j < n; j += GM_CHUNK) { const int q[4] = {(int)k, p0 + j, std::min(GM_CHUNK, n - j), (int)(W + j)}; hc.insert(hc.end(), q, q + 4); }
+        W += n;
+    }
+    const int nchunks = (int)(hc.size() / 4), nblk = (int)((W + GM_RUN_NT - 1) / GM_RUN_NT);
+    c->h_mats.resize((size_t)c->size * 12);
+    for (int k = 0; k < c->size; k++) icp_pose_matrix(poses6 + 6 * (size_t)k, c->h_mats.data() + 12 * (size_t)k);
+    const size_t Wn = std::max<long>(W, 1), tb = vilf_sort_temp_bytes(Wn, 8);
+    HIPCHECK(h, hipSetDevice(h->device));
+    const bool ok = c->gm_chunks.ensure(std::max<size_t>(hc.size(), 4) * 4) && c->gm_part.ensure(std::max(nchunks, 1) * (size_t)24) && c->gm_hdr.ensure(sizeof(GmapHdr)) &&
+                    c->gm_bcount.ensure(std::max(nblk, 1) * (size_t)4) && c->gm_bbase.ensure(std::max(nblk, 1) * (size_t)4) && c->gm_map.ensure(Wn * 16) && c->tp.ensure(Wn * 16) &&
+                    c->k1.ensure(Wn * 8) && c->k2.ensure(Wn * 8) && c->v1.ensure(Wn * 4) && c->v2.ensure(Wn * 4) && c->temp.ensure(tb + 256);
+    if (!ok) { h->err = "hipMalloc failed (global map work arrays)"; return VILF_ERR_DEVICE; }
+    if (nchunks > 0) HIPCHECK(h, hipMemcpyAsync(c->gm_chunks.p, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, h->stream));
+    if (c->size > 0) HIPCHECK(h, hipMemcpyAsync(c->mats.p, c->h_mats.data(), c->h_mats.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, hipMemsetAsync(c->flag.p, 0, 4, h->stream));
+    const GmapDev G{c->pts.as<float4>(), c->mats.as<float>(), c->gm_chunks.as<int4>(), c->gm_part.as<float>(), nchunks, c->tp.as<float4>(), c->gm_map.as<float4>(),
+                    c->k1.as<unsigned long long>(), c->k2.as<unsigned long long>(), c->v1.as<int>(), c->v2.as<int>(), c->gm_hdr.as<GmapHdr>(), c->gm_bcount.as<int>(),
+                    c->gm_bbase.as<int>(), c->flag.as<int>(), (int)W, nblk, (float)c->p.leaf_size};
+    const bool prof = h->profiling != 0;
+    hipEvent_t e = prof ? vilf_prof_event(h) : nullptr;
+    auto span = [&](int slot) { if (prof) { hipEvent_t e1 = vilf_prof_event(h); vilf_prof_span(h, e, e1, &c->gm_ms[slot], &c->gm_launches[slot]); e = e1; } };
+    if (nchunks > 0) hipLaunchKernelGGL(gmap_xf_bbox, dim3(nchunks), dim3(GM_XF_NT), 0, h->stream, G);
+    hipLaunchKernelGGL(gmap_box, dim3(1), dim3(GM_XF_NT), 0, h->stream, G); span(0);
+    if (W > 0) {
+        hipLaunchKernelGGL(gmap_leaf_keys, dim3((unsigned)((W + ICP_PT_NT - 1) / ICP_PT_NT)), dim3(ICP_PT_NT), 0, h->stream, G); span(1);
+        if (vilf_sort_pairs_u64(h->stream, c->temp.p, c->temp.cap, G.k1, G.k2, G.v1, G.v2, (size_t)W, ICP_LEAF_BITS) != 0) { h->err = "vilf_icp_global_map: radix sort failed"; return VILF_ERR_DEVICE; }
+        span(2);
+        hipLaunchKernelGGL(gmap_count, dim3(nblk), dim3(GM_RUN_NT), 0, h->stream, G);
+        hipLaunchKernelGGL(gmap_scan, dim3(1), dim3(GM_RUN_NT), 0, h->stream, G);
+        hipLaunchKernelGGL(gmap_centroids, dim3(nblk), dim3(GM_RUN_NT), 0, h->stream, G); span(3);
+    }
+    HIPCHECK(h, hipGetLastError());
+    GmapHdr H;
+    HIPCHECK(h, hipMemcpyAsync(&H, c->gm_hdr.p, sizeof(H), hipMemcpyDeviceToHost, h->stream));
+    const int rc = icp_finish(h, c);       // the one wait of the build
+    if (rc != VILF_OK) { if (rc == VILF_ERR_UNSUPPORTED) h->err = "vilf_icp_global_map: the map's bounding box holds 2^40 leaves or more"; return rc; }
+    c->gm_built = true; c->gm_n = H.n_out;
+    *n_out = c->gm_n;
+    return VILF_OK;
+}
+
+extern "C" int vilf_icp_global_map_size(vilf_handle *h, long *n_out) {
+    if (!h || !n_out) return VILF_ERR_INVALID_ARGUMENT;
+    *n_out = h->icp ? h->icp->gm_n : 0;
+    return VILF_OK;
+}
+
+extern "C" int vilf_icp_global_map_get(vilf_handle *h, long offset, long count, float *xyzi_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    IcpCtx *c = h->icp;
+    if (!c || !c->gm_built) { h->err = "vilf_icp_global_map_get: no map (vilf_icp_global_map)"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (offset < 0 || count < 0 || offset > c->gm_n || count > c->gm_n - offset || (count > 0 && !xyzi_out)) {
+        h->err = "vilf_icp_global_map_get: [" + std::to_string(offset) + ", " + std::to_string(offset) + " + " + std::to_string(count) + ") outside the map of " + std::to_string(c->gm_n) + " points, or null output";
+        return VILF_ERR_INVALID_ARGUMENT;
+    }
+    if (count == 0) return VILF_OK;
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, vilf_copy_sync(h, xyzi_out, c->gm_map.as<float4>() + offset, (size_t)count * 16, hipMemcpyDeviceToHost));
+    return VILF_OK;
+}
+
+extern "C" int vilf_get_profile_icp_map(vilf_handle *h, double ms_out[4], long launches_out[4]) {
+    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
+    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
+    for (int i = 0; i < 4; i++) { ms_out[i] = h->icp ? h->icp->gm_ms[i] : 0.0; launches_out[i] = h->icp ? h->icp->gm_launches[i] : 0; }
     return VILF_OK;
 }

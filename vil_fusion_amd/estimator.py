@@ -425,6 +425,7 @@ class ScanContext:
         return dict(zip(("sc_descriptor", "sc_ringkey_topk", "sc_distance", "sc_reduce"), ((ms[i], cnt[i]) for i in range(4))))
 
 
+ICP_MAP_KERNELS = ("gmap_xf_bbox", "gmap_leaf_keys", "radix_sort", "gmap_centroids")
 ICP_KERNELS = ("icp_bbox", "icp_leaf_keys", "radix_sort", "icp_voxel", "icp_cell_table", "icp_search", "icp_step", "unused")
 
 
@@ -534,6 +535,32 @@ class LoopICP:
         ms, cnt = (C.c_double * 8)(), (C.c_long * 8)()
         self.s._check(self._L.vilf_get_profile_icp(self.s._h, ms, cnt), "vilf_get_profile_icp")
         return dict(zip(ICP_KERNELS[:7], ((ms[i], cnt[i]) for i in range(7))))
+
+    def global_map(self, poses6, first=0, count=None, skip=1):
+        """publishGlobalMap :310-336: the clouds first, first + skip, ... (< first + count; count=None: to the end of the store), each under its own pose,
+        concatenated and voxel-filtered -> (n, 4) float32. The map stays on the device until the next build (global_map_size, global_map_part)."""
+        p = self._poses(poses6)
+        n = C.c_long(0)
+        cnt = len(self) - int(first) if count is None else int(count)
+        self.s._check(self._L.vilf_icp_global_map(self.s._h, int(first), cnt, int(skip), abi.dptr(p), C.byref(n)), "vilf_icp_global_map")
+        return self.global_map_part(0, n.value)
+
+    def global_map_size(self):
+        n = C.c_long(0)
+        self.s._check(self._L.vilf_icp_global_map_size(self.s._h, C.byref(n)), "vilf_icp_global_map_size")
+        return n.value
+
+    def global_map_part(self, offset, count):
+        """points [offset, offset + count) of the map built last -> (count, 4) float32"""
+        out = np.zeros((max(int(count), 1), 4), dtype=np.float32)
+        self.s._check(self._L.vilf_icp_global_map_get(self.s._h, int(offset), int(count), out.ctypes.data_as(C.POINTER(C.c_float))), "vilf_icp_global_map_get")
+        return out[:max(int(count), 0)]
+
+    def map_profile(self):
+        """ms and launches of the global-map stages since vilf_set_profiling was switched on"""
+        ms, cnt = (C.c_double * 4)(), (C.c_long * 4)()
+        self.s._check(self._L.vilf_get_profile_icp_map(self.s._h, ms, cnt), "vilf_get_profile_icp_map")
+        return dict(zip(ICP_MAP_KERNELS, ((ms[i], cnt[i]) for i in range(4))))
 
 
 class Scan2Map:

@@ -22,6 +22,7 @@ EXPORTED = [
     "vilf_sc_default_params", "vilf_sc_create", "vilf_sc_add_keyframe", "vilf_sc_add_keyframes", "vilf_sc_detect", "vilf_sc_detect_range", "vilf_sc_get", "vilf_sc_size", "vilf_get_profile_sc",
     "vilf_icp_default_params", "vilf_icp_create", "vilf_icp_add_cloud", "vilf_icp_add_clouds", "vilf_icp_size", "vilf_icp_submap", "vilf_icp_align", "vilf_icp_align_pairs",
     "vilf_icp_get_history", "vilf_icp_get_search", "vilf_get_profile_icp",
+    "vilf_icp_global_map", "vilf_icp_global_map_size", "vilf_icp_global_map_get", "vilf_get_profile_icp_map",
 ]
 
 
@@ -129,6 +130,10 @@ def lib():
     L.vilf_icp_get_history.argtypes = [vp, C.c_int, C.POINTER(abi.IcpIter), C.c_int, ip]
     L.vilf_icp_get_search.argtypes = [vp, C.c_int, C.c_int, ip, fpp, C.c_int, ip]
     L.vilf_get_profile_icp.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_icp_global_map.argtypes = [vp, C.c_int, C.c_int, C.c_int, abi.c_double_p, abi.c_long_p]
+    L.vilf_icp_global_map_size.argtypes = [vp, abi.c_long_p]
+    L.vilf_icp_global_map_get.argtypes = [vp, C.c_long, C.c_long, fpp]
+    L.vilf_get_profile_icp_map.argtypes = [vp, C.POINTER(C.c_double), abi.c_long_p]
     _lib = L
     return L
 

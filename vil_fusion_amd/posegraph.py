@@ -10,6 +10,8 @@ What the reference's threads do around gtsam, restated as plain host code over t
   * icpCalculation :376-443         with a verifier attached too (estimator.LoopICP over the device cloud store, vilf_icp_*): every key frame's cloud is stored,
                                    verify_loop(prev, curr) aligns the pair under the current poses and adds the loop edge when the result is accepted;
                                    close_loops() = detect_loop() + verify_loop(). Without a verifier add_loop takes its transform from the caller, as before.
+  * publishGlobalMap :310-336       global_map(): the stored clouds of the key frames before the newest updated one, each under its updated pose, voxel-filtered
+                                   (the verifier's global_map over the device store, vilf_icp_global_map)
 """
 import numpy as np
 
@@ -81,6 +83,7 @@ class PoseGraph:
         self.prev = np.zeros(6); self.curr = np.zeros(6)
         self.nodes = []               # key frames: dict(stamp, pose6d, updated6d)
         self.edges = []               # (i, j, q, t, sigma, robust)
+        self.recent_idx_updated = 0   # recentIdxUpdated (:44), set by update()
 
     def add_odometry(self, stamp, pose_qt, cloud=None):
         """one synchronised odometry message (:483-587) with its down-sampled cloud (thisKeyFrameDS; used only with a detector or a verifier attached, and then needed
@@ -147,7 +150,17 @@ class PoseGraph:
         x = self.backend(x0, PRIOR_SIGMA, self.edges)
         for n, p in zip(self.nodes, x):
             n["updated"] = np.concatenate([p[4:], rpy_from_q(p[:4])])
+        self.recent_idx_updated = len(self.nodes) - 1                        # updatePoses :235
         return x
+
+    def global_map(self, skip=1):
+        """publishGlobalMap (:310-336): None unless recentIdxUpdated > 1 (:312-313), else the (n, 4) map of the key frames [0, recentIdxUpdated) (the newest is left
+        out, :318) under their updated poses, every `skip`-th one"""
+        if self.verifier is None:
+            raise ValueError("no loop verifier attached: the key-frame clouds are not stored")
+        if not self.recent_idx_updated > 1:
+            return None
+        return self.verifier.global_map(np.array([n["updated"] for n in self.nodes]), first=0, count=self.recent_idx_updated, skip=skip)
 
     def save_tum(self, path):
         with open(path, "w") as fh:
