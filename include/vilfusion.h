@@ -549,6 +549,81 @@ int vilf_lidar_extract_features(vilf_handle *h, const float *xyzi, int n_points,
  * camera frame (xyzi), features as normalised image points (x, y, z = 1); depth_out[i] = depth of feature i (what the estimator
  * receives as point(7), estimator_node.cpp) or -1 when the 3 nearest returns do not support one. */
 int vilf_feature_depth(vilf_handle *h, const float *depth_cloud_xyzi, int n_points, const float *features_xyz, int n_features, float *depth_out);
+
+/* ---- Image feature tracker (≙ FeatureTracker::readImage, feature_tracker/feature_tracker.cpp:119-209; device) ----
+ * OpenCV is not available, so this text fixes the arithmetic itself; tests/track_reference.py restates it in numpy and the kernels agree with that to the bit.
+ * It is modelled on what the reference calls: cv::calcOpticalFlowPyrLK(.., Size(21,21), 3) (:151: window, levels, 30 iterations / 0.01 px, the 1e-4 minimum
+ * eigenvalue, 14-bit fixed-point patches, unnormalised Scharr gradients), cv::goodFeaturesToTrack(.., 0.01, MIN_DIST, mask) (:190), setMask (:36-71), inBorder
+ * (:5-11), undistortedPoints (:556-604), updateID. One deliberate difference makes bit identity possible: sums over a window are exact integer sums, where OpenCV
+ * adds floats in an unspecified SIMD order. Agreement with OpenCV itself is not measured and not claimed.
+ *   conventions  images are 8-bit, row-major, W x H. R(i, n) = reflect-101 of an index, applied periodically with period 2 (n - 1), so it is defined for any
+ *                offset. Points are float32 (x, y) pixel coordinates. "fp64 / float32, each operation rounded": every + - * / sqrt is its own IEEE operation
+ *                (no contraction). rint is round-half-to-even.
+ *   pyramid      level 0 is the image; level L + 1 has size ((W_L + 1) / 2, (H_L + 1) / 2) and value (sum_{i,j = -2..2} k_i k_j I_L(R(2x + i), R(2y + j)) + 128) >> 8,
+ *                k = [1 4 6 4 1]. Levels used: 0 .. Lmax, Lmax <= 3 the largest level whose two sides are both > 21.
+ *                Gradients (int): Gx(x, y) = 3 (I(x+1, y-1) - I(x-1, y-1)) + 10 (I(x+1, y) - I(x-1, y)) + 3 (I(x+1, y+1) - I(x-1, y+1)), Gy its transpose, image reads
+ *                through R; Gx = Gy = 0 at positions outside the image.
+ *   LK           per point, from level Lmax down to 0. p_L = float32(prev * 2^-L); q = p_L at Lmax, else 2 * the previous level's q.
+ *                corner: c = p_L - 10 in float32, (ix, iy) = floor(c), (a, b) = c - floor(c). Bounds: ix < -21, ix >= W_L, iy < -21 or iy >= H_L (or a coordinate
+ *                that is not a number): at level 0 status <- 0; at any level the level is skipped and q carried on unchanged.
+ *                weights (int, the products in float32, each operation rounded): w00 = rint((1-a)(1-b) 16384), w01 = rint(a (1-b) 16384), w10 = rint((1-a) b 16384),
+ *                w11 = 16384 - w00 - w01 - w10.
+ *                template, for the 21 x 21 offsets (u, v), bilinear over (ix+u, iy+v) and its right, lower and lower-right neighbours with w00, w01, w10, w11:
+ *                T = (sum w I + 256) >> 9, Tx = (sum w Gx + 8192) >> 14, Ty likewise (>> is arithmetic); image reads through R.
+ *                normal matrix: A11 = sum Tx^2, A12 = sum Tx Ty, A22 = sum Ty^2 as exact integers, a_ij = A_ij 2^-20 in fp64; in fp64, each operation rounded:
+ *                D = a11 a22 - a12 a12, e = ((a11 + a22) - sqrt((a11 - a22)^2 + (4 a12) a12)) / 882. If e < 1e-4 or D < 1.1920929e-7: at level 0 status <- 0; the
+ *                level is skipped.
+ *                iterations, at most 30: corner and weights from q - 10 as above with the same bounds rule (out of bounds ends the level, at level 0 status <- 0);
+ *                J = the same bilinear form on the next image; b1 = sum (J - T) Tx, b2 = sum (J - T) Ty as exact integers, each scaled by 2^-20;
+ *                delta = ((a12 b2 - a22 b1) (1 / D), (a12 b1 - a11 b2) (1 / D)); q <- float32(q + delta); stop if delta . delta <= 1e-4; from the second iteration
+ *                on: if |dx + dx_prev| < 0.01 and |dy + dy_prev| < 0.01 then q <- float32(q - delta / 2) and stop.
+ *                Result: q at level 0, status 1 unless cleared. vilf_track_lk returns exactly this; vilf_track_read_image then clears the status of the points
+ *                whose pixel (rint x, rint y) is not in [1, W-2] x [1, H-2] (inBorder) and drops every point with status 0.
+ *   setMask      the survivors get track_cnt + 1 and are ordered by track_cnt descending, ties by lower index; a point is kept iff its pixel (rint x, rint y) lies
+ *                in no disc dx^2 + dy^2 <= MIN_DIST^2 around the pixel of an already kept point. (cv::circle's raster may differ from this disc at rim pixels and
+ *                std::sort is not stable: deviations, DESIGN.md.)
+ *   detection    n_max = MAX_CNT - kept, skipped if <= 0. Sobel 3 x 3 Sx, Sy (int, reads through R): Sx = (I(x+1, y-1) + 2 I(x+1, y) + I(x+1, y+1)) - (the same at
+ *                x-1), Sy its transpose. P = sum Sx^2, Q = sum Sx Sy, S = sum Sy^2 over the 3 x 3 neighbourhood, the neighbour's coordinates taken through R.
+ *                lambda = (P + S) - sqrt((P - S)^2 + (4 Q) Q) in fp64, each operation rounded. A pixel is allowed iff it lies in none of the kept points' discs;
+ *                lambda_max = the maximum over the allowed pixels. Candidates: allowed, 1 <= x <= W-2, 1 <= y <= H-2, lambda > 0.01 lambda_max, lambda >= lambda of
+ *                every 3 x 3 neighbour; ordered by lambda descending, ties by lower y W + x; accepted greedily while fewer than n_max are accepted: iff
+ *                dx^2 + dy^2 >= MIN_DIST^2 to every accepted corner. New points are appended behind the kept ones with id -1, track_cnt 1; the ids -1 then
+ *                become n_id++ in list order (updateID).
+ *   undistortion (PinholeCamera::liftProjective, PinholeCamera.cc:450-510) fp64, each operation rounded: m = ((1 / fx) u + (-cx / fx), (1 / fy) v + (-cy / fy)).
+ *                If any of k1, k2, p1, p2 is non-zero: 8 rounds of m_u = m - distortion(m_u), starting from m_u = m, with (PinholeCamera::distortion, :646-662)
+ *                rho2 = x x + y y, rad = k1 rho2 + (k2 rho2) rho2, dx = (x rad + (2 p1) (x y)) + p2 (rho2 + 2 (x x)), dy = (y rad + (2 p2) (x y)) + p1 (rho2 + 2 (y y)).
+ *                The result is rounded to float32. velocity = (un_cur - un_prev of the same id) / (t_cur - t_prev) in fp64 from the float32 values, rounded to
+ *                float32; 0 for a new id and on the first frame.
+ * Not here: CLAHE (EQUALIZE; the caller passes the image it wants tracked), rejectWithF, readImage_mask and the fisheye mask. */
+typedef struct vilf_track_params {
+    int width, height;               /* COL, ROW */
+    int max_cnt;                     /* MAX_CNT, 1 .. VILF_MAX_FEATURES */
+    int min_dist;                    /* MIN_DIST, >= 1 */
+    double fx, fy, cx, cy;           /* PinholeCamera::Parameters */
+    double k1, k2, p1, p2;
+} vilf_track_params;
+/* workspace of the tracker, hung off the handle and sized here: four pyramids (current, next, two for the stateless calls), the feature list, the detection
+ * buffers (one candidate slot per pixel). Invalid argument, the handle and an existing tracker untouched: a side <= 21, max_cnt < 1 or > VILF_MAX_FEATURES,
+ * min_dist < 1, a focal length that is not positive, a camera parameter that is not finite. A second call drops the tracker and its state and sizes a new one. */
+int vilf_track_init(vilf_handle *h, const vilf_track_params *p);
+/* a fresh FeatureTracker (feature_tracker.cpp:32-34): no points, no previous image, n_id = 0 */
+int vilf_track_reset(vilf_handle *h);
+/* readImage (:119-209) and the updateID loop (feature_tracker_node.cpp:285-292) for one image (rows row_stride bytes apart): one chain of launches; the host
+ * uploads the image and downloads the list. *n_out = rows of the list. */
+int vilf_track_read_image(vilf_handle *h, const unsigned char *img, int row_stride, double stamp, int *n_out);
+/* the list of the last vilf_track_read_image in list order: ids [n], track_cnt [n], cur_pts / un_pts / velocity [n][2] (any may be NULL). cap < n: invalid
+ * argument, nothing written. */
+int vilf_track_get(vilf_handle *h, int cap, int *ids, int *track_cnt, float *cur_pts, float *un_pts, float *velocity, int *n_out);
+/* stateless pieces (they leave the tracker's state alone): level `level` (0 .. Lmax) of the pyramid of an image, rows tight; */
+int vilf_track_pyramid(vilf_handle *h, const unsigned char *img, int row_stride, int level, unsigned char *out);
+/* calcOpticalFlowPyrLK (:151) between two images (rows tight) for n points [n][2] -> pts_out [n][2], status_out [n]; without inBorder; */
+int vilf_track_lk(vilf_handle *h, const unsigned char *img_prev, const unsigned char *img_next, const float *pts, int n, float *pts_out, unsigned char *status_out);
+/* goodFeaturesToTrack (:190) under the mask of n_kept kept points (finite, within 1e6 pixels; at most VILF_MAX_FEATURES): at most n_max <= VILF_MAX_FEATURES
+ * new corners -> pts_out [n_max][2] in acceptance order, *n_out of them */
+int vilf_track_detect(vilf_handle *h, const unsigned char *img, const float *kept_pts, int n_kept, int n_max, float *pts_out, int *n_out);
+/* vilf_set_profiling: the stages of the last vilf_track_read_image: upload + pyramid, LK, setMask, detection (mask, response, candidates, sorts, acceptance),
+ * ids + undistortion + velocity */
+int vilf_track_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
 #ifdef __cplusplus
 }
 #endif

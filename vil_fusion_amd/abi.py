@@ -151,6 +151,13 @@ class IcpIter(C.Structure):
     _fields_ = [("n_correspondences", C.c_int), ("criterion", C.c_int), ("mse", C.c_double), ("cos_angle", C.c_double), ("translation_sqr", C.c_double)]
 
 
+class TrackParams(C.Structure):
+    """vilf_track_params: COL, ROW, MAX_CNT, MIN_DIST and the pinhole camera of the feature tracker"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("max_cnt", C.c_int), ("min_dist", C.c_int),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double)]
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

@@ -154,6 +154,7 @@ extern "C" void vilf_destroy(vilf_handle *h) {
     vilf_lw_release(h);
     vilf_sc_release(h);
     vilf_icp_release(h);
+    vilf_track_release(h);
     for (auto &b : h->d) b.release();
     h->pin_up.release(); h->pin_down.release();
     if (h->ev0) hipEventDestroy(h->ev0);
@@ -873,6 +874,7 @@ extern "C" int vilf_set_profiling(vilf_handle *h, int on) {
     for (int i = 0; i < 4; i++) { h->marg_ms[i] = 0; h->marg_launches[i] = 0; }
     vilf_sc_profile_reset(h);
     vilf_icp_profile_reset(h);
+    vilf_track_profile_reset(h);
     return VILF_OK;
 }
 extern "C" int vilf_get_profile(vilf_handle *h, double ms_out[4], long launches_out[4]) {

@@ -55,6 +55,7 @@ struct PgCtx;
 struct LwCtx;
 struct ScCtx;
 struct IcpCtx;
+struct TrackCtx;
 
 // deep copy of a window snapshot (estimate_extrinsic / estimate_td: the batched entry points run the general single-window solve per slot and need the inputs again)
 struct OwnedWindow {
@@ -123,6 +124,7 @@ struct vilf_handle {
     LwCtx *lw = nullptr;                     // large-window solve workspace (vilf_lw.hip)
     ScCtx *sc = nullptr;                     // Scan Context descriptor database and search workspace (vilf_sc.hip)
     IcpCtx *icp = nullptr;                   // key-frame cloud store and ICP workspace of the loop verification (vilf_icp.hip)
+    TrackCtx *trk = nullptr;                 // image feature tracker: pyramids, feature list, detection workspace (vilf_track.hip)
 };
 
 // a copy ordered on the handle's stream and waited for: the library's streams are non-blocking (they do not synchronise with the legacy default stream), so a plain
@@ -151,6 +153,8 @@ void vilf_lw_release(vilf_handle *h);
 void vilf_sc_release(vilf_handle *h);
 void vilf_icp_release(vilf_handle *h);
 void vilf_icp_profile_reset(vilf_handle *h);
+void vilf_track_release(vilf_handle *h);
+void vilf_track_profile_reset(vilf_handle *h);
 void vilf_sc_profile_reset(vilf_handle *h);                                 // vilf_set_profiling: the Scan Context spans start from zero
 int vilf_lw_chol_max_n();                                                      // largest n vilf_lw_chol_solve takes (its back substitution keeps the solution in LDS)
 int vilf_lw_chol_solve(vilf_handle *h, int n, double *S, double *y, int *info);   // blocked Cholesky solve on the handle's stream (vilf_lw.hip): S = [(n + 1) x n] row-major, row n = rhs

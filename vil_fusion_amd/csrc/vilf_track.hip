@@ -1,0 +1,673 @@
+// vilf_track.hip — the camera half of the feature-tracker node on the device (≙ FeatureTracker::readImage, feature_tracker/feature_tracker.cpp:119-209, and the
+//   updateID loop, feature_tracker_node.cpp:285-292). The arithmetic is stated once, in include/vilfusion.h ("Image feature tracker"); OpenCV is not a dependency.
+// One frame = one chain of launches on the handle's stream, counts stay on the device:
+//   tk_pyr_down      a 32 x 8 tile of a level through LDS with its 2-pixel halo (one launch per level); the "next" pyramid becomes "current" by a pointer swap
+//   tk_lk            a wave per point, all levels in one launch: the 441 window positions dealt over the 64 lanes, T / Tx / Ty in registers across the iterations,
+//                    exact integer sums reduced over the wave, the 2 x 2 solve and the stopping rules the same in every lane; at most 30 iterations, no spin
+//   tk_setmask       one workgroup: rank by (track_cnt descending, index), then wave 0 keeps the points greedily by their discs
+//   tk_paint         a workgroup per kept point: its disc into the byte mask of forbidden pixels
+//   tk_response      a 32 x 8 tile: Sobel at the tile + 1 ring, the 3 x 3 sums, lambda; the maximum over the allowed pixels by an atomic max on the bit pattern
+//   tk_candidates    threshold / 3 x 3 maximum / allowed -> pixel indices compacted with a counter (the buffer holds W * H entries, see vilf_track_init)
+//   radix sorts      by index, then tk_keys + a stable sort by ~bits(lambda): the order (lambda descending, index ascending), whatever the compaction order was
+//   tk_corners       one wave: the candidates in order, the lanes test one candidate against the accepted corners in LDS
+//   tk_finish        one workgroup: ids, undistortion, velocity against the previous frame's (id, un) table, which it then replaces
+// Per frame the host uploads the image and downloads the list (count + rows, one copy).
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include "vilf_internal.hpp"
+#include "vilf_device.hpp"
+#include "vilf_kernels.hpp"
+#include "vilf_sort.hpp"
+
+#define TK_WIN 21
+#define TK_NPOS (TK_WIN * TK_WIN)
+#define TK_SLOTS ((TK_NPOS + 63) / 64)     // window positions per lane
+#define TK_LEVELS 4
+#define TK_MAX_ITERS 30
+#define TK_MAXN VILF_MAX_FEATURES           // rows of the list; accepted corners of one detection
+#define TK_STAGES 5
+
+struct TkPyr { unsigned char *lv[TK_LEVELS]; int w[TK_LEVELS], h[TK_LEVELS], lmax; };      // rows are tight (stride = width)
+// a feature list in one allocation: hdr[16] (hdr[0] = rows), then ids, track_cnt, cur_pts, un_pts, velocity, each for `cap` rows
+struct TkList { int *hdr, *ids, *cnt; float2 *pts, *un, *vel; };
+#define TK_LIST_HDR 16
+static inline size_t tk_list_bytes(int cap) { return TK_LIST_HDR * 4 + (size_t)cap * 32; }
+static inline TkList tk_list(void *base, int cap) {
+    TkList l;
+    l.hdr = (int *)base; l.ids = l.hdr + TK_LIST_HDR; l.cnt = l.ids + cap;
+    l.pts = (float2 *)(l.cnt + cap); l.un = l.pts + cap; l.vel = l.un + cap;
+    return l;
+}
+// control words of one tracker (device): written by the kernels, never read by the host
+enum { TC_N = 0, TC_KEPT, TC_NMAX, TC_NCAND, TC_NID, TC_PREVN, TC_LAMMAX = 8 /* unsigned long long at ints 8, 9 */, TC_INTS = 16 };
+struct TkCam { double i11, i13, i22, i23, k1, k2, p1, p2; int distort; };
+
+// ---- launch contract -----------------------------------------------------------------------------------------------------
+#define TK_TW 32                        // tk_pyr_down, tk_response: block (32, 8), grid = tiles of the output
+#define TK_TH 8
+#define TK_PYR_LW (2 * TK_TW + 3)
+#define TK_PYR_LH (2 * TK_TH + 3)
+#define TK_LK_WAVES 4                   // tk_lk: grid = ceil(points / 4), a wave per point; no workgroup barrier
+#define TK_NT 256                       // tk_setmask, tk_finish: one workgroup; tk_paint: grid = list capacity; tk_candidates, tk_keys: 1-D over the pixels / slots
+#define TK_CORNERS_NT 64                // tk_corners: one wave
+__global__ void tk_pyr_down(const unsigned char *src, int sw, int sh, unsigned char *dst, int dw, int dh);
+__global__ void tk_lk(TkPyr prev, TkPyr next, const float2 *pts, const int *n_dev, int n_host, float2 *out, unsigned char *status, int border);
+__global__ void tk_setmask(TkList cur, const float2 *fwd, const unsigned char *status, TkList nxt, int *ctl, int max_cnt, long long md2);
+__global__ void tk_paint(const float2 *pts, const int *ctl, unsigned char *mask, int W, int H, long long md, long long md2);
+__global__ void tk_response(const unsigned char *img, const unsigned char *mask, int W, int H, int *ctl, double *lam);
+__global__ void tk_candidates(const double *lam, const unsigned char *mask, int W, int H, int *ctl, unsigned *cidx, int cap);
+__global__ void tk_keys(const double *lam, const unsigned *cidx, const int *ctl, int cap, unsigned long long *key, int *val);
+__global__ void tk_corners(const int *val, int W, int cap, int *ctl, TkList l, long long md2);
+__global__ void tk_finish(TkList l, int *ctl, int *prev_ids, float2 *prev_un, TkCam cam, double dt, int has_prev);
+
+struct TrackCtx {
+    vilf_track_params p;
+    TkPyr pyr[4];                       // [0], [1]: current / next of the tracker (cur says which); [2], [3]: the stateless calls
+    int cur = 0, lcur = 0;
+    long frames = 0;
+    double t_prev = 0;
+    int n_host = 0;                     // rows of the list as downloaded by the last vilf_track_read_image
+    size_t ncell = 0;                   // W * H
+    DBuf pyrmem[4], list[2], tmplist, ctl, tmpctl, prev_ids, prev_un, fwd, status, lkpts, mask, lam, cidx, cidx2, cval, key, key2, val, val2, temp;
+    PinBuf pin, stage[4];               // the downloaded list; the image on its way to level 0 of pyramid k
+    double ms[TK_STAGES] = {0, 0, 0, 0, 0};
+    long launches[TK_STAGES] = {0, 0, 0, 0, 0};
+    void release() {
+        DBuf *all[] = {&pyrmem[0], &pyrmem[1], &pyrmem[2], &pyrmem[3], &list[0], &list[1], &tmplist, &ctl, &tmpctl, &prev_ids, &prev_un, &fwd, &status, &lkpts,
+                       &mask, &lam, &cidx, &cidx2, &cval, &key, &key2, &val, &val2, &temp};
+        for (DBuf *b : all) b->release();
+        pin.release();
+        for (PinBuf &b : stage) b.release();
+    }
+};
+void vilf_track_profile_reset(vilf_handle *h) { if (h->trk) for (int i = 0; i < TK_STAGES; i++) { h->trk->ms[i] = 0; h->trk->launches[i] = 0; } }
+void vilf_track_release(vilf_handle *h) { if (h->trk) { h->trk->release(); delete h->trk; h->trk = nullptr; } }
+
+namespace {
+#define TK_WSYNC __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier()
+
+// R(i, n): reflect-101, periodic with period 2 (n - 1); n >= 2
+VD int tk_r(int i, int n) {
+    if ((unsigned)i < (unsigned)n) return i;
+    const int p = 2 * (n - 1);
+    int m = i % p;
+    m += m < 0 ? p : 0;
+    return m < n ? m : p - m;
+}
+VD long long tk_wave_sum(long long v) {          // exact, so the order is free; every lane gets the total
+    for (int o = 32; o > 0; o >>= 1) {
+        const int lo = __shfl_xor((int)(unsigned)(v & 0xffffffffll), o), hi = __shfl_xor((int)(v >> 32), o);
+        v += ((long long)hi << 32) | (long long)(unsigned)lo;
+    }
+    return v;
+}
+struct TkCorner { int ix, iy, w00, w01, w10, w11; bool ok; };
+// top-left corner of the window around (x, y) and the fixed-point bilinear weights; ok = inside the bounds rule (a NaN is outside)
+VD TkCorner tk_corner(float x, float y, int W, int H) {
+    TkCorner c;
+    const float cx = __fsub_rn(x, 10.f), cy = __fsub_rn(y, 10.f), fx = floorf(cx), fy = floorf(cy);
+    c.ok = fx >= -(float)TK_WIN && fx < (float)W && fy >= -(float)TK_WIN && fy < (float)H;
+    const float a = c.ok ? __fsub_rn(cx, fx) : 0.f, b = c.ok ? __fsub_rn(cy, fy) : 0.f;
+    c.ix = c.ok ? (int)fx : 0; c.iy = c.ok ? (int)fy : 0;
+    const float na = __fsub_rn(1.f, a), nb = __fsub_rn(1.f, b);
+    c.w00 = (int)rintf(__fmul_rn(__fmul_rn(na, nb), 16384.f));
+    c.w01 = (int)rintf(__fmul_rn(__fmul_rn(a, nb), 16384.f));
+    c.w10 = (int)rintf(__fmul_rn(__fmul_rn(na, b), 16384.f));
+    c.w11 = 16384 - c.w00 - c.w01 - c.w10;
+    return c;
+}
+// the bilinear form of the image at window position (x, y): (sum w I + 256) >> 9
+VD int tk_bilinear(const unsigned char *I, int W, int H, int x, int y, const TkCorner &c) {
+    const int x0 = tk_r(x, W), x1 = tk_r(x + 1, W);
+    const unsigned char *r0 = I + (size_t)tk_r(y, H) * W, *r1 = I + (size_t)tk_r(y + 1, H) * W;
+    return (c.w00 * (int)r0[x0] + c.w01 * (int)r0[x1] + c.w10 * (int)r1[x0] + c.w11 * (int)r1[x1] + 256) >> 9;
+}
+}  // namespace
+
+// ---- tk_pyr_down ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_TW * TK_TH) void tk_pyr_down(const unsigned char *src, int sw, int sh, unsigned char *dst, int dw, int dh) {
+    __shared__ unsigned char s[TK_PYR_LH][TK_PYR_LW + 1];
+    const int tx = threadIdx.x, ty = threadIdx.y, t = ty * TK_TW + tx;
+    const int x0 = blockIdx.x * TK_TW, y0 = blockIdx.y * TK_TH;
+    for (int i = t; i < TK_PYR_LH * TK_PYR_LW; i += TK_TW * TK_TH) {
+        const int ly = i / TK_PYR_LW, lx = i % TK_PYR_LW;
+        s[ly][lx] = src[(size_t)tk_r(2 * y0 - 2 + ly, sh) * sw + tk_r(2 * x0 - 2 + lx, sw)];
+    }
+    __syncthreads();
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= dw || y >= dh) return;
+    const int k[5] = {1, 4, 6, 4, 1};
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < 5; j++)
+#pragma unroll
+        for (int i = 0; i < 5; i++) acc += k[i] * k[j] * (int)s[2 * ty + j][2 * tx + i];
+    dst[(size_t)y * dw + x] = (unsigned char)((acc + 128) >> 8);
+}
+
+// ---- tk_lk: a wave per point -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * TK_LK_WAVES) void tk_lk(TkPyr prev, TkPyr next, const float2 *pts, const int *n_dev, int n_host, float2 *out, unsigned char *status, int border) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * TK_LK_WAVES + (threadIdx.x >> 6);
+    const int n = n_dev ? *n_dev : n_host;
+    if (i >= n) return;                                  // the whole wave
+    const float2 p = pts[i];
+    float qx = 0.f, qy = 0.f;
+    int st = 1;
+    for (int L = prev.lmax; L >= 0; L--) {
+        const int W = prev.w[L], H = prev.h[L];
+        const unsigned char *I = prev.lv[L], *J = next.lv[L];
+        const float scale = 1.f / (float)(1 << L);
+        const float px = __fmul_rn(p.x, scale), py = __fmul_rn(p.y, scale);
+        if (L == prev.lmax) { qx = px; qy = py; } else { qx = __fmul_rn(2.f, qx); qy = __fmul_rn(2.f, qy); }
+        const TkCorner c = tk_corner(px, py, W, H);
+        if (!c.ok) { if (L == 0) st = 0; continue; }
+        // template: T, Tx, Ty of this lane's window positions
+        int T[TK_SLOTS], Tx[TK_SLOTS], Ty[TK_SLOTS];
+        long long s11 = 0, s12 = 0, s22 = 0;
+#pragma unroll
+        for (int k = 0; k < TK_SLOTS; k++) {
+            const int pos = lane + 64 * k;
+            T[k] = 0; Tx[k] = 0; Ty[k] = 0;
+            if (pos < TK_NPOS) {
+                const int x = c.ix + pos % TK_WIN, y = c.iy + pos / TK_WIN;
+                int v[4][4];                             // the pixels (x - 1 .. x + 2, y - 1 .. y + 2), read through R
+                int cx[4];
+#pragma unroll
+                for (int a = 0; a < 4; a++) cx[a] = tk_r(x - 1 + a, W);
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const unsigned char *row = I + (size_t)tk_r(y - 1 + b, H) * W;
+#pragma unroll
+                    for (int a = 0; a < 4; a++) v[b][a] = (int)row[cx[a]];
+                }
+                int gx[2][2], gy[2][2];                  // Scharr at (x + a, y + b); 0 outside the image
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int a = 0; a < 2; a++) {
+                        const bool in = (unsigned)(x + a) < (unsigned)W && (unsigned)(y + b) < (unsigned)H;
+                        const int r = 1 + b, q = 1 + a;
+                        const int sx = 3 * (v[r - 1][q + 1] - v[r - 1][q - 1]) + 10 * (v[r][q + 1] - v[r][q - 1]) + 3 * (v[r + 1][q + 1] - v[r + 1][q - 1]);
+                        const int sy = 3 * (v[r + 1][q - 1] - v[r - 1][q - 1]) + 10 * (v[r + 1][q] - v[r - 1][q]) + 3 * (v[r + 1][q + 1] - v[r - 1][q + 1]);
+                        gx[b][a] = in ? sx : 0; gy[b][a] = in ? sy : 0;
+                    }
+                T[k] = (c.w00 * v[1][1] + c.w01 * v[1][2] + c.w10 * v[2][1] + c.w11 * v[2][2] + 256) >> 9;
+                Tx[k] = (c.w00 * gx[0][0] + c.w01 * gx[0][1] + c.w10 * gx[1][0] + c.w11 * gx[1][1] + 8192) >> 14;
+                Ty[k] = (c.w00 * gy[0][0] + c.w01 * gy[0][1] + c.w10 * gy[1][0] + c.w11 * gy[1][1] + 8192) >> 14;
+                s11 += (long long)Tx[k] * Tx[k]; s12 += (long long)Tx[k] * Ty[k]; s22 += (long long)Ty[k] * Ty[k];
+            }
+        }
+        const double sc = 0x1p-20;
+        const double a11 = __dmul_rn((double)tk_wave_sum(s11), sc), a12 = __dmul_rn((double)tk_wave_sum(s12), sc), a22 = __dmul_rn((double)tk_wave_sum(s22), sc);
+        const double D = __dsub_rn(__dmul_rn(a11, a22), __dmul_rn(a12, a12)), d = __dsub_rn(a11, a22);
+        const double e = __ddiv_rn(__dsub_rn(__dadd_rn(a11, a22), __dsqrt_rn(__dadd_rn(__dmul_rn(d, d), __dmul_rn(__dmul_rn(4.0, a12), a12)))), 882.0);
+        if (e < 1e-4 || D < 1.1920929e-7) { if (L == 0) st = 0; continue; }
+        const double inv = __ddiv_rn(1.0, D);
+        double pdx = 0.0, pdy = 0.0;
+        for (int it = 0; it < TK_MAX_ITERS; it++) {
+            const TkCorner cj = tk_corner(qx, qy, W, H);
+            if (!cj.ok) { if (L == 0) st = 0; break; }
+            long long t1 = 0, t2 = 0;
+#pragma unroll
+            for (int k = 0; k < TK_SLOTS; k++) {
+                const int pos = lane + 64 * k;
+                if (pos < TK_NPOS) {
+                    const int df = tk_bilinear(J, W, H, cj.ix + pos % TK_WIN, cj.iy + pos / TK_WIN, cj) - T[k];
+                    t1 += (long long)df * Tx[k]; t2 += (long long)df * Ty[k];
+                }
+            }
+            const double b1 = __dmul_rn((double)tk_wave_sum(t1), sc), b2 = __dmul_rn((double)tk_wave_sum(t2), sc);
+            const double dx = __dmul_rn(__dsub_rn(__dmul_rn(a12, b2), __dmul_rn(a22, b1)), inv), dy = __dmul_rn(__dsub_rn(__dmul_rn(a12, b1), __dmul_rn(a11, b2)), inv);
+            qx = (float)__dadd_rn((double)qx, dx); qy = (float)__dadd_rn((double)qy, dy);
+            if (__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)) <= 1e-4) break;
+            if (it > 0 && fabs(__dadd_rn(dx, pdx)) < 0.01 && fabs(__dadd_rn(dy, pdy)) < 0.01) {
+                qx = (float)__dsub_rn((double)qx, __dmul_rn(dx, 0.5)); qy = (float)__dsub_rn((double)qy, __dmul_rn(dy, 0.5));
+                break;
+            }
+            pdx = dx; pdy = dy;
+        }
+    }
+    if (border) {                                        // inBorder (feature_tracker.cpp:5-11)
+        const float rx = rintf(qx), ry = rintf(qy);
+        if (!(rx >= 1.f && rx <= (float)(prev.w[0] - 2) && ry >= 1.f && ry <= (float)(prev.h[0] - 2))) st = 0;
+    }
+    if (lane == 0) { out[i] = make_float2(qx, qy); status[i] = (unsigned char)st; }
+}
+
+// ---- tk_setmask: one workgroup -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_setmask(TkList cur, const float2 *fwd, const unsigned char *status, TkList nxt, int *ctl, int max_cnt, long long md2) {
+    __shared__ int s_cnt[TK_MAXN], s_order[TK_MAXN], s_src[TK_MAXN];
+    __shared__ int2 s_px[TK_MAXN], s_acc[TK_MAXN];
+    __shared__ int s_m, s_nk;
+    const int t = threadIdx.x, n = min(ctl[TC_N], TK_MAXN);
+    if (t == 0) s_m = 0;
+    for (int i = t; i < n; i += TK_NT) {
+        s_cnt[i] = status[i] ? cur.cnt[i] : -1;          // track counts are positive
+        const float2 f = fwd[i];
+        s_px[i] = make_int2((int)rintf(f.x), (int)rintf(f.y));
+    }
+    __syncthreads();
+    for (int i = t; i < n; i += TK_NT) {
+        const int ci = s_cnt[i];
+        if (ci < 0) continue;
+        int rank = 0;
+        for (int j = 0; j < n; j++) { const int cj = s_cnt[j]; rank += (cj > ci || (cj == ci && j < i)) ? 1 : 0; }      // cj >= 0 > -1 only for survivors when ci >= 0
+        s_order[rank] = i;
+        atomicAdd(&s_m, 1);
+    }
+    __syncthreads();
+    if (t < 64) {                                        // wave 0: the survivors in order, each against the kept pixels
+        const int m = s_m;
+        int nk = 0;
+        for (int r = 0; r < m; r++) {
+            const int src = s_order[r];
+            const int2 c = s_px[src];
+            bool hit = false;
+            for (int k = t; k < nk; k += 64) {
+                const int2 a = s_acc[k];
+                const long long dx = (long long)c.x - a.x, dy = (long long)c.y - a.y;
+                hit |= dx * dx + dy * dy <= md2;
+            }
+            if (!__any(hit)) {
+                if (t == 0) { s_acc[nk] = c; s_src[nk] = src; }
+                nk++;
+                TK_WSYNC;
+            }
+        }
+        if (t == 0) s_nk = nk;
+    }
+    __syncthreads();
+    const int nk = s_nk;
+    for (int k = t; k < nk; k += TK_NT) {
+        const int src = s_src[k];
+        nxt.ids[k] = cur.ids[src]; nxt.cnt[k] = cur.cnt[src] + 1; nxt.pts[k] = fwd[src];
+    }
+    if (t == 0) {
+        ctl[TC_KEPT] = nk; ctl[TC_NMAX] = max_cnt - nk; ctl[TC_NCAND] = 0;
+        *(unsigned long long *)(ctl + TC_LAMMAX) = 0ull;
+    }
+}
+
+// ---- tk_paint: a workgroup per kept point ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_paint(const float2 *pts, const int *ctl, unsigned char *mask, int W, int H, long long md, long long md2) {
+    const int b = blockIdx.x;
+    if (b >= ctl[TC_KEPT] || ctl[TC_NMAX] <= 0) return;
+    const float2 f = pts[b];
+    const long long px = (long long)rintf(f.x), py = (long long)rintf(f.y);
+    const long long x0 = max(px - md, 0ll), x1 = min(px + md, (long long)W - 1), y0 = max(py - md, 0ll), y1 = min(py + md, (long long)H - 1);
+    if (x1 < x0 || y1 < y0) return;
+    const long long bw = x1 - x0 + 1, cells = bw * (y1 - y0 + 1);        // <= W * H
+    for (long long i = threadIdx.x; i < cells; i += TK_NT) {
+        const long long x = x0 + i % bw, y = y0 + i / bw, dx = x - px, dy = y - py;
+        if (dx * dx + dy * dy <= md2) mask[y * W + x] = 1;
+    }
+}
+
+// ---- tk_response: Sobel, 3 x 3 sums, lambda ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_TW * TK_TH) void tk_response(const unsigned char *img, const unsigned char *mask, int W, int H, int *ctl, double *lam) {
+    __shared__ unsigned char s_i[TK_TH + 4][TK_TW + 4];          // pixel (x0 - 2 + lx, y0 - 2 + ly) through R
+    __shared__ short s_sx[TK_TH + 2][TK_TW + 2], s_sy[TK_TH + 2][TK_TW + 2];
+    __shared__ unsigned long long s_max;
+    if (ctl[TC_NMAX] <= 0) return;
+    const int tx = threadIdx.x, ty = threadIdx.y, t = ty * TK_TW + tx;
+    const int x0 = blockIdx.x * TK_TW, y0 = blockIdx.y * TK_TH;
+    if (t == 0) s_max = 0ull;
+    for (int i = t; i < (TK_TH + 4) * (TK_TW + 4); i += TK_TW * TK_TH) {
+        const int ly = i / (TK_TW + 4), lx = i % (TK_TW + 4);
+        s_i[ly][lx] = img[(size_t)tk_r(y0 - 2 + ly, H) * W + tk_r(x0 - 2 + lx, W)];
+    }
+    __syncthreads();
+    for (int i = t; i < (TK_TH + 2) * (TK_TW + 2); i += TK_TW * TK_TH) {
+        const int ly = i / (TK_TW + 2), lx = i % (TK_TW + 2);
+        // the Sobel value of the neighbour coordinate taken through R; its own reads go through R again. A pixel x < W of the tile needs the positions
+        // x - 1 .. x + 1 <= W: R(-1) = 1 reads the columns 0, 2; R(W) = W - 2 reads W - 3, W - 1; a position inside the image reads p - 1 .. p + 1 or their
+        // reflections p + 1, p - 1. All of these lie in [x0 - 2, x0 + TK_TW + 2), the columns the tile holds. Positions past W (no pixel needs them) are clamped
+        // into the tile. Rows likewise.
+        const int gx = tk_r(x0 - 1 + lx, W), gy = tk_r(y0 - 1 + ly, H);
+        const int cl = min(max(tk_r(gx - 1, W) - x0 + 2, 0), TK_TW + 3), cc = min(max(gx - x0 + 2, 0), TK_TW + 3), cr = min(max(tk_r(gx + 1, W) - x0 + 2, 0), TK_TW + 3);
+        const int ru = min(max(tk_r(gy - 1, H) - y0 + 2, 0), TK_TH + 3), rc = min(max(gy - y0 + 2, 0), TK_TH + 3), rd = min(max(tk_r(gy + 1, H) - y0 + 2, 0), TK_TH + 3);
+        const int sx = ((int)s_i[ru][cr] + 2 * (int)s_i[rc][cr] + (int)s_i[rd][cr]) - ((int)s_i[ru][cl] + 2 * (int)s_i[rc][cl] + (int)s_i[rd][cl]);
+        const int sy = ((int)s_i[rd][cl] + 2 * (int)s_i[rd][cc] + (int)s_i[rd][cr]) - ((int)s_i[ru][cl] + 2 * (int)s_i[ru][cc] + (int)s_i[ru][cr]);
+        s_sx[ly][lx] = (short)sx; s_sy[ly][lx] = (short)sy;
+    }
+    __syncthreads();
+    const int x = x0 + tx, y = y0 + ty;
+    if (x < W && y < H) {
+        int P = 0, Q = 0, S = 0;
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+#pragma unroll
+            for (int i = 0; i < 3; i++) { const int a = s_sx[ty + j][tx + i], b = s_sy[ty + j][tx + i]; P += a * a; Q += a * b; S += b * b; }
+        const double Pd = (double)P, Qd = (double)Q, Sd = (double)S, d = __dsub_rn(Pd, Sd);
+        const double l = __dsub_rn(__dadd_rn(Pd, Sd), __dsqrt_rn(__dadd_rn(__dmul_rn(d, d), __dmul_rn(__dmul_rn(4.0, Qd), Qd))));
+        const size_t at = (size_t)y * W + x;
+        lam[at] = l;
+        if (!mask[at] && l > 0.0) atomicMax(&s_max, (unsigned long long)__double_as_longlong(l));      // non-negative doubles order as their bit patterns
+    }
+    __syncthreads();
+    if (t == 0 && s_max) atomicMax((unsigned long long *)(ctl + TC_LAMMAX), s_max);
+}
+
+// ---- tk_candidates ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_candidates(const double *lam, const unsigned char *mask, int W, int H, int *ctl, unsigned *cidx, int cap) {
+    if (ctl[TC_NMAX] <= 0) return;
+    const long long at = (long long)blockIdx.x * TK_NT + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    bool is = false;
+    if (at < (long long)W * H) {
+        const int x = (int)(at % W), y = (int)(at / W);
+        if (x >= 1 && x <= W - 2 && y >= 1 && y <= H - 2 && !mask[at]) {
+            const double lmax = __longlong_as_double((long long)*(const unsigned long long *)(ctl + TC_LAMMAX));
+            const double l = lam[at];
+            is = l > __dmul_rn(0.01, lmax);
+            for (int j = -1; j <= 1; j++) for (int i = -1; i <= 1; i++) is = is && l >= lam[at + (long long)j * W + i];
+        }
+    }
+    const unsigned long long b = __ballot(is);
+    if (!b) return;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(ctl + TC_NCAND, __popcll(b));
+    base = __shfl(base, 0);
+    const int slot = base + __popcll(b & ((1ull << lane) - 1ull));
+    if (is && slot < cap) cidx[slot] = (unsigned)at;
+}
+
+// ---- tk_keys: slot s of the index-sorted candidates -> (~bits(lambda), index); the slots behind the count sort last ------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_keys(const double *lam, const unsigned *cidx, const int *ctl, int cap, unsigned long long *key, int *val) {
+    const long long s = (long long)blockIdx.x * TK_NT + threadIdx.x;
+    if (s >= cap) return;
+    const int cnt = min(ctl[TC_NCAND], cap);
+    const unsigned at = s < cnt ? cidx[s] : 0xffffffffu;
+    if (at < (unsigned)cap) { key[s] = ~(unsigned long long)__double_as_longlong(lam[at]); val[s] = (int)at; }
+    else { key[s] = ~0ull; val[s] = -1; }
+}
+
+// ---- tk_corners: one wave ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_CORNERS_NT) void tk_corners(const int *val, int W, int cap, int *ctl, TkList l, long long md2) {
+    __shared__ int2 s_acc[TK_MAXN];
+    const int lane = threadIdx.x, cnt = min(ctl[TC_NCAND], cap), kept = ctl[TC_KEPT], n_max = min(ctl[TC_NMAX], TK_MAXN);
+    int nacc = 0;
+    for (int base = 0; base < cnt && nacc < n_max; base += 64) {
+        const int mine = base + lane < cnt ? val[base + lane] : 0;
+        const int m = min(64, cnt - base);
+        for (int j = 0; j < m && nacc < n_max; j++) {
+            const int at = __shfl(mine, j);
+            if ((unsigned)at >= (unsigned)cap) continue;          // never a candidate's index; the same in every lane
+            const int2 c = make_int2(at % W, at / W);
+            bool hit = false;
+            for (int k = lane; k < nacc; k += 64) {
+                const int2 a = s_acc[k];
+                const long long dx = (long long)c.x - a.x, dy = (long long)c.y - a.y;
+                hit |= dx * dx + dy * dy < md2;
+            }
+            if (!__any(hit)) {
+                if (lane == 0) {
+                    s_acc[nacc] = c;
+                    l.pts[kept + nacc] = make_float2((float)c.x, (float)c.y); l.ids[kept + nacc] = -1; l.cnt[kept + nacc] = 1;
+                }
+                nacc++;
+                TK_WSYNC;
+            }
+        }
+    }
+    if (lane == 0) ctl[TC_N] = kept + nacc;
+}
+
+// ---- tk_finish: ids, undistortion, velocity -----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_finish(TkList l, int *ctl, int *prev_ids, float2 *prev_un, TkCam cam, double dt, int has_prev) {
+    const int t = threadIdx.x, n = min(ctl[TC_N], TK_MAXN), kept = ctl[TC_KEPT], n_id = ctl[TC_NID], prev_n = ctl[TC_PREVN];
+    for (int i = t; i < n; i += TK_NT) {
+        const int id = i < kept ? l.ids[i] : n_id + (i - kept);      // the new points stand behind the kept ones, in list order (updateID)
+        const float2 p = l.pts[i];
+        const double mx = __dadd_rn(__dmul_rn(cam.i11, (double)p.x), cam.i13), my = __dadd_rn(__dmul_rn(cam.i22, (double)p.y), cam.i23);
+        double ux = mx, uy = my;
+        if (cam.distort) {
+            for (int r = 0; r < 8; r++) {                // PinholeCamera::distortion (PinholeCamera.cc:646-662), every operation rounded on its own
+                const double x2 = __dmul_rn(ux, ux), y2 = __dmul_rn(uy, uy), xy = __dmul_rn(ux, uy), rho2 = __dadd_rn(x2, y2);
+                const double rad = __dadd_rn(__dmul_rn(cam.k1, rho2), __dmul_rn(__dmul_rn(cam.k2, rho2), rho2));
+                const double ddx = __dadd_rn(__dadd_rn(__dmul_rn(ux, rad), __dmul_rn(__dmul_rn(2.0, cam.p1), xy)), __dmul_rn(cam.p2, __dadd_rn(rho2, __dmul_rn(2.0, x2))));
+                const double ddy = __dadd_rn(__dadd_rn(__dmul_rn(uy, rad), __dmul_rn(__dmul_rn(2.0, cam.p2), xy)), __dmul_rn(cam.p1, __dadd_rn(rho2, __dmul_rn(2.0, y2))));
+                ux = __dsub_rn(mx, ddx); uy = __dsub_rn(my, ddy);
+            }
+        }
+        const float2 un = make_float2((float)ux, (float)uy);
+        float2 v = make_float2(0.f, 0.f);
+        if (has_prev && i < kept) {
+            for (int k = 0; k < prev_n; k++)
+                if (prev_ids[k] == id) {
+                    const float2 q = prev_un[k];
+                    v = make_float2((float)__ddiv_rn(__dsub_rn((double)un.x, (double)q.x), dt), (float)__ddiv_rn(__dsub_rn((double)un.y, (double)q.y), dt));
+                    break;
+                }
+        }
+        l.ids[i] = id; l.un[i] = un; l.vel[i] = v;
+    }
+    __syncthreads();                                     // every read of the previous table is done
+    for (int i = t; i < n; i += TK_NT) { prev_ids[i] = l.ids[i]; prev_un[i] = l.un[i]; }
+    if (t == 0) { ctl[TC_PREVN] = n; ctl[TC_NID] = n_id + (n - min(kept, n)); l.hdr[0] = n; }
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------------
+namespace {
+int tk_sort_bits(size_t cap) { int b = 1; while (((size_t)1 << b) <= cap) b++; return b; }      // the fill pattern (all ones) sorts behind every pixel index
+
+// image (row stride in bytes) -> level 0 .. `levels` of a pyramid, on the stream. The rows go through the pyramid's pinned staging (every entry point ends with
+// a wait for the stream, so the staging is free again): a copy from pageable memory, row by row, cost 2.6 ms per frame at 1226 x 370
+int tk_build(vilf_handle *h, TkPyr &P, unsigned char *stage, const unsigned char *img, int row_stride, int levels) {
+    const size_t W = (size_t)P.w[0], H = (size_t)P.h[0];
+    if ((size_t)row_stride == W) std::memcpy(stage, img, W * H);
+    else for (size_t y = 0; y < H; y++) std::memcpy(stage + y * W, img + y * (size_t)row_stride, W);
+    HIPCHECK(h, hipMemcpyAsync(P.lv[0], stage, W * H, hipMemcpyHostToDevice, h->stream));
+    for (int L = 1; L <= levels; L++)
+        hipLaunchKernelGGL(tk_pyr_down, dim3((P.w[L] + TK_TW - 1) / TK_TW, (P.h[L] + TK_TH - 1) / TK_TH), dim3(TK_TW, TK_TH), 0, h->stream, P.lv[L - 1], P.w[L - 1], P.h[L - 1], P.lv[L], P.w[L], P.h[L]);
+    HIPCHECK(h, hipGetLastError());
+    return VILF_OK;
+}
+// mask, response, candidates, the two sorts, the greedy acceptance: ctl holds kept / n_max / candidate count 0 / lambda max 0, l.pts the kept points
+int tk_detect(vilf_handle *h, TrackCtx *c, const unsigned char *img, int *ctl, TkList l, int list_cap) {
+    const int W = c->p.width, H = c->p.height, cap = (int)c->ncell;
+    const long long md = c->p.min_dist, md2 = md * md;
+    HIPCHECK(h, hipMemsetAsync(c->mask.p, 0, c->ncell, h->stream));
+    HIPCHECK(h, hipMemsetAsync(c->cidx.p, 0xff, c->ncell * 4, h->stream));
+    hipLaunchKernelGGL(tk_paint, dim3(list_cap), dim3(TK_NT), 0, h->stream, l.pts, ctl, c->mask.as<unsigned char>(), W, H, md, md2);
+    hipLaunchKernelGGL(tk_response, dim3((W + TK_TW - 1) / TK_TW, (H + TK_TH - 1) / TK_TH), dim3(TK_TW, TK_TH), 0, h->stream, img, c->mask.as<unsigned char>(), W, H, ctl, c->lam.as<double>());
+    const unsigned nb = (unsigned)((c->ncell + TK_NT - 1) / TK_NT);
+    hipLaunchKernelGGL(tk_candidates, dim3(nb), dim3(TK_NT), 0, h->stream, c->lam.as<double>(), c->mask.as<unsigned char>(), W, H, ctl, c->cidx.as<unsigned>(), cap);
+    HIPCHECK(h, hipGetLastError());
+    if (vilf_sort_pairs_u32(h->stream, c->temp.p, c->temp.cap, c->cidx.as<unsigned>(), c->cidx2.as<unsigned>(), c->cidx.as<int>(), c->cval.as<int>(), c->ncell, tk_sort_bits(c->ncell)) != 0) {
+        h->err = "feature tracker: radix sort failed"; return VILF_ERR_DEVICE;
+    }
+    hipLaunchKernelGGL(tk_keys, dim3(nb), dim3(TK_NT), 0, h->stream, c->lam.as<double>(), c->cidx2.as<unsigned>(), ctl, cap, c->key.as<unsigned long long>(), c->val.as<int>());
+    if (vilf_sort_pairs_u64(h->stream, c->temp.p, c->temp.cap, c->key.as<unsigned long long>(), c->key2.as<unsigned long long>(), c->val.as<int>(), c->val2.as<int>(), c->ncell, 64) != 0) {
+        h->err = "feature tracker: radix sort failed"; return VILF_ERR_DEVICE;
+    }
+    hipLaunchKernelGGL(tk_corners, dim3(1), dim3(TK_CORNERS_NT), 0, h->stream, c->val2.as<int>(), W, cap, ctl, l, md2);
+    HIPCHECK(h, hipGetLastError());
+    return VILF_OK;
+}
+TrackCtx *tk_ctx(vilf_handle *h, const char *who) {
+    if (!h->trk) h->err = std::string(who) + ": no tracker (vilf_track_init)";
+    return h->trk;
+}
+}  // namespace
+
+extern "C" int vilf_track_init(vilf_handle *h, const vilf_track_params *p) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    if (!p) { h->err = "vilf_track_init: null parameters"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (p->width <= TK_WIN || p->height <= TK_WIN || p->max_cnt < 1 || p->max_cnt > VILF_MAX_FEATURES || p->min_dist < 1 || !(p->fx > 0) || !(p->fy > 0) ||
+        !std::isfinite(p->fx) || !std::isfinite(p->fy) || !std::isfinite(p->cx) || !std::isfinite(p->cy) || !std::isfinite(p->k1) || !std::isfinite(p->k2) || !std::isfinite(p->p1) || !std::isfinite(p->p2)) {
+        h->err = "vilf_track_init: both sides > 21, 1 <= max_cnt <= VILF_MAX_FEATURES, min_dist >= 1, positive focal lengths, finite camera parameters";
+        return VILF_ERR_INVALID_ARGUMENT;
+    }
+    if ((long long)p->width * p->height > (1ll << 28)) { h->err = "vilf_track_init: more than 2^28 pixels"; return VILF_ERR_UNSUPPORTED; }
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, hipStreamSynchronize(h->stream));
+    vilf_track_release(h);
+    TrackCtx *c = new TrackCtx();
+    c->p = *p;
+    c->ncell = (size_t)p->width * p->height;
+    bool ok = true;
+    for (int k = 0; k < 4 && ok; k++) {
+        TkPyr &P = c->pyr[k];
+        int w = p->width, hh = p->height;
+        size_t total = 0, off[TK_LEVELS];
+        P.lmax = 0;
+        for (int L = 0; L < TK_LEVELS; L++) {
+            if (L > 0) { w = (w + 1) / 2; hh = (hh + 1) / 2; if (P.lmax == L - 1 && w > TK_WIN && hh > TK_WIN) P.lmax = L; }
+            P.w[L] = w; P.h[L] = hh; off[L] = total; total += ((size_t)w * hh + 255) / 256 * 256;
+        }
+        ok = c->pyrmem[k].ensure(total) && c->stage[k].ensure(c->ncell);
+        for (int L = 0; L < TK_LEVELS && ok; L++) P.lv[L] = c->pyrmem[k].as<unsigned char>() + off[L];
+    }
+    const size_t n = c->ncell;
+    // the candidate buffers hold W * H entries. W * H / 4 + 1 would do if two neighbouring 3 x 3 maxima had to differ, but equal neighbours are both maxima: a
+    // texture of period 3 in x and y has the same lambda > 0 at every inner pixel, and all of them are candidates. A buffer of one entry per pixel cannot overflow.
+    ok = ok && c->list[0].ensure(tk_list_bytes(TK_MAXN)) && c->list[1].ensure(tk_list_bytes(TK_MAXN)) && c->tmplist.ensure(tk_list_bytes(2 * TK_MAXN)) && c->ctl.ensure(TC_INTS * 4) &&
+         c->tmpctl.ensure(TC_INTS * 4) && c->prev_ids.ensure(TK_MAXN * 4) && c->prev_un.ensure(TK_MAXN * 8) && c->fwd.ensure(TK_MAXN * 8) && c->status.ensure(TK_MAXN) &&
+         c->lkpts.ensure(TK_MAXN * 8) && c->mask.ensure(n) && c->lam.ensure(n * 8) && c->cidx.ensure(n * 4) && c->cidx2.ensure(n * 4) && c->cval.ensure(n * 4) && c->key.ensure(n * 8) &&
+         c->key2.ensure(n * 8) && c->val.ensure(n * 4) && c->val2.ensure(n * 4) && c->temp.ensure(std::max(vilf_sort_temp_bytes(n, 8), vilf_sort_temp_bytes(n, 4)) + 256) &&
+         c->pin.ensure(tk_list_bytes(TK_MAXN));
+    if (!ok) { c->release(); delete c; h->err = "hipMalloc failed (feature tracker)"; return VILF_ERR_DEVICE; }
+    h->trk = c;
+    return vilf_track_reset(h);
+}
+
+extern "C" int vilf_track_reset(vilf_handle *h) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_reset");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, hipMemsetAsync(c->ctl.p, 0, TC_INTS * 4, h->stream));
+    HIPCHECK(h, hipMemsetAsync(c->list[0].p, 0, TK_LIST_HDR * 4, h->stream));
+    HIPCHECK(h, hipMemsetAsync(c->list[1].p, 0, TK_LIST_HDR * 4, h->stream));
+    HIPCHECK(h, hipStreamSynchronize(h->stream));
+    c->frames = 0; c->n_host = 0; c->t_prev = 0; c->cur = 0; c->lcur = 0;
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_read_image(vilf_handle *h, const unsigned char *img, int row_stride, double stamp, int *n_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_read_image");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!img || row_stride < c->p.width) { h->err = "vilf_track_read_image: null image or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
+    HIPCHECK(h, hipSetDevice(h->device));
+    const bool prof = h->profiling != 0;
+    if (prof) for (int i = 0; i < TK_STAGES; i++) { c->ms[i] = 0; c->launches[i] = 0; }      // the stages of the last frame
+    hipEvent_t ev[TK_STAGES + 1];
+    auto mark = [&](int k) { if (prof) ev[k] = vilf_prof_event(h); };
+    TkPyr &cur = c->pyr[c->cur], &nxt = c->pyr[c->cur ^ 1];
+    TkList lc = tk_list(c->list[c->lcur].p, TK_MAXN), ln = tk_list(c->list[c->lcur ^ 1].p, TK_MAXN);
+    int *ctl = c->ctl.as<int>();
+    const long long md = c->p.min_dist;
+    mark(0);
+    { const int rc = tk_build(h, nxt, (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride, nxt.lmax); if (rc != VILF_OK) return rc; }
+    mark(1);
+    if (c->frames > 0)
+        hipLaunchKernelGGL(tk_lk, dim3((c->p.max_cnt + TK_LK_WAVES - 1) / TK_LK_WAVES), dim3(64 * TK_LK_WAVES), 0, h->stream, cur, nxt, lc.pts, ctl + TC_N, 0, c->fwd.as<float2>(), c->status.as<unsigned char>(), 1);
+    mark(2);
+    hipLaunchKernelGGL(tk_setmask, dim3(1), dim3(TK_NT), 0, h->stream, lc, c->fwd.as<float2>(), c->status.as<unsigned char>(), ln, ctl, c->p.max_cnt, md * md);
+    HIPCHECK(h, hipGetLastError());
+    mark(3);
+    { const int rc = tk_detect(h, c, nxt.lv[0], ctl, ln, c->p.max_cnt); if (rc != VILF_OK) return rc; }
+    mark(4);
+    TkCam cam;
+    cam.i11 = 1.0 / c->p.fx; cam.i13 = -c->p.cx / c->p.fx; cam.i22 = 1.0 / c->p.fy; cam.i23 = -c->p.cy / c->p.fy;
+    cam.k1 = c->p.k1; cam.k2 = c->p.k2; cam.p1 = c->p.p1; cam.p2 = c->p.p2;
+    cam.distort = (c->p.k1 != 0.0 || c->p.k2 != 0.0 || c->p.p1 != 0.0 || c->p.p2 != 0.0) ? 1 : 0;
+    hipLaunchKernelGGL(tk_finish, dim3(1), dim3(TK_NT), 0, h->stream, ln, ctl, c->prev_ids.as<int>(), c->prev_un.as<float2>(), cam, stamp - c->t_prev, c->frames > 0 ? 1 : 0);
+    HIPCHECK(h, hipGetLastError());
+    mark(5);
+    if (prof) for (int k = 0; k < TK_STAGES; k++) vilf_prof_span(h, ev[k], ev[k + 1], &c->ms[k], &c->launches[k]);
+    HIPCHECK(h, vilf_copy_sync(h, c->pin.p, ln.hdr, tk_list_bytes(TK_MAXN), hipMemcpyDeviceToHost));
+    if (prof) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
+    c->cur ^= 1; c->lcur ^= 1; c->frames++; c->t_prev = stamp;
+    c->n_host = std::min(std::max(((const int *)c->pin.p)[0], 0), c->p.max_cnt);
+    if (n_out) *n_out = c->n_host;
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_get(vilf_handle *h, int cap, int *ids, int *track_cnt, float *cur_pts, float *un_pts, float *velocity, int *n_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_get");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    const int n = c->n_host;
+    if (cap < n) { h->err = "vilf_track_get: the list holds " + std::to_string(n) + " rows, cap is " + std::to_string(cap); return VILF_ERR_INVALID_ARGUMENT; }
+    const TkList l = tk_list(c->pin.p, TK_MAXN);          // the host copy of the last frame's list
+    if (ids) std::memcpy(ids, l.ids, (size_t)n * 4);
+    if (track_cnt) std::memcpy(track_cnt, l.cnt, (size_t)n * 4);
+    if (cur_pts) std::memcpy(cur_pts, l.pts, (size_t)n * 8);
+    if (un_pts) std::memcpy(un_pts, l.un, (size_t)n * 8);
+    if (velocity) std::memcpy(velocity, l.vel, (size_t)n * 8);
+    if (n_out) *n_out = n;
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_pyramid(vilf_handle *h, const unsigned char *img, int row_stride, int level, unsigned char *out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_pyramid");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    TkPyr &P = c->pyr[2];
+    if (!img || !out || row_stride < c->p.width || level < 0 || level > P.lmax) { h->err = "vilf_track_pyramid: null pointer, row_stride < width or a level outside 0 .. Lmax"; return VILF_ERR_INVALID_ARGUMENT; }
+    HIPCHECK(h, hipSetDevice(h->device));
+    { const int rc = tk_build(h, P, (unsigned char *)c->stage[2].p, img, row_stride, level); if (rc != VILF_OK) return rc; }
+    HIPCHECK(h, vilf_copy_sync(h, out, P.lv[level], (size_t)P.w[level] * P.h[level], hipMemcpyDeviceToHost));
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_lk(vilf_handle *h, const unsigned char *img_prev, const unsigned char *img_next, const float *pts, int n, float *pts_out, unsigned char *status_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_lk");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!img_prev || !img_next || n < 0 || (n > 0 && (!pts || !pts_out || !status_out))) { h->err = "vilf_track_lk: null pointer or negative count"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return VILF_OK;
+    HIPCHECK(h, hipSetDevice(h->device));
+    const size_t sn = (size_t)std::max(n, TK_MAXN);
+    if (sn * 8 > c->lkpts.cap || sn * 8 > c->fwd.cap || sn > c->status.cap) HIPCHECK(h, hipStreamSynchronize(h->stream));      // a buffer is about to be replaced
+    if (!c->lkpts.ensure(sn * 8) || !c->fwd.ensure(sn * 8) || !c->status.ensure(sn)) { h->err = "hipMalloc failed (feature tracker, points)"; return VILF_ERR_DEVICE; }
+    TkPyr &A = c->pyr[2], &B = c->pyr[3];
+    { const int rc = tk_build(h, A, (unsigned char *)c->stage[2].p, img_prev, A.w[0], A.lmax); if (rc != VILF_OK) return rc; }
+    { const int rc = tk_build(h, B, (unsigned char *)c->stage[3].p, img_next, B.w[0], B.lmax); if (rc != VILF_OK) return rc; }
+    HIPCHECK(h, hipMemcpyAsync(c->lkpts.p, pts, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(tk_lk, dim3((n + TK_LK_WAVES - 1) / TK_LK_WAVES), dim3(64 * TK_LK_WAVES), 0, h->stream, A, B, c->lkpts.as<float2>(), (const int *)nullptr, n, c->fwd.as<float2>(), c->status.as<unsigned char>(), 0);
+    HIPCHECK(h, hipGetLastError());
+    HIPCHECK(h, hipMemcpyAsync(pts_out, c->fwd.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(h, vilf_copy_sync(h, status_out, c->status.p, (size_t)n, hipMemcpyDeviceToHost));
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_detect(vilf_handle *h, const unsigned char *img, const float *kept_pts, int n_kept, int n_max, float *pts_out, int *n_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_detect");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!img || !n_out || n_kept < 0 || n_kept > TK_MAXN || (n_kept > 0 && !kept_pts) || n_max > TK_MAXN || (n_max > 0 && !pts_out)) {
+        h->err = "vilf_track_detect: null pointer, or more than VILF_MAX_FEATURES kept points or new corners"; return VILF_ERR_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < 2 * n_kept; i++)
+        if (!(std::fabs(kept_pts[i]) <= 1.0e6f)) { h->err = "vilf_track_detect: a kept point that is not finite or beyond 1e6 pixels"; return VILF_ERR_INVALID_ARGUMENT; }
+    *n_out = 0;
+    if (n_max <= 0) return VILF_OK;
+    HIPCHECK(h, hipSetDevice(h->device));
+    TkPyr &P = c->pyr[2];
+    TkList l = tk_list(c->tmplist.p, 2 * TK_MAXN);
+    int ctl[TC_INTS];
+    std::memset(ctl, 0, sizeof(ctl));
+    ctl[TC_N] = n_kept; ctl[TC_KEPT] = n_kept; ctl[TC_NMAX] = n_max;
+    HIPCHECK(h, hipMemcpyAsync(c->tmpctl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, h->stream));
+    if (n_kept > 0) HIPCHECK(h, hipMemcpyAsync(l.pts, kept_pts, (size_t)n_kept * 8, hipMemcpyHostToDevice, h->stream));
+    { const int rc = tk_build(h, P, (unsigned char *)c->stage[2].p, img, P.w[0], 0); if (rc != VILF_OK) return rc; }
+    { const int rc = tk_detect(h, c, P.lv[0], c->tmpctl.as<int>(), l, std::max(n_kept, 1)); if (rc != VILF_OK) return rc; }
+    HIPCHECK(h, vilf_copy_sync(h, ctl, c->tmpctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+    const int n_new = std::min(std::max(ctl[TC_N] - n_kept, 0), n_max);
+    if (n_new > 0) HIPCHECK(h, vilf_copy_sync(h, pts_out, l.pts + n_kept, (size_t)n_new * 8, hipMemcpyDeviceToHost));
+    *n_out = n_new;
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_profile(vilf_handle *h, double ms_out[5], long launches_out[5]) {
+    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
+    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
+    for (int i = 0; i < TK_STAGES; i++) { ms_out[i] = h->trk ? h->trk->ms[i] : 0.0; launches_out[i] = h->trk ? h->trk->launches[i] : 0; }
+    return VILF_OK;
+}

@@ -678,3 +678,103 @@ class FeatureExtraction:
         out = np.zeros(max(len(f), 1), dtype=np.float32)
         self.s._check(self._L.vilf_feature_depth(self.s._h, c.ctypes.data_as(fp), len(c), f.ctypes.data_as(fp), len(f), out.ctypes.data_as(fp)), "vilf_feature_depth")
         return out[:len(f)].copy()
+
+
+TRACK_STAGES = ("pyramid", "lk", "set_mask", "detect", "undistort")
+
+
+class FeatureTracker:
+    """Host mirror of FeatureTracker (feature_tracker/feature_tracker.cpp) over the device tracker of a BackendSolver handle (vilf_track_*): the camera half of the
+    feature-tracker node. Images are (height, width) uint8 arrays; camera = (fx, fy, cx, cy, k1, k2, p1, p2). The arithmetic is the contract in include/vilfusion.h."""
+
+    def __init__(self, solver, width, height, camera, max_cnt=200, min_dist=20):
+        self.s, self._L = solver, solver._L
+        self.width, self.height, self.max_cnt, self.min_dist = int(width), int(height), int(max_cnt), int(min_dist)
+        self.camera = tuple(float(v) for v in camera)
+        assert len(self.camera) == 8, "camera = (fx, fy, cx, cy, k1, k2, p1, p2)"
+        self.params = abi.TrackParams(self.width, self.height, self.max_cnt, self.min_dist, *self.camera)
+        self.s._check(self._L.vilf_track_init(self.s._h, C.byref(self.params)), "vilf_track_init")
+        self._clear()
+
+    def _clear(self):
+        self.ids, self.track_cnt = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+        self.cur_pts, self.cur_un_pts, self.pts_velocity = (np.zeros((0, 2), dtype=np.float32) for _ in range(3))
+
+    def _img(self, img):
+        a = np.asarray(img)
+        assert a.dtype == np.uint8 and a.ndim == 2 and a.shape == (self.height, self.width) and a.strides[1] == 1 and a.strides[0] >= self.width, (a.dtype, a.shape, a.strides)
+        return a
+
+    @staticmethod
+    def _u8(a):
+        return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    @staticmethod
+    def _fp(a):
+        return a.ctypes.data_as(C.POINTER(C.c_float))
+
+    def reset(self):
+        """a fresh FeatureTracker: no points, no previous image, n_id = 0"""
+        self.s._check(self._L.vilf_track_reset(self.s._h), "vilf_track_reset")
+        self._clear()
+
+    def readImage(self, img, stamp):
+        """:119-209 and the updateID loop (feature_tracker_node.cpp:285-292). A row stride larger than the width is passed on as it is. Returns the number of points."""
+        a = self._img(img)
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_track_read_image(self.s._h, self._u8(a), int(a.strides[0]), float(stamp), C.byref(n)), "vilf_track_read_image")
+        m = max(n.value, 1)
+        ids, cnt = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+        pts, un, vel = (np.zeros((m, 2), dtype=np.float32) for _ in range(3))
+        ip = C.POINTER(C.c_int)
+        self.s._check(self._L.vilf_track_get(self.s._h, m, ids.ctypes.data_as(ip), cnt.ctypes.data_as(ip), self._fp(pts), self._fp(un), self._fp(vel), C.byref(n)), "vilf_track_get")
+        k = n.value
+        self.ids, self.track_cnt, self.cur_pts, self.cur_un_pts, self.pts_velocity = ids[:k], cnt[:k], pts[:k], un[:k], vel[:k]
+        return k
+
+    def pyramid(self, img, level):
+        """level `level` (0 .. Lmax) of the image's pyramid"""
+        a = self._img(img)
+        w, h = self.width, self.height
+        for _ in range(int(level)):
+            w, h = (w + 1) // 2, (h + 1) // 2
+        out = np.zeros((h, w), dtype=np.uint8)
+        self.s._check(self._L.vilf_track_pyramid(self.s._h, self._u8(a), int(a.strides[0]), int(level), self._u8(out)), "vilf_track_pyramid")
+        return out
+
+    def lk(self, img_prev, img_next, pts):
+        """calcOpticalFlowPyrLK between two images -> (points (n, 2) float32, status (n,) uint8), without inBorder"""
+        a, b = np.ascontiguousarray(self._img(img_prev)), np.ascontiguousarray(self._img(img_next))
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 2)
+        out, st = np.zeros((max(len(p), 1), 2), dtype=np.float32), np.zeros(max(len(p), 1), dtype=np.uint8)
+        self.s._check(self._L.vilf_track_lk(self.s._h, self._u8(a), self._u8(b), self._fp(p), len(p), self._fp(out), self._u8(st)), "vilf_track_lk")
+        return out[:len(p)], st[:len(p)]
+
+    def detect(self, img, kept_pts, n_max):
+        """goodFeaturesToTrack under the mask of the kept points -> new corners (n, 2) float32 in acceptance order"""
+        a = np.ascontiguousarray(self._img(img))
+        kp = np.ascontiguousarray(kept_pts, dtype=np.float32).reshape(-1, 2)
+        out = np.zeros((max(int(n_max), 1), 2), dtype=np.float32)
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_track_detect(self.s._h, self._u8(a), self._fp(kp), len(kp), int(n_max), self._fp(out), C.byref(n)), "vilf_track_detect")
+        return out[:n.value].copy()
+
+    def feature_message(self, depths=None):
+        """the rows with track_cnt > 1 as {id: (x, y, 1, u, v, vx, vy, depth)} (feature_tracker_node.cpp:311-336): what SlidingWindowEstimator.process_image takes.
+        depths: one value per such row, as FeatureExtraction.getFeatureDepth returns for message_points(); None = no LiDAR depth (-1)"""
+        rows = np.flatnonzero(self.track_cnt > 1)
+        assert depths is None or len(depths) == len(rows)
+        return {int(self.ids[i]): (float(self.cur_un_pts[i, 0]), float(self.cur_un_pts[i, 1]), 1.0, float(self.cur_pts[i, 0]), float(self.cur_pts[i, 1]),
+                                   float(self.pts_velocity[i, 0]), float(self.pts_velocity[i, 1]), -1.0 if depths is None else float(depths[k]))
+                for k, i in enumerate(rows)}
+
+    def message_points(self):
+        """(x, y, 1) of the rows feature_message() publishes, (m, 3) float32: the features_xyz of FeatureExtraction.getFeatureDepth"""
+        rows = np.flatnonzero(self.track_cnt > 1)
+        return np.concatenate([self.cur_un_pts[rows], np.ones((len(rows), 1), dtype=np.float32)], axis=1)
+
+    def profile(self):
+        """ms and launches of the stages of the last readImage (vilf_set_profiling)"""
+        ms, cnt = (C.c_double * 5)(), (C.c_long * 5)()
+        self.s._check(self._L.vilf_track_profile(self.s._h, ms, cnt), "vilf_track_profile")
+        return dict(zip(TRACK_STAGES, ((ms[i], cnt[i]) for i in range(5))))

@@ -23,6 +23,7 @@ EXPORTED = [
     "vilf_icp_default_params", "vilf_icp_create", "vilf_icp_add_cloud", "vilf_icp_add_clouds", "vilf_icp_size", "vilf_icp_submap", "vilf_icp_align", "vilf_icp_align_pairs",
     "vilf_icp_get_history", "vilf_icp_get_search", "vilf_get_profile_icp",
     "vilf_icp_global_map", "vilf_icp_global_map_size", "vilf_icp_global_map_get", "vilf_get_profile_icp_map",
+    "vilf_track_init", "vilf_track_reset", "vilf_track_read_image", "vilf_track_get", "vilf_track_pyramid", "vilf_track_lk", "vilf_track_detect", "vilf_track_profile",
 ]
 
 
@@ -134,6 +135,15 @@ def lib():
     L.vilf_icp_global_map_size.argtypes = [vp, abi.c_long_p]
     L.vilf_icp_global_map_get.argtypes = [vp, C.c_long, C.c_long, fpp]
     L.vilf_get_profile_icp_map.argtypes = [vp, C.POINTER(C.c_double), abi.c_long_p]
+    u8p = C.POINTER(C.c_uint8)
+    L.vilf_track_init.argtypes = [vp, C.POINTER(abi.TrackParams)]
+    L.vilf_track_reset.argtypes = [vp]
+    L.vilf_track_read_image.argtypes = [vp, u8p, C.c_int, C.c_double, ip]
+    L.vilf_track_get.argtypes = [vp, C.c_int, ip, ip, fpp, fpp, fpp, ip]
+    L.vilf_track_pyramid.argtypes = [vp, u8p, C.c_int, C.c_int, u8p]
+    L.vilf_track_lk.argtypes = [vp, u8p, u8p, fpp, C.c_int, fpp, u8p]
+    L.vilf_track_detect.argtypes = [vp, u8p, fpp, C.c_int, C.c_int, fpp, ip]
+    L.vilf_track_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 
