@@ -541,7 +541,9 @@ int vilf_scan2map_batch_get_map(vilf_handle *h, int stream, int which, float *xy
 /* ---- LiDAR feature extraction (≙ featureExtraction::extractFeature, feature_tracker/include/featureExtraction.hpp:54-232) ----
  * raw scan (xyzi, firing order) -> edge / surf feature clouds, the inputs of vilf_scan2map_*: ring assignment from the vertical
  * angle (n_scans 16 / 32 / 64), per-ring 10-neighbour curvature, six sectors per ring, <= 20 edge picks per sector with +-5
- * neighbour suppression, the remaining points as surf. Outputs are truncated to the capacities; the counts are always complete. */
+ * neighbour suppression, the remaining points as surf. Outputs are truncated to the capacities; the counts are always complete.
+ * A negative capacity is VILF_ERR_INVALID_ARGUMENT, before any device work. A sector of more than 1024 elements (a ring of more than
+ * 6160 accepted returns) is VILF_ERR_UNSUPPORTED with both counts 0; the handle stays usable. */
 int vilf_lidar_extract_features(vilf_handle *h, const float *xyzi, int n_points, int n_scans, double min_range, double max_range,
                                 double edge_threshold, float *edge_xyzi_out, int cap_edge, int *n_edge,
                                 float *surf_xyzi_out, int cap_surf, int *n_surf);

@@ -7,6 +7,7 @@
 // picked but emitted neither as edge nor as surf (:128-137); neighbour suppression is local to a sector.
 // One deliberate definition: std::sort's order of EXACTLY equal curvatures is unspecified in the reference; here ties are broken
 // by the point index (ascending), and the HIP path does the same.
+// tests/test_lidar_features.py holds this file bit for bit to tests/feat_reference.py, a numpy restatement written from the same text.
 #include "oracle_api.h"
 #include <algorithm>
 #include <cmath>
@@ -33,9 +34,16 @@ int ring_of(const P4 &p, int n_scans, double min_r, double max_r) {
 }
 }  // namespace
 
+// getLaserCloud alone: the ring of every input point, -1 for a rejected one (the tests probe the ring boundaries with it)
+extern "C" int vilo_lidar_rings(const float *xyzi, int n, int n_scans, double min_range, double max_range, int *ring_out) {
+    if (n < 0 || (n && (!xyzi || !ring_out)) || (n_scans != 16 && n_scans != 32 && n_scans != 64)) return VILF_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n; i++) ring_out[i] = ring_of(P4{xyzi[4 * i], xyzi[4 * i + 1], xyzi[4 * i + 2], xyzi[4 * i + 3]}, n_scans, min_range, max_range);
+    return VILF_OK;
+}
+
 extern "C" int vilo_extract_features(const float *xyzi, int n, int n_scans, double min_range, double max_range, double edge_threshold,
                                      float *edge_out, int cap_edge, int *n_edge, float *surf_out, int cap_surf, int *n_surf) {
-    if (n < 0 || (n_scans != 16 && n_scans != 32 && n_scans != 64) || !n_edge || !n_surf) return VILF_ERR_INVALID_ARGUMENT;
+    if (n < 0 || (n_scans != 16 && n_scans != 32 && n_scans != 64) || !n_edge || !n_surf || cap_edge < 0 || cap_surf < 0) return VILF_ERR_INVALID_ARGUMENT;
     std::vector<std::vector<P4>> rings(n_scans);
     for (int i = 0; i < n; i++) {
         const P4 p{xyzi[4 * i], xyzi[4 * i + 1], xyzi[4 * i + 2], xyzi[4 * i + 3]};

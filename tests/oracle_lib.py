@@ -160,6 +160,17 @@ def extract_features(xyzi, n_scans=64, min_range=3.0, max_range=100.0, edge_thre
     return e[:ne.value].copy(), s[:ns.value].copy()
 
 
+def lidar_rings(xyzi, n_scans=64, min_range=3.0, max_range=100.0):
+    """getLaserCloud's ring per point on the oracle, -1 = rejected"""
+    L = lib()
+    L.vilo_lidar_rings.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int)]
+    a = np.ascontiguousarray(xyzi, dtype=np.float32)
+    out = np.zeros(max(len(a), 1), dtype=np.int32)
+    rc = L.vilo_lidar_rings(a.ctypes.data_as(C.POINTER(C.c_float)), len(a), n_scans, min_range, max_range, out.ctypes.data_as(C.POINTER(C.c_int)))
+    assert rc == 0, rc
+    return out[:len(a)].copy()
+
+
 def feature_depth(cloud_xyzi, feat_xyz):
     """getFeatureDepth on the oracle: depth per feature (-1 = none)"""
     L = lib()

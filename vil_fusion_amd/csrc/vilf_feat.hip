@@ -250,6 +250,7 @@ void vilf_feat_release(vilf_handle *h) {
 extern "C" int vilf_lidar_extract_features(vilf_handle *h, const float *xyzi, int n, int n_scans, double min_range, double max_range, double edge_threshold,
                                            float *edge_out, int cap_edge, int *n_edge, float *surf_out, int cap_surf, int *n_surf) {
     if (!h || n < 0 || (n && !xyzi) || !n_edge || !n_surf || (n_scans != 16 && n_scans != 32 && n_scans != 64)) return VILF_ERR_INVALID_ARGUMENT;
+    if (cap_edge < 0 || cap_surf < 0) { h->err = "feature extraction: negative output capacity"; return VILF_ERR_INVALID_ARGUMENT; }     // would become a ~2^64 byte copy below
     HIPCHECK(h, hipSetDevice(h->device));
     *n_edge = 0; *n_surf = 0;
     if (n == 0) return VILF_OK;
@@ -291,6 +292,32 @@ extern "C" int vilf_lidar_extract_features(vilf_handle *h, const float *xyzi, in
     if (surf_out && tot[1] > 0) HIPCHECK(h, hipMemcpyAsync(surf_out, c->outs.p, (size_t)std::min(tot[1], cap_surf) * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
     return VILF_OK;
+}
+
+// Test hook, not part of include/vilfusion.h (like vilf_debug_sort_pairs): fe_ring alone. ring_out[i] = the ring of point i, -1 = rejected.
+extern "C" int vilf_debug_lidar_rings(vilf_handle *h, const float *xyzi, int n, int n_scans, double min_range, double max_range, int *ring_out) {
+    if (!h || n < 0 || (n && (!xyzi || !ring_out)) || (n_scans != 16 && n_scans != 32 && n_scans != 64)) return VILF_ERR_INVALID_ARGUMENT;
+    HIPCHECK(h, hipSetDevice(h->device));
+    if (n == 0) return VILF_OK;
+    DBuf pts, keys, vals;
+    const size_t sn = (size_t)n;
+    int rc = VILF_OK;
+    if (!pts.ensure(sn * 16) || !keys.ensure(sn * 4) || !vals.ensure(sn * 4)) { h->err = "hipMalloc failed (ring hook)"; rc = VILF_ERR_DEVICE; }
+    hipError_t e = hipSuccess;
+    if (rc == VILF_OK) {
+        e = hipMemcpyAsync(pts.p, xyzi, sn * 16, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(fe_ring, dim3((n + 255) / 256), dim3(256), 0, h->stream, pts.as<float4>(), n, n_scans, min_range, max_range, keys.as<unsigned int>(), vals.as<int>());
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(ring_out, keys.p, sn * 4, hipMemcpyDeviceToHost, h->stream);
+        const hipError_t e2 = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = VILF_ERR_DEVICE; }
+    }
+    pts.release(); keys.release(); vals.release();
+    if (rc == VILF_OK) for (int i = 0; i < n; i++) if (ring_out[i] == n_scans) ring_out[i] = -1;      // the key of a rejected point
+    return rc;
 }
 
 extern "C" int vilf_feature_depth(vilf_handle *h, const float *cloud_xyzi, int n, const float *feat_xyz, int m, float *depth_out) {
