@@ -596,7 +596,45 @@ int vilf_feature_depth(vilf_handle *h, const float *depth_cloud_xyzi, int n_poin
  *                rho2 = x x + y y, rad = k1 rho2 + (k2 rho2) rho2, dx = (x rad + (2 p1) (x y)) + p2 (rho2 + 2 (x x)), dy = (y rad + (2 p2) (x y)) + p1 (rho2 + 2 (y y)).
  *                The result is rounded to float32. velocity = (un_cur - un_prev of the same id) / (t_cur - t_prev) in fp64 from the float32 values, rounded to
  *                float32; 0 for a new id and on the first frame.
- * Not here: CLAHE (EQUALIZE; the caller passes the image it wants tracked), rejectWithF, readImage_mask and the fisheye mask. */
+ *   CLAHE        optional (vilf_track_configure, equalize), in front of everything else: the pyramid, LK and the detection see the equalised image. Modelled on
+ *                cv::createCLAHE(3.0, Size(8, 8))->apply (:127); clip c and the tiles tx x ty are parameters. Agreement with OpenCV is neither measured nor claimed.
+ *                padding: if W % tx == 0 and H % ty == 0 there is none, W' = W, H' = H. Otherwise W' = W + (tx - W % tx) and H' = H + (ty - H % ty), the new columns
+ *                and rows read through R: I'(x, y) = I(R(x, W), R(y, H)). A direction that does divide is then padded by a whole tx or ty. That is what the
+ *                model does, and it is kept. Tile (tw, th) = (W' / tx, H' / ty), area = tw th; tile (i, j) covers x in [i tw, (i + 1) tw), y in [j th, (j + 1) th).
+ *                limit (int): 0 (no clipping) if c <= 0, else max(1, (int)((c * (double)area) / 256.0)), the product and the quotient in fp64, each rounded.
+ *                per tile: hist[256] = counts of I' over the tile (int). If limit > 0: excess = sum max(hist - limit, 0), hist = min(hist, limit),
+ *                batch = excess / 256, residual = excess - 256 batch (int); every bin + batch; if residual > 0, with step = max(256 / residual, 1) (int) the bins
+ *                0, step, 2 step, .. < 256 get + 1 each while residual lasts (bin b iff b % step == 0 and b / step < residual).
+ *                lut[b] = sat_u8(rint(float32(sum_{a <= b} hist[a]) * (255.f / float32(area)))): an int sum, a float32 quotient, a float32 product, each rounded.
+ *                remap, per pixel (x, y) of the unpadded image with value v, float32, each operation rounded: txf = float32(x) * (1.f / float32(tw)) - 0.5f,
+ *                x1 = floor(txf), xa = txf - x1, x2 = x1 + 1, then x1 and x2 clamped to [0, tx - 1]; y1, ya, y2 likewise from y and th;
+ *                out = sat_u8(rint((lut[y1, x1][v] * (1 - xa) + lut[y1, x2][v] * xa) * (1 - ya) + (lut[y2, x1][v] * (1 - xa) + lut[y2, x2][v] * xa) * ya)).
+ *   rejectWithF  optional (vilf_track_configure, reject_f), after the inBorder drop and before setMask, on the surviving points in list order (n of them;
+ *                x = the point in the current image, x' = where LK found it in the new one). Skipped when n < 8 (:385). Modelled on :383-420, but
+ *                cv::findFundamentalMat(FM_RANSAC) draws random samples, so the search itself is a design of this project (deviations: DESIGN.md §3i).
+ *                lift: both points through the undistortion text above in fp64 (before its rounding to float32), then u = FOCAL_LENGTH x + W / 2.0,
+ *                v = FOCAL_LENGTH y + H / 2.0 in fp64, each operation rounded, and (u, v) rounded to float32 (cv::Point2f). All that follows is fp64 on these values.
+ *                hypotheses: a fixed number K (1 .. 2048, default 512), no adaptive stopping. With 8-point samples and an inlier share w the chance that no
+ *                sample is all inliers is (1 - w^8)^K: about e^-30 at w = 0.7 and 0.13 at w = 0.5 for K = 512.
+ *                sample of hypothesis k: mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32, wrapping).
+ *                g(k, d) = mix(mix(mix(seed + 0x9e3779b9) + k) + d). Slot j = 0 .. 7 takes i = (uint64(g(k, j)) * n) >> 32; while i equals the index of an earlier
+ *                slot, i <- (i + 1) mod n (at most j steps; no second draw, so the loop is bounded). No state: hypothesis k is the same wherever it is computed.
+ *                8-point solve, each side of the sample on its own: c = (sum_j p_j) / 8, the sums from 0 in slot order; mean = (sum_j sqrt(dx dx + dy dy)) / 8 with
+ *                (dx, dy) = p_j - c; s = sqrt(2.0) / mean; p^_j = (p_j - c) s. Row j of A: (x^' x^, x^' y^, x^', y^' x^, y^' y^, y^', x^, y^, 1). M = A^T A, each of
+ *                the 45 upper entries a sum from 0 over j in slot order, a product and an addition per term. Jacobi(M, 9): V = I; 10 sweeps; in each, the pairs
+ *                (p, q), p < q, in row-major order; a pair with a_pq == 0 exactly is skipped; theta = (a_qq - a_pp) / (2 a_pq);
+ *                t = (theta < 0 ? -1 : 1) / (|theta| + sqrt(theta theta + 1)); c = 1 / sqrt(t t + 1); s = t c; for r != p, q:
+ *                a_rp' = c a_rp - s a_rq, a_rq' = s a_rp + c a_rq (and their mirror images); a_pp' = a_pp - t a_pq; a_qq' = a_qq + t a_pq; a_pq = 0; for every r:
+ *                v_rp' = c v_rp - s v_rq, v_rq' = s v_rp + c v_rq. f = the column of V under the smallest a_ii (compared with <, so ties and NaNs leave the lower
+ *                index); F^ = f as a row-major 3 x 3. Rank 2: G = F^^T F^ (g_pq = sum_r F^_rp F^_rq from 0), Jacobi(G, 3) as above, v = the column under the
+ *                smallest g_ii, w_r = (F^_r0 v_0 + F^_r1 v_1) + F^_r2 v_2, F^_rc <- F^_rc - w_r v_c. Denormalise with (tx, ty) = (s c_x, s c_y) of each side:
+ *                B_r0 = F^_r0 s, B_r1 = F^_r1 s, B_r2 = (F^_r2 - F^_r0 tx) - F^_r1 ty; F_0c = s' B_0c, F_1c = s' B_1c, F_2c = (B_2c - tx' B_0c) - ty' B_1c.
+ *                The hypothesis is invalid (score -1) unless s, s' and the nine F_rc are finite. (FM_RANSAC uses 7-point samples: one solution, no cubic here.)
+ *                score: for every point l' = F x (l'_r = (F_r0 x + F_r1 y) + F_r2), l = F^T x' (l_c = (F_0c x' + F_1c y') + F_2c), d = (x' l'_0 + y' l'_1) + l'_2;
+ *                inlier iff d d / (l'_0 l'_0 + l'_1 l'_1) <= F_THRESHOLD^2 and d d / (l_0 l_0 + l_1 l_1) <= F_THRESHOLD^2 (the larger of the two errors; a NaN
+ *                compares false: an outlier). Score = the number of inliers. The winner is the valid hypothesis of the highest score, ties to the lower k; the
+ *                status is its inlier mask, there is no refit. No valid hypothesis: nothing is rejected (every status 1, best = -1).
+ * Not here: readImage_mask and the fisheye mask. */
 typedef struct vilf_track_params {
     int width, height;               /* COL, ROW */
     int max_cnt;                     /* MAX_CNT, 1 .. VILF_MAX_FEATURES */
@@ -626,6 +664,27 @@ int vilf_track_detect(vilf_handle *h, const unsigned char *img, const float *kep
 /* vilf_set_profiling: the stages of the last vilf_track_read_image: upload + pyramid, LK, setMask, detection (mask, response, candidates, sorts, acceptance),
  * ids + undistortion + velocity */
 int vilf_track_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
+/* The two optional steps of readImage (the paragraphs CLAHE and rejectWithF above). Both are off after vilf_track_init, and a tracker that is never configured
+ * computes what it computed before they existed. */
+typedef struct vilf_track_frontend {
+    int equalize; double clahe_clip; int clahe_tiles_x, clahe_tiles_y;                  /* 0/1, 3.0, 8, 8 */
+    int reject_f; double f_threshold, focal_length; int n_hypotheses; unsigned seed;    /* 0/1, 1.0, 460, 512 */
+} vilf_track_frontend;
+#define VILF_TRACK_MAX_TILES 1024        /* tiles_x * tiles_y: the LUT storage sized by vilf_track_init */
+#define VILF_TRACK_MAX_HYPOTHESES 2048
+/* after vilf_track_init; a later vilf_track_init returns to "both off" with the defaults in the comments above. Every field is checked whether its step is on or
+ * not. Invalid argument, the handle and the tracker untouched: no tracker, tiles < 1 or tiles_x * tiles_y > VILF_TRACK_MAX_TILES, a clip that is negative or not
+ * finite, a threshold or focal length that is not positive and finite, n_hypotheses outside 1 .. VILF_TRACK_MAX_HYPOTHESES. The tracked state is kept. */
+int vilf_track_configure(vilf_handle *h, const vilf_track_frontend *fe);
+/* stateless: CLAHE of an image (rows row_stride bytes apart) with the configured clip and tiles (the defaults if never configured) -> out, rows tight */
+int vilf_track_clahe(vilf_handle *h, const unsigned char *img, int row_stride, unsigned char *out);
+/* stateless: rejectWithF on n point pairs [n][2] with the tracker's camera and the configured threshold, focal length, K and seed -> status_out [n], F_out (row-major),
+ * *best_out = the winning k, *n_inliers_out. n < 8 or no valid hypothesis: every status 1, best -1, n_inliers n, F 0; that is no error. Invalid argument, nothing
+ * written: a null pointer, n < 0, n > VILF_MAX_FEATURES, a coordinate that is not finite. */
+int vilf_track_reject_f(vilf_handle *h, const float *cur_pts, const float *forw_pts, int n, unsigned char *status_out, double F_out[9], int *best_out, int *n_inliers_out);
+/* vilf_set_profiling: CLAHE (both kernels) and rejectWithF (lift, hypotheses, score, apply) of the last vilf_track_read_image; 0 for a step that is off. The
+ * five stages of vilf_track_profile are as before: CLAHE falls into the first of them, rejectWithF into the second. */
+int vilf_track_profile_frontend(vilf_handle *h, double ms_out[2], long launches_out[2]);
 #ifdef __cplusplus
 }
 #endif

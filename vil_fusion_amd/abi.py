@@ -158,6 +158,16 @@ class TrackParams(C.Structure):
                 ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double)]
 
 
+class TrackFrontend(C.Structure):
+    """vilf_track_frontend: the two optional steps of readImage, CLAHE (EQUALIZE) and rejectWithF (F_THRESHOLD, FOCAL_LENGTH)"""
+    _fields_ = [("equalize", C.c_int), ("clahe_clip", C.c_double), ("clahe_tiles_x", C.c_int), ("clahe_tiles_y", C.c_int),
+                ("reject_f", C.c_int), ("f_threshold", C.c_double), ("focal_length", C.c_double), ("n_hypotheses", C.c_int), ("seed", C.c_uint)]
+
+
+VILF_TRACK_MAX_TILES = 1024
+VILF_TRACK_MAX_HYPOTHESES = 2048
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

@@ -11,6 +11,13 @@
 //   radix sorts      by index, then tk_keys + a stable sort by ~bits(lambda): the order (lambda descending, index ascending), whatever the compaction order was
 //   tk_corners       one wave: the candidates in order, the lanes test one candidate against the accepted corners in LDS
 //   tk_finish        one workgroup: ids, undistortion, velocity against the previous frame's (id, un) table, which it then replaces
+// The two optional steps (vilf_track_configure; both off unless asked for):
+//   tk_clahe_lut     a workgroup per tile: the 256-bin histogram of the padded tile by LDS integer atomics, clip, redistribute, prefix sum -> the tile's 256-byte LUT
+//   tk_clahe_remap   a 32 x 8 tile: the four neighbouring LUTs interpolated in float32, written into level 0 of the "next" pyramid (the raw image has its own buffer)
+//   tk_f_lift        one workgroup: the survivors of LK's status, in list order, both points lifted to the float32 pixels of the virtual camera
+//   tk_f_hypotheses  a lane per hypothesis: sample, Hartley, M = A^T A and the Jacobi vectors in LDS (a column per lane), rank 2, denormalise -> F_k, valid_k
+//   tk_f_score       a wave per hypothesis: the lanes stride over the points, an integer wave sum, one 64-bit atomicMax of (score + 1, K - 1 - k)
+//   tk_f_apply       one workgroup: the winner's inlier mask into LK's status bytes, which tk_setmask reads as before
 // Per frame the host uploads the image and downloads the list (count + rows, one copy).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -28,6 +35,9 @@
 #define TK_MAX_ITERS 30
 #define TK_MAXN VILF_MAX_FEATURES           // rows of the list; accepted corners of one detection
 #define TK_STAGES 5
+#define TK_FE_STAGES 2                      // CLAHE, rejectWithF
+#define TK_F_SWEEPS 10
+#define TK_F_MAXK VILF_TRACK_MAX_HYPOTHESES
 
 struct TkPyr { unsigned char *lv[TK_LEVELS]; int w[TK_LEVELS], h[TK_LEVELS], lmax; };      // rows are tight (stride = width)
 // a feature list in one allocation: hdr[16] (hdr[0] = rows), then ids, track_cnt, cur_pts, un_pts, velocity, each for `cap` rows
@@ -43,6 +53,11 @@ static inline TkList tk_list(void *base, int cap) {
 // control words of one tracker (device): written by the kernels, never read by the host
 enum { TC_N = 0, TC_KEPT, TC_NMAX, TC_NCAND, TC_NID, TC_PREVN, TC_LAMMAX = 8 /* unsigned long long at ints 8, 9 */, TC_INTS = 16 };
 struct TkCam { double i11, i13, i22, i23, k1, k2, p1, p2; int distort; };
+// rejectWithF on the device: the lifted survivors and their rows in the list, control words (FC_*), F and valid flag per hypothesis, the result record
+// (best, inliers, F as 11 doubles)
+enum { FC_M = 0, FC_BEST = 2 /* unsigned long long at ints 2, 3: (score + 1) << 32 | (K - 1 - k); 0 = no valid hypothesis */, FC_INTS = 4 };
+#define TK_F_RES 11
+struct TkF { float2 *ua, *ub; int *src, *fctl; double *F; int *valid; double *res; };
 
 // ---- launch contract -----------------------------------------------------------------------------------------------------
 #define TK_TW 32                        // tk_pyr_down, tk_response: block (32, 8), grid = tiles of the output
@@ -61,6 +76,14 @@ __global__ void tk_candidates(const double *lam, const unsigned char *mask, int 
 __global__ void tk_keys(const double *lam, const unsigned *cidx, const int *ctl, int cap, unsigned long long *key, int *val);
 __global__ void tk_corners(const int *val, int W, int cap, int *ctl, TkList l, long long md2);
 __global__ void tk_finish(TkList l, int *ctl, int *prev_ids, float2 *prev_un, TkCam cam, double dt, int has_prev);
+#define TK_F_LANES 64                   // tk_f_hypotheses: block 64 (one wave), grid = ceil(K / 64), a lane per hypothesis, its matrices a column of the LDS arrays; no barrier
+#define TK_F_WAVES 4                    // tk_f_score: block 256, grid = ceil(K / 4), a wave per hypothesis; no workgroup barrier
+__global__ void tk_clahe_lut(const unsigned char *img, int W, int H, int tw, int th, int limit, float scale, unsigned char *lut);      // grid (tx, ty), block TK_NT
+__global__ void tk_clahe_remap(const unsigned char *img, int W, int H, int tx, int ty, float inv_tw, float inv_th, const unsigned char *lut, unsigned char *out);   // block (32, 8), tiles of the image
+__global__ void tk_f_lift(const float2 *cur, const float2 *fwd, const unsigned char *status, const int *n_dev, int n_host, TkCam cam, double focal, double half_w, double half_h, TkF f);   // one workgroup, TK_NT
+__global__ void tk_f_hypotheses(TkF f, int K, unsigned seed);
+__global__ void tk_f_score(TkF f, int K, double thr2);
+__global__ void tk_f_apply(TkF f, int K, double thr2, unsigned char *status);      // one workgroup, TK_NT
 
 struct TrackCtx {
     vilf_track_params p;
@@ -71,18 +94,26 @@ struct TrackCtx {
     int n_host = 0;                     // rows of the list as downloaded by the last vilf_track_read_image
     size_t ncell = 0;                   // W * H
     DBuf pyrmem[4], list[2], tmplist, ctl, tmpctl, prev_ids, prev_un, fwd, status, lkpts, mask, lam, cidx, cidx2, cval, key, key2, val, val2, temp;
+    DBuf raw, lut, fmem;                // the optional steps: the image before CLAHE, the tiles' LUTs (VILF_TRACK_MAX_TILES), everything of rejectWithF (tk_f)
+    vilf_track_frontend fe;             // both off and the defaults after vilf_track_init
+    double fe_ms[TK_FE_STAGES] = {0, 0};
+    long fe_launches[TK_FE_STAGES] = {0, 0};
     PinBuf pin, stage[4];               // the downloaded list; the image on its way to level 0 of pyramid k
     double ms[TK_STAGES] = {0, 0, 0, 0, 0};
     long launches[TK_STAGES] = {0, 0, 0, 0, 0};
     void release() {
         DBuf *all[] = {&pyrmem[0], &pyrmem[1], &pyrmem[2], &pyrmem[3], &list[0], &list[1], &tmplist, &ctl, &tmpctl, &prev_ids, &prev_un, &fwd, &status, &lkpts,
-                       &mask, &lam, &cidx, &cidx2, &cval, &key, &key2, &val, &val2, &temp};
+                       &mask, &lam, &cidx, &cidx2, &cval, &key, &key2, &val, &val2, &temp, &raw, &lut, &fmem};
         for (DBuf *b : all) b->release();
         pin.release();
         for (PinBuf &b : stage) b.release();
     }
 };
-void vilf_track_profile_reset(vilf_handle *h) { if (h->trk) for (int i = 0; i < TK_STAGES; i++) { h->trk->ms[i] = 0; h->trk->launches[i] = 0; } }
+void vilf_track_profile_reset(vilf_handle *h) {
+    if (!h->trk) return;
+    for (int i = 0; i < TK_STAGES; i++) { h->trk->ms[i] = 0; h->trk->launches[i] = 0; }
+    for (int i = 0; i < TK_FE_STAGES; i++) { h->trk->fe_ms[i] = 0; h->trk->fe_launches[i] = 0; }
+}
 void vilf_track_release(vilf_handle *h) { if (h->trk) { h->trk->release(); delete h->trk; h->trk = nullptr; } }
 
 namespace {
@@ -123,6 +154,20 @@ VD int tk_bilinear(const unsigned char *I, int W, int H, int x, int y, const TkC
     const int x0 = tk_r(x, W), x1 = tk_r(x + 1, W);
     const unsigned char *r0 = I + (size_t)tk_r(y, H) * W, *r1 = I + (size_t)tk_r(y + 1, H) * W;
     return (c.w00 * (int)r0[x0] + c.w01 * (int)r0[x1] + c.w10 * (int)r1[x0] + c.w11 * (int)r1[x1] + 256) >> 9;
+}
+// the undistortion text in fp64: liftProjective of the float32 pixel p, before any rounding to float32
+VD void tk_undistort(const TkCam &cam, float2 p, double &ux, double &uy) {
+    const double mx = __dadd_rn(__dmul_rn(cam.i11, (double)p.x), cam.i13), my = __dadd_rn(__dmul_rn(cam.i22, (double)p.y), cam.i23);
+    ux = mx; uy = my;
+    if (cam.distort) {
+        for (int r = 0; r < 8; r++) {                // PinholeCamera::distortion (PinholeCamera.cc:646-662), every operation rounded on its own
+            const double x2 = __dmul_rn(ux, ux), y2 = __dmul_rn(uy, uy), xy = __dmul_rn(ux, uy), rho2 = __dadd_rn(x2, y2);
+            const double rad = __dadd_rn(__dmul_rn(cam.k1, rho2), __dmul_rn(__dmul_rn(cam.k2, rho2), rho2));
+            const double ddx = __dadd_rn(__dadd_rn(__dmul_rn(ux, rad), __dmul_rn(__dmul_rn(2.0, cam.p1), xy)), __dmul_rn(cam.p2, __dadd_rn(rho2, __dmul_rn(2.0, x2))));
+            const double ddy = __dadd_rn(__dadd_rn(__dmul_rn(uy, rad), __dmul_rn(__dmul_rn(2.0, cam.p2), xy)), __dmul_rn(cam.p1, __dadd_rn(rho2, __dmul_rn(2.0, y2))));
+            ux = __dsub_rn(mx, ddx); uy = __dsub_rn(my, ddy);
+        }
+    }
 }
 }  // namespace
 
@@ -421,17 +466,8 @@ __global__ __launch_bounds__(TK_NT) void tk_finish(TkList l, int *ctl, int *prev
     for (int i = t; i < n; i += TK_NT) {
         const int id = i < kept ? l.ids[i] : n_id + (i - kept);      // the new points stand behind the kept ones, in list order (updateID)
         const float2 p = l.pts[i];
-        const double mx = __dadd_rn(__dmul_rn(cam.i11, (double)p.x), cam.i13), my = __dadd_rn(__dmul_rn(cam.i22, (double)p.y), cam.i23);
-        double ux = mx, uy = my;
-        if (cam.distort) {
-            for (int r = 0; r < 8; r++) {                // PinholeCamera::distortion (PinholeCamera.cc:646-662), every operation rounded on its own
-                const double x2 = __dmul_rn(ux, ux), y2 = __dmul_rn(uy, uy), xy = __dmul_rn(ux, uy), rho2 = __dadd_rn(x2, y2);
-                const double rad = __dadd_rn(__dmul_rn(cam.k1, rho2), __dmul_rn(__dmul_rn(cam.k2, rho2), rho2));
-                const double ddx = __dadd_rn(__dadd_rn(__dmul_rn(ux, rad), __dmul_rn(__dmul_rn(2.0, cam.p1), xy)), __dmul_rn(cam.p2, __dadd_rn(rho2, __dmul_rn(2.0, x2))));
-                const double ddy = __dadd_rn(__dadd_rn(__dmul_rn(uy, rad), __dmul_rn(__dmul_rn(2.0, cam.p2), xy)), __dmul_rn(cam.p1, __dadd_rn(rho2, __dmul_rn(2.0, y2))));
-                ux = __dsub_rn(mx, ddx); uy = __dsub_rn(my, ddy);
-            }
-        }
+        double ux, uy;
+        tk_undistort(cam, p, ux, uy);
         const float2 un = make_float2((float)ux, (float)uy);
         float2 v = make_float2(0.f, 0.f);
         if (has_prev && i < kept) {
@@ -449,21 +485,338 @@ __global__ __launch_bounds__(TK_NT) void tk_finish(TkList l, int *ctl, int *prev
     if (t == 0) { ctl[TC_PREVN] = n; ctl[TC_NID] = n_id + (n - min(kept, n)); l.hdr[0] = n; }
 }
 
+// ---- tk_clahe_lut: a workgroup per tile ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_clahe_lut(const unsigned char *img, int W, int H, int tw, int th, int limit, float scale, unsigned char *lut) {
+    __shared__ int s_h[256], s_ex;
+    const int t = threadIdx.x, x0 = blockIdx.x * tw, y0 = blockIdx.y * th, area = tw * th;
+    s_h[t] = 0;
+    if (t == 0) s_ex = 0;
+    __syncthreads();
+    for (int i = t; i < area; i += TK_NT) {                  // the padded tile through R: every read lies inside the image
+        const int lx = i % tw, ly = i / tw;
+        atomicAdd(&s_h[img[(size_t)tk_r(y0 + ly, H) * W + tk_r(x0 + lx, W)]], 1);      // integers: exact, so the order is free
+    }
+    __syncthreads();
+    int hst = s_h[t];
+    if (limit > 0) {
+        const long long e = tk_wave_sum((long long)max(hst - limit, 0));
+        if ((t & 63) == 0) atomicAdd(&s_ex, (int)e);
+    }
+    __syncthreads();
+    if (limit > 0) {
+        const int excess = s_ex, batch = excess / 256, residual = excess - 256 * batch;
+        hst = min(hst, limit) + batch;
+        if (residual > 0) { const int step = max(256 / residual, 1); hst += (t % step == 0 && t / step < residual) ? 1 : 0; }
+    }
+    s_h[t] = hst;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {                      // inclusive prefix sum of the 256 bins
+        const int v = t >= o ? s_h[t - o] : 0;
+        __syncthreads();
+        s_h[t] += v;
+        __syncthreads();
+    }
+    const float v = rintf(__fmul_rn((float)s_h[t], scale));
+    lut[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + t] = (unsigned char)fminf(fmaxf(v, 0.f), 255.f);
+}
+
+// ---- tk_clahe_remap -------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_TW * TK_TH) void tk_clahe_remap(const unsigned char *img, int W, int H, int tx, int ty, float inv_tw, float inv_th, const unsigned char *lut, unsigned char *out) {
+    const int x = blockIdx.x * TK_TW + threadIdx.x, y = blockIdx.y * TK_TH + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const float txf = __fsub_rn(__fmul_rn((float)x, inv_tw), 0.5f), tyf = __fsub_rn(__fmul_rn((float)y, inv_th), 0.5f);
+    const float fx1 = floorf(txf), fy1 = floorf(tyf);
+    const float xa = __fsub_rn(txf, fx1), ya = __fsub_rn(tyf, fy1), nxa = __fsub_rn(1.f, xa), nya = __fsub_rn(1.f, ya);
+    const int x1 = min(max((int)fx1, 0), tx - 1), x2 = min(max((int)fx1 + 1, 0), tx - 1), y1 = min(max((int)fy1, 0), ty - 1), y2 = min(max((int)fy1 + 1, 0), ty - 1);
+    const size_t at = (size_t)y * W + x;
+    const int v = img[at];
+    const float l11 = (float)lut[((size_t)y1 * tx + x1) * 256 + v], l12 = (float)lut[((size_t)y1 * tx + x2) * 256 + v];
+    const float l21 = (float)lut[((size_t)y2 * tx + x1) * 256 + v], l22 = (float)lut[((size_t)y2 * tx + x2) * 256 + v];
+    const float top = __fadd_rn(__fmul_rn(l11, nxa), __fmul_rn(l12, xa)), bot = __fadd_rn(__fmul_rn(l21, nxa), __fmul_rn(l22, xa));
+    const float r = rintf(__fadd_rn(__fmul_rn(top, nya), __fmul_rn(bot, ya)));
+    out[at] = (unsigned char)fminf(fmaxf(r, 0.f), 255.f);
+}
+
+// ---- rejectWithF ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+VD unsigned tk_mix(unsigned x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
+VD int tk_iu(int N, int p, int q) { return p * N - p * (p - 1) / 2 + (q - p); }      // upper triangle, p <= q
+VD int tk_is(int N, int p, int q) { return p <= q ? tk_iu(N, p, q) : tk_iu(N, q, p); }
+// cyclic Jacobi of the symmetric N x N matrix in column `lane` of M (upper triangle) -> eigenvectors in the columns of V (row-major N x N in column `lane`)
+template <int N> VD void tk_jacobi(double (*M)[TK_F_LANES], double (*V)[TK_F_LANES], int lane) {
+    for (int r = 0; r < N; r++) for (int c = 0; c < N; c++) V[r * N + c][lane] = r == c ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < TK_F_SWEEPS; sweep++)
+        for (int p = 0; p < N - 1; p++)
+            for (int q = p + 1; q < N; q++) {
+                const int ipq = tk_iu(N, p, q), ipp = tk_iu(N, p, p), iqq = tk_iu(N, q, q);
+                const double apq = M[ipq][lane];
+                if (apq == 0.0) continue;
+                const double app = M[ipp][lane], aqq = M[iqq][lane];
+                const double theta = __ddiv_rn(__dsub_rn(aqq, app), __dmul_rn(2.0, apq));
+                const double t = __ddiv_rn(theta < 0.0 ? -1.0 : 1.0, __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
+                const double c = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0))), s = __dmul_rn(t, c);
+                for (int r = 0; r < N; r++) {
+                    if (r == p || r == q) continue;
+                    const int irp = tk_is(N, r, p), irq = tk_is(N, r, q);
+                    const double arp = M[irp][lane], arq = M[irq][lane];
+                    M[irp][lane] = __dsub_rn(__dmul_rn(c, arp), __dmul_rn(s, arq));
+                    M[irq][lane] = __dadd_rn(__dmul_rn(s, arp), __dmul_rn(c, arq));
+                }
+                const double tap = __dmul_rn(t, apq);
+                M[ipp][lane] = __dsub_rn(app, tap); M[iqq][lane] = __dadd_rn(aqq, tap); M[ipq][lane] = 0.0;
+                for (int r = 0; r < N; r++) {
+                    const double vrp = V[r * N + p][lane], vrq = V[r * N + q][lane];
+                    V[r * N + p][lane] = __dsub_rn(__dmul_rn(c, vrp), __dmul_rn(s, vrq));
+                    V[r * N + q][lane] = __dadd_rn(__dmul_rn(s, vrp), __dmul_rn(c, vrq));
+                }
+            }
+}
+template <int N> VD int tk_smallest(double (*M)[TK_F_LANES], int lane) {
+    int at = 0;
+    double best = M[0][lane];
+    for (int i = 1; i < N; i++) { const double a = M[tk_iu(N, i, i)][lane]; if (a < best) { best = a; at = i; } }
+    return at;
+}
+// Hartley normalisation of the eight points (x in P[0 .. 7], y in P[8 .. 15], column `lane`), in place -> centroid and scale
+VD void tk_hartley(double (*P)[TK_F_LANES], int lane, double &cx, double &cy, double &s) {
+    double sx = 0.0, sy = 0.0, md = 0.0;
+    for (int j = 0; j < 8; j++) { sx = __dadd_rn(sx, P[j][lane]); sy = __dadd_rn(sy, P[8 + j][lane]); }
+    cx = __ddiv_rn(sx, 8.0); cy = __ddiv_rn(sy, 8.0);
+    for (int j = 0; j < 8; j++) {
+        const double dx = __dsub_rn(P[j][lane], cx), dy = __dsub_rn(P[8 + j][lane], cy);
+        md = __dadd_rn(md, __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy))));
+    }
+    md = __ddiv_rn(md, 8.0);
+    s = __ddiv_rn(__dsqrt_rn(2.0), md);
+    for (int j = 0; j < 8; j++) { P[j][lane] = __dmul_rn(__dsub_rn(P[j][lane], cx), s); P[8 + j][lane] = __dmul_rn(__dsub_rn(P[8 + j][lane], cy), s); }
+}
+// the score's inlier rule for the point pair (a, b) under F (row-major)
+VD bool tk_f_inlier(const double *F, float2 a, float2 b, double thr2) {
+    const double x = (double)a.x, y = (double)a.y, xp = (double)b.x, yp = (double)b.y;
+    const double lp0 = __dadd_rn(__dadd_rn(__dmul_rn(F[0], x), __dmul_rn(F[1], y)), F[2]), lp1 = __dadd_rn(__dadd_rn(__dmul_rn(F[3], x), __dmul_rn(F[4], y)), F[5]);
+    const double lp2 = __dadd_rn(__dadd_rn(__dmul_rn(F[6], x), __dmul_rn(F[7], y)), F[8]);
+    const double l0 = __dadd_rn(__dadd_rn(__dmul_rn(F[0], xp), __dmul_rn(F[3], yp)), F[6]), l1 = __dadd_rn(__dadd_rn(__dmul_rn(F[1], xp), __dmul_rn(F[4], yp)), F[7]);
+    const double d = __dadd_rn(__dadd_rn(__dmul_rn(xp, lp0), __dmul_rn(yp, lp1)), lp2), d2 = __dmul_rn(d, d);
+    const double e1 = __ddiv_rn(d2, __dadd_rn(__dmul_rn(lp0, lp0), __dmul_rn(lp1, lp1))), e2 = __ddiv_rn(d2, __dadd_rn(__dmul_rn(l0, l0), __dmul_rn(l1, l1)));
+    return e1 <= thr2 && e2 <= thr2;
+}
+}  // namespace
+
+// ---- tk_f_lift: one workgroup -----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_f_lift(const float2 *cur, const float2 *fwd, const unsigned char *status, const int *n_dev, int n_host, TkCam cam, double focal, double half_w, double half_h, TkF f) {
+    __shared__ unsigned char s_st[TK_MAXN];
+    const int t = threadIdx.x, n = min(n_dev ? *n_dev : n_host, TK_MAXN);
+    for (int i = t; i < n; i += TK_NT) s_st[i] = status[i] ? 1 : 0;
+    __syncthreads();
+    for (int i = t; i < n; i += TK_NT) {
+        if (!s_st[i]) continue;
+        int rank = 0;
+        for (int j = 0; j < i; j++) rank += s_st[j];         // list order; rank < n <= TK_MAXN, the rows of ua, ub, src
+        double ux, uy;
+        tk_undistort(cam, cur[i], ux, uy);
+        f.ua[rank] = make_float2((float)__dadd_rn(__dmul_rn(focal, ux), half_w), (float)__dadd_rn(__dmul_rn(focal, uy), half_h));
+        tk_undistort(cam, fwd[i], ux, uy);
+        f.ub[rank] = make_float2((float)__dadd_rn(__dmul_rn(focal, ux), half_w), (float)__dadd_rn(__dmul_rn(focal, uy), half_h));
+        f.src[rank] = i;
+    }
+    if (t == 0) {
+        int m = 0;
+        for (int j = 0; j < n; j++) m += s_st[j];
+        f.fctl[FC_M] = m;
+        *(unsigned long long *)(f.fctl + FC_BEST) = 0ull;
+    }
+}
+
+// ---- tk_f_hypotheses: a lane per hypothesis ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_F_LANES) void tk_f_hypotheses(TkF f, int K, unsigned seed) {
+    __shared__ double s_M[45][TK_F_LANES], s_V[81][TK_F_LANES];          // 64 512 bytes: a column per lane, so a lane's accesses never meet another's
+    const int lane = threadIdx.x, k = blockIdx.x * TK_F_LANES + lane, n = f.fctl[FC_M];
+    if (n < 8 || k >= K) return;
+    // sample: slot j in registers (every loop over the slots is unrolled, so S is never indexed by a run-time value)
+    int S[8];
+    const unsigned base = tk_mix(tk_mix(seed + 0x9e3779b9u) + (unsigned)k);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        int i = (int)(((unsigned long long)tk_mix(base + (unsigned)j) * (unsigned long long)n) >> 32);
+#pragma unroll
+        for (int step = 0; step < j; step++) {
+            bool dup = false;
+#pragma unroll
+            for (int e = 0; e < j; e++) dup |= S[e] == i;
+            i = dup ? (i + 1 == n ? 0 : i + 1) : i;
+        }
+        S[j] = i;
+    }
+    // the sample's points: side 1 in s_V[0 .. 15], side 2 in s_V[16 .. 31] (V is not needed before the Jacobi)
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const float2 a = f.ua[S[j]], b = f.ub[S[j]];         // S[j] < n <= TK_MAXN
+        s_V[j][lane] = (double)a.x; s_V[8 + j][lane] = (double)a.y; s_V[16 + j][lane] = (double)b.x; s_V[24 + j][lane] = (double)b.y;
+    }
+    double cx1, cy1, s1, cx2, cy2, s2;
+    tk_hartley(s_V, lane, cx1, cy1, s1);
+    tk_hartley(s_V + 16, lane, cx2, cy2, s2);
+    for (int e = 0; e < 45; e++) s_M[e][lane] = 0.0;
+    for (int j = 0; j < 8; j++) {
+        const double x = s_V[j][lane], y = s_V[8 + j][lane], xp = s_V[16 + j][lane], yp = s_V[24 + j][lane];
+        const double r[9] = {__dmul_rn(xp, x), __dmul_rn(xp, y), xp, __dmul_rn(yp, x), __dmul_rn(yp, y), yp, x, y, 1.0};
+        int e = 0;
+#pragma unroll
+        for (int p = 0; p < 9; p++)
+#pragma unroll
+            for (int q = p; q < 9; q++, e++) s_M[e][lane] = __dadd_rn(s_M[e][lane], __dmul_rn(r[p], r[q]));
+    }
+    tk_jacobi<9>(s_M, s_V, lane);
+    double Fh[9];
+    {
+        const int at = tk_smallest<9>(s_M, lane);
+#pragma unroll
+        for (int c = 0; c < 9; c++) Fh[c] = s_V[c * 9 + at][lane];
+    }
+    // rank 2: the same Jacobi at size 3 on G = Fh^T Fh
+#pragma unroll
+    for (int p = 0; p < 3; p++)
+#pragma unroll
+        for (int q = p; q < 3; q++) {
+            double acc = 0.0;
+#pragma unroll
+            for (int r = 0; r < 3; r++) acc = __dadd_rn(acc, __dmul_rn(Fh[r * 3 + p], Fh[r * 3 + q]));
+            s_M[tk_iu(3, p, q)][lane] = acc;
+        }
+    tk_jacobi<3>(s_M, s_V, lane);
+    {
+        const int at = tk_smallest<3>(s_M, lane);
+        const double v0 = s_V[at][lane], v1 = s_V[3 + at][lane], v2 = s_V[6 + at][lane];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const double w = __dadd_rn(__dadd_rn(__dmul_rn(Fh[r * 3], v0), __dmul_rn(Fh[r * 3 + 1], v1)), __dmul_rn(Fh[r * 3 + 2], v2));
+            Fh[r * 3] = __dsub_rn(Fh[r * 3], __dmul_rn(w, v0)); Fh[r * 3 + 1] = __dsub_rn(Fh[r * 3 + 1], __dmul_rn(w, v1)); Fh[r * 3 + 2] = __dsub_rn(Fh[r * 3 + 2], __dmul_rn(w, v2));
+        }
+    }
+    // F = T'^T Fh T
+    const double t1x = __dmul_rn(s1, cx1), t1y = __dmul_rn(s1, cy1), t2x = __dmul_rn(s2, cx2), t2y = __dmul_rn(s2, cy2);
+    double B[9], F[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        B[r * 3] = __dmul_rn(Fh[r * 3], s1); B[r * 3 + 1] = __dmul_rn(Fh[r * 3 + 1], s1);
+        B[r * 3 + 2] = __dsub_rn(__dsub_rn(Fh[r * 3 + 2], __dmul_rn(Fh[r * 3], t1x)), __dmul_rn(Fh[r * 3 + 1], t1y));
+    }
+    bool ok = isfinite(s1) && isfinite(s2);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        F[c] = __dmul_rn(s2, B[c]); F[3 + c] = __dmul_rn(s2, B[3 + c]);
+        F[6 + c] = __dsub_rn(__dsub_rn(B[6 + c], __dmul_rn(t2x, B[c])), __dmul_rn(t2y, B[3 + c]));
+    }
+#pragma unroll
+    for (int e = 0; e < 9; e++) { ok = ok && isfinite(F[e]); f.F[(size_t)k * 9 + e] = F[e]; }      // k < K <= TK_F_MAXK rows
+    f.valid[k] = ok ? 1 : 0;
+}
+
+// ---- tk_f_score: a wave per hypothesis --------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * TK_F_WAVES) void tk_f_score(TkF f, int K, double thr2) {
+    const int lane = threadIdx.x & 63, k = blockIdx.x * TK_F_WAVES + (threadIdx.x >> 6), n = f.fctl[FC_M];
+    if (n < 8 || k >= K || !f.valid[k]) return;             // the whole wave
+    double F[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) F[e] = f.F[(size_t)k * 9 + e];
+    int cnt = 0;
+    for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        const bool in = i < n && tk_f_inlier(F, f.ua[i], f.ub[i], thr2);
+        cnt += __popcll(__ballot(in));
+    }
+    if (lane == 0) atomicMax((unsigned long long *)(f.fctl + FC_BEST), ((unsigned long long)(cnt + 1) << 32) | (unsigned long long)(unsigned)(K - 1 - k));
+}
+
+// ---- tk_f_apply: one workgroup ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_f_apply(TkF f, int K, double thr2, unsigned char *status) {
+    const int t = threadIdx.x, n = min(f.fctl[FC_M], TK_MAXN);
+    const unsigned long long word = *(const unsigned long long *)(f.fctl + FC_BEST);
+    if (n < 8 || word == 0ull) {                             // nothing is rejected
+        if (t < TK_F_RES) f.res[t] = t == 0 ? -1.0 : t == 1 ? (double)n : 0.0;
+        return;
+    }
+    const int k = min(max(K - 1 - (int)(unsigned)(word & 0xffffffffull), 0), K - 1);
+    double F[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) F[e] = f.F[(size_t)k * 9 + e];
+    for (int i = t; i < n; i += TK_NT)
+        if (!tk_f_inlier(F, f.ua[i], f.ub[i], thr2)) status[f.src[i]] = 0;      // src < the list's rows
+    if (t == 0) { f.res[0] = (double)k; f.res[1] = (double)((long long)(word >> 32) - 1); }
+    if (t < 9) f.res[2 + t] = F[t];
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------------
 namespace {
 int tk_sort_bits(size_t cap) { int b = 1; while (((size_t)1 << b) <= cap) b++; return b; }      // the fill pattern (all ones) sorts behind every pixel index
 
 // image (row stride in bytes) -> level 0 .. `levels` of a pyramid, on the stream. The rows go through the pyramid's pinned staging (every entry point ends with
 // a wait for the stream, so the staging is free again): a copy from pageable memory, row by row, cost 2.6 ms per frame at 1226 x 370
-int tk_build(vilf_handle *h, TkPyr &P, unsigned char *stage, const unsigned char *img, int row_stride, int levels) {
+int tk_upload(vilf_handle *h, const TkPyr &P, unsigned char *dst, unsigned char *stage, const unsigned char *img, int row_stride) {
     const size_t W = (size_t)P.w[0], H = (size_t)P.h[0];
     if ((size_t)row_stride == W) std::memcpy(stage, img, W * H);
     else for (size_t y = 0; y < H; y++) std::memcpy(stage + y * W, img + y * (size_t)row_stride, W);
-    HIPCHECK(h, hipMemcpyAsync(P.lv[0], stage, W * H, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, hipMemcpyAsync(dst, stage, W * H, hipMemcpyHostToDevice, h->stream));
+    return VILF_OK;
+}
+int tk_levels(vilf_handle *h, TkPyr &P, int levels) {
     for (int L = 1; L <= levels; L++)
         hipLaunchKernelGGL(tk_pyr_down, dim3((P.w[L] + TK_TW - 1) / TK_TW, (P.h[L] + TK_TH - 1) / TK_TH), dim3(TK_TW, TK_TH), 0, h->stream, P.lv[L - 1], P.w[L - 1], P.h[L - 1], P.lv[L], P.w[L], P.h[L]);
     HIPCHECK(h, hipGetLastError());
     return VILF_OK;
+}
+int tk_build(vilf_handle *h, TkPyr &P, unsigned char *stage, const unsigned char *img, int row_stride, int levels) {
+    const int rc = tk_upload(h, P, P.lv[0], stage, img, row_stride);
+    return rc != VILF_OK ? rc : tk_levels(h, P, levels);
+}
+// CLAHE of the W x H image at src -> dst (both on the device, rows tight) with the configured clip and tiles; the geometry and the integer limit of the text
+int tk_clahe(vilf_handle *h, TrackCtx *c, const unsigned char *src, unsigned char *dst) {
+    const int W = c->p.width, H = c->p.height, tx = c->fe.clahe_tiles_x, ty = c->fe.clahe_tiles_y;
+    const bool fits = W % tx == 0 && H % ty == 0;
+    const int Wp = fits ? W : W + (tx - W % tx), Hp = fits ? H : H + (ty - H % ty), tw = Wp / tx, th = Hp / ty, area = tw * th;      // area <= 4 W H <= 2^30
+    const int limit = c->fe.clahe_clip > 0 ? std::max(1, (int)((c->fe.clahe_clip * (double)area) / 256.0)) : 0;
+    hipLaunchKernelGGL(tk_clahe_lut, dim3(tx, ty), dim3(TK_NT), 0, h->stream, src, W, H, tw, th, limit, 255.f / (float)area, c->lut.as<unsigned char>());
+    hipLaunchKernelGGL(tk_clahe_remap, dim3((W + TK_TW - 1) / TK_TW, (H + TK_TH - 1) / TK_TH), dim3(TK_TW, TK_TH), 0, h->stream, src, W, H, tx, ty, 1.f / (float)tw, 1.f / (float)th,
+                       c->lut.as<unsigned char>(), dst);
+    HIPCHECK(h, hipGetLastError());
+    return VILF_OK;
+}
+// the arrays of rejectWithF inside fmem
+enum : size_t { TKF_UA = 0, TKF_UB = TKF_UA + TK_MAXN * 8, TKF_SRC = TKF_UB + TK_MAXN * 8, TKF_CTL = TKF_SRC + TK_MAXN * 4, TKF_F = TKF_CTL + 64,
+                TKF_VALID = TKF_F + (size_t)TK_F_MAXK * 72, TKF_RES = TKF_VALID + (size_t)TK_F_MAXK * 4, TKF_BYTES = TKF_RES + TK_F_RES * 8 };
+static_assert(TKF_CTL % 8 == 0 && TKF_F % 8 == 0 && TKF_RES % 8 == 0, "the 64-bit words of fmem are aligned");
+TkF tk_f(TrackCtx *c) {
+    char *b = c->fmem.as<char>();
+    TkF f;
+    f.ua = (float2 *)(b + TKF_UA); f.ub = (float2 *)(b + TKF_UB); f.src = (int *)(b + TKF_SRC); f.fctl = (int *)(b + TKF_CTL);
+    f.F = (double *)(b + TKF_F); f.valid = (int *)(b + TKF_VALID); f.res = (double *)(b + TKF_RES);
+    return f;
+}
+TkCam tk_cam(const vilf_track_params &p) {
+    TkCam cam;
+    cam.i11 = 1.0 / p.fx; cam.i13 = -p.cx / p.fx; cam.i22 = 1.0 / p.fy; cam.i23 = -p.cy / p.fy;
+    cam.k1 = p.k1; cam.k2 = p.k2; cam.p1 = p.p1; cam.p2 = p.p2;
+    cam.distort = (p.k1 != 0.0 || p.k2 != 0.0 || p.p1 != 0.0 || p.p2 != 0.0) ? 1 : 0;
+    return cam;
+}
+// rejectWithF on the pairs (cur[i], fwd[i]) whose status is set (the count on the device, or n_host): the outliers' status bytes are cleared. Fixed grids; the
+// kernels read the survivors' count themselves and leave at once when it is below 8
+int tk_reject(vilf_handle *h, TrackCtx *c, const float2 *cur, const float2 *fwd, unsigned char *status, const int *n_dev, int n_host) {
+    const TkF f = tk_f(c);
+    const int K = c->fe.n_hypotheses;
+    const double thr2 = c->fe.f_threshold * c->fe.f_threshold;
+    hipLaunchKernelGGL(tk_f_lift, dim3(1), dim3(TK_NT), 0, h->stream, cur, fwd, status, n_dev, n_host, tk_cam(c->p), c->fe.focal_length, c->p.width / 2.0, c->p.height / 2.0, f);
+    hipLaunchKernelGGL(tk_f_hypotheses, dim3((K + TK_F_LANES - 1) / TK_F_LANES), dim3(TK_F_LANES), 0, h->stream, f, K, c->fe.seed);
+    hipLaunchKernelGGL(tk_f_score, dim3((K + TK_F_WAVES - 1) / TK_F_WAVES), dim3(64 * TK_F_WAVES), 0, h->stream, f, K, thr2);
+    hipLaunchKernelGGL(tk_f_apply, dim3(1), dim3(TK_NT), 0, h->stream, f, K, thr2, status);
+    HIPCHECK(h, hipGetLastError());
+    return VILF_OK;
+}
+vilf_track_frontend tk_fe_defaults() {
+    vilf_track_frontend fe;
+    std::memset(&fe, 0, sizeof(fe));
+    fe.clahe_clip = 3.0; fe.clahe_tiles_x = 8; fe.clahe_tiles_y = 8; fe.f_threshold = 1.0; fe.focal_length = 460.0; fe.n_hypotheses = 512;
+    return fe;
 }
 // mask, response, candidates, the two sorts, the greedy acceptance: ctl holds kept / n_max / candidate count 0 / lambda max 0, l.pts the kept points
 int tk_detect(vilf_handle *h, TrackCtx *c, const unsigned char *img, int *ctl, TkList l, int list_cap) {
@@ -507,6 +860,7 @@ extern "C" int vilf_track_init(vilf_handle *h, const vilf_track_params *p) {
     vilf_track_release(h);
     TrackCtx *c = new TrackCtx();
     c->p = *p;
+    c->fe = tk_fe_defaults();
     c->ncell = (size_t)p->width * p->height;
     bool ok = true;
     for (int k = 0; k < 4 && ok; k++) {
@@ -528,7 +882,7 @@ extern "C" int vilf_track_init(vilf_handle *h, const vilf_track_params *p) {
          c->tmpctl.ensure(TC_INTS * 4) && c->prev_ids.ensure(TK_MAXN * 4) && c->prev_un.ensure(TK_MAXN * 8) && c->fwd.ensure(TK_MAXN * 8) && c->status.ensure(TK_MAXN) &&
          c->lkpts.ensure(TK_MAXN * 8) && c->mask.ensure(n) && c->lam.ensure(n * 8) && c->cidx.ensure(n * 4) && c->cidx2.ensure(n * 4) && c->cval.ensure(n * 4) && c->key.ensure(n * 8) &&
          c->key2.ensure(n * 8) && c->val.ensure(n * 4) && c->val2.ensure(n * 4) && c->temp.ensure(std::max(vilf_sort_temp_bytes(n, 8), vilf_sort_temp_bytes(n, 4)) + 256) &&
-         c->pin.ensure(tk_list_bytes(TK_MAXN));
+         c->pin.ensure(tk_list_bytes(TK_MAXN)) && c->raw.ensure(n) && c->lut.ensure((size_t)VILF_TRACK_MAX_TILES * 256) && c->fmem.ensure(TKF_BYTES);
     if (!ok) { c->release(); delete c; h->err = "hipMalloc failed (feature tracker)"; return VILF_ERR_DEVICE; }
     h->trk = c;
     return vilf_track_reset(h);
@@ -554,32 +908,42 @@ extern "C" int vilf_track_read_image(vilf_handle *h, const unsigned char *img, i
     if (!img || row_stride < c->p.width) { h->err = "vilf_track_read_image: null image or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
     HIPCHECK(h, hipSetDevice(h->device));
     const bool prof = h->profiling != 0;
-    if (prof) for (int i = 0; i < TK_STAGES; i++) { c->ms[i] = 0; c->launches[i] = 0; }      // the stages of the last frame
-    hipEvent_t ev[TK_STAGES + 1];
+    if (prof) vilf_track_profile_reset(h);                  // the stages of the last frame
+    hipEvent_t ev[TK_STAGES + 1], fev[2 * TK_FE_STAGES];
+    const bool eq = c->fe.equalize != 0, rej = c->fe.reject_f != 0 && c->frames > 0;
     auto mark = [&](int k) { if (prof) ev[k] = vilf_prof_event(h); };
     TkPyr &cur = c->pyr[c->cur], &nxt = c->pyr[c->cur ^ 1];
     TkList lc = tk_list(c->list[c->lcur].p, TK_MAXN), ln = tk_list(c->list[c->lcur ^ 1].p, TK_MAXN);
     int *ctl = c->ctl.as<int>();
     const long long md = c->p.min_dist;
     mark(0);
-    { const int rc = tk_build(h, nxt, (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride, nxt.lmax); if (rc != VILF_OK) return rc; }
+    if (eq) {                                                // the raw image into its own buffer, the equalised one straight into level 0
+        { const int rc = tk_upload(h, nxt, c->raw.as<unsigned char>(), (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride); if (rc != VILF_OK) return rc; }
+        if (prof) fev[0] = vilf_prof_event(h);
+        { const int rc = tk_clahe(h, c, c->raw.as<unsigned char>(), nxt.lv[0]); if (rc != VILF_OK) return rc; }
+        if (prof) fev[1] = vilf_prof_event(h);
+        { const int rc = tk_levels(h, nxt, nxt.lmax); if (rc != VILF_OK) return rc; }
+    } else { const int rc = tk_build(h, nxt, (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride, nxt.lmax); if (rc != VILF_OK) return rc; }
     mark(1);
     if (c->frames > 0)
         hipLaunchKernelGGL(tk_lk, dim3((c->p.max_cnt + TK_LK_WAVES - 1) / TK_LK_WAVES), dim3(64 * TK_LK_WAVES), 0, h->stream, cur, nxt, lc.pts, ctl + TC_N, 0, c->fwd.as<float2>(), c->status.as<unsigned char>(), 1);
+    if (rej) {                                               // between the inBorder drop (LK's status) and setMask, which reads the same status bytes
+        if (prof) fev[2] = vilf_prof_event(h);
+        { const int rc = tk_reject(h, c, lc.pts, c->fwd.as<float2>(), c->status.as<unsigned char>(), ctl + TC_N, 0); if (rc != VILF_OK) return rc; }
+        if (prof) fev[3] = vilf_prof_event(h);
+    }
     mark(2);
     hipLaunchKernelGGL(tk_setmask, dim3(1), dim3(TK_NT), 0, h->stream, lc, c->fwd.as<float2>(), c->status.as<unsigned char>(), ln, ctl, c->p.max_cnt, md * md);
     HIPCHECK(h, hipGetLastError());
     mark(3);
     { const int rc = tk_detect(h, c, nxt.lv[0], ctl, ln, c->p.max_cnt); if (rc != VILF_OK) return rc; }
     mark(4);
-    TkCam cam;
-    cam.i11 = 1.0 / c->p.fx; cam.i13 = -c->p.cx / c->p.fx; cam.i22 = 1.0 / c->p.fy; cam.i23 = -c->p.cy / c->p.fy;
-    cam.k1 = c->p.k1; cam.k2 = c->p.k2; cam.p1 = c->p.p1; cam.p2 = c->p.p2;
-    cam.distort = (c->p.k1 != 0.0 || c->p.k2 != 0.0 || c->p.p1 != 0.0 || c->p.p2 != 0.0) ? 1 : 0;
-    hipLaunchKernelGGL(tk_finish, dim3(1), dim3(TK_NT), 0, h->stream, ln, ctl, c->prev_ids.as<int>(), c->prev_un.as<float2>(), cam, stamp - c->t_prev, c->frames > 0 ? 1 : 0);
+    hipLaunchKernelGGL(tk_finish, dim3(1), dim3(TK_NT), 0, h->stream, ln, ctl, c->prev_ids.as<int>(), c->prev_un.as<float2>(), tk_cam(c->p), stamp - c->t_prev, c->frames > 0 ? 1 : 0);
     HIPCHECK(h, hipGetLastError());
     mark(5);
     if (prof) for (int k = 0; k < TK_STAGES; k++) vilf_prof_span(h, ev[k], ev[k + 1], &c->ms[k], &c->launches[k]);
+    if (prof && eq) vilf_prof_span(h, fev[0], fev[1], &c->fe_ms[0], &c->fe_launches[0]);
+    if (prof && rej) vilf_prof_span(h, fev[2], fev[3], &c->fe_ms[1], &c->fe_launches[1]);
     HIPCHECK(h, vilf_copy_sync(h, c->pin.p, ln.hdr, tk_list_bytes(TK_MAXN), hipMemcpyDeviceToHost));
     if (prof) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
     c->cur ^= 1; c->lcur ^= 1; c->frames++; c->t_prev = stamp;
@@ -669,5 +1033,69 @@ extern "C" int vilf_track_profile(vilf_handle *h, double ms_out[5], long launche
     if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
     { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
     for (int i = 0; i < TK_STAGES; i++) { ms_out[i] = h->trk ? h->trk->ms[i] : 0.0; launches_out[i] = h->trk ? h->trk->launches[i] : 0; }
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_configure(vilf_handle *h, const vilf_track_frontend *fe) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_configure");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!fe) { h->err = "vilf_track_configure: null parameters"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (fe->clahe_tiles_x < 1 || fe->clahe_tiles_y < 1 || (long long)fe->clahe_tiles_x * fe->clahe_tiles_y > VILF_TRACK_MAX_TILES || !std::isfinite(fe->clahe_clip) || fe->clahe_clip < 0 ||
+        !std::isfinite(fe->f_threshold) || !(fe->f_threshold > 0) || !std::isfinite(fe->focal_length) || !(fe->focal_length > 0) || fe->n_hypotheses < 1 ||
+        fe->n_hypotheses > VILF_TRACK_MAX_HYPOTHESES) {
+        h->err = "vilf_track_configure: 1 <= tiles, tiles_x * tiles_y <= VILF_TRACK_MAX_TILES, a finite clip >= 0, a positive finite threshold and focal length, 1 <= n_hypotheses <= VILF_TRACK_MAX_HYPOTHESES";
+        return VILF_ERR_INVALID_ARGUMENT;
+    }
+    c->fe = *fe;
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_clahe(vilf_handle *h, const unsigned char *img, int row_stride, unsigned char *out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_clahe");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!img || !out || row_stride < c->p.width) { h->err = "vilf_track_clahe: null pointer or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
+    HIPCHECK(h, hipSetDevice(h->device));
+    TkPyr &A = c->pyr[2], &B = c->pyr[3];                     // the stateless calls' pyramids: the image into level 0 of one, the result into level 0 of the other
+    { const int rc = tk_upload(h, A, A.lv[0], (unsigned char *)c->stage[2].p, img, row_stride); if (rc != VILF_OK) return rc; }
+    { const int rc = tk_clahe(h, c, A.lv[0], B.lv[0]); if (rc != VILF_OK) return rc; }
+    HIPCHECK(h, vilf_copy_sync(h, out, B.lv[0], c->ncell, hipMemcpyDeviceToHost));
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_reject_f(vilf_handle *h, const float *cur_pts, const float *forw_pts, int n, unsigned char *status_out, double F_out[9], int *best_out, int *n_inliers_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_reject_f");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (n < 0 || n > TK_MAXN || !F_out || !best_out || !n_inliers_out || (n > 0 && (!cur_pts || !forw_pts || !status_out))) {
+        h->err = "vilf_track_reject_f: null pointer, n < 0 or n > VILF_MAX_FEATURES"; return VILF_ERR_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < 2 * n; i++)
+        if (!std::isfinite(cur_pts[i]) || !std::isfinite(forw_pts[i])) { h->err = "vilf_track_reject_f: a coordinate that is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (n >= 8) {
+        HIPCHECK(h, hipSetDevice(h->device));
+        // lkpts, fwd and status are scratch of a single call (a frame's LK or vilf_track_lk): nothing of the tracked state lives in them between calls
+        HIPCHECK(h, hipMemcpyAsync(c->lkpts.p, cur_pts, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(h, hipMemcpyAsync(c->fwd.p, forw_pts, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(h, hipMemsetAsync(c->status.p, 1, (size_t)n, h->stream));
+        { const int rc = tk_reject(h, c, c->lkpts.as<float2>(), c->fwd.as<float2>(), c->status.as<unsigned char>(), nullptr, n); if (rc != VILF_OK) return rc; }
+        double res[TK_F_RES];
+        HIPCHECK(h, hipMemcpyAsync(status_out, c->status.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(h, vilf_copy_sync(h, res, tk_f(c).res, sizeof(res), hipMemcpyDeviceToHost));
+        *best_out = (int)res[0]; *n_inliers_out = (int)res[1];
+        for (int e = 0; e < 9; e++) F_out[e] = res[2 + e];
+        return VILF_OK;
+    }
+    for (int i = 0; i < n; i++) status_out[i] = 1;           // fewer than 8 pairs: rejectWithF does nothing (:385)
+    for (int e = 0; e < 9; e++) F_out[e] = 0.0;
+    *best_out = -1; *n_inliers_out = n;
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_profile_frontend(vilf_handle *h, double ms_out[2], long launches_out[2]) {
+    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
+    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
+    for (int i = 0; i < TK_FE_STAGES; i++) { ms_out[i] = h->trk ? h->trk->fe_ms[i] : 0.0; launches_out[i] = h->trk ? h->trk->fe_launches[i] : 0; }
     return VILF_OK;
 }

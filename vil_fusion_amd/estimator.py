@@ -685,15 +685,22 @@ TRACK_STAGES = ("pyramid", "lk", "set_mask", "detect", "undistort")
 
 class FeatureTracker:
     """Host mirror of FeatureTracker (feature_tracker/feature_tracker.cpp) over the device tracker of a BackendSolver handle (vilf_track_*): the camera half of the
-    feature-tracker node. Images are (height, width) uint8 arrays; camera = (fx, fy, cx, cy, k1, k2, p1, p2). The arithmetic is the contract in include/vilfusion.h."""
+    feature-tracker node. Images are (height, width) uint8 arrays; camera = (fx, fy, cx, cy, k1, k2, p1, p2). The arithmetic is the contract in include/vilfusion.h.
+    equalize = True puts CLAHE (clahe = (clip, tiles_x, tiles_y)) in front of everything; f_threshold = a number of pixels turns rejectWithF on (focal_length,
+    n_hypotheses, seed). With both at their defaults the tracker is never configured and runs as it did before these steps existed."""
 
-    def __init__(self, solver, width, height, camera, max_cnt=200, min_dist=20):
+    def __init__(self, solver, width, height, camera, max_cnt=200, min_dist=20, equalize=False, f_threshold=None, focal_length=460.0, clahe=(3.0, 8, 8),
+                 n_hypotheses=512, seed=0):
         self.s, self._L = solver, solver._L
         self.width, self.height, self.max_cnt, self.min_dist = int(width), int(height), int(max_cnt), int(min_dist)
         self.camera = tuple(float(v) for v in camera)
         assert len(self.camera) == 8, "camera = (fx, fy, cx, cy, k1, k2, p1, p2)"
         self.params = abi.TrackParams(self.width, self.height, self.max_cnt, self.min_dist, *self.camera)
         self.s._check(self._L.vilf_track_init(self.s._h, C.byref(self.params)), "vilf_track_init")
+        self.frontend = abi.TrackFrontend(int(bool(equalize)), float(clahe[0]), int(clahe[1]), int(clahe[2]), int(f_threshold is not None),
+                                          1.0 if f_threshold is None else float(f_threshold), float(focal_length), int(n_hypotheses), int(seed))
+        if (bool(equalize), f_threshold, float(focal_length), tuple(clahe), int(n_hypotheses), int(seed)) != (False, None, 460.0, (3.0, 8, 8), 512, 0):
+            self.s._check(self._L.vilf_track_configure(self.s._h, C.byref(self.frontend)), "vilf_track_configure")
         self._clear()
 
     def _clear(self):
@@ -758,6 +765,28 @@ class FeatureTracker:
         n = C.c_int(0)
         self.s._check(self._L.vilf_track_detect(self.s._h, self._u8(a), self._fp(kp), len(kp), int(n_max), self._fp(out), C.byref(n)), "vilf_track_detect")
         return out[:n.value].copy()
+
+    def clahe(self, img):
+        """CLAHE of an image with the configured clip and tiles (stateless)"""
+        a = self._img(img)
+        out = np.zeros((self.height, self.width), dtype=np.uint8)
+        self.s._check(self._L.vilf_track_clahe(self.s._h, self._u8(a), int(a.strides[0]), self._u8(out)), "vilf_track_clahe")
+        return out
+
+    def reject_f(self, cur_pts, forw_pts):
+        """rejectWithF on point pairs (stateless) -> (status (n,) uint8, best, n_inliers, F (9,) float64); best = -1: nothing rejected"""
+        a, b = (np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 2) for p in (cur_pts, forw_pts))
+        assert len(a) == len(b)
+        st, F = np.zeros(max(len(a), 1), dtype=np.uint8), np.zeros(9)
+        best, n_in = C.c_int(0), C.c_int(0)
+        self.s._check(self._L.vilf_track_reject_f(self.s._h, self._fp(a), self._fp(b), len(a), self._u8(st), abi.dptr(F), C.byref(best), C.byref(n_in)), "vilf_track_reject_f")
+        return st[:len(a)], best.value, n_in.value, F
+
+    def profile_frontend(self):
+        """ms and launches of CLAHE and rejectWithF in the last readImage (vilf_set_profiling)"""
+        ms, cnt = (C.c_double * 2)(), (C.c_long * 2)()
+        self.s._check(self._L.vilf_track_profile_frontend(self.s._h, ms, cnt), "vilf_track_profile_frontend")
+        return {"clahe": (ms[0], cnt[0]), "reject_f": (ms[1], cnt[1])}
 
     def feature_message(self, depths=None):
         """the rows with track_cnt > 1 as {id: (x, y, 1, u, v, vx, vy, depth)} (feature_tracker_node.cpp:311-336): what SlidingWindowEstimator.process_image takes.

@@ -24,6 +24,7 @@ EXPORTED = [
     "vilf_icp_get_history", "vilf_icp_get_search", "vilf_get_profile_icp",
     "vilf_icp_global_map", "vilf_icp_global_map_size", "vilf_icp_global_map_get", "vilf_get_profile_icp_map",
     "vilf_track_init", "vilf_track_reset", "vilf_track_read_image", "vilf_track_get", "vilf_track_pyramid", "vilf_track_lk", "vilf_track_detect", "vilf_track_profile",
+    "vilf_track_configure", "vilf_track_clahe", "vilf_track_reject_f", "vilf_track_profile_frontend",
 ]
 
 
@@ -144,6 +145,10 @@ def lib():
     L.vilf_track_lk.argtypes = [vp, u8p, u8p, fpp, C.c_int, fpp, u8p]
     L.vilf_track_detect.argtypes = [vp, u8p, fpp, C.c_int, C.c_int, fpp, ip]
     L.vilf_track_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_track_configure.argtypes = [vp, C.POINTER(abi.TrackFrontend)]
+    L.vilf_track_clahe.argtypes = [vp, u8p, C.c_int, u8p]
+    L.vilf_track_reject_f.argtypes = [vp, fpp, fpp, C.c_int, u8p, abi.c_double_p, ip, ip]
+    L.vilf_track_profile_frontend.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 
