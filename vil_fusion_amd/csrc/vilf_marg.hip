@@ -475,7 +475,9 @@ __device__ __forceinline__ void marg_prepare_body(const VbBatch &b, const VbMarg
     __syncthreads();
     MG_STAMP(0, 15);
     // ---- dense-variable normal equations: owner-computes over the (nd x nd) entries ---------------------------------------
-    {
+    // MARGIN_OLD only: SECOND_NEW has neither factor, and its prior need not hold Pose[0] / Pose[1] (the prior a MARGIN_OLD step leaves behind with USE_LIDAR_CONST starts at
+    // Pose[1]), so their offsets may be -1 there: the LiDAR scatter then added its zeros in front of this window's Hd / gd — in front of the allocation for window 0.
+    if (mode == 0) {
         const int opose0 = s_off_pose[0], opose1 = s_off_pose[1], osb0 = s_off_sb[0], osb1 = s_off_sb[1], oex = s_off_ex;
         // IMU block variable offsets (local 30 columns): P0 6, SB0 9, P1 6, SB1 9
         auto imu_off = [&](int c) -> int { if (c < 6) return opose0 + c; if (c < 15) return osb0 + (c - 6); if (c < 21) return opose1 + (c - 15); return osb1 < 0 ? -1 : osb1 + (c - 21); };
