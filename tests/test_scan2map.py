@@ -45,9 +45,22 @@ def test_oracle_knn5_and_plane_line_fits(oracle, opts):
     L.vilo_s2m_associate_surf(mp.ctypes.data_as(C.POINTER(C.c_float)), 4000, pts.ctypes.data_as(C.POINTER(C.c_float)), 200, abi.dptr(pose), valid.ctypes.data_as(C.POINTER(C.c_uint8)), abi.dptr(nrm), abi.dptr(d))
     ok = valid == 1
     assert ok.mean() > 0.5
-    # the 5x3 fit A n = -1 on a plane through the origin is ill-posed by construction (d = 1/|n| -> tiny): F-LOAM relies on the
-    # map being far from the origin; here just check the residual test was honoured
     assert np.all(np.isfinite(nrm[ok]))
+    # ... and against the independent restatement of the reference's text (tests/s2m_reference.py): the same five indices and float distances bit for bit, the same
+    # verdict wherever it is not inside its own rounding error, and the plane within the derived tolerance. (The fit A n = -1 on a ground through the origin is
+    # ill-conditioned by construction — d = 1/|n| is tiny — which the tolerance's condition number accounts for.)
+    import s2m_reference as R
+    ref = R.associate(mp, pts, pose, True)
+    assert np.array_equal(idx, ref["idx"]) and d5.tobytes() == ref["d2"].tobytes()
+    rb = ref["robust"] & (ref["d2"][:, 4] < 1)
+    assert rb.sum() > 100 and np.array_equal(valid[rb] * 2, ref["kind"][rb])
+    checked = 0
+    for i in np.nonzero(rb & (ref["kind"] == 2))[0]:
+        tol, _ = R.rule_tolerances(mp[ref["idx"][i], :3].astype(np.float64), True)
+        if np.isfinite(tol):
+            assert R.record_error(2, np.array([*nrm[i], d[i]]), ref["rec"][i]) <= tol
+            checked += 1
+    assert checked > 50
 
 
 def test_oracle_scan2map_tracks_the_truth(oracle, opts):

@@ -1651,8 +1651,10 @@ struct AssocArgs {
 #define S2M_KIND_TIE 3      // fkind of a query whose 5-NN met exactly equal distances: b_associate_ties redoes it in the reference's order (b_solve skips kinds other than 1, 2)
 // one thread per query point of one stream. Edge queries write records [0, n_ds_edge), surf queries [n_ds_edge, n_ds_edge + n_ds_surf).
 // one query i of the cloud described by a. TIES: the exact redo of a query that met equal distances
-template <bool TIES>
-__device__ __forceinline__ void assoc_one(const AssocArgs &a, int i, int sid, bool stamp) {
+// DBG (vilf_debug_s2m_associate only; production instantiates DBG = false and passes no pointer): the query's neighbour list as the search left it, per record slot
+struct AssocDbg { int *pos; float *nb; float *d2; };      // pos[5]: position in the searched array (the original index for the sorted copy of an unordered map), -1 = none; nb[15]: xyz of the five; d2[5]
+template <bool TIES, bool DBG = false>
+__device__ __forceinline__ void assoc_one(const AssocArgs &a, int i, int sid, bool stamp, const AssocDbg *dbg = nullptr) {
     const int slot = a.is_surf ? a.n_ds_edge[sid] + i : i;
     int *fk = a.fkind_all + (size_t)sid * a.capq + slot;
     const double *pose = a.pose_all + 24 * sid;
@@ -1681,6 +1683,17 @@ __device__ __forceinline__ void assoc_one(const AssocArgs &a, int i, int sid, bo
 #ifdef VILF_STAMPS
     st1_ = __builtin_readcyclecounter();
 #endif
+    if (DBG) {
+        const size_t o = ((size_t)sid * a.capq + slot) * 5;
+        for (int k = 0; k < 5; k++) {
+            const float qn = __int_as_float(0x7fc00000);
+            float4 m = make_float4(qn, qn, qn, qn);
+            if (idx[k] >= 0) m = sorted[idx[k]];
+            dbg->pos[o + k] = idx[k] < 0 ? -1 : (a.w_is_index ? __float_as_int(m.w) : idx[k]);
+            dbg->nb[3 * (o + k)] = m.x; dbg->nb[3 * (o + k) + 1] = m.y; dbg->nb[3 * (o + k) + 2] = m.z;
+            dbg->d2[o + k] = d2[k];
+        }
+    }
     assoc_fit_write(sorted, idx, nmap >= 5 && d2[4] < 1.0f, a.is_surf, p, frec, fk);
 #ifdef VILF_STAMPS
     if (stamp) { const int kid = 6 + a.is_surf; s2m_dbg[kid * 32 + 0] = st1_ - st0_; s2m_dbg[kid * 32 + 1] = __builtin_readcyclecounter() - st1_; s2m_dbg[kid * 32 + 30] = a.ds.n[sid]; }
@@ -1688,30 +1701,39 @@ __device__ __forceinline__ void assoc_one(const AssocArgs &a, int i, int sid, bo
     (void)stamp;
 }
 // ONE launch serves both query sets: blocks [0, nblk_edge) take the edge cloud against the edge map (arguments ae), the others the surf cloud (as).
-__global__ void b_associate(AssocArgs ae, AssocArgs as, int nblk_edge) {
+template <bool DBG>
+__device__ __forceinline__ void associate_block(const AssocArgs &ae, const AssocArgs &as, int nblk_edge, const AssocDbg *dbg) {
     const bool second = (int)blockIdx.x >= nblk_edge;
     const AssocArgs &a = second ? as : ae;
     const int i = ((int)blockIdx.x - (second ? nblk_edge : 0)) * blockDim.x + threadIdx.x, sid = blockIdx.y;
     if (i >= a.ds.n[sid] || !a.res[sid].do_opt) return;
     bool stamp = false;
 #ifdef VILF_STAMPS
-    stamp = blockIdx.y == S2M_STAMP_WG && (blockIdx.x == 2 || (int)blockIdx.x == nblk_edge + 2) && threadIdx.x == 0;
+    stamp = !DBG && blockIdx.y == S2M_STAMP_WG && (blockIdx.x == 2 || (int)blockIdx.x == nblk_edge + 2) && threadIdx.x == 0;
 #endif
-    assoc_one<false>(a, i, sid, stamp);
+    assoc_one<false, DBG>(a, i, sid, stamp, dbg);
 }
-// the queries that met exactly equal distances, redone in the reference's order: one block per stream, which leaves at once unless its stream counted a tie
-__global__ void b_associate_ties(AssocArgs ae, AssocArgs as) {
-    const int sid = blockIdx.x;
-    if (ae.tie_count[sid] == 0) return;
-    const int ne = ae.ds.n[sid], nq = ne + as.ds.n[sid];
-    const int *fkind = ae.fkind_all + (size_t)sid * ae.capq;
-    for (int slot = threadIdx.x; slot < nq; slot += blockDim.x) {
-        if (fkind[slot] != S2M_KIND_TIE) continue;
-        if (slot < ne) assoc_one<true>(ae, slot, sid, false); else assoc_one<true>(as, slot - ne, sid, false);
-    }
-    __syncthreads();
+__global__ void b_associate(AssocArgs ae, AssocArgs as, int nblk_edge) { associate_block<false>(ae, as, nblk_edge, nullptr); }
+// the queries that met exactly equal distances, redone in the reference's order: one block per stream, which leaves at once unless its stream counted a tie.
+// (One body for the kernel and its test twin; a macro, not a template: the step's kernel keeps the code it had.)
+#define ASSOC_TIES_BODY(ONE_EDGE, ONE_SURF)                                                             \
+    const int sid = blockIdx.x;                                                                         \
+    if (ae.tie_count[sid] == 0) return;                                                                 \
+    const int ne = ae.ds.n[sid], nq = ne + as.ds.n[sid];                                                \
+    const int *fkind = ae.fkind_all + (size_t)sid * ae.capq;                                            \
+    for (int slot = threadIdx.x; slot < nq; slot += blockDim.x) {                                       \
+        if (fkind[slot] != S2M_KIND_TIE) continue;                                                      \
+        if (slot < ne) ONE_EDGE; else ONE_SURF;                                                         \
+    }                                                                                                   \
+    __syncthreads();                                                                                    \
     if (threadIdx.x == 0) ae.tie_count[sid] = 0;
+__global__ void b_associate_ties(AssocArgs ae, AssocArgs as) { ASSOC_TIES_BODY(assoc_one<true>(ae, slot, sid, false), assoc_one<true>(as, slot - ne, sid, false)) }
+// the same two kernels with the neighbour lists written out (vilf_debug_s2m_associate): a step never launches them
+__global__ void b_associate_dbg(AssocArgs ae, AssocArgs as, int nblk_edge, AssocDbg dbg) { associate_block<true>(ae, as, nblk_edge, &dbg); }
+__global__ void b_associate_ties_dbg(AssocArgs ae, AssocArgs as, AssocDbg dbg) {
+    ASSOC_TIES_BODY((assoc_one<true, true>(ae, slot, sid, false, &dbg)), (assoc_one<true, true>(as, slot - ne, sid, false, &dbg)))
 }
+#undef ASSOC_TIES_BODY
 
 // ---- the persistent LM solve -------------------------------------------------------------------------------------------
 
@@ -2317,6 +2339,24 @@ static int s2b_resolve_order(vilf_handle *h, S2B *c, int w) {
     return VILF_OK;
 }
 
+// the two argument blocks of the association launch (edge, surf) on the context's current maps and directories: query clouds ds[2] (their edge count places the surf
+// records), poses, per-stream results (do_opt) and the record / kind arrays. One builder for the step and for the test hook.
+static void s2b_assoc_args(vilf_handle *h, S2B *c, const CSet ds[2], const double *d_pose, const S2BRes *d_res, double *frec, int *fkind, AssocArgs aa[2]) {
+    const float leaf[2] = {(float)h->opts.edge_leaf_size, (float)h->opts.surf_leaf_size};
+    for (int w = 0; w < 2; w++) {
+        AssocArgs &a = aa[w];
+        a.ds = ds[w]; a.is_surf = w; a.n_ds_edge = ds[0].n; a.pose_all = d_pose;
+        a.sorted_all = c->idx_copy[w] ? c->sorted[w].as<float4>() : c->map[w].as<float4>(); a.n_map = c->nMap[w].as<int>(); a.cap_map = c->capMap[w];
+        a.dir_all = c->bstart[w].as<unsigned>(); a.tag = c->dir_tag[w]; a.inv = 1.0f / leaf[w]; a.cs = c->cs_idx[w]; a.w_is_index = c->idx_copy[w] ? 1 : 0;
+        a.res = d_res; a.frec_all = frec; a.fkind_all = fkind; a.capq = c->capScan[0] + c->capScan[1]; a.tie_count = c->bcnt.as<int>();
+    }
+}
+// the association launch itself: edge and surf blocks in one grid sized by the scan capacities, a grid row per stream
+static inline void s2b_assoc_grid(const S2B *c, int *nblk_e, dim3 *grid) {
+    *nblk_e = (c->capScan[0] + 255) / 256;
+    *grid = dim3(*nblk_e + (c->capScan[1] + 255) / 256, c->S);
+}
+
 // one optimation_processing() for every stream; everything is enqueued on the handle's stream, no host round trip
 static int s2b_step(vilf_handle *h, S2B *c) {
     const int S = c->S;
@@ -2382,16 +2422,12 @@ static int s2b_step(vilf_handle *h, S2B *c) {
     }
     const int capq = c->capScan[0] + c->capScan[1];
     AssocArgs aa[2];
-    for (int w = 0; w < 2; w++) {
-        AssocArgs &a = aa[w];
-        a.ds = c->cs_ds(w); a.is_surf = w; a.n_ds_edge = c->nDs[0].as<int>(); a.pose_all = d_pose;
-        a.sorted_all = c->idx_copy[w] ? c->sorted[w].as<float4>() : c->map[w].as<float4>(); a.n_map = c->nMap[w].as<int>(); a.cap_map = c->capMap[w];
-        a.dir_all = c->bstart[w].as<unsigned>(); a.tag = c->dir_tag[w]; a.inv = 1.0f / leaf[w]; a.cs = c->cs_idx[w]; a.w_is_index = c->idx_copy[w] ? 1 : 0;
-        a.res = d_res; a.frec_all = c->frec.as<double>(); a.fkind_all = c->fkind.as<int>(); a.capq = capq; a.tie_count = c->bcnt.as<int>();
-    }
-    const int nblk_e = (c->capScan[0] + 255) / 256, nblk_s = (c->capScan[1] + 255) / 256;
+    const CSet ds2[2] = {c->cs_ds(0), c->cs_ds(1)};
+    s2b_assoc_args(h, c, ds2, d_pose, d_res, c->frec.as<double>(), c->fkind.as<int>(), aa);
+    int nblk_e; dim3 agrid;
+    s2b_assoc_grid(c, &nblk_e, &agrid);
     for (int pass = 0; pass < h->opts.s2m_outer_iterations && pass < 2; pass++) {
-        hipLaunchKernelGGL(b_associate, dim3(nblk_e + nblk_s, S), dim3(256), 0, h->stream, aa[0], aa[1], nblk_e);
+        hipLaunchKernelGGL(b_associate, agrid, dim3(256), 0, h->stream, aa[0], aa[1], nblk_e);
         hipLaunchKernelGGL(b_associate_ties, dim3(S), dim3(256), 0, h->stream, aa[0], aa[1]);      // queries that met exactly equal distances (rare), in the reference's order
         PROF(3)
         hipLaunchKernelGGL(b_solve, dim3(S), dim3(S2M_NT), 0, h->stream, d_pose, c->frec.as<double>(), c->fkind.as<int>(), capq, c->nDs[0].as<int>(), c->nDs[1].as<int>(), h->opts.huber_a,
@@ -2769,4 +2805,73 @@ extern "C" int vilf_scan2map_batch_get_map(vilf_handle *h, int stream, int which
     S2B_CHECK(h, stream)
     if (!n_out || which < 0 || which > 1) return VILF_ERR_INVALID_ARGUMENT;
     return s2b_get_map(h, c, stream, which, out, cap, n_out);
+}
+
+// ---- test hook (exported, not declared in vilfusion.h): what association does with given queries at a given pose ------------------------
+// Runs what a step runs between the voxel filter and the solve — s2b_resolve_order, s2b_build_index (a no-op when the last map update wrote the directory), the
+// association launch (edge and surf blocks in one grid of the production geometry, every stream of the batch present, the other streams without queries) and the tie
+// redo — on the stream's current local maps, with the kernels' DBG instantiations. Queries, pose, records and neighbour lists live in buffers of the call: of the
+// context only what the next step rebuilds anyway is touched (order_state, the directory of a map that has none yet, sort scratch), so a later step cannot tell.
+// stream: -1 = the single-stream context. Per query (edge queries first): kind_out[1], rec_out[6], pos_out[5], nb_out[15], d2_out[5].
+extern "C" int vilf_debug_s2m_associate(vilf_handle *h, int stream, const double *pose_qt, const float *edge_xyzi, int ne, const float *surf_xyzi, int ns,
+                                        int *kind_out, double *rec_out, int *pos_out, float *nb_out, float *d2_out) {
+    if (!h || !pose_qt || ne < 0 || ns < 0 || (ne && !edge_xyzi) || (ns && !surf_xyzi)) return VILF_ERR_INVALID_ARGUMENT;
+    S2B *c = stream == -1 ? h->s2m : h->s2b;
+    if (!c || c->S < 1 || c->capScan[0] < 1 || c->capScan[1] < 1 || c->capMap[0] < 1 || c->capMap[1] < 1) return VILF_ERR_INVALID_ARGUMENT;
+    const int sid = stream == -1 ? 0 : stream;
+    if (stream < -1 || sid >= c->S || ne > c->capScan[0] || ns > c->capScan[1]) return VILF_ERR_INVALID_ARGUMENT;
+    const int nq = ne + ns;
+    if (nq && (!kind_out || !rec_out || !pos_out || !nb_out || !d2_out)) return VILF_ERR_INVALID_ARGUMENT;
+    HIPCHECK(h, hipSetDevice(h->device));
+    const int S = c->S, capq = c->capScan[0] + c->capScan[1];
+    int rc;
+    for (int w = 0; w < 2; w++) {
+        if ((rc = s2b_resolve_order(h, c, w)) != VILF_OK) return rc;
+        if ((rc = s2b_build_index(h, c, w)) != VILF_OK) return rc;
+    }
+    DBuf q[2], nq_d[2], pose, res, frec, fkind, dpos, dnb, dd2;
+    auto done = [&](int r) { for (DBuf *b : {&q[0], &q[1], &nq_d[0], &nq_d[1], &pose, &res, &frec, &fkind, &dpos, &dnb, &dd2}) b->release(); return r; };
+#define DBGCHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string("vilf_debug_s2m_associate: ") + hipGetErrorString(e_); return done(VILF_ERR_DEVICE); } } while (0)
+    const size_t nslot = (size_t)S * capq;
+    if (!pose.ensure((size_t)S * 24 * 8) || !res.ensure((size_t)S * sizeof(S2BRes)) || !frec.ensure(nslot * S2M_FREC * 8) || !fkind.ensure(nslot * 4) ||
+        !dpos.ensure(nslot * 5 * 4) || !dnb.ensure(nslot * 15 * 4) || !dd2.ensure(nslot * 5 * 4)) return done(VILF_ERR_DEVICE);
+    const float *src[2] = {edge_xyzi, surf_xyzi}; const int nn[2] = {ne, ns};
+    for (int w = 0; w < 2; w++) {
+        if (!q[w].ensure((size_t)S * c->capScan[w] * 16) || !nq_d[w].ensure((size_t)S * 4)) return done(VILF_ERR_DEVICE);
+        std::vector<int> cnt(S, 0);
+        cnt[sid] = nn[w];
+        DBGCHECK(vilf_copy_sync(h, nq_d[w].p, cnt.data(), (size_t)S * 4, hipMemcpyHostToDevice));
+        if (nn[w]) DBGCHECK(vilf_copy_sync(h, q[w].as<float4>() + (size_t)sid * c->capScan[w], src[w], (size_t)nn[w] * 16, hipMemcpyHostToDevice));
+    }
+    std::vector<double> hp((size_t)S * 24, 0.0);
+    for (int s = 0; s < S; s++) { hp[24 * s + 3] = 1.0; hp[24 * s + 11] = 1.0; hp[24 * s + 19] = 1.0; }
+    for (int k = 0; k < 7; k++) hp[24 * (size_t)sid + k] = pose_qt[k];
+    DBGCHECK(vilf_copy_sync(h, pose.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice));
+    std::vector<S2BRes> hr(S, S2BRes{});
+    for (int s = 0; s < S; s++) hr[s].do_opt = 1;
+    DBGCHECK(vilf_copy_sync(h, res.p, hr.data(), hr.size() * sizeof(S2BRes), hipMemcpyHostToDevice));
+    DBGCHECK(hipMemsetAsync(frec.p, 0, nslot * S2M_FREC * 8, h->stream));
+    DBGCHECK(hipMemsetAsync(fkind.p, 0, nslot * 4, h->stream));
+    AssocArgs aa[2];
+    const CSet ds2[2] = {CSet{q[0].as<float4>(), nq_d[0].as<int>(), c->capScan[0]}, CSet{q[1].as<float4>(), nq_d[1].as<int>(), c->capScan[1]}};
+    s2b_assoc_args(h, c, ds2, pose.as<double>(), res.as<S2BRes>(), frec.as<double>(), fkind.as<int>(), aa);
+    const AssocDbg dbg{dpos.as<int>(), dnb.as<float>(), dd2.as<float>()};
+    int nblk_e; dim3 agrid;
+    s2b_assoc_grid(c, &nblk_e, &agrid);
+    hipLaunchKernelGGL(b_associate_dbg, agrid, dim3(256), 0, h->stream, aa[0], aa[1], nblk_e, dbg);
+    hipLaunchKernelGGL(b_associate_ties_dbg, dim3(S), dim3(256), 0, h->stream, aa[0], aa[1], dbg);
+    DBGCHECK(hipGetLastError());
+    DBGCHECK(hipStreamSynchronize(h->stream));
+    if (nq) {
+        std::vector<double> hrec((size_t)nq * S2M_FREC);
+        const size_t o = (size_t)sid * capq;
+        DBGCHECK(vilf_copy_sync(h, hrec.data(), frec.as<double>() + o * S2M_FREC, hrec.size() * 8, hipMemcpyDeviceToHost));
+        DBGCHECK(vilf_copy_sync(h, kind_out, fkind.as<int>() + o, (size_t)nq * 4, hipMemcpyDeviceToHost));
+        DBGCHECK(vilf_copy_sync(h, pos_out, dpos.as<int>() + o * 5, (size_t)nq * 5 * 4, hipMemcpyDeviceToHost));
+        DBGCHECK(vilf_copy_sync(h, nb_out, dnb.as<float>() + o * 15, (size_t)nq * 15 * 4, hipMemcpyDeviceToHost));
+        DBGCHECK(vilf_copy_sync(h, d2_out, dd2.as<float>() + o * 5, (size_t)nq * 5 * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nq; i++) for (int k = 0; k < 6; k++) rec_out[6 * (size_t)i + k] = hrec[(size_t)i * S2M_FREC + k];
+    }
+#undef DBGCHECK
+    return done(VILF_OK);
 }
