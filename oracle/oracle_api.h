@@ -90,6 +90,9 @@ int vilo_s2m_associate_edge(const float *map_xyzi, int n_map, const float *pts_x
                             unsigned char *valid, double *point_a /*[n][3]*/, double *point_b /*[n][3]*/);
 int vilo_s2m_associate_surf(const float *map_xyzi, int n_map, const float *pts_xyzi, int n_pts, const double pose_qt[7],
                             unsigned char *valid, double *norm /*[n][3]*/, double *d /*[n]*/);
+/* the LM solve of one scan-to-map pass on given factor records (kind 1: pa[3] pb[3], kind 2: n[3] d; other kinds skipped); pose in / out */
+int vilo_s2m_solve_factors(const vilf_options *opts, double pose_qt[7], int n, const int *kind, const double *rec6, const float *cp3, int max_it,
+                           int *iterations_out, double *final_cost_out);
 
 #ifdef __cplusplus
 }

@@ -263,3 +263,27 @@ extern "C" int vilo_s2m_associate_surf(const float *map, int nm, const float *pt
     for (int i = 0; i < np; i++) { V3 n; double dd; valid[i] = surf_association(c, nullptr, pose, p[i], n, dd) ? 1 : 0; if (valid[i]) { nrm[3 * i] = n.x; nrm[3 * i + 1] = n.y; nrm[3 * i + 2] = n.z; d[i] = dd; } }
     return VILF_OK;
 }
+
+// The LM solve of one pass on GIVEN factors (tests/test_scan2map_solve.py): the oracle's own EdgeCostFunction / SurfCostFunction / HuberLoss(opts->huber_a) / solve
+// on records as the association writes them. kind[i]: 1 edge (rec = pa[3] pb[3]), 2 surf (rec = n[3] d); every other kind is skipped. pose is read and written.
+extern "C" int vilo_s2m_solve_factors(const vilf_options *o, double pose[7], int n, const int *kind, const double *rec6, const float *cp3, int max_it, int *its_out, double *cost_out) {
+    HuberLoss loss(o->huber_a);
+    Problem pb;
+    int blk = pb.add_parameter_block(pose, 7, PARAM_SE3);
+    std::vector<std::unique_ptr<CostFunction>> costs;
+    for (int i = 0; i < n; i++) {
+        const double *r = rec6 + 6 * (size_t)i;
+        const V3 cp(cp3[3 * (size_t)i], cp3[3 * (size_t)i + 1], cp3[3 * (size_t)i + 2]);
+        if (kind[i] == 1) costs.emplace_back(new EdgeCostFunction(cp, V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5])));
+        else if (kind[i] == 2) costs.emplace_back(new SurfCostFunction(cp, V3(r[0], r[1], r[2]), r[3]));
+        else continue;
+        pb.add_residual_block(costs.back().get(), &loss, {blk});
+    }
+    SolverOptions so;
+    so.strategy = STRATEGY_LM;
+    so.max_num_iterations = max_it;
+    SolveSummary sum;
+    if (!costs.empty()) solve(so, pb, sum);
+    *its_out = sum.num_iterations; *cost_out = sum.final_cost;
+    return VILF_OK;
+}

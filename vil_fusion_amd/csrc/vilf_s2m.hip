@@ -1827,11 +1827,29 @@ __device__ void s2m_evaluate(const double *x, const double *frec, const unsigned
     if (threadIdx.x < 28 && (JAC || threadIdx.x == 27)) { double r = 0; for (int w = 0; w < S2M_NW; w++) r += s_red[w * 28 + threadIdx.x]; s_out[threadIdx.x] = r; }
     __syncthreads();
 }
+// the test twin's own copy of the sweep (the same text, inlined into a function of its own): s2m_evaluate stays a function that b_solve alone calls, so the twin's
+// call sites do not reach into its register allocation
+template <bool JAC>
+__device__ void s2m_evaluate_dbg(const double *x, const double *frec, const unsigned short *list, int n_edge, int nfac, double huber_a, double *s_red, double *s_out) {
+    [[clang::always_inline]] s2m_evaluate<JAC>(x, frec, list, n_edge, nfac, huber_a, s_red, s_out);
+}
 // ONE persistent 256-thread workgroup per stream; the optimised pose is written back to the stream's pose slot.
 #ifndef S2M_SOLVE_WPE
 #define S2M_SOLVE_WPE 2
 #endif
-__global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_all, const double *frec_all, const int *fkind_all, int capq, const int *n_ds_edge, const int *n_ds_surf, double huber_a, int max_it, int pass, S2BRes *res) {
+// DBG (vilf_debug_s2m_solve only; production instantiates DBG = false and passes no pointer): the trace of stream dbg_sid, S2M_TR doubles per row. Row 0, the
+// first evaluation: x[7] cost g[6] H[21] scale[6], then (written at the end) why the loop ended and how many rows were written. Row k >= 1, iteration k: valid accept
+// stop reason | the scaled diagonal used [6] | the step of the scaled system [6] | candidate x[7] | candidate cost | mcc | radius and decrease_factor after the decision
+#define S2M_TR 64
+#define S2M_STOP_PARAMETER 1
+#define S2M_STOP_FUNCTION 2
+#define S2M_STOP_GRADIENT 3
+#define S2M_STOP_BUDGET 4
+#define S2M_STOP_RADIUS 5
+#define S2M_STOP_INVALID 6
+template <bool DBG>
+__device__ __forceinline__ void solve_block(double *pose_all, const double *frec_all, const int *fkind_all, int capq, const int *n_ds_edge, const int *n_ds_surf, double huber_a, int max_it, int pass, S2BRes *res,
+                                            double *trace, int dbg_sid) {
     const int sid = blockIdx.x;
     if (!res[sid].do_opt) return;
     double *pose_in = pose_all + 24 * sid;
@@ -1850,24 +1868,26 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
     // records): every thread counts the edge / plane factors of its contiguous slice of the slots, a block scan gives the offsets, a second walk over the slice fills
     // the list — edge factors first, both parts ascending. Falls back to visiting every slot when the list would not fit.
     __shared__ unsigned short s_list[S2M_LCAP];
-    __shared__ int s_scan[S2M_NW];
+    __shared__ long long s_scan[S2M_NW];
     const int per = (nfac + S2M_NT - 1) / S2M_NT, a0 = min(nfac, tid * per), a1 = min(nfac, a0 + per);
     int ne = 0, ns = 0;
     for (int i = a0; i < a1; i++) { const int k = fkind[i]; if (k == 1) ne++; else if (k == 2) ns++; }
-    int incl = ne | (ns << 16);                                   // two packed counts (<= 65535 each: slots are 16-bit)
-    const int mine = incl, lane_ = tid & 63, wave_ = tid >> 6;
+    long long incl = (long long)ne | ((long long)ns << 32);      // two packed counts, 32 bits each: the scan capacities have no bound of their own
+    const long long mine = incl;
+    const int lane_ = tid & 63, wave_ = tid >> 6;
 #pragma unroll
-    for (int of = 1; of < 64; of <<= 1) { const int u = __shfl_up(incl, of, 64); if (lane_ >= of) incl += u; }
+    for (int of = 1; of < 64; of <<= 1) { const long long u = __shfl_up(incl, of, 64); if (lane_ >= of) incl += u; }
     if (lane_ == 63) s_scan[wave_] = incl;
     __syncthreads();
-    int off = 0, tot = 0;
+    long long off = 0, tot = 0;
 #pragma unroll
     for (int k = 0; k < S2M_NW; k++) { if (k < wave_) off += s_scan[k]; tot += s_scan[k]; }
-    const int tne = tot & 0xffff, tns = tot >> 16, excl = off + incl - mine;
+    const int tne = (int)(tot & 0xffffffffLL), tns = (int)(tot >> 32);
+    const long long excl = off + incl - mine;
     if (tne + tns == 0) { if (tid == 0) { out->cost[pass] = 0; out->its[pass] = 0; out->nfe[pass] = 0; out->nfs[pass] = 0; } return; }
     const bool use_list = tne + tns <= S2M_LCAP && nfac <= 65535;
     if (use_list) {
-        int pe = excl & 0xffff, ps = tne + (excl >> 16);
+        int pe = (int)(excl & 0xffffffffLL), ps = tne + (int)(excl >> 32);
         for (int i = a0; i < a1; i++) { const int k = fkind[i]; if (k == 1) s_list[pe++] = (unsigned short)i; else if (k == 2) s_list[ps++] = (unsigned short)i; }
     }
     const unsigned short *list = use_list ? s_list : nullptr;
@@ -1882,7 +1902,9 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
 #define SB_ADD(v) do { } while (0)
 #endif
     SB_T0();
-    s2m_evaluate<true>(s_x, frec, list, ev_ne, ev_n, huber_a, s_red, s_ev);
+    // (two spellings of ONE call, here and at the candidate below: the twin's goes through s2m_evaluate_dbg. Keep their arguments textually parallel.)
+    if (DBG) s2m_evaluate_dbg<true>(s_x, frec, list, ev_ne, ev_n, huber_a, s_red, s_ev);
+    else s2m_evaluate<true>(s_x, frec, list, ev_ne, ev_n, huber_a, s_red, s_ev);
     SB_ADD(sb_eval);
     // wave-0 scalars of the trust-region loop (trust_region_minimizer.cc + levenberg_marquardt_strategy.cc)
     double x_cost = s_ev[27], radius = 1e4, decrease_factor = 2.0, x_norm = 0, mcc = 0;
@@ -1894,6 +1916,14 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
     for (int k = 0; k < 7; k++) x_norm += s_x[k] * s_x[k];
     x_norm = sqrt(x_norm);
     __syncthreads();
+    const bool tr_on = DBG && sid == dbg_sid;
+    int why = 0;                                                  // DBG: why the loop ended (wave 0)
+    if (tr_on && tid == 0) {
+        for (int k = 0; k < 7; k++) trace[k] = s_x[k];
+        trace[7] = s_ev[27];
+        for (int k = 0; k < 6; k++) { trace[8 + k] = s_ev[21 + k]; trace[35 + k] = s_scale[k]; }
+        for (int k = 0; k < 21; k++) trace[14 + k] = s_ev[k];
+    }
     for (;;) {
         SB_T0();
         // The trust-region step of an iteration, by WAVE 0 (every lane runs the scalar part with the same values; LDS is written by one lane). The 6 x 6 part —
@@ -1904,14 +1934,14 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
         // the same k order): results to the bit.
         if (wave_ == 0) {
             int go = 1;
-            if (iteration >= max_it) go = 0;
+            if (iteration >= max_it) { go = 0; why = S2M_STOP_BUDGET; }
             else {
                 double d[6], xp[7], gm = 0;
                 for (int c = 0; c < 6; c++) d[c] = -s_ev[21 + c];
                 se3_plus(s_x, d, xp);
                 for (int k = 0; k < 7; k++) gm = fmax(gm, fabs(s_x[k] - xp[k]));
-                if (gm <= 1e-10) go = 0;
-                if (radius <= 1e-32) go = 0;
+                if (gm <= 1e-10) { go = 0; why = S2M_STOP_GRADIENT; }
+                else if (radius <= 1e-32) { go = 0; why = S2M_STOP_RADIUS; }
             }
             int valid = 0;
             if (go) {
@@ -1969,6 +1999,10 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
 #pragma unroll
                         for (int a = 0; a < 6; a++) s_step[a] = step[a];
                     }
+                    if (tr_on && lane_ == 0) {
+#pragma unroll
+                        for (int a = 0; a < 6; a++) trace[(size_t)iteration * S2M_TR + 10 + a] = step[a];
+                    }
                     double t_r = 0;
 #pragma unroll
                     for (int b2 = 0; b2 < 6; b2++) t_r += hs[b2] * step[b2];
@@ -1989,8 +2023,13 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
                 if (!valid) {   // StepIsInvalid -> StepRejected(0)
                     invalid++;
                     radius = radius / decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
-                    if (invalid >= 5) go = 0;
+                    if (invalid >= 5) { go = 0; why = S2M_STOP_INVALID; }
                 } else invalid = 0;
+                if (tr_on && lane_ < 6) trace[(size_t)iteration * S2M_TR + 4 + lane_] = dr;
+                if (tr_on && lane_ == 0) {
+                    double *row = trace + (size_t)iteration * S2M_TR;
+                    row[0] = valid; row[1] = 0; row[2] = 0; row[3] = 0; row[24] = mcc; row[25] = radius; row[26] = decrease_factor;
+                }
             }
             if (lane_ == 0) { s_ctl[0] = go; s_ctl[1] = valid; s_ctl[2] = (iteration >= max_it) ? 1 : 0; }
         }
@@ -2004,7 +2043,11 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
         // cost AND linearisation at the candidate in one sweep over the factor records: an accepted step (the usual case) then needs no
         // second sweep; a rejected one leaves s_ev (the linearisation at x) untouched
         // ... except at the last iteration of the budget: nothing would use that linearisation, the cost alone decides the step
-        if (last) s2m_evaluate<false>(s_c, frec, list, ev_ne, ev_n, huber_a, s_red, s_cand);
+        // (the DBG spelling must stay textually parallel to the production one under it)
+        if (DBG) {
+            if (last) s2m_evaluate_dbg<false>(s_c, frec, list, ev_ne, ev_n, huber_a, s_red, s_cand);
+            else s2m_evaluate_dbg<true>(s_c, frec, list, ev_ne, ev_n, huber_a, s_red, s_cand);
+        } else if (last) s2m_evaluate<false>(s_c, frec, list, ev_ne, ev_n, huber_a, s_red, s_cand);
         else s2m_evaluate<true>(s_c, frec, list, ev_ne, ev_n, huber_a, s_red, s_cand);
         SB_ADD(sb_eval);
         SB_T0();
@@ -2013,8 +2056,8 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
             double sn = 0, xc[7];
             for (int k = 0; k < 7; k++) { xc[k] = s_c[k]; sn += (s_x[k] - xc[k]) * (s_x[k] - xc[k]); }
             int stop = 0, accept = 0;
-            if (sqrt(sn) <= 1e-8 * (x_norm + 1e-8)) stop = 1;
-            else if (fabs(x_cost - cand) <= 1e-6 * x_cost) stop = 1;
+            if (sqrt(sn) <= 1e-8 * (x_norm + 1e-8)) { stop = 1; why = S2M_STOP_PARAMETER; }
+            else if (fabs(x_cost - cand) <= 1e-6 * x_cost) { stop = 1; why = S2M_STOP_FUNCTION; }
             else {
                 const double rd = (x_cost - cand) / mcc;
                 if (rd > 1e-3) {
@@ -2028,6 +2071,12 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
                 } else { radius = radius / decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true; }
             }
             if (lane_ == 0) { s_ctl[2] = stop; s_ctl[3] = accept; }
+            if (tr_on && lane_ == 0) {
+                double *row = trace + (size_t)iteration * S2M_TR;
+                row[1] = accept; row[2] = stop; row[3] = stop ? why : 0;
+                for (int k = 0; k < 7; k++) row[16 + k] = xc[k];
+                row[23] = cand; row[25] = radius; row[26] = decrease_factor;
+            }
         }
         __syncthreads();
         const int stop = s_ctl[2], accept = s_ctl[3];
@@ -2049,7 +2098,16 @@ __global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_al
     if (tid == 0) {
         for (int k = 0; k < 7; k++) pose_in[k] = s_x[k];
         out->cost[pass] = x_cost; out->its[pass] = iteration; out->nfe[pass] = tne; out->nfs[pass] = tns;
+        if (tr_on) { trace[41] = why; trace[42] = iteration + 1; }
     }
+}
+__global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve(double *pose_all, const double *frec_all, const int *fkind_all, int capq, const int *n_ds_edge, const int *n_ds_surf, double huber_a, int max_it, int pass, S2BRes *res) {
+    solve_block<false>(pose_all, frec_all, fkind_all, capq, n_ds_edge, n_ds_surf, huber_a, max_it, pass, res, nullptr, -1);
+}
+// the same kernel with the per-iteration trace written out (vilf_debug_s2m_solve): a step never launches it
+__global__ __launch_bounds__(S2M_NT, S2M_SOLVE_WPE) void b_solve_dbg(double *pose_all, const double *frec_all, const int *fkind_all, int capq, const int *n_ds_edge, const int *n_ds_surf, double huber_a, int max_it, int pass, S2BRes *res,
+                                                                    double *trace, int dbg_sid) {
+    solve_block<true>(pose_all, frec_all, fkind_all, capq, n_ds_edge, n_ds_surf, huber_a, max_it, pass, res, trace, dbg_sid);
 }
 
 // ---- createSubMap (:298-352): transform + append, crop box, voxel grid -------------------------------------------------
@@ -2872,6 +2930,77 @@ extern "C" int vilf_debug_s2m_associate(vilf_handle *h, int stream, const double
         DBGCHECK(vilf_copy_sync(h, d2_out, dd2.as<float>() + o * 5, (size_t)nq * 5 * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < nq; i++) for (int k = 0; k < 6; k++) rec_out[6 * (size_t)i + k] = hrec[(size_t)i * S2M_FREC + k];
     }
+#undef DBGCHECK
+    return done(VILF_OK);
+}
+
+// ---- test hook (exported, not declared in vilfusion.h): what the LM solve does with given factor records at a given pose ---------------------
+// Per query slot (edge queries [0, n_edge_q), surf queries behind them): kind (0 invalid, 1 edge, 2 surf, 3 the tie marker), six record doubles, the scan point as
+// three floats. The hook packs the 64-byte records as assoc_fit_write does (the kind in fkind and in double 7) into buffers of the call laid out for every stream
+// of the context — the other streams with zero queries and do_opt = 1 — and launches the production grid (dim3(S), S2M_NT) of b_solve_dbg. Nothing of the
+// context is written: a later step cannot tell. stream: -1 = the single-stream context. trace: trace_rows rows of S2M_TR doubles (layout at solve_block), rows
+// that no iteration wrote stay NaN; max_it + 1 > trace_rows is refused.
+extern "C" int vilf_debug_s2m_solve(vilf_handle *h, int stream, const double *pose_qt, int n_edge_q, int n_surf_q, const int *kind, const double *rec6, const float *cp3,
+                                    double huber_a, int max_it, int pass, double *pose_out, double *cost_out, int *its_out, int *nfe_out, int *nfs_out, double *trace, int trace_rows) {
+    if (!h || !pose_qt || n_edge_q < 0 || n_surf_q < 0 || pass < 0 || pass > 1 || max_it < 0 || trace_rows < 1 || max_it > trace_rows - 1) return VILF_ERR_INVALID_ARGUMENT;
+    if (!pose_out || !cost_out || !its_out || !nfe_out || !nfs_out || !trace) return VILF_ERR_INVALID_ARGUMENT;
+    S2B *c = stream == -1 ? h->s2m : h->s2b;
+    if (!c || c->S < 1 || c->capScan[0] < 1 || c->capScan[1] < 1) return VILF_ERR_INVALID_ARGUMENT;
+    const int sid = stream == -1 ? 0 : stream;
+    if (stream < -1 || sid >= c->S || n_edge_q > c->capScan[0] || n_surf_q > c->capScan[1]) return VILF_ERR_INVALID_ARGUMENT;
+    const int nq = n_edge_q + n_surf_q;
+    if (nq && (!kind || !rec6 || !cp3)) return VILF_ERR_INVALID_ARGUMENT;
+    HIPCHECK(h, hipSetDevice(h->device));
+    const int S = c->S, capq = c->capScan[0] + c->capScan[1];
+    DBuf nq_d[2], pose, res, frec, fkind, dtrace;
+    auto done = [&](int r) { for (DBuf *b : {&nq_d[0], &nq_d[1], &pose, &res, &frec, &fkind, &dtrace}) b->release(); return r; };
+#define DBGCHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string("vilf_debug_s2m_solve: ") + hipGetErrorString(e_); return done(VILF_ERR_DEVICE); } } while (0)
+    const size_t nslot = (size_t)S * capq, ntr = (size_t)trace_rows * S2M_TR;
+    if (!pose.ensure((size_t)S * 24 * 8) || !res.ensure((size_t)S * sizeof(S2BRes)) || !frec.ensure(nslot * S2M_FREC * 8) || !fkind.ensure(nslot * 4) || !dtrace.ensure(ntr * 8) ||
+        !nq_d[0].ensure((size_t)S * 4) || !nq_d[1].ensure((size_t)S * 4)) return done(VILF_ERR_DEVICE);
+    const int nn[2] = {n_edge_q, n_surf_q};
+    for (int w = 0; w < 2; w++) {
+        std::vector<int> cnt(S, 0);
+        cnt[sid] = nn[w];
+        DBGCHECK(vilf_copy_sync(h, nq_d[w].p, cnt.data(), (size_t)S * 4, hipMemcpyHostToDevice));
+    }
+    std::vector<double> hp((size_t)S * 24, 0.0);
+    for (int s = 0; s < S; s++) { hp[24 * s + 3] = 1.0; hp[24 * s + 11] = 1.0; hp[24 * s + 19] = 1.0; }
+    for (int k = 0; k < 7; k++) hp[24 * (size_t)sid + k] = pose_qt[k];
+    DBGCHECK(vilf_copy_sync(h, pose.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice));
+    std::vector<S2BRes> hr(S, S2BRes{});
+    for (int s = 0; s < S; s++) hr[s].do_opt = 1;
+    DBGCHECK(vilf_copy_sync(h, res.p, hr.data(), hr.size() * sizeof(S2BRes), hipMemcpyHostToDevice));
+    DBGCHECK(hipMemsetAsync(frec.p, 0, nslot * S2M_FREC * 8, h->stream));
+    DBGCHECK(hipMemsetAsync(fkind.p, 0, nslot * 4, h->stream));
+    DBGCHECK(hipMemsetAsync(dtrace.p, 0xff, ntr * 8, h->stream));                  // NaN: a row no iteration wrote
+    if (nq) {
+        std::vector<double> hrec((size_t)nq * S2M_FREC, 0.0);
+        for (int i = 0; i < nq; i++) {
+            double *r = hrec.data() + (size_t)i * S2M_FREC;
+            for (int k = 0; k < 6; k++) r[k] = rec6[6 * (size_t)i + k];
+            unsigned u[3];
+            std::memcpy(u, cp3 + 3 * (size_t)i, 12);
+            const unsigned long long a = ((unsigned long long)u[1] << 32) | u[0], b = ((unsigned long long)(unsigned)kind[i] << 32) | u[2];
+            std::memcpy(r + 6, &a, 8); std::memcpy(r + 7, &b, 8);
+        }
+        const size_t o = (size_t)sid * capq;
+        DBGCHECK(vilf_copy_sync(h, frec.as<double>() + o * S2M_FREC, hrec.data(), hrec.size() * 8, hipMemcpyHostToDevice));
+        DBGCHECK(vilf_copy_sync(h, fkind.as<int>() + o, kind, (size_t)nq * 4, hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(b_solve_dbg, dim3(S), dim3(S2M_NT), 0, h->stream, pose.as<double>(), frec.as<double>(), fkind.as<int>(), capq, nq_d[0].as<int>(), nq_d[1].as<int>(), huber_a, max_it, pass,
+                       res.as<S2BRes>(), dtrace.as<double>(), sid);
+    DBGCHECK(hipGetLastError());
+    DBGCHECK(hipStreamSynchronize(h->stream));
+    S2BRes r1;
+    std::vector<double> htr(ntr);
+    double hpose[7];
+    DBGCHECK(vilf_copy_sync(h, &r1, res.as<S2BRes>() + sid, sizeof(S2BRes), hipMemcpyDeviceToHost));
+    DBGCHECK(vilf_copy_sync(h, hpose, pose.as<double>() + 24 * (size_t)sid, 7 * 8, hipMemcpyDeviceToHost));
+    DBGCHECK(vilf_copy_sync(h, htr.data(), dtrace.p, ntr * 8, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 7; k++) pose_out[k] = hpose[k];
+    *cost_out = r1.cost[pass]; *its_out = r1.its[pass]; *nfe_out = r1.nfe[pass]; *nfs_out = r1.nfs[pass];
+    std::memcpy(trace, htr.data(), ntr * 8);
 #undef DBGCHECK
     return done(VILF_OK);
 }
