@@ -552,8 +552,8 @@ int vilf_lidar_extract_features(vilf_handle *h, const float *xyzi, int n_points,
  * receives as point(7), estimator_node.cpp) or -1 when the 3 nearest returns do not support one. */
 int vilf_feature_depth(vilf_handle *h, const float *depth_cloud_xyzi, int n_points, const float *features_xyz, int n_features, float *depth_out);
 
-/* ---- Image feature tracker (≙ FeatureTracker::readImage, feature_tracker/feature_tracker.cpp:119-209; device) ----
- * OpenCV is not available, so this text fixes the arithmetic itself; tests/track_reference.py restates it in numpy and the kernels agree with that to the bit.
+/* ---- Image feature tracker (≙ FeatureTracker::readImage and readImage_mask, feature_tracker/feature_tracker.cpp:119-209, :212-381; device) ----
+ * OpenCV is not available, so this text fixes the arithmetic itself; tests/track_reference.py restates it in numpy (frontend_reference.py and mask_reference.py the optional steps) and the kernels agree with that to the bit.
  * It is modelled on what the reference calls: cv::calcOpticalFlowPyrLK(.., Size(21,21), 3) (:151: window, levels, 30 iterations / 0.01 px, the 1e-4 minimum
  * eigenvalue, 14-bit fixed-point patches, unnormalised Scharr gradients), cv::goodFeaturesToTrack(.., 0.01, MIN_DIST, mask) (:190), setMask (:36-71), inBorder
  * (:5-11), undistortedPoints (:556-604), updateID. One deliberate difference makes bit identity possible: sums over a window are exact integer sums, where OpenCV
@@ -634,7 +634,33 @@ int vilf_feature_depth(vilf_handle *h, const float *depth_cloud_xyzi, int n_poin
  *                inlier iff d d / (l'_0 l'_0 + l'_1 l'_1) <= F_THRESHOLD^2 and d d / (l_0 l_0 + l_1 l_1) <= F_THRESHOLD^2 (the larger of the two errors; a NaN
  *                compares false: an outlier). Score = the number of inliers. The winner is the valid hypothesis of the highest score, ties to the lower k; the
  *                status is its inlier mask, there is no refit. No valid hypothesis: nothing is rejected (every status 1, best = -1).
- * Not here: readImage_mask and the fisheye mask. */
+ *   mask image   (readImage_mask, :212-381, the front-end of feature_tracker_node_mask.cpp) an 8-bit W x H image that marks dynamic objects: a pixel means "static /
+ *                allowed" iff it is != 0 and "dynamic" iff it is 0, which is what the node's copyTo (feature_tracker_node_mask.cpp:276-278) makes of the message.
+ *   erode        (the node's cv::erode with an 11 x 11 MORPH_ELLIPSE, :283-290) radius r is a parameter, default 5, 0 .. VILF_TRACK_MAX_ERODE. The element is the
+ *                offsets (dx, dy) with |dy| <= r and |dx| <= hw(|dy|), hw(d) = rint(sqrt((double)(r r - d d))); for r = 5 the half-widths are 5, 5, 5, 4, 3, 0.
+ *                E(x, y) = 255 iff mask(x + dx, y + dy) != 0 for every offset whose pixel lies inside the image, else 0: pixels outside the image do not erode
+ *                (OpenCV's default border for erode). r = 0 only binarises. The element's shape is this text's, not OpenCV's raster (deviations: DESIGN.md §3i).
+ *   probe        (:256-290) for each point that survived LK and inBorder, with (x, y) its pixel (rint x, rint y) in the new image and d the probe distance
+ *                (parameter, default 5, 1 .. 64): if x > d, y > d, x < W - d and y < H - d, the point is static iff E(x, y - d), E(x, y + d), E(x - d, y) and
+ *                E(x + d, y) are all != 0; if the guard does not hold, the point is static. (The reference reads mask_img.at<uchar>(col, row -+ 5), transposed,
+ *                and guards with col < ROW - 5: deviations)
+ *   rejectWithF_mask (:423-500) after the probe and before setMask, only if the mask parameters' reject is on, on a frame that has a previous one. S = the static
+ *                survivors in list order, m = |S|; if m < 8 nothing is rejected. Otherwise all survivors are lifted exactly as in rejectWithF; the hypotheses
+ *                are drawn exactly as there, with the configured K, seed and focal length and with S in place of the list (sample indices address S); scored
+ *                over S with the mask parameters' f_threshold (default 0.1, :449); winner = highest score, ties to the lower k, no refit. Then for every
+ *                survivor, static or not, with (x, y) its lifted point in the current image and (x', y') in the new one: A = (F00 x + F01 y) + F02,
+ *                B = (F10 x + F11 y) + F12, C = (F20 x + F21 y) + F22, dd = |(A x' + B y') + C| / sqrt(A A + B B) in fp64, each operation rounded; the point
+ *                is dropped iff dd > epi_threshold (default 1.0, :485); a NaN compares false, so the point is kept. No valid hypothesis: nothing is rejected.
+ *                The inlier mask of the search itself is not used and the test on all points is one-sided, both as in the reference.
+ *   fisheye mask (:38-39) an optional W x H image held by the tracker, for both readImage variants. With it setMask keeps a point only if the fisheye mask at its
+ *                pixel is == 255 (:61) and the pixel lies in no disc, and the detection allows a pixel only if the fisheye mask there is != 0
+ *                (goodFeaturesToTrack's mask rule) and the pixel lies in no disc. The two rules differ for the values 1 .. 254: there a tracked point is dropped
+ *                while a new corner may be found; the difference is the reference's and is kept. Without the image everything is as above.
+ *   detection under the dynamic mask (:356-360) a pixel is allowed iff E != 0 there, the fisheye rule holds there and it lies in no disc; lambda_max is the
+ *                maximum over the allowed pixels, as before, and nothing else of the detection paragraph changes.
+ *   frame order of readImage_mask: CLAHE if on, LK, inBorder, probe, rejectWithF_mask, setMask, detection under E, undistortion; on the first frame there is no LK,
+ *                probe or rejection. The reject_f switch of vilf_track_configure does not act here (the reference calls only rejectWithF_mask, :318-319). Plain
+ *                and masked calls may alternate on one tracker; they share all state, as the reference's two methods do. */
 typedef struct vilf_track_params {
     int width, height;               /* COL, ROW */
     int max_cnt;                     /* MAX_CNT, 1 .. VILF_MAX_FEATURES */
@@ -685,6 +711,36 @@ int vilf_track_reject_f(vilf_handle *h, const float *cur_pts, const float *forw_
 /* vilf_set_profiling: CLAHE (both kernels) and rejectWithF (lift, hypotheses, score, apply) of the last vilf_track_read_image; 0 for a step that is off. The
  * five stages of vilf_track_profile are as before: CLAHE falls into the first of them, rejectWithF into the second. */
 int vilf_track_profile_frontend(vilf_handle *h, double ms_out[2], long launches_out[2]);
+/* The dynamic-object mask and the fisheye mask (the paragraphs mask image .. frame order above). A tracker that never sets a fisheye mask and never calls the
+ * masked entry point computes what it computed before they existed, with the same launches. */
+#define VILF_TRACK_MAX_ERODE 16
+typedef struct vilf_track_mask_params {
+    int erode_radius, probe, reject;          /* 5, 5, 1 */
+    double f_threshold, epi_threshold;        /* 0.1, 1.0 */
+} vilf_track_mask_params;
+/* after vilf_track_init; a later vilf_track_init returns to the defaults in the comments above and drops the fisheye mask, vilf_track_reset keeps both (the node
+ * loads the fisheye mask once, after construction). Invalid argument, the handle and the tracker untouched: no tracker, null parameters, a radius outside
+ * 0 .. VILF_TRACK_MAX_ERODE, a probe outside 1 .. 64, reject other than 0 or 1, a threshold that is not positive and finite. */
+int vilf_track_configure_mask(vilf_handle *h, const vilf_track_mask_params *mp);
+/* the fisheye mask, W x H, rows row_stride bytes apart (copied); NULL: none. It applies to both readImage variants and to both detection calls. */
+int vilf_track_set_fisheye_mask(vilf_handle *h, const unsigned char *mask, int row_stride);
+/* readImage_mask (:212-381) and the updateID loop for one image and its mask image: one chain of launches; the host uploads the image and the mask and downloads
+ * the list, which vilf_track_get returns. Invalid argument, nothing changed: a null pointer, a stride below the width. */
+int vilf_track_read_image_mask(vilf_handle *h, const unsigned char *img, int row_stride, const unsigned char *mask, int mask_row_stride, double stamp, int *n_out);
+/* stateless pieces (they leave the tracked state alone): the erosion of a mask image with the configured radius -> out, rows tight; */
+int vilf_track_erode(vilf_handle *h, const unsigned char *mask, int row_stride, unsigned char *out);
+/* the probe of n points [n][2] (finite; at most VILF_MAX_FEATURES) in an eroded mask (rows tight) with the configured distance -> static_out [n], 1 = static; */
+int vilf_track_probe(vilf_handle *h, const unsigned char *eroded, const float *pts, int n, unsigned char *static_out);
+/* rejectWithF_mask on n point pairs, all of them survivors, those with is_static[i] != 0 static -> status_out [n], F_out (row-major), *best_out = the winning k,
+ * *n_static_inliers_out = its score over the static pairs. Fewer than 8 static pairs or no valid hypothesis: every status 1, best -1, F 0,
+ * n_static_inliers = the number of static pairs; that is no error. Invalid argument, nothing written: as vilf_track_reject_f; */
+int vilf_track_reject_f_mask(vilf_handle *h, const float *cur_pts, const float *forw_pts, const unsigned char *is_static, int n, unsigned char *status_out, double F_out[9], int *best_out,
+                             int *n_static_inliers_out);
+/* vilf_track_detect under an eroded mask (rows tight) as well: "detection under the dynamic mask". Both calls honour the fisheye mask when one is set. */
+int vilf_track_detect_masked(vilf_handle *h, const unsigned char *img, const unsigned char *eroded, const float *kept_pts, int n_kept, int n_max, float *pts_out, int *n_out);
+/* vilf_set_profiling: the erosion, and the probe with rejectWithF_mask (probe, lift, hypotheses, score, apply), of the last vilf_track_read_image_mask; 0 for a
+ * plain frame. In the five stages of vilf_track_profile the mask's upload and the erosion fall into the first, the probe and the rejection into the second. */
+int vilf_track_profile_mask(vilf_handle *h, double ms_out[2], long launches_out[2]);
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,14 @@ VILF_TRACK_MAX_TILES = 1024
 VILF_TRACK_MAX_HYPOTHESES = 2048
 
 
+class TrackMaskParams(C.Structure):
+    """vilf_track_mask_params: readImage_mask's erosion radius, probe distance and rejectWithF_mask (on / off, the search's and the final test's thresholds)"""
+    _fields_ = [("erode_radius", C.c_int), ("probe", C.c_int), ("reject", C.c_int), ("f_threshold", C.c_double), ("epi_threshold", C.c_double)]
+
+
+VILF_TRACK_MAX_ERODE = 16
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

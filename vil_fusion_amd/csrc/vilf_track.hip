@@ -18,7 +18,13 @@
 //   tk_f_hypotheses  a lane per hypothesis: sample, Hartley, M = A^T A and the Jacobi vectors in LDS (a column per lane), rank 2, denormalise -> F_k, valid_k
 //   tk_f_score       a wave per hypothesis: the lanes stride over the points, an integer wave sum, one 64-bit atomicMax of (score + 1, K - 1 - k)
 //   tk_f_apply       one workgroup: the winner's inlier mask into LK's status bytes, which tk_setmask reads as before
-// Per frame the host uploads the image and downloads the list (count + rows, one copy).
+// The dynamic-object and fisheye masks (vilf_track_read_image_mask, vilf_track_set_fisheye_mask; a tracker that uses neither issues the launches above, no more):
+//   tk_mask_erode    a 32 x 8 tile: the mask binarised into LDS with a halo of r (outside the image = set), every thread tests its pixel against the element's row spans
+//   tk_mask_probe    a thread per point: static = LK's status AND the four probes of E, into a status array of its own (setMask's bytes are not touched)
+//   tk_f_lift / tk_f_hypotheses / tk_f_score as they are, on the static status array, then
+//   tk_fm_apply      one workgroup: the winner by the same packed word, every survivor lifted again and tested one-sidedly against the winner's F
+//   tk_mask_init     the forbidden-pixel map from E and the fisheye mask, in place of the memset in front of tk_paint
+// Per frame the host uploads the image (and the mask) and downloads the list (count + rows, one copy).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -36,6 +42,8 @@
 #define TK_MAXN VILF_MAX_FEATURES           // rows of the list; accepted corners of one detection
 #define TK_STAGES 5
 #define TK_FE_STAGES 2                      // CLAHE, rejectWithF
+#define TK_MK_STAGES 2                      // erode, probe + rejectWithF_mask
+#define TK_ER_MAX VILF_TRACK_MAX_ERODE
 #define TK_F_SWEEPS 10
 #define TK_F_MAXK VILF_TRACK_MAX_HYPOTHESES
 
@@ -69,7 +77,7 @@ struct TkF { float2 *ua, *ub; int *src, *fctl; double *F; int *valid; double *re
 #define TK_CORNERS_NT 64                // tk_corners: one wave
 __global__ void tk_pyr_down(const unsigned char *src, int sw, int sh, unsigned char *dst, int dw, int dh);
 __global__ void tk_lk(TkPyr prev, TkPyr next, const float2 *pts, const int *n_dev, int n_host, float2 *out, unsigned char *status, int border);
-__global__ void tk_setmask(TkList cur, const float2 *fwd, const unsigned char *status, TkList nxt, int *ctl, int max_cnt, long long md2);
+__global__ void tk_setmask(TkList cur, const float2 *fwd, const unsigned char *status, TkList nxt, int *ctl, int max_cnt, long long md2, const unsigned char *fish, int W, int H);   // fish: the fisheye mask or null
 __global__ void tk_paint(const float2 *pts, const int *ctl, unsigned char *mask, int W, int H, long long md, long long md2);
 __global__ void tk_response(const unsigned char *img, const unsigned char *mask, int W, int H, int *ctl, double *lam);
 __global__ void tk_candidates(const double *lam, const unsigned char *mask, int W, int H, int *ctl, unsigned *cidx, int cap);
@@ -84,6 +92,11 @@ __global__ void tk_f_lift(const float2 *cur, const float2 *fwd, const unsigned c
 __global__ void tk_f_hypotheses(TkF f, int K, unsigned seed);
 __global__ void tk_f_score(TkF f, int K, double thr2);
 __global__ void tk_f_apply(TkF f, int K, double thr2, unsigned char *status);      // one workgroup, TK_NT
+struct TkSpans { int r, hw[TK_ER_MAX + 1]; };      // the structuring element: row |dy| covers |dx| <= hw[|dy|]
+__global__ void tk_mask_erode(const unsigned char *mask, int W, int H, TkSpans sp, unsigned char *E);      // block (32, 8), tiles of the image; LDS (8 + 2 * 16) x (32 + 2 * 16) bytes
+__global__ void tk_mask_probe(const unsigned char *E, const float2 *fwd, const unsigned char *status, const int *n_dev, int n_host, int W, int H, int d, unsigned char *is_static);   // 1-D over the list's rows, TK_NT
+__global__ void tk_fm_apply(TkF f, int K, const float2 *cur, const float2 *fwd, const int *n_dev, int n_host, TkCam cam, double focal, double half_w, double half_h, double epi, unsigned char *status);   // one workgroup, TK_NT
+__global__ void tk_mask_init(const unsigned char *E, const unsigned char *fish, size_t n, unsigned char *mask);      // 1-D, TK_NT, four pixels per thread
 
 struct TrackCtx {
     vilf_track_params p;
@@ -95,6 +108,12 @@ struct TrackCtx {
     size_t ncell = 0;                   // W * H
     DBuf pyrmem[4], list[2], tmplist, ctl, tmpctl, prev_ids, prev_un, fwd, status, lkpts, mask, lam, cidx, cidx2, cval, key, key2, val, val2, temp;
     DBuf raw, lut, fmem;                // the optional steps: the image before CLAHE, the tiles' LUTs (VILF_TRACK_MAX_TILES), everything of rejectWithF (tk_f)
+    DBuf mraw, er, fish, sstatus;       // the masks: the uploaded mask image, E, the fisheye mask (has_fish), the static status of the probe
+    PinBuf mstage;                      // a mask on its way to the device
+    vilf_track_mask_params mp;          // the defaults after vilf_track_init
+    bool has_fish = false;
+    double mk_ms[TK_MK_STAGES] = {0, 0};
+    long mk_launches[TK_MK_STAGES] = {0, 0};
     vilf_track_frontend fe;             // both off and the defaults after vilf_track_init
     double fe_ms[TK_FE_STAGES] = {0, 0};
     long fe_launches[TK_FE_STAGES] = {0, 0};
@@ -103,9 +122,9 @@ struct TrackCtx {
     long launches[TK_STAGES] = {0, 0, 0, 0, 0};
     void release() {
         DBuf *all[] = {&pyrmem[0], &pyrmem[1], &pyrmem[2], &pyrmem[3], &list[0], &list[1], &tmplist, &ctl, &tmpctl, &prev_ids, &prev_un, &fwd, &status, &lkpts,
-                       &mask, &lam, &cidx, &cidx2, &cval, &key, &key2, &val, &val2, &temp, &raw, &lut, &fmem};
+                       &mask, &lam, &cidx, &cidx2, &cval, &key, &key2, &val, &val2, &temp, &raw, &lut, &fmem, &mraw, &er, &fish, &sstatus};
         for (DBuf *b : all) b->release();
-        pin.release();
+        pin.release(); mstage.release();
         for (PinBuf &b : stage) b.release();
     }
 };
@@ -113,6 +132,7 @@ void vilf_track_profile_reset(vilf_handle *h) {
     if (!h->trk) return;
     for (int i = 0; i < TK_STAGES; i++) { h->trk->ms[i] = 0; h->trk->launches[i] = 0; }
     for (int i = 0; i < TK_FE_STAGES; i++) { h->trk->fe_ms[i] = 0; h->trk->fe_launches[i] = 0; }
+    for (int i = 0; i < TK_MK_STAGES; i++) { h->trk->mk_ms[i] = 0; h->trk->mk_launches[i] = 0; }
 }
 void vilf_track_release(vilf_handle *h) { if (h->trk) { h->trk->release(); delete h->trk; h->trk = nullptr; } }
 
@@ -282,16 +302,22 @@ __global__ __launch_bounds__(64 * TK_LK_WAVES) void tk_lk(TkPyr prev, TkPyr next
 }
 
 // ---- tk_setmask: one workgroup -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TK_NT) void tk_setmask(TkList cur, const float2 *fwd, const unsigned char *status, TkList nxt, int *ctl, int max_cnt, long long md2) {
+__global__ __launch_bounds__(TK_NT) void tk_setmask(TkList cur, const float2 *fwd, const unsigned char *status, TkList nxt, int *ctl, int max_cnt, long long md2, const unsigned char *fish, int W, int H) {
     __shared__ int s_cnt[TK_MAXN], s_order[TK_MAXN], s_src[TK_MAXN];
     __shared__ int2 s_px[TK_MAXN], s_acc[TK_MAXN];
     __shared__ int s_m, s_nk;
     const int t = threadIdx.x, n = min(ctl[TC_N], TK_MAXN);
     if (t == 0) s_m = 0;
     for (int i = t; i < n; i += TK_NT) {
-        s_cnt[i] = status[i] ? cur.cnt[i] : -1;          // track counts are positive
         const float2 f = fwd[i];
-        s_px[i] = make_int2((int)rintf(f.x), (int)rintf(f.y));
+        const int2 px = make_int2((int)rintf(f.x), (int)rintf(f.y));
+        bool keep = status[i] != 0;
+        if (fish) {                                      // a survivor's pixel is inside the image (inBorder); the address is clamped all the same, the value selected after the load
+            const unsigned char v = fish[(size_t)min(max(px.y, 0), H - 1) * W + min(max(px.x, 0), W - 1)];
+            keep = keep && v == 255;
+        }
+        s_cnt[i] = keep ? cur.cnt[i] : -1;               // track counts are positive
+        s_px[i] = px;
     }
     __syncthreads();
     for (int i = t; i < n; i += TK_NT) {
@@ -590,6 +616,12 @@ VD void tk_hartley(double (*P)[TK_F_LANES], int lane, double &cx, double &cy, do
     s = __ddiv_rn(__dsqrt_rn(2.0), md);
     for (int j = 0; j < 8; j++) { P[j][lane] = __dmul_rn(__dsub_rn(P[j][lane], cx), s); P[8 + j][lane] = __dmul_rn(__dsub_rn(P[8 + j][lane], cy), s); }
 }
+// the lift of rejectWithF: liftProjective in fp64, then the virtual camera's pixel, rounded to float32
+VD float2 tk_f_liftpt(const TkCam &cam, float2 p, double focal, double half_w, double half_h) {
+    double ux, uy;
+    tk_undistort(cam, p, ux, uy);
+    return make_float2((float)__dadd_rn(__dmul_rn(focal, ux), half_w), (float)__dadd_rn(__dmul_rn(focal, uy), half_h));
+}
 // the score's inlier rule for the point pair (a, b) under F (row-major)
 VD bool tk_f_inlier(const double *F, float2 a, float2 b, double thr2) {
     const double x = (double)a.x, y = (double)a.y, xp = (double)b.x, yp = (double)b.y;
@@ -612,11 +644,8 @@ __global__ __launch_bounds__(TK_NT) void tk_f_lift(const float2 *cur, const floa
         if (!s_st[i]) continue;
         int rank = 0;
         for (int j = 0; j < i; j++) rank += s_st[j];         // list order; rank < n <= TK_MAXN, the rows of ua, ub, src
-        double ux, uy;
-        tk_undistort(cam, cur[i], ux, uy);
-        f.ua[rank] = make_float2((float)__dadd_rn(__dmul_rn(focal, ux), half_w), (float)__dadd_rn(__dmul_rn(focal, uy), half_h));
-        tk_undistort(cam, fwd[i], ux, uy);
-        f.ub[rank] = make_float2((float)__dadd_rn(__dmul_rn(focal, ux), half_w), (float)__dadd_rn(__dmul_rn(focal, uy), half_h));
+        f.ua[rank] = tk_f_liftpt(cam, cur[i], focal, half_w, half_h);
+        f.ub[rank] = tk_f_liftpt(cam, fwd[i], focal, half_w, half_h);
         f.src[rank] = i;
     }
     if (t == 0) {
@@ -746,6 +775,86 @@ __global__ __launch_bounds__(TK_NT) void tk_f_apply(TkF f, int K, double thr2, u
     if (t < 9) f.res[2 + t] = F[t];
 }
 
+// ---- tk_mask_erode: a tile through LDS with a halo of r ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_TW * TK_TH) void tk_mask_erode(const unsigned char *mask, int W, int H, TkSpans sp, unsigned char *E) {
+    __shared__ unsigned char s[TK_TH + 2 * TK_ER_MAX][TK_TW + 2 * TK_ER_MAX];      // 1 = set; pixel (x0 - r + lx, y0 - r + ly)
+    const int tx = threadIdx.x, ty = threadIdx.y, t = ty * TK_TW + tx;
+    const int x0 = blockIdx.x * TK_TW, y0 = blockIdx.y * TK_TH;
+    const int r = min(max(sp.r, 0), TK_ER_MAX), lw = TK_TW + 2 * r, lh = TK_TH + 2 * r;
+    for (int i = t; i < lw * lh; i += TK_TW * TK_TH) {
+        const int ly = i / lw, lx = i % lw, gx = x0 - r + lx, gy = y0 - r + ly;
+        const bool in = (unsigned)gx < (unsigned)W && (unsigned)gy < (unsigned)H;
+        const unsigned char v = mask[(size_t)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1)];      // clamped address, the value selected afterwards
+        s[ly][lx] = (in && v == 0) ? 0 : 1;              // outside the image does not erode
+    }
+    __syncthreads();
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= W || y >= H) return;
+    unsigned all = 1;
+    for (int dy = -r; dy <= r; dy++) {
+        const int hw = min(max(sp.hw[dy < 0 ? -dy : dy], 0), r);
+        const unsigned char *row = &s[ty + r + dy][tx + r];      // rows ty .. ty + 2 r < lh, columns tx + r - hw .. tx + r + hw < lw
+        for (int dx = -hw; dx <= hw; dx++) all &= row[dx];
+    }
+    E[(size_t)y * W + x] = all ? 255 : 0;
+}
+
+// ---- tk_mask_probe: a thread per point ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_mask_probe(const unsigned char *E, const float2 *fwd, const unsigned char *status, const int *n_dev, int n_host, int W, int H, int d, unsigned char *is_static) {
+    const int i = blockIdx.x * TK_NT + threadIdx.x, n = min(n_dev ? *n_dev : n_host, TK_MAXN);
+    if (i >= n) return;
+    const float2 f = fwd[i];
+    const float rx = rintf(f.x), ry = rintf(f.y);
+    const bool guard = rx > (float)d && ry > (float)d && rx < (float)(W - d) && ry < (float)(H - d);      // false for a NaN
+    const int x = guard ? (int)rx : 0, y = guard ? (int)ry : 0;
+    const int xl = min(max(x - d, 0), W - 1), xr = min(max(x + d, 0), W - 1), xc = min(max(x, 0), W - 1);
+    const int yu = min(max(y - d, 0), H - 1), yd = min(max(y + d, 0), H - 1), yc = min(max(y, 0), H - 1);
+    const unsigned char up = E[(size_t)yu * W + xc], dn = E[(size_t)yd * W + xc], lf = E[(size_t)yc * W + xl], rt = E[(size_t)yc * W + xr];
+    const bool probe = !guard || (up != 0 && dn != 0 && lf != 0 && rt != 0);
+    is_static[i] = ((status ? status[i] != 0 : true) && probe) ? 1 : 0;
+}
+
+// ---- tk_fm_apply: one workgroup ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_fm_apply(TkF f, int K, const float2 *cur, const float2 *fwd, const int *n_dev, int n_host, TkCam cam, double focal, double half_w, double half_h, double epi,
+                                                     unsigned char *status) {
+    const int t = threadIdx.x, m = min(f.fctl[FC_M], TK_MAXN), n = min(n_dev ? *n_dev : n_host, TK_MAXN);
+    const unsigned long long word = *(const unsigned long long *)(f.fctl + FC_BEST);
+    if (m < 8 || word == 0ull) {                             // nothing is rejected
+        if (t < TK_F_RES) f.res[t] = t == 0 ? -1.0 : t == 1 ? (double)m : 0.0;
+        return;
+    }
+    const int k = min(max(K - 1 - (int)(unsigned)(word & 0xffffffffull), 0), K - 1);
+    double F[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) F[e] = f.F[(size_t)k * 9 + e];
+    for (int i = t; i < n; i += TK_NT) {
+        if (!status[i]) continue;
+        const float2 a = tk_f_liftpt(cam, cur[i], focal, half_w, half_h), b = tk_f_liftpt(cam, fwd[i], focal, half_w, half_h);
+        const double x = (double)a.x, y = (double)a.y, xp = (double)b.x, yp = (double)b.y;
+        const double A = __dadd_rn(__dadd_rn(__dmul_rn(F[0], x), __dmul_rn(F[1], y)), F[2]), B = __dadd_rn(__dadd_rn(__dmul_rn(F[3], x), __dmul_rn(F[4], y)), F[5]);
+        const double Cc = __dadd_rn(__dadd_rn(__dmul_rn(F[6], x), __dmul_rn(F[7], y)), F[8]);
+        const double dd = __ddiv_rn(fabs(__dadd_rn(__dadd_rn(__dmul_rn(A, xp), __dmul_rn(B, yp)), Cc)), __dsqrt_rn(__dadd_rn(__dmul_rn(A, A), __dmul_rn(B, B))));
+        if (dd > epi) status[i] = 0;                         // one-sided; a NaN compares false and the point stays
+    }
+    if (t == 0) { f.res[0] = (double)k; f.res[1] = (double)((long long)(word >> 32) - 1); }
+    if (t < 9) f.res[2 + t] = F[t];
+}
+
+// ---- tk_mask_init: forbidden = dynamic (E == 0) or outside the fisheye mask (== 0) ------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_NT) void tk_mask_init(const unsigned char *E, const unsigned char *fish, size_t n, unsigned char *mask) {
+    const size_t at = ((size_t)blockIdx.x * TK_NT + threadIdx.x) * 4;
+    if (at >= n) return;
+    if (at + 4 <= n) {                                       // the buffers come from hipMalloc, so at is 4-byte aligned in all of them
+        const unsigned e = E ? *(const unsigned *)(E + at) : 0xffffffffu, g = fish ? *(const unsigned *)(fish + at) : 0xffffffffu;
+        unsigned out = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) out |= (((e >> (8 * b)) & 0xffu) == 0u || ((g >> (8 * b)) & 0xffu) == 0u) ? (1u << (8 * b)) : 0u;
+        *(unsigned *)(mask + at) = out;
+    } else {
+        for (size_t i = at; i < n; i++) mask[i] = ((E && E[i] == 0) || (fish && fish[i] == 0)) ? 1 : 0;
+    }
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------------
 namespace {
 int tk_sort_bits(size_t cap) { int b = 1; while (((size_t)1 << b) <= cap) b++; return b; }      // the fill pattern (all ones) sorts behind every pixel index
@@ -812,17 +921,60 @@ int tk_reject(vilf_handle *h, TrackCtx *c, const float2 *cur, const float2 *fwd,
     HIPCHECK(h, hipGetLastError());
     return VILF_OK;
 }
+// a W x H byte image (a mask) -> dst on the device, through the pinned mask staging, on the stream
+int tk_upload_mask(vilf_handle *h, TrackCtx *c, unsigned char *dst, const unsigned char *src, int row_stride) {
+    const size_t W = (size_t)c->p.width, H = (size_t)c->p.height;
+    unsigned char *stage = (unsigned char *)c->mstage.p;
+    if ((size_t)row_stride == W) std::memcpy(stage, src, W * H);
+    else for (size_t y = 0; y < H; y++) std::memcpy(stage + y * W, src + y * (size_t)row_stride, W);
+    HIPCHECK(h, hipMemcpyAsync(dst, stage, W * H, hipMemcpyHostToDevice, h->stream));
+    return VILF_OK;
+}
+// the erosion of the text: mask -> E (both on the device, rows tight) with the configured radius
+int tk_erode(vilf_handle *h, TrackCtx *c, const unsigned char *mask, unsigned char *E) {
+    const int W = c->p.width, H = c->p.height, r = c->mp.erode_radius;
+    TkSpans sp;
+    std::memset(&sp, 0, sizeof(sp));
+    sp.r = r;
+    for (int d = 0; d <= r; d++) sp.hw[d] = (int)std::nearbyint(std::sqrt((double)(r * r - d * d)));      // round-half-to-even, the default rounding mode
+    hipLaunchKernelGGL(tk_mask_erode, dim3((W + TK_TW - 1) / TK_TW, (H + TK_TH - 1) / TK_TH), dim3(TK_TW, TK_TH), 0, h->stream, mask, W, H, sp, E);
+    HIPCHECK(h, hipGetLastError());
+    return VILF_OK;
+}
+// rejectWithF_mask: the search of rejectWithF on the pairs flagged in is_static (the mask parameters' threshold; K, seed and focal length as configured), then every
+// pair whose status is set is tested against the winner. Fixed grids, the counts are read on the device
+int tk_reject_mask(vilf_handle *h, TrackCtx *c, const float2 *cur, const float2 *fwd, const unsigned char *is_static, unsigned char *status, const int *n_dev, int n_host) {
+    const TkF f = tk_f(c);
+    const int K = c->fe.n_hypotheses;
+    const double thr2 = c->mp.f_threshold * c->mp.f_threshold, hw = c->p.width / 2.0, hh = c->p.height / 2.0;
+    const TkCam cam = tk_cam(c->p);
+    hipLaunchKernelGGL(tk_f_lift, dim3(1), dim3(TK_NT), 0, h->stream, cur, fwd, is_static, n_dev, n_host, cam, c->fe.focal_length, hw, hh, f);
+    hipLaunchKernelGGL(tk_f_hypotheses, dim3((K + TK_F_LANES - 1) / TK_F_LANES), dim3(TK_F_LANES), 0, h->stream, f, K, c->fe.seed);
+    hipLaunchKernelGGL(tk_f_score, dim3((K + TK_F_WAVES - 1) / TK_F_WAVES), dim3(64 * TK_F_WAVES), 0, h->stream, f, K, thr2);
+    hipLaunchKernelGGL(tk_fm_apply, dim3(1), dim3(TK_NT), 0, h->stream, f, K, cur, fwd, n_dev, n_host, cam, c->fe.focal_length, hw, hh, c->mp.epi_threshold, status);
+    HIPCHECK(h, hipGetLastError());
+    return VILF_OK;
+}
+vilf_track_mask_params tk_mp_defaults() {
+    vilf_track_mask_params mp;
+    std::memset(&mp, 0, sizeof(mp));
+    mp.erode_radius = 5; mp.probe = 5; mp.reject = 1; mp.f_threshold = 0.1; mp.epi_threshold = 1.0;
+    return mp;
+}
 vilf_track_frontend tk_fe_defaults() {
     vilf_track_frontend fe;
     std::memset(&fe, 0, sizeof(fe));
     fe.clahe_clip = 3.0; fe.clahe_tiles_x = 8; fe.clahe_tiles_y = 8; fe.f_threshold = 1.0; fe.focal_length = 460.0; fe.n_hypotheses = 512;
     return fe;
 }
-// mask, response, candidates, the two sorts, the greedy acceptance: ctl holds kept / n_max / candidate count 0 / lambda max 0, l.pts the kept points
-int tk_detect(vilf_handle *h, TrackCtx *c, const unsigned char *img, int *ctl, TkList l, int list_cap) {
+// mask, response, candidates, the two sorts, the greedy acceptance: ctl holds kept / n_max / candidate count 0 / lambda max 0, l.pts the kept points. E: the eroded
+// dynamic mask (device) or null; the fisheye mask is the tracker's. With neither the forbidden-pixel map starts from a memset, as it always did
+int tk_detect(vilf_handle *h, TrackCtx *c, const unsigned char *img, const unsigned char *E, int *ctl, TkList l, int list_cap) {
     const int W = c->p.width, H = c->p.height, cap = (int)c->ncell;
     const long long md = c->p.min_dist, md2 = md * md;
-    HIPCHECK(h, hipMemsetAsync(c->mask.p, 0, c->ncell, h->stream));
+    const unsigned char *fish = c->has_fish ? c->fish.as<unsigned char>() : nullptr;
+    if (E || fish) hipLaunchKernelGGL(tk_mask_init, dim3((unsigned)((c->ncell + 4 * TK_NT - 1) / (4 * TK_NT))), dim3(TK_NT), 0, h->stream, E, fish, c->ncell, c->mask.as<unsigned char>());
+    else HIPCHECK(h, hipMemsetAsync(c->mask.p, 0, c->ncell, h->stream));
     HIPCHECK(h, hipMemsetAsync(c->cidx.p, 0xff, c->ncell * 4, h->stream));
     hipLaunchKernelGGL(tk_paint, dim3(list_cap), dim3(TK_NT), 0, h->stream, l.pts, ctl, c->mask.as<unsigned char>(), W, H, md, md2);
     hipLaunchKernelGGL(tk_response, dim3((W + TK_TW - 1) / TK_TW, (H + TK_TH - 1) / TK_TH), dim3(TK_TW, TK_TH), 0, h->stream, img, c->mask.as<unsigned char>(), W, H, ctl, c->lam.as<double>());
@@ -861,6 +1013,7 @@ extern "C" int vilf_track_init(vilf_handle *h, const vilf_track_params *p) {
     TrackCtx *c = new TrackCtx();
     c->p = *p;
     c->fe = tk_fe_defaults();
+    c->mp = tk_mp_defaults();
     c->ncell = (size_t)p->width * p->height;
     bool ok = true;
     for (int k = 0; k < 4 && ok; k++) {
@@ -882,7 +1035,8 @@ extern "C" int vilf_track_init(vilf_handle *h, const vilf_track_params *p) {
          c->tmpctl.ensure(TC_INTS * 4) && c->prev_ids.ensure(TK_MAXN * 4) && c->prev_un.ensure(TK_MAXN * 8) && c->fwd.ensure(TK_MAXN * 8) && c->status.ensure(TK_MAXN) &&
          c->lkpts.ensure(TK_MAXN * 8) && c->mask.ensure(n) && c->lam.ensure(n * 8) && c->cidx.ensure(n * 4) && c->cidx2.ensure(n * 4) && c->cval.ensure(n * 4) && c->key.ensure(n * 8) &&
          c->key2.ensure(n * 8) && c->val.ensure(n * 4) && c->val2.ensure(n * 4) && c->temp.ensure(std::max(vilf_sort_temp_bytes(n, 8), vilf_sort_temp_bytes(n, 4)) + 256) &&
-         c->pin.ensure(tk_list_bytes(TK_MAXN)) && c->raw.ensure(n) && c->lut.ensure((size_t)VILF_TRACK_MAX_TILES * 256) && c->fmem.ensure(TKF_BYTES);
+         c->pin.ensure(tk_list_bytes(TK_MAXN)) && c->raw.ensure(n) && c->lut.ensure((size_t)VILF_TRACK_MAX_TILES * 256) && c->fmem.ensure(TKF_BYTES) &&
+         c->mraw.ensure(n) && c->er.ensure(n) && c->fish.ensure(n) && c->sstatus.ensure(TK_MAXN) && c->mstage.ensure(n);
     if (!ok) { c->release(); delete c; h->err = "hipMalloc failed (feature tracker)"; return VILF_ERR_DEVICE; }
     h->trk = c;
     return vilf_track_reset(h);
@@ -901,16 +1055,14 @@ extern "C" int vilf_track_reset(vilf_handle *h) {
     return VILF_OK;
 }
 
-extern "C" int vilf_track_read_image(vilf_handle *h, const unsigned char *img, int row_stride, double stamp, int *n_out) {
-    if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    TrackCtx *c = tk_ctx(h, "vilf_track_read_image");
-    if (!c) return VILF_ERR_INVALID_ARGUMENT;
-    if (!img || row_stride < c->p.width) { h->err = "vilf_track_read_image: null image or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
+namespace {
+// one frame of readImage (mask == null) or readImage_mask: the arguments are checked by the two entry points
+int tk_frame(vilf_handle *h, TrackCtx *c, const unsigned char *img, int row_stride, const unsigned char *mask, int mask_row_stride, double stamp, int *n_out) {
     HIPCHECK(h, hipSetDevice(h->device));
     const bool prof = h->profiling != 0;
     if (prof) vilf_track_profile_reset(h);                  // the stages of the last frame
-    hipEvent_t ev[TK_STAGES + 1], fev[2 * TK_FE_STAGES];
-    const bool eq = c->fe.equalize != 0, rej = c->fe.reject_f != 0 && c->frames > 0;
+    hipEvent_t ev[TK_STAGES + 1], fev[2 * TK_FE_STAGES], mev[2 * TK_MK_STAGES];
+    const bool eq = c->fe.equalize != 0, rej = !mask && c->fe.reject_f != 0 && c->frames > 0, trk = mask && c->frames > 0;      // the masked entry point has its own rejection
     auto mark = [&](int k) { if (prof) ev[k] = vilf_prof_event(h); };
     TkPyr &cur = c->pyr[c->cur], &nxt = c->pyr[c->cur ^ 1];
     TkList lc = tk_list(c->list[c->lcur].p, TK_MAXN), ln = tk_list(c->list[c->lcur ^ 1].p, TK_MAXN);
@@ -919,11 +1071,21 @@ extern "C" int vilf_track_read_image(vilf_handle *h, const unsigned char *img, i
     mark(0);
     if (eq) {                                                // the raw image into its own buffer, the equalised one straight into level 0
         { const int rc = tk_upload(h, nxt, c->raw.as<unsigned char>(), (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride); if (rc != VILF_OK) return rc; }
+        if (mask) { const int rc = tk_upload_mask(h, c, c->mraw.as<unsigned char>(), mask, mask_row_stride); if (rc != VILF_OK) return rc; }
         if (prof) fev[0] = vilf_prof_event(h);
         { const int rc = tk_clahe(h, c, c->raw.as<unsigned char>(), nxt.lv[0]); if (rc != VILF_OK) return rc; }
         if (prof) fev[1] = vilf_prof_event(h);
         { const int rc = tk_levels(h, nxt, nxt.lmax); if (rc != VILF_OK) return rc; }
+    } else if (mask) {                                       // both uploads in front of the kernels
+        { const int rc = tk_upload(h, nxt, nxt.lv[0], (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride); if (rc != VILF_OK) return rc; }
+        { const int rc = tk_upload_mask(h, c, c->mraw.as<unsigned char>(), mask, mask_row_stride); if (rc != VILF_OK) return rc; }
+        { const int rc = tk_levels(h, nxt, nxt.lmax); if (rc != VILF_OK) return rc; }
     } else { const int rc = tk_build(h, nxt, (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride, nxt.lmax); if (rc != VILF_OK) return rc; }
+    if (mask) {                                              // E serves the probe and the detection, so it is made on the first frame too
+        if (prof) mev[0] = vilf_prof_event(h);
+        { const int rc = tk_erode(h, c, c->mraw.as<unsigned char>(), c->er.as<unsigned char>()); if (rc != VILF_OK) return rc; }
+        if (prof) mev[1] = vilf_prof_event(h);
+    }
     mark(1);
     if (c->frames > 0)
         hipLaunchKernelGGL(tk_lk, dim3((c->p.max_cnt + TK_LK_WAVES - 1) / TK_LK_WAVES), dim3(64 * TK_LK_WAVES), 0, h->stream, cur, nxt, lc.pts, ctl + TC_N, 0, c->fwd.as<float2>(), c->status.as<unsigned char>(), 1);
@@ -932,11 +1094,19 @@ extern "C" int vilf_track_read_image(vilf_handle *h, const unsigned char *img, i
         { const int rc = tk_reject(h, c, lc.pts, c->fwd.as<float2>(), c->status.as<unsigned char>(), ctl + TC_N, 0); if (rc != VILF_OK) return rc; }
         if (prof) fev[3] = vilf_prof_event(h);
     }
+    if (trk) {                                               // probe -> the static status; the rejection clears LK's status bytes, which tk_setmask reads
+        if (prof) mev[2] = vilf_prof_event(h);
+        hipLaunchKernelGGL(tk_mask_probe, dim3((c->p.max_cnt + TK_NT - 1) / TK_NT), dim3(TK_NT), 0, h->stream, c->er.as<unsigned char>(), c->fwd.as<float2>(), c->status.as<unsigned char>(), ctl + TC_N, 0,
+                           c->p.width, c->p.height, c->mp.probe, c->sstatus.as<unsigned char>());
+        if (c->mp.reject) { const int rc = tk_reject_mask(h, c, lc.pts, c->fwd.as<float2>(), c->sstatus.as<unsigned char>(), c->status.as<unsigned char>(), ctl + TC_N, 0); if (rc != VILF_OK) return rc; }
+        if (prof) mev[3] = vilf_prof_event(h);
+    }
     mark(2);
-    hipLaunchKernelGGL(tk_setmask, dim3(1), dim3(TK_NT), 0, h->stream, lc, c->fwd.as<float2>(), c->status.as<unsigned char>(), ln, ctl, c->p.max_cnt, md * md);
+    hipLaunchKernelGGL(tk_setmask, dim3(1), dim3(TK_NT), 0, h->stream, lc, c->fwd.as<float2>(), c->status.as<unsigned char>(), ln, ctl, c->p.max_cnt, md * md,
+                       c->has_fish ? c->fish.as<unsigned char>() : (const unsigned char *)nullptr, c->p.width, c->p.height);
     HIPCHECK(h, hipGetLastError());
     mark(3);
-    { const int rc = tk_detect(h, c, nxt.lv[0], ctl, ln, c->p.max_cnt); if (rc != VILF_OK) return rc; }
+    { const int rc = tk_detect(h, c, nxt.lv[0], mask ? c->er.as<unsigned char>() : nullptr, ctl, ln, c->p.max_cnt); if (rc != VILF_OK) return rc; }
     mark(4);
     hipLaunchKernelGGL(tk_finish, dim3(1), dim3(TK_NT), 0, h->stream, ln, ctl, c->prev_ids.as<int>(), c->prev_un.as<float2>(), tk_cam(c->p), stamp - c->t_prev, c->frames > 0 ? 1 : 0);
     HIPCHECK(h, hipGetLastError());
@@ -944,12 +1114,31 @@ extern "C" int vilf_track_read_image(vilf_handle *h, const unsigned char *img, i
     if (prof) for (int k = 0; k < TK_STAGES; k++) vilf_prof_span(h, ev[k], ev[k + 1], &c->ms[k], &c->launches[k]);
     if (prof && eq) vilf_prof_span(h, fev[0], fev[1], &c->fe_ms[0], &c->fe_launches[0]);
     if (prof && rej) vilf_prof_span(h, fev[2], fev[3], &c->fe_ms[1], &c->fe_launches[1]);
+    if (prof && mask) vilf_prof_span(h, mev[0], mev[1], &c->mk_ms[0], &c->mk_launches[0]);
+    if (prof && trk) vilf_prof_span(h, mev[2], mev[3], &c->mk_ms[1], &c->mk_launches[1]);
     HIPCHECK(h, vilf_copy_sync(h, c->pin.p, ln.hdr, tk_list_bytes(TK_MAXN), hipMemcpyDeviceToHost));
     if (prof) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
     c->cur ^= 1; c->lcur ^= 1; c->frames++; c->t_prev = stamp;
     c->n_host = std::min(std::max(((const int *)c->pin.p)[0], 0), c->p.max_cnt);
     if (n_out) *n_out = c->n_host;
     return VILF_OK;
+}
+}  // namespace
+
+extern "C" int vilf_track_read_image(vilf_handle *h, const unsigned char *img, int row_stride, double stamp, int *n_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_read_image");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!img || row_stride < c->p.width) { h->err = "vilf_track_read_image: null image or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
+    return tk_frame(h, c, img, row_stride, nullptr, 0, stamp, n_out);
+}
+
+extern "C" int vilf_track_read_image_mask(vilf_handle *h, const unsigned char *img, int row_stride, const unsigned char *mask, int mask_row_stride, double stamp, int *n_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_read_image_mask");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!img || !mask || row_stride < c->p.width || mask_row_stride < c->p.width) { h->err = "vilf_track_read_image_mask: null image or mask, or a row stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
+    return tk_frame(h, c, img, row_stride, mask, mask_row_stride, stamp, n_out);
 }
 
 extern "C" int vilf_track_get(vilf_handle *h, int cap, int *ids, int *track_cnt, float *cur_pts, float *un_pts, float *velocity, int *n_out) {
@@ -1001,15 +1190,17 @@ extern "C" int vilf_track_lk(vilf_handle *h, const unsigned char *img_prev, cons
     return VILF_OK;
 }
 
-extern "C" int vilf_track_detect(vilf_handle *h, const unsigned char *img, const float *kept_pts, int n_kept, int n_max, float *pts_out, int *n_out) {
+namespace {
+// vilf_track_detect (eroded == null) and vilf_track_detect_masked
+int tk_detect_call(vilf_handle *h, const char *who, const unsigned char *img, const unsigned char *eroded, bool masked, const float *kept_pts, int n_kept, int n_max, float *pts_out, int *n_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    TrackCtx *c = tk_ctx(h, "vilf_track_detect");
+    TrackCtx *c = tk_ctx(h, who);
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
-    if (!img || !n_out || n_kept < 0 || n_kept > TK_MAXN || (n_kept > 0 && !kept_pts) || n_max > TK_MAXN || (n_max > 0 && !pts_out)) {
-        h->err = "vilf_track_detect: null pointer, or more than VILF_MAX_FEATURES kept points or new corners"; return VILF_ERR_INVALID_ARGUMENT;
+    if (!img || (masked && !eroded) || !n_out || n_kept < 0 || n_kept > TK_MAXN || (n_kept > 0 && !kept_pts) || n_max > TK_MAXN || (n_max > 0 && !pts_out)) {
+        h->err = std::string(who) + ": null pointer, or more than VILF_MAX_FEATURES kept points or new corners"; return VILF_ERR_INVALID_ARGUMENT;
     }
     for (int i = 0; i < 2 * n_kept; i++)
-        if (!(std::fabs(kept_pts[i]) <= 1.0e6f)) { h->err = "vilf_track_detect: a kept point that is not finite or beyond 1e6 pixels"; return VILF_ERR_INVALID_ARGUMENT; }
+        if (!(std::fabs(kept_pts[i]) <= 1.0e6f)) { h->err = std::string(who) + ": a kept point that is not finite or beyond 1e6 pixels"; return VILF_ERR_INVALID_ARGUMENT; }
     *n_out = 0;
     if (n_max <= 0) return VILF_OK;
     HIPCHECK(h, hipSetDevice(h->device));
@@ -1021,12 +1212,22 @@ extern "C" int vilf_track_detect(vilf_handle *h, const unsigned char *img, const
     HIPCHECK(h, hipMemcpyAsync(c->tmpctl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, h->stream));
     if (n_kept > 0) HIPCHECK(h, hipMemcpyAsync(l.pts, kept_pts, (size_t)n_kept * 8, hipMemcpyHostToDevice, h->stream));
     { const int rc = tk_build(h, P, (unsigned char *)c->stage[2].p, img, P.w[0], 0); if (rc != VILF_OK) return rc; }
-    { const int rc = tk_detect(h, c, P.lv[0], c->tmpctl.as<int>(), l, std::max(n_kept, 1)); if (rc != VILF_OK) return rc; }
+    if (eroded) { const int rc = tk_upload_mask(h, c, c->er.as<unsigned char>(), eroded, c->p.width); if (rc != VILF_OK) return rc; }      // E is scratch of a single call
+    { const int rc = tk_detect(h, c, P.lv[0], eroded ? c->er.as<unsigned char>() : nullptr, c->tmpctl.as<int>(), l, std::max(n_kept, 1)); if (rc != VILF_OK) return rc; }
     HIPCHECK(h, vilf_copy_sync(h, ctl, c->tmpctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
     const int n_new = std::min(std::max(ctl[TC_N] - n_kept, 0), n_max);
     if (n_new > 0) HIPCHECK(h, vilf_copy_sync(h, pts_out, l.pts + n_kept, (size_t)n_new * 8, hipMemcpyDeviceToHost));
     *n_out = n_new;
     return VILF_OK;
+}
+}  // namespace
+
+extern "C" int vilf_track_detect(vilf_handle *h, const unsigned char *img, const float *kept_pts, int n_kept, int n_max, float *pts_out, int *n_out) {
+    return tk_detect_call(h, "vilf_track_detect", img, nullptr, false, kept_pts, n_kept, n_max, pts_out, n_out);
+}
+
+extern "C" int vilf_track_detect_masked(vilf_handle *h, const unsigned char *img, const unsigned char *eroded, const float *kept_pts, int n_kept, int n_max, float *pts_out, int *n_out) {
+    return tk_detect_call(h, "vilf_track_detect_masked", img, eroded, true, kept_pts, n_kept, n_max, pts_out, n_out);
 }
 
 extern "C" int vilf_track_profile(vilf_handle *h, double ms_out[5], long launches_out[5]) {
@@ -1097,5 +1298,102 @@ extern "C" int vilf_track_profile_frontend(vilf_handle *h, double ms_out[2], lon
     if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
     { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
     for (int i = 0; i < TK_FE_STAGES; i++) { ms_out[i] = h->trk ? h->trk->fe_ms[i] : 0.0; launches_out[i] = h->trk ? h->trk->fe_launches[i] : 0; }
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_configure_mask(vilf_handle *h, const vilf_track_mask_params *mp) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_configure_mask");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!mp) { h->err = "vilf_track_configure_mask: null parameters"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (mp->erode_radius < 0 || mp->erode_radius > VILF_TRACK_MAX_ERODE || mp->probe < 1 || mp->probe > 64 || (mp->reject != 0 && mp->reject != 1) || !std::isfinite(mp->f_threshold) ||
+        !(mp->f_threshold > 0) || !std::isfinite(mp->epi_threshold) || !(mp->epi_threshold > 0)) {
+        h->err = "vilf_track_configure_mask: 0 <= erode_radius <= VILF_TRACK_MAX_ERODE, 1 <= probe <= 64, reject 0 or 1, positive finite thresholds";
+        return VILF_ERR_INVALID_ARGUMENT;
+    }
+    c->mp = *mp;
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_set_fisheye_mask(vilf_handle *h, const unsigned char *mask, int row_stride) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_set_fisheye_mask");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!mask) { c->has_fish = false; return VILF_OK; }
+    if (row_stride < c->p.width) { h->err = "vilf_track_set_fisheye_mask: row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
+    HIPCHECK(h, hipSetDevice(h->device));
+    { const int rc = tk_upload_mask(h, c, c->fish.as<unsigned char>(), mask, row_stride); if (rc != VILF_OK) return rc; }
+    HIPCHECK(h, hipStreamSynchronize(h->stream));
+    c->has_fish = true;
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_erode(vilf_handle *h, const unsigned char *mask, int row_stride, unsigned char *out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_erode");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!mask || !out || row_stride < c->p.width) { h->err = "vilf_track_erode: null pointer or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
+    HIPCHECK(h, hipSetDevice(h->device));
+    // mraw, er and sstatus are scratch of a single call (a masked frame or a stateless call): nothing of the tracked state lives in them between calls
+    { const int rc = tk_upload_mask(h, c, c->mraw.as<unsigned char>(), mask, row_stride); if (rc != VILF_OK) return rc; }
+    { const int rc = tk_erode(h, c, c->mraw.as<unsigned char>(), c->er.as<unsigned char>()); if (rc != VILF_OK) return rc; }
+    HIPCHECK(h, vilf_copy_sync(h, out, c->er.p, c->ncell, hipMemcpyDeviceToHost));
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_probe(vilf_handle *h, const unsigned char *eroded, const float *pts, int n, unsigned char *static_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_probe");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (!eroded || n < 0 || n > TK_MAXN || (n > 0 && (!pts || !static_out))) { h->err = "vilf_track_probe: null pointer, n < 0 or n > VILF_MAX_FEATURES"; return VILF_ERR_INVALID_ARGUMENT; }
+    for (int i = 0; i < 2 * n; i++)
+        if (!std::isfinite(pts[i])) { h->err = "vilf_track_probe: a coordinate that is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return VILF_OK;
+    HIPCHECK(h, hipSetDevice(h->device));
+    { const int rc = tk_upload_mask(h, c, c->er.as<unsigned char>(), eroded, c->p.width); if (rc != VILF_OK) return rc; }
+    HIPCHECK(h, hipMemcpyAsync(c->fwd.p, pts, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(tk_mask_probe, dim3((n + TK_NT - 1) / TK_NT), dim3(TK_NT), 0, h->stream, c->er.as<unsigned char>(), c->fwd.as<float2>(), (const unsigned char *)nullptr, (const int *)nullptr, n,
+                       c->p.width, c->p.height, c->mp.probe, c->sstatus.as<unsigned char>());
+    HIPCHECK(h, hipGetLastError());
+    HIPCHECK(h, vilf_copy_sync(h, static_out, c->sstatus.p, (size_t)n, hipMemcpyDeviceToHost));
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_reject_f_mask(vilf_handle *h, const float *cur_pts, const float *forw_pts, const unsigned char *is_static, int n, unsigned char *status_out, double F_out[9], int *best_out,
+                                        int *n_static_inliers_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    TrackCtx *c = tk_ctx(h, "vilf_track_reject_f_mask");
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;
+    if (n < 0 || n > TK_MAXN || !F_out || !best_out || !n_static_inliers_out || (n > 0 && (!cur_pts || !forw_pts || !is_static || !status_out))) {
+        h->err = "vilf_track_reject_f_mask: null pointer, n < 0 or n > VILF_MAX_FEATURES"; return VILF_ERR_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < 2 * n; i++)
+        if (!std::isfinite(cur_pts[i]) || !std::isfinite(forw_pts[i])) { h->err = "vilf_track_reject_f_mask: a coordinate that is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
+    int m = 0;
+    for (int i = 0; i < n; i++) m += is_static[i] ? 1 : 0;
+    if (m >= 8) {
+        HIPCHECK(h, hipSetDevice(h->device));
+        HIPCHECK(h, hipMemcpyAsync(c->lkpts.p, cur_pts, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(h, hipMemcpyAsync(c->fwd.p, forw_pts, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(h, hipMemcpyAsync(c->sstatus.p, is_static, (size_t)n, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(h, hipMemsetAsync(c->status.p, 1, (size_t)n, h->stream));
+        { const int rc = tk_reject_mask(h, c, c->lkpts.as<float2>(), c->fwd.as<float2>(), c->sstatus.as<unsigned char>(), c->status.as<unsigned char>(), nullptr, n); if (rc != VILF_OK) return rc; }
+        double res[TK_F_RES];
+        HIPCHECK(h, hipMemcpyAsync(status_out, c->status.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(h, vilf_copy_sync(h, res, tk_f(c).res, sizeof(res), hipMemcpyDeviceToHost));
+        *best_out = (int)res[0]; *n_static_inliers_out = (int)res[1];
+        for (int e = 0; e < 9; e++) F_out[e] = res[2 + e];
+        return VILF_OK;
+    }
+    for (int i = 0; i < n; i++) status_out[i] = 1;           // fewer than 8 static pairs: rejectWithF_mask does nothing
+    for (int e = 0; e < 9; e++) F_out[e] = 0.0;
+    *best_out = -1; *n_static_inliers_out = m;
+    return VILF_OK;
+}
+
+extern "C" int vilf_track_profile_mask(vilf_handle *h, double ms_out[2], long launches_out[2]) {
+    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
+    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
+    for (int i = 0; i < TK_MK_STAGES; i++) { ms_out[i] = h->trk ? h->trk->mk_ms[i] : 0.0; launches_out[i] = h->trk ? h->trk->mk_launches[i] : 0; }
     return VILF_OK;
 }

@@ -687,7 +687,9 @@ class FeatureTracker:
     """Host mirror of FeatureTracker (feature_tracker/feature_tracker.cpp) over the device tracker of a BackendSolver handle (vilf_track_*): the camera half of the
     feature-tracker node. Images are (height, width) uint8 arrays; camera = (fx, fy, cx, cy, k1, k2, p1, p2). The arithmetic is the contract in include/vilfusion.h.
     equalize = True puts CLAHE (clahe = (clip, tiles_x, tiles_y)) in front of everything; f_threshold = a number of pixels turns rejectWithF on (focal_length,
-    n_hypotheses, seed). With both at their defaults the tracker is never configured and runs as it did before these steps existed."""
+    n_hypotheses, seed). With both at their defaults the tracker is never configured and runs as it did before these steps existed.
+    readImage_mask is the front-end of the second node (feature_tracker_node_mask.cpp): a mask image marks dynamic objects (0 = dynamic); configure_mask sets its
+    parameters, set_fisheye_mask the fixed image that setMask and the detection of both readImage variants start from."""
 
     def __init__(self, solver, width, height, camera, max_cnt=200, min_dist=20, equalize=False, f_threshold=None, focal_length=460.0, clahe=(3.0, 8, 8),
                  n_hypotheses=512, seed=0):
@@ -701,6 +703,7 @@ class FeatureTracker:
                                           1.0 if f_threshold is None else float(f_threshold), float(focal_length), int(n_hypotheses), int(seed))
         if (bool(equalize), f_threshold, float(focal_length), tuple(clahe), int(n_hypotheses), int(seed)) != (False, None, 460.0, (3.0, 8, 8), 512, 0):
             self.s._check(self._L.vilf_track_configure(self.s._h, C.byref(self.frontend)), "vilf_track_configure")
+        self.mask_params = abi.TrackMaskParams(5, 5, 1, 0.1, 1.0)          # the defaults of vilf_track_init
         self._clear()
 
     def _clear(self):
@@ -730,6 +733,16 @@ class FeatureTracker:
         a = self._img(img)
         n = C.c_int(0)
         self.s._check(self._L.vilf_track_read_image(self.s._h, self._u8(a), int(a.strides[0]), float(stamp), C.byref(n)), "vilf_track_read_image")
+        return self._fetch(n)
+
+    def readImage_mask(self, img, mask, stamp):
+        """:212-381: readImage under a mask image of dynamic objects (0 = dynamic, anything else = static). Returns the number of points."""
+        a, m = self._img(img), self._img(mask)
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_track_read_image_mask(self.s._h, self._u8(a), int(a.strides[0]), self._u8(m), int(m.strides[0]), float(stamp), C.byref(n)), "vilf_track_read_image_mask")
+        return self._fetch(n)
+
+    def _fetch(self, n):
         m = max(n.value, 1)
         ids, cnt = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
         pts, un, vel = (np.zeros((m, 2), dtype=np.float32) for _ in range(3))
@@ -781,6 +794,63 @@ class FeatureTracker:
         best, n_in = C.c_int(0), C.c_int(0)
         self.s._check(self._L.vilf_track_reject_f(self.s._h, self._fp(a), self._fp(b), len(a), self._u8(st), abi.dptr(F), C.byref(best), C.byref(n_in)), "vilf_track_reject_f")
         return st[:len(a)], best.value, n_in.value, F
+
+    def configure_mask(self, erode_radius=5, probe=5, reject=True, f_threshold=0.1, epi_threshold=1.0):
+        """the parameters of readImage_mask: the erosion radius, the probe distance, rejectWithF_mask on / off and its two thresholds"""
+        mp = abi.TrackMaskParams(int(erode_radius), int(probe), int(bool(reject)), float(f_threshold), float(epi_threshold))
+        self.s._check(self._L.vilf_track_configure_mask(self.s._h, C.byref(mp)), "vilf_track_configure_mask")
+        self.mask_params = mp
+
+    def set_fisheye_mask(self, mask):
+        """the fisheye mask (None: none): setMask keeps a point only where it is 255, the detection finds corners only where it is not 0"""
+        if mask is None:
+            self.s._check(self._L.vilf_track_set_fisheye_mask(self.s._h, None, 0), "vilf_track_set_fisheye_mask")
+            return
+        m = self._img(mask)
+        self.s._check(self._L.vilf_track_set_fisheye_mask(self.s._h, self._u8(m), int(m.strides[0])), "vilf_track_set_fisheye_mask")
+
+    def erode(self, mask):
+        """the erosion of a mask image with the configured radius (stateless) -> (height, width) uint8, 255 or 0"""
+        m = self._img(mask)
+        out = np.zeros((self.height, self.width), dtype=np.uint8)
+        self.s._check(self._L.vilf_track_erode(self.s._h, self._u8(m), int(m.strides[0]), self._u8(out)), "vilf_track_erode")
+        return out
+
+    def probe(self, eroded, pts):
+        """the probe of points in an eroded mask with the configured distance (stateless) -> (n,) uint8, 1 = static"""
+        e = np.ascontiguousarray(self._img(eroded))
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 2)
+        st = np.zeros(max(len(p), 1), dtype=np.uint8)
+        self.s._check(self._L.vilf_track_probe(self.s._h, self._u8(e), self._fp(p), len(p), self._u8(st)), "vilf_track_probe")
+        return st[:len(p)]
+
+    def reject_f_mask(self, cur_pts, forw_pts, is_static):
+        """rejectWithF_mask on point pairs (stateless) -> (status (n,) uint8, best, n_static_inliers, F (9,) float64); best = -1: nothing rejected"""
+        a, b = (np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 2) for p in (cur_pts, forw_pts))
+        s = np.ascontiguousarray(np.asarray(is_static) != 0, dtype=np.uint8).reshape(-1)
+        assert len(a) == len(b) == len(s)
+        if len(s) == 0:
+            s = np.zeros(1, dtype=np.uint8)
+        st, F = np.zeros(max(len(a), 1), dtype=np.uint8), np.zeros(9)
+        best, n_in = C.c_int(0), C.c_int(0)
+        self.s._check(self._L.vilf_track_reject_f_mask(self.s._h, self._fp(a), self._fp(b), self._u8(s), len(a), self._u8(st), abi.dptr(F), C.byref(best), C.byref(n_in)),
+                      "vilf_track_reject_f_mask")
+        return st[:len(a)], best.value, n_in.value, F
+
+    def detect_masked(self, img, eroded, kept_pts, n_max):
+        """detect() under an eroded mask as well: corners only where it is not 0"""
+        a, e = np.ascontiguousarray(self._img(img)), np.ascontiguousarray(self._img(eroded))
+        kp = np.ascontiguousarray(kept_pts, dtype=np.float32).reshape(-1, 2)
+        out = np.zeros((max(int(n_max), 1), 2), dtype=np.float32)
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_track_detect_masked(self.s._h, self._u8(a), self._u8(e), self._fp(kp), len(kp), int(n_max), self._fp(out), C.byref(n)), "vilf_track_detect_masked")
+        return out[:n.value].copy()
+
+    def profile_mask(self):
+        """ms and launches of the erosion and of the probe with rejectWithF_mask in the last readImage_mask (vilf_set_profiling)"""
+        ms, cnt = (C.c_double * 2)(), (C.c_long * 2)()
+        self.s._check(self._L.vilf_track_profile_mask(self.s._h, ms, cnt), "vilf_track_profile_mask")
+        return {"erode": (ms[0], cnt[0]), "probe_reject": (ms[1], cnt[1])}
 
     def profile_frontend(self):
         """ms and launches of CLAHE and rejectWithF in the last readImage (vilf_set_profiling)"""

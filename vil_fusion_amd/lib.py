@@ -25,6 +25,8 @@ EXPORTED = [
     "vilf_icp_global_map", "vilf_icp_global_map_size", "vilf_icp_global_map_get", "vilf_get_profile_icp_map",
     "vilf_track_init", "vilf_track_reset", "vilf_track_read_image", "vilf_track_get", "vilf_track_pyramid", "vilf_track_lk", "vilf_track_detect", "vilf_track_profile",
     "vilf_track_configure", "vilf_track_clahe", "vilf_track_reject_f", "vilf_track_profile_frontend",
+    "vilf_track_configure_mask", "vilf_track_set_fisheye_mask", "vilf_track_read_image_mask", "vilf_track_erode", "vilf_track_probe", "vilf_track_reject_f_mask",
+    "vilf_track_detect_masked", "vilf_track_profile_mask",
 ]
 
 
@@ -149,6 +151,14 @@ def lib():
     L.vilf_track_clahe.argtypes = [vp, u8p, C.c_int, u8p]
     L.vilf_track_reject_f.argtypes = [vp, fpp, fpp, C.c_int, u8p, abi.c_double_p, ip, ip]
     L.vilf_track_profile_frontend.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_track_configure_mask.argtypes = [vp, C.POINTER(abi.TrackMaskParams)]
+    L.vilf_track_set_fisheye_mask.argtypes = [vp, u8p, C.c_int]
+    L.vilf_track_read_image_mask.argtypes = [vp, u8p, C.c_int, u8p, C.c_int, C.c_double, ip]
+    L.vilf_track_erode.argtypes = [vp, u8p, C.c_int, u8p]
+    L.vilf_track_probe.argtypes = [vp, u8p, fpp, C.c_int, u8p]
+    L.vilf_track_reject_f_mask.argtypes = [vp, fpp, fpp, u8p, C.c_int, u8p, abi.c_double_p, ip, ip]
+    L.vilf_track_detect_masked.argtypes = [vp, u8p, u8p, fpp, C.c_int, C.c_int, fpp, ip]
+    L.vilf_track_profile_mask.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 
