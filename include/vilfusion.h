@@ -533,6 +533,9 @@ int vilf_scan2map_batch_set_scan(vilf_handle *h, int stream, const float *edge_x
 /* stream dst := stream src (local maps, poses, resident scan) by device copies: replicas of a few distinct streams without one upload per stream */
 int vilf_scan2map_batch_copy_stream(vilf_handle *h, int src, int dst);
 int vilf_scan2map_batch_step(vilf_handle *h, int sync);                 /* optimation_processing (:235) for every stream */
+/* A snapshot holds until the next one. A call that writes a stream's map outside a step (vilf_scan2map_batch_init,
+ * vilf_scan2map_batch_copy_stream) drops it: vilf_scan2map_batch_rewind then fails with VILF_ERR_INVALID_ARGUMENT
+ * ("no snapshot") until a new snapshot is taken. */
 int vilf_scan2map_batch_snapshot(vilf_handle *h);                       /* remember maps + poses ... */
 int vilf_scan2map_batch_rewind(vilf_handle *h);                         /* ... and restore them (bench loop: repeated identical steps) */
 int vilf_scan2map_batch_results(vilf_handle *h, int first, int n, vilf_scan2map_result *res);

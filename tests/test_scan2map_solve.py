@@ -13,6 +13,7 @@ import pytest
 from vil_fusion_amd import abi
 import s2m_solve_reference as R
 import s2m_solve_cases as cases_mod
+from s2m_scene import scene as _scene
 
 CASES = cases_mod.all_cases()
 CASE_BY_NAME = {c["name"]: c for c in CASES}
@@ -340,19 +341,6 @@ def test_hook_refusals_leave_the_outputs_untouched(opts, contexts):
     rc, o = call_hook(s2, 1, c["pose"], 1, 300, c["kind_slot"], c["rec_slot"], c["cp_slot"], 0.1, 7, trace_rows=8)
     assert rc == 0 and o["nfe"][0] + o["nfs"][0] == c["n_valid"]
     s2.close()
-
-
-def _scene(seed):
-    """a room: floor, two walls and four poles, one point per 0.8 m leaf at most after the filter"""
-    rng = np.random.default_rng(seed)
-    g = np.arange(-8.0, 8.01, 0.25)
-    floor = np.array([[x, y, -1.5] for x in g for y in g])
-    wall1 = np.array([[8.0, y, z] for y in g for z in np.arange(-1.5, 2.01, 0.25)])
-    wall2 = np.array([[x, -8.0, z] for x in g for z in np.arange(-1.5, 2.01, 0.25)])
-    surf = np.vstack([floor, wall1, wall2])
-    poles = np.vstack([np.array([[px, py, z] for z in np.arange(-1.5, 2.5, 0.05)]) for px, py in ((3.0, 2.0), (-4.0, 5.0), (5.0, -5.0), (-3.0, -4.0))])
-    f4 = lambda p: np.column_stack([p + rng.normal(0, 0.004, p.shape), np.ones(len(p))]).astype(np.float32)
-    return f4(poles), f4(surf)
 
 
 def _one_per_leaf(pts, leaf):

@@ -24,6 +24,7 @@
 #include <climits>
 #include <algorithm>
 #include <utility>
+#include <type_traits>
 #include "vilf_sort.hpp"
 #include "vilf_internal.hpp"
 #include "vilf_device.hpp"
@@ -2164,44 +2165,67 @@ __global__ void b_finish(const double *pose_all, const int *n_map_e, const int *
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host
+struct S2BMapState {            // what a snapshot has to remember about a local map on the host
+    int order = 0;              // in ascending (cell-major) leaf order? 0 unknown, 1 yes (every step leaves it so), 2 no (as initialised)
+    bool dir_ok = false;        // dir is the directory of pts for every stream (entries tagged dir_tag)
+    unsigned dir_tag = 0;
+    std::vector<int> cmn;       // per stream: how many leading points are in cell-major order and therefore handed out in PCL order by get_map (INT_MAX: all — the state after a step)
+};
+struct S2BMap {                 // one local map (edge = 0, surf = 1) of every stream
+    // pts: the current map; alt: where the next step writes its map. The neighbour directory travels with its map: dir pairs with pts, dirAlt with alt (the map update
+    // writes the directory of the map it emits). sorted: cell-major copy of an unordered map, afterwards the map update's queue of uncommon points.
+    DBuf pts, alt, n, dir, dirAlt, sorted, fixq;
+    void release() { for (DBuf *b : {&pts, &alt, &n, &dir, &dirAlt, &sorted, &fixq}) b->release(); }
+    int cap = 0, cs_cfg = 0;    // fixed at reserve time: capacity per stream, cell shift of the cell-major order (s2b_cell_shift), leaf size and its inverse
+    float leaf = 0.0f, inv = 0.0f;
+    S2BMapState st;
+    int cs_idx = 0;             // rebuilt by every s2b_build_index: the cell shift of this step's directory (larger for an unordered map whose extent needs it) and whether
+    bool idx_copy = false;      // this step's search runs on the sorted COPY of an unordered map (w = original index) instead of the map itself
+    std::vector<int> h_n;       // host mirror of the counts (as uploaded; single stream: after every step)
+    CSet cur() { return CSet{pts.as<float4>(), n.as<int>(), cap}; }
+    CSet out() { return CSet{alt.as<float4>(), n.as<int>(), cap}; }
+    float4 *row(int sid) { return pts.as<float4>() + (size_t)sid * cap; }
+    void swap_buffers() { std::swap(pts, alt); std::swap(dir, dirAlt); }
+};
+struct S2BScan {                // the scan side of one feature kind: resident scans (raw) and their voxel grids (ds)
+    DBuf raw, n, ds, nDs;
+    DBuf svlist;                // streams b_scan_voxel_runs hands back to b_scan_voxel: [0] count, [1..] stream ids
+    DBuf bigmap;                // streams whose scan cloud does not fit the in-LDS voxel grid (b_scan_voxel): the global-sort path takes them as a sub-batch (h_big: as uploaded)
+    void release() { for (DBuf *b : {&raw, &n, &ds, &nDs, &svlist, &bigmap}) b->release(); }
+    int cap = 0;
+    std::vector<int> h_n, h_big;
+    CSet cur() { return CSet{raw.as<float4>(), n.as<int>(), cap}; }
+    CSet down() { return CSet{ds.as<float4>(), nDs.as<int>(), cap}; }
+    float4 *row(int sid) { return raw.as<float4>() + (size_t)sid * cap; }
+};
+// While `live`, the snapshot's maps are the buffers live_ptr (a step never overwrites its input maps: rewind = swap back); the step that is about to overwrite them
+// saves them to pts / dir first (s2b_snapshot_save_if_target). A call that writes a stream's map outside a step drops the snapshot (valid = false).
+struct S2BSnap {
+    S2BMapState st[2];
+    DBuf pts[2], n[2], dir[2], pose;
+    void release() { for (DBuf *b : {&pts[0], &pts[1], &n[0], &n[1], &dir[0], &dir[1], &pose}) b->release(); }
+    bool valid = false, live = false;
+    void *live_ptr[2] = {nullptr, nullptr};
+};
 struct S2B {
     int S = 0;
-    int capScan[2] = {0, 0}, capMap[2] = {0, 0};
-    DBuf scan[2], nScan[2], ds[2], nDs[2], map[2], mapAlt[2], nMap[2], tmpB, nTmp, sorted[2], bstart[2], bcnt;   // map: current local maps; mapAlt: where the next step writes its maps
-    DBuf nOld, mOld;                                     // map point counts before the append / surviving the crop (unsorted-map path)
-    DBuf keys, keys2, vals, vals2, temp, mm, frec, fkind, pose, res, err, bits;
-    DBuf map0[2], nMap0[2], pose0, muT, tileHeads;
-    DBuf svlist[2];                              // streams b_scan_voxel_runs hands back to b_scan_voxel: [0] count, [1..] stream ids
-    DBuf bigmap[2]; std::vector<int> h_big[2];   // streams whose scan cloud does not fit the in-LDS voxel grid (b_scan_voxel): the global-sort path takes them as a sub-batch
-    // The neighbour directory travels with its map: bstart pairs with map, bstartAlt with mapAlt (the map update writes the directory of the map it emits), dir0 with map0.
-    DBuf bstartAlt[2], dir0[2], fixq[2];
-    bool dir_ok[2] = {false, false}, snap_dir_ok[2] = {false, false};      // bstart[w] is the directory of map[w] for every stream (tag dir_tag[w])
-    unsigned dir_tag[2] = {0, 0}, snap_dir_tag[2] = {0, 0};
-    unsigned next_tag() { epoch++; return (epoch % 255u + 1u) << 24; }
-    int order_state[2] = {0, 0}, snap_order[2] = {0, 0};   // local maps in ascending (cell-major) leaf order? 0 unknown, 1 yes (every step leaves them so), 2 no (as initialised)
-    int cs_cfg[2] = {0, 0};            // cell shift of the maps' cell-major order (s2b_cell_shift of the leaf size and the crop box)
-    int cs_idx[2] = {0, 0};            // ... of this step's neighbour directory (larger for an unordered map whose extent needs it)
-    bool idx_copy[2] = {false, false}; // this step's search runs on the cell-major-sorted COPY of an unordered map (w = original index) instead of the map itself
-    unsigned epoch = 0;                // directory entries carry (epoch % 255 + 1) << 24: a slot this step did not write reads as empty
-    // how many leading points of a stream's map are in cell-major order and therefore handed out in PCL order by get_map (INT_MAX: all of it — the state after a step)
-    std::vector<int> h_cmn[2], snap_cmn[2];
-    bool has_snapshot = false, scan_dirty = true;
-    bool snap_live = false;            // the snapshot's maps still live in a map / mapAlt buffer (rewind = pointer swap, no copy)
-    void *snap_ptr[2] = {nullptr, nullptr};
-    size_t temp_bytes = 0, work_n = 0;
-    std::vector<int> h_nScan[2], h_nMap[2];
-    std::vector<S2BRes> h_res;
-    CSet cs_scan(int w) { return CSet{scan[w].as<float4>(), nScan[w].as<int>(), capScan[w]}; }
-    CSet cs_ds(int w) { return CSet{ds[w].as<float4>(), nDs[w].as<int>(), capScan[w]}; }
-    CSet cs_map(int w) { return CSet{map[w].as<float4>(), nMap[w].as<int>(), capMap[w]}; }
-    CSet cs_tmp(int w) { return CSet{tmpB.as<float4>(), nTmp.as<int>(), capMap[w]}; }
-    CSet cs_mapout(int w) { return CSet{mapAlt[w].as<float4>(), nMap[w].as<int>(), capMap[w]}; }
+    S2BMap m[2];
+    S2BScan sc[2];
+    S2BSnap snap;
+    DBuf tmpB, nTmp, bcnt, nOld, mOld;                   // nOld, mOld: map point counts before the append / surviving the crop (unsorted-map path)
+    DBuf keys, keys2, vals, vals2, temp, mm, frec, fkind, pose, res, err, bits, muT, tileHeads;
     void release() {
-        DBuf *all[] = {&scan[0], &scan[1], &nScan[0], &nScan[1], &ds[0], &ds[1], &nDs[0], &nDs[1], &map[0], &map[1], &mapAlt[0], &mapAlt[1], &nMap[0], &nMap[1], &tmpB, &nTmp, &sorted[0], &sorted[1],
-                       &bstart[0], &bstart[1], &bcnt, &nOld, &mOld, &keys, &keys2, &vals, &vals2, &temp, &mm, &frec, &fkind, &pose, &res, &err, &bits,
-                       &map0[0], &map0[1], &nMap0[0], &nMap0[1], &pose0, &muT, &tileHeads, &bstartAlt[0], &bstartAlt[1], &dir0[0], &dir0[1], &fixq[0], &fixq[1], &bigmap[0], &bigmap[1]};
-        for (DBuf *b : all) b->release();
+        for (int w = 0; w < 2; w++) { m[w].release(); sc[w].release(); }
+        snap.release();
+        for (DBuf *b : {&tmpB, &nTmp, &bcnt, &nOld, &mOld, &keys, &keys2, &vals, &vals2, &temp, &mm, &frec, &fkind, &pose, &res, &err, &bits, &muT, &tileHeads}) b->release();
     }
+    unsigned epoch = 0;                // directory entries carry (epoch % 255 + 1) << 24: a slot this step did not write reads as empty
+    unsigned next_tag() { epoch++; return (epoch % 255u + 1u) << 24; }
+    bool scan_dirty = true;
+    size_t temp_bytes = 0, work_n = 0;
+    std::vector<S2BRes> h_res;
+    CSet cs_tmp(int w) { return CSet{tmpB.as<float4>(), nTmp.as<int>(), m[w].cap}; }
+    int capq() const { return sc[0].cap + sc[1].cap; }
 };
 
 void vilf_s2m_release(vilf_handle *h) {
@@ -2234,22 +2258,18 @@ static int s2b_reserve(vilf_handle *h, S2B *c, int S, int capScanE, int capScanS
     const int wantScan[2] = {std::max(capScanE, 1), std::max(capScanS, 1)}, wantMap[2] = {std::max(capMapE, 1), std::max(capMapS, 1)};
     if (S != c->S) {
         c->release();
-        c->S = S; c->capScan[0] = c->capScan[1] = c->capMap[0] = c->capMap[1] = 0; c->work_n = 0; c->has_snapshot = false; c->order_state[0] = c->order_state[1] = 0;
-        c->h_big[0].clear(); c->h_big[1].clear();
+        *c = S2B(); c->S = S;
         if (!c->pose.ensure((size_t)S * 24 * 8) || !c->res.ensure((size_t)S * sizeof(S2BRes)) || !c->err.ensure((size_t)S * 4) || !c->mm.ensure((size_t)S * sizeof(MinMax)) || !c->nTmp.ensure((size_t)S * 4) || !c->bits.ensure(64) || !c->nOld.ensure((size_t)S * 4) || !c->mOld.ensure((size_t)S * 4) || !c->bcnt.ensure((size_t)S * 4)) return VILF_ERR_DEVICE;
         HIPCHECK(h, hipMemsetAsync(c->bcnt.p, 0, (size_t)S * 4, h->stream));
         for (int w = 0; w < 2; w++) {
-            if (!c->nScan[w].ensure((size_t)S * 4) || !c->nDs[w].ensure((size_t)S * 4) || !c->nMap[w].ensure((size_t)S * 4) || !c->bstart[w].ensure((size_t)S * S2B_NBS * 4)) return VILF_ERR_DEVICE;
-            if (!c->bstartAlt[w].ensure((size_t)S * S2B_NBS * 4)) return VILF_ERR_DEVICE;
-            HIPCHECK(h, hipMemsetAsync(c->bstart[w].p, 0, (size_t)S * S2B_NBS * 4, h->stream));      // tag 0: no slot is valid yet
-            HIPCHECK(h, hipMemsetAsync(c->bstartAlt[w].p, 0, (size_t)S * S2B_NBS * 4, h->stream));
-            c->dir_ok[w] = false;
-            c->h_cmn[w].assign(S, 0);
-            c->cs_cfg[w] = s2b_cell_shift((float)(w == 0 ? h->opts.edge_leaf_size : h->opts.surf_leaf_size), h->opts.s2m_crop_half);
-            HIPCHECK(h, hipMemsetAsync(c->nScan[w].p, 0, (size_t)S * 4, h->stream));
-            HIPCHECK(h, hipMemsetAsync(c->nDs[w].p, 0, (size_t)S * 4, h->stream));
-            HIPCHECK(h, hipMemsetAsync(c->nMap[w].p, 0, (size_t)S * 4, h->stream));
-            c->h_nScan[w].assign(S, 0); c->h_nMap[w].assign(S, 0);
+            S2BMap &m = c->m[w]; S2BScan &sc = c->sc[w];
+            if (!sc.n.ensure((size_t)S * 4) || !sc.nDs.ensure((size_t)S * 4) || !m.n.ensure((size_t)S * 4) || !m.dir.ensure((size_t)S * S2B_NBS * 4) || !m.dirAlt.ensure((size_t)S * S2B_NBS * 4)) return VILF_ERR_DEVICE;
+            HIPCHECK(h, hipMemsetAsync(m.dir.p, 0, (size_t)S * S2B_NBS * 4, h->stream));      // tag 0: no slot is valid yet
+            HIPCHECK(h, hipMemsetAsync(m.dirAlt.p, 0, (size_t)S * S2B_NBS * 4, h->stream));
+            m.leaf = (float)(w == 0 ? h->opts.edge_leaf_size : h->opts.surf_leaf_size); m.inv = 1.0f / m.leaf;
+            m.cs_cfg = s2b_cell_shift(m.leaf, h->opts.s2m_crop_half);
+            for (DBuf *b : {&sc.n, &sc.nDs, &m.n}) HIPCHECK(h, hipMemsetAsync(b->p, 0, (size_t)S * 4, h->stream));
+            m.st.cmn.assign(S, 0); m.h_n.assign(S, 0); sc.h_n.assign(S, 0);
         }
         std::vector<double> ident((size_t)S * 24, 0.0);
         for (int s = 0; s < S; s++) { ident[24 * s + 3] = 1.0; ident[24 * s + 11] = 1.0; ident[24 * s + 19] = 1.0; }
@@ -2264,32 +2284,32 @@ static int s2b_reserve(vilf_handle *h, S2B *c, int S, int capScanE, int capScanS
     }
     bool grew = false;
     for (int w = 0; w < 2; w++) {
-        if (wantScan[w] > c->capScan[w]) {
-            const int nc = c->capScan[w] ? std::max(wantScan[w], 2 * c->capScan[w]) : wantScan[w];
-            if (!c->scan[w].ensure((size_t)S * nc * 16) || !c->ds[w].ensure((size_t)S * nc * 16)) return VILF_ERR_DEVICE;
-            c->capScan[w] = nc; grew = true; c->scan_dirty = true;
+        S2BMap &m = c->m[w]; S2BScan &sc = c->sc[w];
+        if (wantScan[w] > sc.cap) {
+            const int nc = sc.cap ? std::max(wantScan[w], 2 * sc.cap) : wantScan[w];
+            if (!sc.raw.ensure((size_t)S * nc * 16) || !sc.ds.ensure((size_t)S * nc * 16)) return VILF_ERR_DEVICE;
+            sc.cap = nc; grew = true; c->scan_dirty = true;
         }
-        if (wantMap[w] > c->capMap[w]) {
-            const int oc = c->capMap[w], nc = oc ? std::max(wantMap[w], 2 * oc) : wantMap[w];
+        if (wantMap[w] > m.cap) {
+            const int oc = m.cap, nc = oc ? std::max(wantMap[w], 2 * oc) : wantMap[w];
             if (nc >= (1 << 24)) { h->err = "scan2map: local-map capacity beyond 2^24 points per stream (directory positions are 24 bits)"; return VILF_ERR_UNSUPPORTED; }
             DBuf nb;
             if (!nb.ensure((size_t)S * nc * 16)) return VILF_ERR_DEVICE;
             if (oc) {
-                HIPCHECK(h, hipMemcpy2DAsync(nb.p, (size_t)nc * 16, c->map[w].p, (size_t)oc * 16, (size_t)oc * 16, S, hipMemcpyDeviceToDevice, h->stream));
+                HIPCHECK(h, hipMemcpy2DAsync(nb.p, (size_t)nc * 16, m.pts.p, (size_t)oc * 16, (size_t)oc * 16, S, hipMemcpyDeviceToDevice, h->stream));
                 HIPCHECK(h, hipStreamSynchronize(h->stream));
             }
-            c->map[w].release();
-            c->map[w] = nb;
-            c->capMap[w] = nc; grew = true; c->has_snapshot = false; c->snap_live = false;
-            if (!c->sorted[w].ensure((size_t)S * nc * 16) || !c->mapAlt[w].ensure((size_t)S * nc * 16)) return VILF_ERR_DEVICE;
-            if (!c->fixq[w].ensure((size_t)S * nc * 4)) return VILF_ERR_DEVICE;
+            m.pts.release();
+            m.pts = nb;
+            m.cap = nc; grew = true; c->snap.valid = c->snap.live = false;
+            if (!m.sorted.ensure((size_t)S * nc * 16) || !m.alt.ensure((size_t)S * nc * 16) || !m.fixq.ensure((size_t)S * nc * 4)) return VILF_ERR_DEVICE;
         }
     }
     if (grew) {
-        const int maxMap = std::max(c->capMap[0], c->capMap[1]);
-        const size_t n = (size_t)S * std::max(std::max(c->capScan[0], c->capScan[1]), maxMap);
+        const int maxMap = std::max(c->m[0].cap, c->m[1].cap);
+        const size_t n = (size_t)S * std::max(std::max(c->sc[0].cap, c->sc[1].cap), maxMap);
         if (!c->tmpB.ensure((size_t)S * maxMap * 16)) return VILF_ERR_DEVICE;
-        const size_t capq = (size_t)c->capScan[0] + c->capScan[1];
+        const size_t capq = (size_t)c->capq();
         if (!c->frec.ensure((size_t)S * capq * S2M_FREC * 8) || !c->fkind.ensure((size_t)S * capq * 4)) return VILF_ERR_DEVICE;
         if (n > c->work_n) {
             if (!c->keys.ensure(n * 8) || !c->keys2.ensure(n * 8) || !c->vals.ensure(n * 4) || !c->vals2.ensure(n * 4)) return VILF_ERR_DEVICE;
@@ -2361,23 +2381,25 @@ static int s2b_voxel(vilf_handle *h, S2B *c, CSet in, float leaf, CSet out, int 
 
 // The neighbour directory of local map w for this step. A map in cell-major order (every step leaves it so) is searched in place: one pass writes the directory. A map
 // that is not a voxel grid yet (as initialised) is first copied in cell-major order (global sort; the original index travels in w and breaks distance ties).
+// a fresh directory (new tag) of map m over the points arr (the map itself, or its sorted copy) with cells of 2^cs leaves
+static void s2b_dir_build(vilf_handle *h, S2B *c, S2BMap &m, const float4 *arr, int cs) {
+    m.st.dir_tag = c->next_tag();
+    const dim3 dgrid((m.cap + 256 * DIR_PT - 1) / (256 * DIR_PT), c->S);
+    hipLaunchKernelGGL(b_dir_build, dgrid, dim3(256), 0, h->stream, arr, m.n.as<int>(), m.cap, m.inv, cs, m.st.dir_tag, m.dir.as<unsigned>());
+}
 static int s2b_build_index(vilf_handle *h, S2B *c, int w) {
-    CSet map = c->cs_map(w);
-    const float leaf = (float)(w == 0 ? h->opts.edge_leaf_size : h->opts.surf_leaf_size);
-    c->cs_idx[w] = c->cs_cfg[w]; c->idx_copy[w] = false;
-    if (c->order_state[w] == 1 && c->dir_ok[w]) return VILF_OK;        // the map update that emitted this map wrote its directory: nothing to do
-    const float4 *arr = map.p;
-    if (c->order_state[w] != 1) {
+    S2BMap &m = c->m[w];
+    m.cs_idx = m.cs_cfg; m.idx_copy = false;
+    if (m.st.order == 1 && m.st.dir_ok) return VILF_OK;        // the map update that emitted this map wrote its directory: nothing to do
+    if (m.st.order != 1) {
         bool wide;
-        int rc = s2b_sort_keys(h, c, map, leaf, c->cs_cfg[w], &c->cs_idx[w], &wide);
+        int rc = s2b_sort_keys(h, c, m.cur(), m.leaf, m.cs_cfg, &m.cs_idx, &wide);
         if (rc != VILF_OK) return rc;
-        hipLaunchKernelGGL(b_gather_sorted, GRID2(map.cap, c->S), 0, h->stream, map, c->vals2.as<int>(), c->sorted[w].as<float4>());
-        arr = c->sorted[w].as<float4>(); c->idx_copy[w] = true;
+        hipLaunchKernelGGL(b_gather_sorted, GRID2(m.cap, c->S), 0, h->stream, m.cur(), c->vals2.as<int>(), m.sorted.as<float4>());
+        m.idx_copy = true;
     }
-    c->dir_tag[w] = c->next_tag();
-    const dim3 dgrid((map.cap + 256 * DIR_PT - 1) / (256 * DIR_PT), c->S);
-    hipLaunchKernelGGL(b_dir_build, dgrid, dim3(256), 0, h->stream, arr, map.n, map.cap, 1.0f / leaf, c->cs_idx[w], c->dir_tag[w], c->bstart[w].as<unsigned>());
-    c->dir_ok[w] = !c->idx_copy[w];         // (a directory over the sorted copy of an unordered map serves this step only)
+    s2b_dir_build(h, c, m, m.idx_copy ? m.sorted.as<float4>() : m.pts.as<float4>(), m.cs_idx);
+    m.st.dir_ok = !m.idx_copy;              // (a directory over the sorted copy of an unordered map serves this step only)
     PROF(2)
     return VILF_OK;
 }
@@ -2386,33 +2408,52 @@ static int mu_lds_cap(int cap_scan) { int p2 = 2; while (p2 < cap_scan) p2 <<= 1
 // is every stream's local map w in ascending leaf order (a voxel grid of an earlier step)? One check + 4-byte read-back when unknown
 // (after an init); a step always leaves the maps ordered, so the steady state never comes here.
 static int s2b_resolve_order(vilf_handle *h, S2B *c, int w) {
-    if (c->order_state[w] != 0) return VILF_OK;
-    const float leaf = (float)(w == 0 ? h->opts.edge_leaf_size : h->opts.surf_leaf_size);
+    S2BMap &m = c->m[w];
+    if (m.st.order != 0) return VILF_OK;
     int flag = 0;
     HIPCHECK(h, hipMemsetAsync(c->bits.p, 0, 4, h->stream));
-    hipLaunchKernelGGL(b_check_order, dim3(64, c->S), dim3(256), 0, h->stream, c->cs_map(w), 1.0f / leaf, c->cs_cfg[w], c->capScan[w] > mu_lds_cap(c->capScan[w]) ? 16 : 17, c->bits.as<int>());
+    hipLaunchKernelGGL(b_check_order, dim3(64, c->S), dim3(256), 0, h->stream, m.cur(), m.inv, m.cs_cfg, c->sc[w].cap > mu_lds_cap(c->sc[w].cap) ? 16 : 17, c->bits.as<int>());
     HIPCHECK(h, hipMemcpyAsync(&flag, c->bits.p, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
-    c->order_state[w] = flag ? 2 : 1;
+    m.st.order = flag ? 2 : 1;
     return VILF_OK;
 }
 
 // the two argument blocks of the association launch (edge, surf) on the context's current maps and directories: query clouds ds[2] (their edge count places the surf
-// records), poses, per-stream results (do_opt) and the record / kind arrays. One builder for the step and for the test hook.
-static void s2b_assoc_args(vilf_handle *h, S2B *c, const CSet ds[2], const double *d_pose, const S2BRes *d_res, double *frec, int *fkind, AssocArgs aa[2]) {
-    const float leaf[2] = {(float)h->opts.edge_leaf_size, (float)h->opts.surf_leaf_size};
+// records), poses, per-stream results (do_opt) and the record / kind arrays — and the launch's geometry: edge and surf blocks in one grid sized by the scan capacities,
+// a grid row per stream. One builder for the step and for the test hook.
+struct S2BAssoc { AssocArgs a[2]; int nblk_e; dim3 grid; };
+static S2BAssoc s2b_assoc_args(S2B *c, const CSet ds[2], const double *d_pose, const S2BRes *d_res, double *frec, int *fkind) {
+    S2BAssoc l;
+    l.nblk_e = (c->sc[0].cap + 255) / 256;
+    l.grid = dim3(l.nblk_e + (c->sc[1].cap + 255) / 256, c->S);
     for (int w = 0; w < 2; w++) {
-        AssocArgs &a = aa[w];
+        S2BMap &m = c->m[w];
+        AssocArgs &a = l.a[w];
         a.ds = ds[w]; a.is_surf = w; a.n_ds_edge = ds[0].n; a.pose_all = d_pose;
-        a.sorted_all = c->idx_copy[w] ? c->sorted[w].as<float4>() : c->map[w].as<float4>(); a.n_map = c->nMap[w].as<int>(); a.cap_map = c->capMap[w];
-        a.dir_all = c->bstart[w].as<unsigned>(); a.tag = c->dir_tag[w]; a.inv = 1.0f / leaf[w]; a.cs = c->cs_idx[w]; a.w_is_index = c->idx_copy[w] ? 1 : 0;
-        a.res = d_res; a.frec_all = frec; a.fkind_all = fkind; a.capq = c->capScan[0] + c->capScan[1]; a.tie_count = c->bcnt.as<int>();
+        a.sorted_all = m.idx_copy ? m.sorted.as<float4>() : m.pts.as<float4>(); a.n_map = m.n.as<int>(); a.cap_map = m.cap;
+        a.dir_all = m.dir.as<unsigned>(); a.tag = m.st.dir_tag; a.inv = m.inv; a.cs = m.cs_idx; a.w_is_index = m.idx_copy ? 1 : 0;
+        a.res = d_res; a.frec_all = frec; a.fkind_all = fkind; a.capq = c->capq(); a.tie_count = c->bcnt.as<int>();
     }
+    return l;
 }
-// the association launch itself: edge and surf blocks in one grid sized by the scan capacities, a grid row per stream
-static inline void s2b_assoc_grid(const S2B *c, int *nblk_e, dim3 *grid) {
-    *nblk_e = (c->capScan[0] + 255) / 256;
-    *grid = dim3(*nblk_e + (c->capScan[1] + 255) / 256, c->S);
+
+// A step writes map w's successor into m.alt (the old map stays intact up to its old count: a snapshot taken on it is restored by swapping back). If that buffer is
+// where a live snapshot sits, save the snapshot — both maps and, where it has them, their directories — to its own buffers first: from then on a rewind copies.
+static int s2b_snapshot_save_if_target(vilf_handle *h, S2B *c, int w) {
+    S2BSnap &sn = c->snap;
+    if (!sn.valid || !sn.live || c->m[w].alt.p != sn.live_ptr[w]) return VILF_OK;
+    for (int v = 0; v < 2; v++) {
+        S2BMap &m = c->m[v];
+        const bool cur = m.pts.p == sn.live_ptr[v];
+        if (!sn.pts[v].ensure((size_t)c->S * m.cap * 16)) return VILF_ERR_DEVICE;
+        HIPCHECK(h, hipMemcpyAsync(sn.pts[v].p, cur ? m.pts.p : m.alt.p, (size_t)c->S * m.cap * 16, hipMemcpyDeviceToDevice, h->stream));
+        if (!sn.st[v].dir_ok) continue;
+        if (!sn.dir[v].ensure((size_t)c->S * S2B_NBS * 4)) return VILF_ERR_DEVICE;
+        HIPCHECK(h, hipMemcpyAsync(sn.dir[v].p, cur ? m.dir.p : m.dirAlt.p, (size_t)c->S * S2B_NBS * 4, hipMemcpyDeviceToDevice, h->stream));
+    }
+    sn.live = false;
+    return VILF_OK;
 }
 
 // one optimation_processing() for every stream; everything is enqueued on the handle's stream, no host round trip
@@ -2420,7 +2461,7 @@ static int s2b_step(vilf_handle *h, S2B *c) {
     const int S = c->S;
     int rc;
     if (c->scan_dirty) {
-        for (int w = 0; w < 2; w++) HIPCHECK(h, hipMemcpyAsync(c->nScan[w].p, c->h_nScan[w].data(), (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
+        for (int w = 0; w < 2; w++) HIPCHECK(h, hipMemcpyAsync(c->sc[w].n.p, c->sc[w].h_n.data(), (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
         c->scan_dirty = false;
     }
     double *d_pose = c->pose.as<double>();
@@ -2430,13 +2471,14 @@ static int s2b_step(vilf_handle *h, S2B *c) {
     PROF(6)
     hipLaunchKernelGGL(b_predict, GRIDS(S), 0, h->stream, d_pose, S);
     PROF(6)
-    const float leaf[2] = {(float)h->opts.edge_leaf_size, (float)h->opts.surf_leaf_size};
-    for (int w = 0; w < 2; w++) {
+    for (int w = 0; w < 2; w++) {     // pcl::VoxelGrid of the resident scans
         // the host knows every stream's scan size (vilf_scan2map_batch_set_scan): clouds that fit the LDS get the one-workgroup grid (its layout sized for the largest of them),
         // the others — if any — go through the global-sort path as a sub-batch (grid row -> stream map), not the whole batch
+        S2BScan &sc = c->sc[w];
+        const float inv = c->m[w].inv;
         int nmax = 0;
         std::vector<int> big;
-        for (int i = 0; i < S; i++) { const int n = c->h_nScan[w][i]; if (n > SV_MAXPTS24) big.push_back(i); else nmax = std::max(nmax, n); }
+        for (int i = 0; i < S; i++) { const int n = sc.h_n[i]; if (n > SV_MAXPTS24) big.push_back(i); else nmax = std::max(nmax, n); }
         if ((int)big.size() < S) {
             int cap = (std::max(nmax, 1) + 15) & ~15;
             // small clouds: the tile staging area (32 KB) gets its own LDS — unless that would not fit (15.1 k .. 16.4 k points: the launch asked for up to 172 KB and failed with
@@ -2450,101 +2492,77 @@ static int s2b_step(vilf_handle *h, S2B *c) {
             const int rc = std::max(64, std::min(SR_RC, rc_env)) & ~1;
             int *d_list = nullptr;
             if (!no_runs) {
-                if (!c->svlist[w].ensure(((size_t)S + 1) * 4)) return VILF_ERR_DEVICE;
-                d_list = c->svlist[w].as<int>();
+                if (!sc.svlist.ensure(((size_t)S + 1) * 4)) return VILF_ERR_DEVICE;
+                d_list = sc.svlist.as<int>();
                 HIPCHECK(h, hipMemsetAsync(d_list, 0, 4, h->stream));
-                hipLaunchKernelGGL(b_scan_voxel_runs, dim3(S), dim3(SR_T), sr_lds_bytes(rc), h->stream, c->cs_scan(w), 1.0f / leaf[w], c->cs_ds(w), SV_MAXPTS24, rc, d_list, w == 1 ? 0 : 1);
+                hipLaunchKernelGGL(b_scan_voxel_runs, dim3(S), dim3(SR_T), sr_lds_bytes(rc), h->stream, sc.cur(), inv, sc.down(), SV_MAXPTS24, rc, d_list, w == 1 ? 0 : 1);
             }
             const dim3 gsv(d_list ? (unsigned)std::min(S, 128) : (unsigned)S);
-            if (cap <= SV_MAXPTS32) hipLaunchKernelGGL(b_scan_voxel<false>, gsv, dim3(SV_T), (size_t)cap * 8 + 8192 + stage, h->stream, c->cs_scan(w), 1.0f / leaf[w], c->cs_ds(w), cap, d_err, d_list);
-            else hipLaunchKernelGGL(b_scan_voxel<true>, gsv, dim3(SV_T), (size_t)cap * 7 + 8192 + stage, h->stream, c->cs_scan(w), 1.0f / leaf[w], c->cs_ds(w), cap, d_err, d_list);
+            if (cap <= SV_MAXPTS32) hipLaunchKernelGGL(b_scan_voxel<false>, gsv, dim3(SV_T), (size_t)cap * 8 + 8192 + stage, h->stream, sc.cur(), inv, sc.down(), cap, d_err, d_list);
+            else hipLaunchKernelGGL(b_scan_voxel<true>, gsv, dim3(SV_T), (size_t)cap * 7 + 8192 + stage, h->stream, sc.cur(), inv, sc.down(), cap, d_err, d_list);
             PROF(0)
         }
         if (!big.empty()) {
-            if (big != c->h_big[w]) {
-                if (!c->bigmap[w].ensure(big.size() * 4)) return VILF_ERR_DEVICE;
-                HIPCHECK(h, hipMemcpyAsync(c->bigmap[w].p, big.data(), big.size() * 4, hipMemcpyHostToDevice, h->stream));
+            if (big != sc.h_big) {
+                if (!sc.bigmap.ensure(big.size() * 4)) return VILF_ERR_DEVICE;
+                HIPCHECK(h, hipMemcpyAsync(sc.bigmap.p, big.data(), big.size() * 4, hipMemcpyHostToDevice, h->stream));
                 HIPCHECK(h, hipStreamSynchronize(h->stream));          // `big` is a temporary
-                c->h_big[w] = big;
+                sc.h_big = big;
             }
-            CSet in = c->cs_scan(w), out = c->cs_ds(w);
-            in.smap = out.smap = c->bigmap[w].as<int>();
-            if ((rc = s2b_voxel(h, c, in, leaf[w], out, -1, (int)big.size())) != VILF_OK) return rc;
+            CSet in = sc.cur(), out = sc.down();
+            in.smap = out.smap = sc.bigmap.as<int>();
+            if ((rc = s2b_voxel(h, c, in, c->m[w].leaf, out, -1, (int)big.size())) != VILF_OK) return rc;
         }
     }
-    hipLaunchKernelGGL(b_gate, GRIDS(S), 0, h->stream, c->nMap[0].as<int>(), c->nMap[1].as<int>(), c->nDs[0].as<int>(), c->nDs[1].as<int>(), d_res, d_err, S);
+    hipLaunchKernelGGL(b_gate, GRIDS(S), 0, h->stream, c->m[0].n.as<int>(), c->m[1].n.as<int>(), c->sc[0].nDs.as<int>(), c->sc[1].nDs.as<int>(), d_res, d_err, S);
     PROF(6)
     for (int w = 0; w < 2; w++) {
         if ((rc = s2b_resolve_order(h, c, w)) != VILF_OK) return rc;
         if ((rc = s2b_build_index(h, c, w)) != VILF_OK) return rc;
     }
-    const int capq = c->capScan[0] + c->capScan[1];
-    AssocArgs aa[2];
-    const CSet ds2[2] = {c->cs_ds(0), c->cs_ds(1)};
-    s2b_assoc_args(h, c, ds2, d_pose, d_res, c->frec.as<double>(), c->fkind.as<int>(), aa);
-    int nblk_e; dim3 agrid;
-    s2b_assoc_grid(c, &nblk_e, &agrid);
+    const CSet ds2[2] = {c->sc[0].down(), c->sc[1].down()};
+    const S2BAssoc as = s2b_assoc_args(c, ds2, d_pose, d_res, c->frec.as<double>(), c->fkind.as<int>());
     for (int pass = 0; pass < h->opts.s2m_outer_iterations && pass < 2; pass++) {
-        hipLaunchKernelGGL(b_associate, agrid, dim3(256), 0, h->stream, aa[0], aa[1], nblk_e);
-        hipLaunchKernelGGL(b_associate_ties, dim3(S), dim3(256), 0, h->stream, aa[0], aa[1]);      // queries that met exactly equal distances (rare), in the reference's order
+        hipLaunchKernelGGL(b_associate, as.grid, dim3(256), 0, h->stream, as.a[0], as.a[1], as.nblk_e);
+        hipLaunchKernelGGL(b_associate_ties, dim3(S), dim3(256), 0, h->stream, as.a[0], as.a[1]);      // queries that met exactly equal distances (rare), in the reference's order
         PROF(3)
-        hipLaunchKernelGGL(b_solve, dim3(S), dim3(S2M_NT), 0, h->stream, d_pose, c->frec.as<double>(), c->fkind.as<int>(), capq, c->nDs[0].as<int>(), c->nDs[1].as<int>(), h->opts.huber_a,
+        hipLaunchKernelGGL(b_solve, dim3(S), dim3(S2M_NT), 0, h->stream, d_pose, c->frec.as<double>(), c->fkind.as<int>(), c->capq(), c->sc[0].nDs.as<int>(), c->sc[1].nDs.as<int>(), h->opts.huber_a,
                            h->opts.s2m_max_iterations, pass, d_res);
         PROF(4)
     }
-    bool new_dir_ok[2] = {false, false};
-    const unsigned new_tag[2] = {c->next_tag(), c->next_tag()};      // tags of the directories the map updates write (for the maps they emit)
+    S2BMapState next[2];              // of the maps the updates emit: cell-major from end to end; the fused update writes their directory (tag dir_tag), the full sort does not
     for (int w = 0; w < 2; w++) {     // createSubMap: append registered points, crop, voxel grid
-        CSet map = c->cs_map(w), dsw = c->cs_ds(w), tmp = c->cs_tmp(w);
+        S2BMap &m = c->m[w];
+        const int cap_scan = c->sc[w].cap;
+        const CSet map = m.cur(), dsw = c->sc[w].down();
+        next[w].order = 1; next[w].dir_ok = m.st.order == 1; next[w].dir_tag = c->next_tag(); next[w].cmn.assign(S, INT_MAX);
         hipLaunchKernelGGL(b_transform_append, GRID2(dsw.cap, S), 0, h->stream, dsw, d_pose, map, d_err);
         hipLaunchKernelGGL(b_bump, GRIDS(S), 0, h->stream, map, dsw, c->nOld.as<int>(), S);
         PROF(5)
-        // the new map goes to the other buffer (the old one stays intact up to its old count: a snapshot taken on it can be
-        // restored by swapping back). If that other buffer is where a live snapshot sits, save the snapshot first.
-        if (c->has_snapshot && c->snap_live && c->mapAlt[w].p == c->snap_ptr[w]) {
-            for (int v = 0; v < 2; v++) {
-                if (!c->map0[v].ensure((size_t)S * c->capMap[v] * 16)) return VILF_ERR_DEVICE;
-                const bool cur = c->map[v].p == c->snap_ptr[v];
-                HIPCHECK(h, hipMemcpyAsync(c->map0[v].p, cur ? c->map[v].p : c->mapAlt[v].p, (size_t)S * c->capMap[v] * 16, hipMemcpyDeviceToDevice, h->stream));
-                if (c->snap_dir_ok[v]) {
-                    if (!c->dir0[v].ensure((size_t)S * S2B_NBS * 4)) return VILF_ERR_DEVICE;
-                    HIPCHECK(h, hipMemcpyAsync(c->dir0[v].p, cur ? c->bstart[v].p : c->bstartAlt[v].p, (size_t)S * S2B_NBS * 4, hipMemcpyDeviceToDevice, h->stream));
-                }
-            }
-            c->snap_live = false;
-        }
-        if (c->order_state[w] == 1) {  // steady state: one fused pass (crop + merge of the sorted tail + centroids), no host round trip
+        if ((rc = s2b_snapshot_save_if_target(h, c, w)) != VILF_OK) return rc;         // the new map goes to m.alt
+        if (m.st.order == 1) {        // steady state: one fused pass (crop + merge of the sorted tail + centroids), no host round trip
             // tail-size classes: <= 4096 new points (32 KB of LDS for the sorted tail: two workgroups per CU), <= 8192 (64 KB), larger (global memory).
             // The bucket-sorted copy of this map is dead by now (the next step rebuilds it): its buffer holds the queue of uncommon points.
-            const int lds_cap = mu_lds_cap(c->capScan[w]), lds_half = std::min(lds_cap, MU_LDS_TAIL / 2);
-            int *gq = c->sorted[w].as<int>();
-            const size_t gq_stride = (size_t)c->capMap[w] * 4;
-            hipLaunchKernelGGL(b_map_update<false>, dim3(S), dim3(MU_T), ((size_t)lds_half * 8 + (size_t)MU_TILE * 12), h->stream, map, c->nOld.as<int>(), d_pose, h->opts.s2m_crop_half, 1.0f / leaf[w], c->cs_cfg[w], c->cs_mapout(w), c->bstartAlt[w].as<unsigned>(), new_tag[w], c->fixq[w].as<int>(),
-                               c->tmpB.as<float4>(), c->capScan[w], (unsigned long long *)nullptr, 0, -1, lds_half, gq, gq_stride, d_err);
-            if (lds_cap > lds_half)
-                hipLaunchKernelGGL(b_map_update<false>, dim3(S), dim3(MU_T), ((size_t)lds_cap * 8 + (size_t)MU_TILE * 12), h->stream, map, c->nOld.as<int>(), d_pose, h->opts.s2m_crop_half, 1.0f / leaf[w], c->cs_cfg[w], c->cs_mapout(w), c->bstartAlt[w].as<unsigned>(), new_tag[w], c->fixq[w].as<int>(),
-                                   c->tmpB.as<float4>(), c->capScan[w], (unsigned long long *)nullptr, 0, lds_half, lds_cap, gq, gq_stride, d_err);
-            if (c->capScan[w] > lds_cap) {
-                int p2 = 2; while (p2 < c->capScan[w]) p2 <<= 1;
+            const int lds_cap = mu_lds_cap(cap_scan), lds_half = std::min(lds_cap, MU_LDS_TAIL / 2);
+            auto launch = [&](auto big, size_t lds_tail, int lds_lo, int lds_hi, unsigned long long *gT, int gT_stride) {
+                hipLaunchKernelGGL(b_map_update<decltype(big)::value>, dim3(S), dim3(MU_T), lds_tail * 8 + (size_t)MU_TILE * 12, h->stream, map, c->nOld.as<int>(), d_pose, h->opts.s2m_crop_half, m.inv, m.cs_cfg, m.out(), m.dirAlt.as<unsigned>(), next[w].dir_tag, m.fixq.as<int>(), c->tmpB.as<float4>(), cap_scan, gT, gT_stride, lds_lo, lds_hi, m.sorted.as<int>(), (size_t)m.cap * 4, d_err);
+            };
+            launch(std::false_type{}, lds_half, -1, lds_half, nullptr, 0);
+            if (lds_cap > lds_half) launch(std::false_type{}, lds_cap, lds_half, lds_cap, nullptr, 0);
+            if (cap_scan > lds_cap) {
+                int p2 = 2; while (p2 < cap_scan) p2 <<= 1;
                 if (!c->muT.ensure((size_t)S * p2 * 8)) return VILF_ERR_DEVICE;
-                hipLaunchKernelGGL(b_map_update<true>, dim3(S), dim3(MU_T), (size_t)MU_TILE * 12, h->stream, map, c->nOld.as<int>(), d_pose, h->opts.s2m_crop_half, 1.0f / leaf[w], c->cs_cfg[w], c->cs_mapout(w), c->bstartAlt[w].as<unsigned>(), new_tag[w], c->fixq[w].as<int>(),
-                                   c->tmpB.as<float4>(), c->capScan[w], c->muT.as<unsigned long long>(), p2, 0, lds_cap, gq, gq_stride, d_err);
+                launch(std::true_type{}, 0, 0, lds_cap, c->muT.as<unsigned long long>(), p2);
             }
             PROF(7)
-            new_dir_ok[w] = true;      // (of the map the swap below makes current)
-        } else {                       // a map that is not a voxel grid yet (as initialised): crop copy + full sort
-            hipLaunchKernelGGL(b_crop_compact, dim3(S), dim3(S2B_VT), 0, h->stream, map, d_pose, h->opts.s2m_crop_half, tmp, c->nOld.as<int>(), c->mOld.as<int>());
+        } else {                      // a map that is not a voxel grid yet (as initialised): crop copy + full sort
+            hipLaunchKernelGGL(b_crop_compact, dim3(S), dim3(S2B_VT), 0, h->stream, map, d_pose, h->opts.s2m_crop_half, c->cs_tmp(w), c->nOld.as<int>(), c->mOld.as<int>());
             PROF(5)
-            if ((rc = s2b_voxel(h, c, tmp, leaf[w], c->cs_mapout(w), c->cs_cfg[w])) != VILF_OK) return rc;
+            if ((rc = s2b_voxel(h, c, c->cs_tmp(w), m.leaf, m.out(), m.cs_cfg)) != VILF_OK) return rc;
         }
-        c->order_state[w] = 1;
-        std::fill(c->h_cmn[w].begin(), c->h_cmn[w].end(), INT_MAX);
     }
-    for (int w = 0; w < 2; w++) {
-        std::swap(c->map[w], c->mapAlt[w]); std::swap(c->bstart[w], c->bstartAlt[w]);
-        c->dir_ok[w] = new_dir_ok[w]; c->dir_tag[w] = new_tag[w];
-    }
-    hipLaunchKernelGGL(b_finish, GRIDS(S), 0, h->stream, d_pose, c->nMap[0].as<int>(), c->nMap[1].as<int>(), d_err, d_res, S);
+    for (int w = 0; w < 2; w++) { c->m[w].swap_buffers(); c->m[w].st = std::move(next[w]); }
+    hipLaunchKernelGGL(b_finish, GRIDS(S), 0, h->stream, d_pose, c->m[0].n.as<int>(), c->m[1].n.as<int>(), d_err, d_res, S);
     PROF(6)
     HIPCHECK(h, hipGetLastError());
     if (h->profiling && h->prof_used.size() > 4096) return vilf_prof_flush(h);      // asynchronous steps without a reader: bound the pool
@@ -2578,8 +2596,14 @@ static int s2b_err_to_rc(vilf_handle *h, int err) {
              ((err & S2B_ERR_ORDER) ? "local map not in leaf order (internal); " : "");
     return VILF_ERR_UNSUPPORTED;
 }
-static int s2b_set_cloud(vilf_handle *h, S2B *c, DBuf &buf, int cap, int sid, int offset, const float *xyzi, int n) {
-    if (n > 0) HIPCHECK(h, hipMemcpyAsync(buf.as<float4>() + (size_t)sid * cap + offset, xyzi, (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
+// stream sid's resident scans := the clouds (asynchronous: the caller waits before its buffers may change)
+static int s2b_upload_scans(vilf_handle *h, S2B *c, int sid, const float *e, int ne, const float *s, int ns) {
+    const float *src[2] = {e, s}; const int nn[2] = {ne, ns};
+    for (int w = 0; w < 2; w++) {
+        if (nn[w] > 0) HIPCHECK(h, hipMemcpyAsync(c->sc[w].row(sid), src[w], (size_t)nn[w] * 16, hipMemcpyHostToDevice, h->stream));
+        c->sc[w].h_n[sid] = nn[w];
+    }
+    c->scan_dirty = true;
     return VILF_OK;
 }
 
@@ -2625,6 +2649,17 @@ static void s2b_host_pcl_order(float *xyzi, int m, float leaf) {
     for (int i = 0; i < m; i++) std::memcpy(&tmp[4 * (size_t)i], xyzi + 4 * (size_t)kp[i].second, 16);
     std::memcpy(xyzi, tmp.data(), (size_t)m * 16);
 }
+// localMapInited for stream sid of map m: the cloud goes behind the map's first old_n points (0: it replaces the map). cm: staging that has to outlive the copy
+static int s2b_upload_map(vilf_handle *h, S2BMap &m, int sid, int old_n, const float *xyzi, int n, std::vector<float> &cm) {
+    const int keep = m.st.order == 1 ? old_n : std::min(m.st.cmn[sid], old_n);      // what was in cell-major order stays so; the appended cloud is raw ...
+    if (m.st.order == 1) std::fill(m.st.cmn.begin(), m.st.cmn.end(), INT_MAX);      // (so do the other streams' maps)
+    const bool conv = old_n == 0 && s2b_host_cell_major(xyzi, n, m.leaf, m.cs_cfg, cm);   // ... unless it is a whole voxel grid
+    if (n > 0) HIPCHECK(h, hipMemcpyAsync(m.row(sid) + old_n, conv ? cm.data() : xyzi, (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
+    m.st.cmn[sid] = conv ? n : keep;
+    m.h_n[sid] = old_n + n; m.st.order = 0; m.st.dir_ok = false;
+    HIPCHECK(h, hipMemcpyAsync(m.n.as<int>() + sid, &m.h_n[sid], 4, hipMemcpyHostToDevice, h->stream));
+    return VILF_OK;
+}
 
 // ---- single-stream ABI (S = 1, capacities grow on demand) ---------------------------------------------------------------
 static S2B *single(vilf_handle *h) { if (!h->s2m) h->s2m = new S2B(); return h->s2m; }
@@ -2633,20 +2668,12 @@ extern "C" int vilf_scan2map_init(vilf_handle *h, const float *e, int ne, const 
     if (!h || ne < 0 || ns < 0 || (ne && !e) || (ns && !s)) return VILF_ERR_INVALID_ARGUMENT;
     HIPCHECK(h, hipSetDevice(h->device));
     S2B *c = single(h);
-    const int oe = c->S ? c->h_nMap[0][0] : 0, os = c->S ? c->h_nMap[1][0] : 0;
+    const int oe = c->S ? c->m[0].h_n[0] : 0, os = c->S ? c->m[1].h_n[0] : 0;
     int rc = s2b_reserve(h, c, 1, ne, ns, oe + ne, os + ns);
     if (rc != VILF_OK) return rc;
     const float *src[2] = {e, s}; const int nn[2] = {ne, ns};                       // localMapInited (:105): map += cloud
     std::vector<float> cm[2];
-    for (int w = 0; w < 2; w++) {
-        const int old_n = c->h_nMap[w][0];
-        const int keep = c->order_state[w] == 1 ? old_n : std::min(c->h_cmn[w][0], old_n);      // what was in cell-major order stays so; the appended cloud is raw ...
-        const bool conv = old_n == 0 && s2b_host_cell_major(src[w], nn[w], (float)(w == 0 ? h->opts.edge_leaf_size : h->opts.surf_leaf_size), c->cs_cfg[w], cm[w]);   // ... unless it is a whole voxel grid
-        if ((rc = s2b_set_cloud(h, c, c->map[w], c->capMap[w], 0, old_n, conv ? cm[w].data() : src[w], nn[w])) != VILF_OK) return rc;
-        c->h_cmn[w][0] = conv ? nn[w] : keep;
-        c->h_nMap[w][0] += nn[w]; c->order_state[w] = 0; c->dir_ok[w] = false;
-        HIPCHECK(h, hipMemcpyAsync(c->nMap[w].p, c->h_nMap[w].data(), 4, hipMemcpyHostToDevice, h->stream));
-    }
+    for (int w = 0; w < 2; w++) if ((rc = s2b_upload_map(h, c->m[w], 0, c->m[w].h_n[0], src[w], nn[w], cm[w])) != VILF_OK) return rc;
     HIPCHECK(h, hipStreamSynchronize(h->stream));
     return VILF_OK;
 }
@@ -2655,7 +2682,7 @@ extern "C" int vilf_scan2map_set_pose(vilf_handle *h, const double p[7], const d
     if (!h || !p || !pl) return VILF_ERR_INVALID_ARGUMENT;
     HIPCHECK(h, hipSetDevice(h->device));
     S2B *c = single(h);
-    int rc = s2b_reserve(h, c, 1, c->capScan[0], c->capScan[1], c->capMap[0], c->capMap[1]);
+    int rc = s2b_reserve(h, c, 1, c->sc[0].cap, c->sc[1].cap, c->m[0].cap, c->m[1].cap);
     if (rc != VILF_OK) return rc;
     HIPCHECK(h, vilf_copy_sync(h, c->pose.p, p, 56, hipMemcpyHostToDevice));
     HIPCHECK(h, vilf_copy_sync(h, c->pose.as<double>() + 8, pl, 56, hipMemcpyHostToDevice));
@@ -2663,23 +2690,19 @@ extern "C" int vilf_scan2map_set_pose(vilf_handle *h, const double p[7], const d
 }
 
 static int s2b_get_map(vilf_handle *h, S2B *c, int sid, int which, float *out, int cap, int *n_out) {
+    S2BMap &mp = c->m[which];
     int n = 0;
-    if (c->S) HIPCHECK(h, vilf_copy_sync(h, &n, c->nMap[which].as<int>() + sid, 4, hipMemcpyDeviceToHost));
+    if (c->S) HIPCHECK(h, vilf_copy_sync(h, &n, mp.n.as<int>() + sid, 4, hipMemcpyDeviceToHost));
     *n_out = n;
     const int k = std::min(cap, n);
     if (k > 0 && out) {
         // the map lives in cell-major order on the device (mu_leaf); what the caller sees is pcl::VoxelGrid's order, as the reference's map has it
-        const int m = std::min(c->order_state[which] == 1 ? n : c->h_cmn[which][sid], n);
-        const float leaf = (float)(which == 0 ? h->opts.edge_leaf_size : h->opts.surf_leaf_size);
-        if (m <= k) {
-            HIPCHECK(h, vilf_copy_sync(h, out, c->map[which].as<float4>() + (size_t)sid * c->capMap[which], (size_t)k * 16, hipMemcpyDeviceToHost));
-            s2b_host_pcl_order(out, m, leaf);
-        } else {                                            // a truncated read: order the whole prefix first, then hand out its first k points
-            std::vector<float> all((size_t)n * 4);
-            HIPCHECK(h, vilf_copy_sync(h, all.data(), c->map[which].as<float4>() + (size_t)sid * c->capMap[which], (size_t)n * 16, hipMemcpyDeviceToHost));
-            s2b_host_pcl_order(all.data(), m, leaf);
-            std::memcpy(out, all.data(), (size_t)k * 16);
-        }
+        const int m = std::min(mp.st.order == 1 ? n : mp.st.cmn[sid], n);
+        std::vector<float> all(m <= k ? 0 : (size_t)n * 4);     // a truncated read: order the whole prefix first, then hand out its first k points
+        float *dst = m <= k ? out : all.data();
+        HIPCHECK(h, vilf_copy_sync(h, dst, mp.row(sid), (size_t)(m <= k ? k : n) * 16, hipMemcpyDeviceToHost));
+        s2b_host_pcl_order(dst, m, mp.leaf);
+        if (dst != out) std::memcpy(out, dst, (size_t)k * 16);
     }
     return VILF_OK;
 }
@@ -2694,20 +2717,15 @@ extern "C" int vilf_scan2map_step(vilf_handle *h, const float *e, int ne, const 
     HIPCHECK(h, hipSetDevice(h->device));
     S2B *c = single(h);
     std::memset(res, 0, sizeof(*res));
-    const int oe = c->S ? c->h_nMap[0][0] : 0, os = c->S ? c->h_nMap[1][0] : 0;
+    const int oe = c->S ? c->m[0].h_n[0] : 0, os = c->S ? c->m[1].h_n[0] : 0;
     int rc = s2b_reserve(h, c, 1, ne, ns, oe + ne, os + ns);
     if (rc != VILF_OK) return rc;
-    const float *src[2] = {e, s}; const int nn[2] = {ne, ns};
-    for (int w = 0; w < 2; w++) {
-        if ((rc = s2b_set_cloud(h, c, c->scan[w], c->capScan[w], 0, 0, src[w], nn[w])) != VILF_OK) return rc;
-        c->h_nScan[w][0] = nn[w];
-    }
-    c->scan_dirty = true;
+    if ((rc = s2b_upload_scans(h, c, 0, e, ne, s, ns)) != VILF_OK) return rc;
     if ((rc = s2b_step(h, c)) != VILF_OK) return rc;
     HIPCHECK(h, hipMemcpyAsync(c->h_res.data(), c->res.p, sizeof(S2BRes), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
     const S2BRes &r = c->h_res[0];
-    c->h_nMap[0][0] = r.map_n[0]; c->h_nMap[1][0] = r.map_n[1];
+    c->m[0].h_n[0] = r.map_n[0]; c->m[1].h_n[0] = r.map_n[1];
     s2b_fill_result(r, res);
     if (r.err) { HIPCHECK(h, hipMemsetAsync(c->err.p, 0, 4, h->stream)); }
     return s2b_err_to_rc(h, r.err);
@@ -2729,18 +2747,12 @@ extern "C" int vilf_scan2map_batch_create(vilf_handle *h, int n_streams, int cap
 
 extern "C" int vilf_scan2map_batch_init(vilf_handle *h, int stream, const float *e, int ne, const float *s, int ns, const double *pose_qt, const double *pose_last_qt) {
     S2B_CHECK(h, stream)
-    if (ne < 0 || ns < 0 || ne > c->capMap[0] || ns > c->capMap[1] || (ne && !e) || (ns && !s)) return VILF_ERR_INVALID_ARGUMENT;
+    if (ne < 0 || ns < 0 || ne > c->m[0].cap || ns > c->m[1].cap || (ne && !e) || (ns && !s)) return VILF_ERR_INVALID_ARGUMENT;
     const float *src[2] = {e, s}; const int nn[2] = {ne, ns};
     int rc;
     std::vector<float> cm[2];
-    for (int w = 0; w < 2; w++) {                                                   // the stream's local map := cloud
-        if (c->order_state[w] == 1) std::fill(c->h_cmn[w].begin(), c->h_cmn[w].end(), INT_MAX);   // the other streams' maps stay in cell-major order
-        const bool conv = s2b_host_cell_major(src[w], nn[w], (float)(w == 0 ? h->opts.edge_leaf_size : h->opts.surf_leaf_size), c->cs_cfg[w], cm[w]);
-        if ((rc = s2b_set_cloud(h, c, c->map[w], c->capMap[w], stream, 0, conv ? cm[w].data() : src[w], nn[w])) != VILF_OK) return rc;
-        c->h_cmn[w][stream] = conv ? nn[w] : 0;
-        c->h_nMap[w][stream] = nn[w]; c->order_state[w] = 0; c->dir_ok[w] = false;
-        HIPCHECK(h, hipMemcpyAsync(c->nMap[w].as<int>() + stream, &c->h_nMap[w][stream], 4, hipMemcpyHostToDevice, h->stream));
-    }
+    c->snap.valid = false;                                                          // a map written outside a step: the snapshot no longer describes the buffers
+    for (int w = 0; w < 2; w++) if ((rc = s2b_upload_map(h, c->m[w], stream, 0, src[w], nn[w], cm[w])) != VILF_OK) return rc;   // the stream's local map := cloud
     double p[24] = {0};
     p[3] = p[11] = p[19] = 1.0;
     if (pose_qt) for (int k = 0; k < 7; k++) p[k] = p[8 + k] = p[16 + k] = pose_qt[k];
@@ -2766,33 +2778,28 @@ extern "C" int vilf_scan2map_batch_copy_stream(vilf_handle *h, int src, int dst)
     if (src == dst) return VILF_OK;
     CopyJob job; job.n = 0;
     auto add = [&](const void *s_, void *d_, size_t bytes) { job.src[job.n] = s_; job.dst[job.n] = d_; job.bytes[job.n] = bytes; job.n++; };
-    size_t largest = 0;
+    c->snap.valid = false;                                     // a map written outside a step: the snapshot no longer describes the buffers
     for (int w = 0; w < 2; w++) {
-        add(c->map[w].as<float4>() + (size_t)src * c->capMap[w], c->map[w].as<float4>() + (size_t)dst * c->capMap[w], (size_t)c->capMap[w] * 16);
-        if (c->dir_ok[w]) add(c->bstart[w].as<unsigned>() + (size_t)src * S2B_NBS, c->bstart[w].as<unsigned>() + (size_t)dst * S2B_NBS, (size_t)S2B_NBS * 4);
-        add(c->nMap[w].as<int>() + src, c->nMap[w].as<int>() + dst, 4);
-        c->h_nMap[w][dst] = c->h_nMap[w][src]; c->h_nScan[w][dst] = c->h_nScan[w][src]; c->h_cmn[w][dst] = c->h_cmn[w][src];
+        S2BMap &m = c->m[w];
+        add(m.row(src), m.row(dst), (size_t)m.cap * 16);
+        if (m.st.dir_ok) add(m.dir.as<unsigned>() + (size_t)src * S2B_NBS, m.dir.as<unsigned>() + (size_t)dst * S2B_NBS, (size_t)S2B_NBS * 4);
+        add(m.n.as<int>() + src, m.n.as<int>() + dst, 4);
+        m.h_n[dst] = m.h_n[src]; c->sc[w].h_n[dst] = c->sc[w].h_n[src]; m.st.cmn[dst] = m.st.cmn[src];
     }
     hipLaunchKernelGGL(b_copy_regions, dim3(64, job.n), dim3(256), 0, h->stream, job);
     job.n = 0;
-    for (int w = 0; w < 2; w++) add(c->scan[w].as<float4>() + (size_t)src * c->capScan[w], c->scan[w].as<float4>() + (size_t)dst * c->capScan[w], (size_t)c->capScan[w] * 16);
+    for (int w = 0; w < 2; w++) add(c->sc[w].row(src), c->sc[w].row(dst), (size_t)c->sc[w].cap * 16);
     add(c->pose.as<double>() + 24 * (size_t)src, c->pose.as<double>() + 24 * (size_t)dst, 24 * 8);
     hipLaunchKernelGGL(b_copy_regions, dim3(16, job.n), dim3(256), 0, h->stream, job);
-    (void)largest;
     HIPCHECK(h, hipGetLastError());
     c->scan_dirty = true;
     return VILF_OK;
 }
 extern "C" int vilf_scan2map_batch_set_scan(vilf_handle *h, int stream, const float *e, int ne, const float *s, int ns) {
     S2B_CHECK(h, stream)
-    if (ne < 0 || ns < 0 || ne > c->capScan[0] || ns > c->capScan[1] || (ne && !e) || (ns && !s)) return VILF_ERR_INVALID_ARGUMENT;
-    const float *src[2] = {e, s}; const int nn[2] = {ne, ns};
-    int rc;
-    for (int w = 0; w < 2; w++) {
-        if ((rc = s2b_set_cloud(h, c, c->scan[w], c->capScan[w], stream, 0, src[w], nn[w])) != VILF_OK) return rc;
-        c->h_nScan[w][stream] = nn[w];
-    }
-    c->scan_dirty = true;
+    if (ne < 0 || ns < 0 || ne > c->sc[0].cap || ns > c->sc[1].cap || (ne && !e) || (ns && !s)) return VILF_ERR_INVALID_ARGUMENT;
+    const int rc = s2b_upload_scans(h, c, stream, e, ne, s, ns);
+    if (rc != VILF_OK) return rc;
     HIPCHECK(h, hipStreamSynchronize(h->stream));          // the caller's buffers may be re-used after return
     return VILF_OK;
 }
@@ -2811,42 +2818,42 @@ extern "C" int vilf_get_profile_scan2map(vilf_handle *h, double ms_out[8], long 
 }
 extern "C" int vilf_scan2map_batch_snapshot(vilf_handle *h) {
     S2B_CHECK(h, 0)
-    for (int w = 0; w < 2; w++) {                 // the maps are not copied: a step never overwrites its input maps (see s2b_step)
+    S2BSnap &sn = c->snap;
+    sn.valid = false;
+    for (int w = 0; w < 2; w++) {                 // the maps are not copied: a step never overwrites its input maps (see s2b_map_update)
+        S2BMap &m = c->m[w];
         int rc = s2b_resolve_order(h, c, w);
         if (rc != VILF_OK) return rc;
-        c->snap_order[w] = c->order_state[w]; c->snap_cmn[w] = c->h_cmn[w];
-        if (c->order_state[w] == 1 && !c->dir_ok[w]) {          // the snapshot carries the maps' directory, as a map that came out of a step does
-            const float leaf = (float)(w == 0 ? h->opts.edge_leaf_size : h->opts.surf_leaf_size);
-            c->dir_tag[w] = c->next_tag();
-            hipLaunchKernelGGL(b_dir_build, dim3((c->capMap[w] + 256 * DIR_PT - 1) / (256 * DIR_PT), c->S), dim3(256), 0, h->stream, c->map[w].as<float4>(), c->nMap[w].as<int>(), c->capMap[w], 1.0f / leaf,
-                               c->cs_cfg[w], c->dir_tag[w], c->bstart[w].as<unsigned>());
-            c->dir_ok[w] = true;
+        if (m.st.order == 1 && !m.st.dir_ok) {    // the snapshot carries the maps' directory, as a map that came out of a step does
+            s2b_dir_build(h, c, m, m.pts.as<float4>(), m.cs_cfg);
+            m.st.dir_ok = true;
         }
-        c->snap_dir_ok[w] = c->dir_ok[w]; c->snap_dir_tag[w] = c->dir_tag[w];
-        if (!c->nMap0[w].ensure((size_t)c->S * 4)) return VILF_ERR_DEVICE;
-        HIPCHECK(h, hipMemcpyAsync(c->nMap0[w].p, c->nMap[w].p, (size_t)c->S * 4, hipMemcpyDeviceToDevice, h->stream));
-        c->snap_ptr[w] = c->map[w].p;
+        sn.st[w] = m.st;
+        if (!sn.n[w].ensure((size_t)c->S * 4)) return VILF_ERR_DEVICE;
+        HIPCHECK(h, hipMemcpyAsync(sn.n[w].p, m.n.p, (size_t)c->S * 4, hipMemcpyDeviceToDevice, h->stream));
+        sn.live_ptr[w] = m.pts.p;
     }
-    if (!c->pose0.ensure((size_t)c->S * 24 * 8)) return VILF_ERR_DEVICE;
-    HIPCHECK(h, hipMemcpyAsync(c->pose0.p, c->pose.p, (size_t)c->S * 24 * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (!sn.pose.ensure((size_t)c->S * 24 * 8)) return VILF_ERR_DEVICE;
+    HIPCHECK(h, hipMemcpyAsync(sn.pose.p, c->pose.p, (size_t)c->S * 24 * 8, hipMemcpyDeviceToDevice, h->stream));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
-    c->has_snapshot = true; c->snap_live = true;
+    sn.valid = sn.live = true;
     return VILF_OK;
 }
 extern "C" int vilf_scan2map_batch_rewind(vilf_handle *h) {
     S2B_CHECK(h, 0)
-    if (!c->has_snapshot) { h->err = "scan2map_batch_rewind: no snapshot"; return VILF_ERR_INVALID_ARGUMENT; }
+    S2BSnap &sn = c->snap;
+    if (!sn.valid) { h->err = "scan2map_batch_rewind: no snapshot"; return VILF_ERR_INVALID_ARGUMENT; }
     for (int w = 0; w < 2; w++) {
-        if (c->snap_live) { if (c->map[w].p != c->snap_ptr[w]) { std::swap(c->map[w], c->mapAlt[w]); std::swap(c->bstart[w], c->bstartAlt[w]); } }
+        S2BMap &m = c->m[w];
+        if (sn.live) { if (m.pts.p != sn.live_ptr[w]) m.swap_buffers(); }
         else {
-            HIPCHECK(h, hipMemcpyAsync(c->map[w].p, c->map0[w].p, (size_t)c->S * c->capMap[w] * 16, hipMemcpyDeviceToDevice, h->stream));
-            if (c->snap_dir_ok[w]) HIPCHECK(h, hipMemcpyAsync(c->bstart[w].p, c->dir0[w].p, (size_t)c->S * S2B_NBS * 4, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHECK(h, hipMemcpyAsync(m.pts.p, sn.pts[w].p, (size_t)c->S * m.cap * 16, hipMemcpyDeviceToDevice, h->stream));
+            if (sn.st[w].dir_ok) HIPCHECK(h, hipMemcpyAsync(m.dir.p, sn.dir[w].p, (size_t)c->S * S2B_NBS * 4, hipMemcpyDeviceToDevice, h->stream));
         }
-        c->dir_ok[w] = c->snap_dir_ok[w]; c->dir_tag[w] = c->snap_dir_tag[w];
-        HIPCHECK(h, hipMemcpyAsync(c->nMap[w].p, c->nMap0[w].p, (size_t)c->S * 4, hipMemcpyDeviceToDevice, h->stream));
-        c->order_state[w] = c->snap_order[w]; c->h_cmn[w] = c->snap_cmn[w];
+        m.st = sn.st[w];
+        HIPCHECK(h, hipMemcpyAsync(m.n.p, sn.n[w].p, (size_t)c->S * 4, hipMemcpyDeviceToDevice, h->stream));
     }
-    HIPCHECK(h, hipMemcpyAsync(c->pose.p, c->pose0.p, (size_t)c->S * 24 * 8, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHECK(h, hipMemcpyAsync(c->pose.p, sn.pose.p, (size_t)c->S * 24 * 8, hipMemcpyDeviceToDevice, h->stream));
     HIPCHECK(h, hipMemsetAsync(c->err.p, 0, (size_t)c->S * 4, h->stream));
     return VILF_OK;
 }
@@ -2865,73 +2872,89 @@ extern "C" int vilf_scan2map_batch_get_map(vilf_handle *h, int stream, int which
     return s2b_get_map(h, c, stream, which, out, cap, n_out);
 }
 
-// ---- test hook (exported, not declared in vilfusion.h): what association does with given queries at a given pose ------------------------
-// Runs what a step runs between the voxel filter and the solve — s2b_resolve_order, s2b_build_index (a no-op when the last map update wrote the directory), the
-// association launch (edge and surf blocks in one grid of the production geometry, every stream of the batch present, the other streams without queries) and the tie
-// redo — on the stream's current local maps, with the kernels' DBG instantiations. Queries, pose, records and neighbour lists live in buffers of the call: of the
-// context only what the next step rebuilds anyway is touched (order_state, the directory of a map that has none yet, sort scratch), so a later step cannot tell.
-// stream: -1 = the single-stream context. Per query (edge queries first): kind_out[1], rec_out[6], pos_out[5], nb_out[15], d2_out[5].
-extern "C" int vilf_debug_s2m_associate(vilf_handle *h, int stream, const double *pose_qt, const float *edge_xyzi, int ne, const float *surf_xyzi, int ns,
-                                        int *kind_out, double *rec_out, int *pos_out, float *nb_out, float *d2_out) {
-    if (!h || !pose_qt || ne < 0 || ns < 0 || (ne && !edge_xyzi) || (ns && !surf_xyzi)) return VILF_ERR_INVALID_ARGUMENT;
-    S2B *c = stream == -1 ? h->s2m : h->s2b;
-    if (!c || c->S < 1 || c->capScan[0] < 1 || c->capScan[1] < 1 || c->capMap[0] < 1 || c->capMap[1] < 1) return VILF_ERR_INVALID_ARGUMENT;
-    const int sid = stream == -1 ? 0 : stream;
-    if (stream < -1 || sid >= c->S || ne > c->capScan[0] || ns > c->capScan[1]) return VILF_ERR_INVALID_ARGUMENT;
-    const int nq = ne + ns;
-    if (nq && (!kind_out || !rec_out || !pos_out || !nb_out || !d2_out)) return VILF_ERR_INVALID_ARGUMENT;
+// ---- what the two test hooks share ----------------------------------------------------------------------------------------------------
+#define DBGCHECK(who, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(who) + ": " + hipGetErrorString(e_); return VILF_ERR_DEVICE; } } while (0)
+// The buffers of one hook call, laid out for every stream of the context and released when the call returns, on every path. s2b_dbg_stage picks the context (stream:
+// -1 = the single-stream one) and the stream's row sid in it, refuses what does not fit, and fills what both hooks need: identity poses with stream sid at pose_qt,
+// results with do_opt = 1, zeroed records and kinds, query counts nn[2] for stream sid and none for the others.
+struct S2BDbgStage {
+    S2B *c = nullptr; int sid = 0;
+    DBuf nq[2], pose, res, frec, fkind;
+    DBuf q[2], out[3];          // the hook's own: query clouds (associate), neighbour lists (associate) / trace (solve)
+    ~S2BDbgStage() { for (DBuf *b : {&nq[0], &nq[1], &pose, &res, &frec, &fkind, &q[0], &q[1], &out[0], &out[1], &out[2]}) b->release(); }
+};
+static int s2b_dbg_stage(vilf_handle *h, const char *who, int stream, const double *pose_qt, const int nn[2], S2BDbgStage &g) {
+    S2B *c = g.c = stream == -1 ? h->s2m : h->s2b;
+    const int sid = g.sid = stream == -1 ? 0 : stream;
+    if (!c || c->S < 1 || c->sc[0].cap < 1 || c->sc[1].cap < 1 || c->m[0].cap < 1 || c->m[1].cap < 1) return VILF_ERR_INVALID_ARGUMENT;
+    if (stream < -1 || sid >= c->S || nn[0] > c->sc[0].cap || nn[1] > c->sc[1].cap) return VILF_ERR_INVALID_ARGUMENT;
     HIPCHECK(h, hipSetDevice(h->device));
-    const int S = c->S, capq = c->capScan[0] + c->capScan[1];
-    int rc;
+    const int S = c->S;
+    const size_t nslot = (size_t)S * c->capq();
+    if (!g.pose.ensure((size_t)S * 24 * 8) || !g.res.ensure((size_t)S * sizeof(S2BRes)) || !g.frec.ensure(nslot * S2M_FREC * 8) || !g.fkind.ensure(nslot * 4) || !g.nq[0].ensure((size_t)S * 4) || !g.nq[1].ensure((size_t)S * 4)) return VILF_ERR_DEVICE;
     for (int w = 0; w < 2; w++) {
-        if ((rc = s2b_resolve_order(h, c, w)) != VILF_OK) return rc;
-        if ((rc = s2b_build_index(h, c, w)) != VILF_OK) return rc;
-    }
-    DBuf q[2], nq_d[2], pose, res, frec, fkind, dpos, dnb, dd2;
-    auto done = [&](int r) { for (DBuf *b : {&q[0], &q[1], &nq_d[0], &nq_d[1], &pose, &res, &frec, &fkind, &dpos, &dnb, &dd2}) b->release(); return r; };
-#define DBGCHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string("vilf_debug_s2m_associate: ") + hipGetErrorString(e_); return done(VILF_ERR_DEVICE); } } while (0)
-    const size_t nslot = (size_t)S * capq;
-    if (!pose.ensure((size_t)S * 24 * 8) || !res.ensure((size_t)S * sizeof(S2BRes)) || !frec.ensure(nslot * S2M_FREC * 8) || !fkind.ensure(nslot * 4) ||
-        !dpos.ensure(nslot * 5 * 4) || !dnb.ensure(nslot * 15 * 4) || !dd2.ensure(nslot * 5 * 4)) return done(VILF_ERR_DEVICE);
-    const float *src[2] = {edge_xyzi, surf_xyzi}; const int nn[2] = {ne, ns};
-    for (int w = 0; w < 2; w++) {
-        if (!q[w].ensure((size_t)S * c->capScan[w] * 16) || !nq_d[w].ensure((size_t)S * 4)) return done(VILF_ERR_DEVICE);
         std::vector<int> cnt(S, 0);
         cnt[sid] = nn[w];
-        DBGCHECK(vilf_copy_sync(h, nq_d[w].p, cnt.data(), (size_t)S * 4, hipMemcpyHostToDevice));
-        if (nn[w]) DBGCHECK(vilf_copy_sync(h, q[w].as<float4>() + (size_t)sid * c->capScan[w], src[w], (size_t)nn[w] * 16, hipMemcpyHostToDevice));
+        DBGCHECK(who, vilf_copy_sync(h, g.nq[w].p, cnt.data(), (size_t)S * 4, hipMemcpyHostToDevice));
     }
     std::vector<double> hp((size_t)S * 24, 0.0);
     for (int s = 0; s < S; s++) { hp[24 * s + 3] = 1.0; hp[24 * s + 11] = 1.0; hp[24 * s + 19] = 1.0; }
     for (int k = 0; k < 7; k++) hp[24 * (size_t)sid + k] = pose_qt[k];
-    DBGCHECK(vilf_copy_sync(h, pose.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice));
+    DBGCHECK(who, vilf_copy_sync(h, g.pose.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice));
     std::vector<S2BRes> hr(S, S2BRes{});
     for (int s = 0; s < S; s++) hr[s].do_opt = 1;
-    DBGCHECK(vilf_copy_sync(h, res.p, hr.data(), hr.size() * sizeof(S2BRes), hipMemcpyHostToDevice));
-    DBGCHECK(hipMemsetAsync(frec.p, 0, nslot * S2M_FREC * 8, h->stream));
-    DBGCHECK(hipMemsetAsync(fkind.p, 0, nslot * 4, h->stream));
-    AssocArgs aa[2];
-    const CSet ds2[2] = {CSet{q[0].as<float4>(), nq_d[0].as<int>(), c->capScan[0]}, CSet{q[1].as<float4>(), nq_d[1].as<int>(), c->capScan[1]}};
-    s2b_assoc_args(h, c, ds2, pose.as<double>(), res.as<S2BRes>(), frec.as<double>(), fkind.as<int>(), aa);
+    DBGCHECK(who, vilf_copy_sync(h, g.res.p, hr.data(), hr.size() * sizeof(S2BRes), hipMemcpyHostToDevice));
+    DBGCHECK(who, hipMemsetAsync(g.frec.p, 0, nslot * S2M_FREC * 8, h->stream));
+    DBGCHECK(who, hipMemsetAsync(g.fkind.p, 0, nslot * 4, h->stream));
+    return VILF_OK;
+}
+
+// ---- test hook (exported, not declared in vilfusion.h): what association does with given queries at a given pose ------------------------
+// Runs what a step runs between the voxel filter and the solve — s2b_resolve_order, s2b_build_index (a no-op when the last map update wrote the directory), the
+// association launch (edge and surf blocks in one grid of the production geometry, every stream of the batch present, the other streams without queries) and the tie
+// redo — on the stream's current local maps, with the kernels' DBG instantiations. Queries, pose, records and neighbour lists live in buffers of the call: of the
+// context only what the next step rebuilds anyway is touched (a map's resolved order, the directory of a map that has none yet, sort scratch), so a later step cannot tell.
+// stream: -1 = the single-stream context. Per query (edge queries first): kind_out[1], rec_out[6], pos_out[5], nb_out[15], d2_out[5].
+extern "C" int vilf_debug_s2m_associate(vilf_handle *h, int stream, const double *pose_qt, const float *edge_xyzi, int ne, const float *surf_xyzi, int ns,
+                                        int *kind_out, double *rec_out, int *pos_out, float *nb_out, float *d2_out) {
+    if (!h || !pose_qt || ne < 0 || ns < 0 || (ne && !edge_xyzi) || (ns && !surf_xyzi)) return VILF_ERR_INVALID_ARGUMENT;
+    const float *src[2] = {edge_xyzi, surf_xyzi}; const int nn[2] = {ne, ns}, nq = ne + ns;
+    if (nq && (!kind_out || !rec_out || !pos_out || !nb_out || !d2_out)) return VILF_ERR_INVALID_ARGUMENT;
+    const char *who = "vilf_debug_s2m_associate";
+    S2BDbgStage g;
+    DBuf &dpos = g.out[0], &dnb = g.out[1], &dd2 = g.out[2];
+    int rc = s2b_dbg_stage(h, who, stream, pose_qt, nn, g);
+    if (rc != VILF_OK) return rc;
+    S2B *c = g.c;
+    const int S = c->S, sid = g.sid;
+    for (int w = 0; w < 2; w++) {
+        if ((rc = s2b_resolve_order(h, c, w)) != VILF_OK) return rc;
+        if ((rc = s2b_build_index(h, c, w)) != VILF_OK) return rc;
+    }
+    const size_t nslot = (size_t)S * c->capq();
+    if (!dpos.ensure(nslot * 5 * 4) || !dnb.ensure(nslot * 15 * 4) || !dd2.ensure(nslot * 5 * 4)) return VILF_ERR_DEVICE;
+    for (int w = 0; w < 2; w++) {
+        if (!g.q[w].ensure((size_t)S * c->sc[w].cap * 16)) return VILF_ERR_DEVICE;
+        if (nn[w]) DBGCHECK(who, vilf_copy_sync(h, g.q[w].as<float4>() + (size_t)sid * c->sc[w].cap, src[w], (size_t)nn[w] * 16, hipMemcpyHostToDevice));
+    }
+    const CSet ds2[2] = {CSet{g.q[0].as<float4>(), g.nq[0].as<int>(), c->sc[0].cap}, CSet{g.q[1].as<float4>(), g.nq[1].as<int>(), c->sc[1].cap}};
+    const S2BAssoc as = s2b_assoc_args(c, ds2, g.pose.as<double>(), g.res.as<S2BRes>(), g.frec.as<double>(), g.fkind.as<int>());
     const AssocDbg dbg{dpos.as<int>(), dnb.as<float>(), dd2.as<float>()};
-    int nblk_e; dim3 agrid;
-    s2b_assoc_grid(c, &nblk_e, &agrid);
-    hipLaunchKernelGGL(b_associate_dbg, agrid, dim3(256), 0, h->stream, aa[0], aa[1], nblk_e, dbg);
-    hipLaunchKernelGGL(b_associate_ties_dbg, dim3(S), dim3(256), 0, h->stream, aa[0], aa[1], dbg);
-    DBGCHECK(hipGetLastError());
-    DBGCHECK(hipStreamSynchronize(h->stream));
+    hipLaunchKernelGGL(b_associate_dbg, as.grid, dim3(256), 0, h->stream, as.a[0], as.a[1], as.nblk_e, dbg);
+    hipLaunchKernelGGL(b_associate_ties_dbg, dim3(S), dim3(256), 0, h->stream, as.a[0], as.a[1], dbg);
+    DBGCHECK(who, hipGetLastError());
+    DBGCHECK(who, hipStreamSynchronize(h->stream));
     if (nq) {
         std::vector<double> hrec((size_t)nq * S2M_FREC);
-        const size_t o = (size_t)sid * capq;
-        DBGCHECK(vilf_copy_sync(h, hrec.data(), frec.as<double>() + o * S2M_FREC, hrec.size() * 8, hipMemcpyDeviceToHost));
-        DBGCHECK(vilf_copy_sync(h, kind_out, fkind.as<int>() + o, (size_t)nq * 4, hipMemcpyDeviceToHost));
-        DBGCHECK(vilf_copy_sync(h, pos_out, dpos.as<int>() + o * 5, (size_t)nq * 5 * 4, hipMemcpyDeviceToHost));
-        DBGCHECK(vilf_copy_sync(h, nb_out, dnb.as<float>() + o * 15, (size_t)nq * 15 * 4, hipMemcpyDeviceToHost));
-        DBGCHECK(vilf_copy_sync(h, d2_out, dd2.as<float>() + o * 5, (size_t)nq * 5 * 4, hipMemcpyDeviceToHost));
+        const size_t o = (size_t)sid * c->capq();
+        DBGCHECK(who, vilf_copy_sync(h, hrec.data(), g.frec.as<double>() + o * S2M_FREC, hrec.size() * 8, hipMemcpyDeviceToHost));
+        DBGCHECK(who, vilf_copy_sync(h, kind_out, g.fkind.as<int>() + o, (size_t)nq * 4, hipMemcpyDeviceToHost));
+        DBGCHECK(who, vilf_copy_sync(h, pos_out, dpos.as<int>() + o * 5, (size_t)nq * 5 * 4, hipMemcpyDeviceToHost));
+        DBGCHECK(who, vilf_copy_sync(h, nb_out, dnb.as<float>() + o * 15, (size_t)nq * 15 * 4, hipMemcpyDeviceToHost));
+        DBGCHECK(who, vilf_copy_sync(h, d2_out, dd2.as<float>() + o * 5, (size_t)nq * 5 * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < nq; i++) for (int k = 0; k < 6; k++) rec_out[6 * (size_t)i + k] = hrec[(size_t)i * S2M_FREC + k];
     }
-#undef DBGCHECK
-    return done(VILF_OK);
+    return VILF_OK;
 }
 
 // ---- test hook (exported, not declared in vilfusion.h): what the LM solve does with given factor records at a given pose ---------------------
@@ -2944,36 +2967,17 @@ extern "C" int vilf_debug_s2m_solve(vilf_handle *h, int stream, const double *po
                                     double huber_a, int max_it, int pass, double *pose_out, double *cost_out, int *its_out, int *nfe_out, int *nfs_out, double *trace, int trace_rows) {
     if (!h || !pose_qt || n_edge_q < 0 || n_surf_q < 0 || pass < 0 || pass > 1 || max_it < 0 || trace_rows < 1 || max_it > trace_rows - 1) return VILF_ERR_INVALID_ARGUMENT;
     if (!pose_out || !cost_out || !its_out || !nfe_out || !nfs_out || !trace) return VILF_ERR_INVALID_ARGUMENT;
-    S2B *c = stream == -1 ? h->s2m : h->s2b;
-    if (!c || c->S < 1 || c->capScan[0] < 1 || c->capScan[1] < 1) return VILF_ERR_INVALID_ARGUMENT;
-    const int sid = stream == -1 ? 0 : stream;
-    if (stream < -1 || sid >= c->S || n_edge_q > c->capScan[0] || n_surf_q > c->capScan[1]) return VILF_ERR_INVALID_ARGUMENT;
-    const int nq = n_edge_q + n_surf_q;
+    const int nn[2] = {n_edge_q, n_surf_q}, nq = n_edge_q + n_surf_q;
     if (nq && (!kind || !rec6 || !cp3)) return VILF_ERR_INVALID_ARGUMENT;
-    HIPCHECK(h, hipSetDevice(h->device));
-    const int S = c->S, capq = c->capScan[0] + c->capScan[1];
-    DBuf nq_d[2], pose, res, frec, fkind, dtrace;
-    auto done = [&](int r) { for (DBuf *b : {&nq_d[0], &nq_d[1], &pose, &res, &frec, &fkind, &dtrace}) b->release(); return r; };
-#define DBGCHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string("vilf_debug_s2m_solve: ") + hipGetErrorString(e_); return done(VILF_ERR_DEVICE); } } while (0)
-    const size_t nslot = (size_t)S * capq, ntr = (size_t)trace_rows * S2M_TR;
-    if (!pose.ensure((size_t)S * 24 * 8) || !res.ensure((size_t)S * sizeof(S2BRes)) || !frec.ensure(nslot * S2M_FREC * 8) || !fkind.ensure(nslot * 4) || !dtrace.ensure(ntr * 8) ||
-        !nq_d[0].ensure((size_t)S * 4) || !nq_d[1].ensure((size_t)S * 4)) return done(VILF_ERR_DEVICE);
-    const int nn[2] = {n_edge_q, n_surf_q};
-    for (int w = 0; w < 2; w++) {
-        std::vector<int> cnt(S, 0);
-        cnt[sid] = nn[w];
-        DBGCHECK(vilf_copy_sync(h, nq_d[w].p, cnt.data(), (size_t)S * 4, hipMemcpyHostToDevice));
-    }
-    std::vector<double> hp((size_t)S * 24, 0.0);
-    for (int s = 0; s < S; s++) { hp[24 * s + 3] = 1.0; hp[24 * s + 11] = 1.0; hp[24 * s + 19] = 1.0; }
-    for (int k = 0; k < 7; k++) hp[24 * (size_t)sid + k] = pose_qt[k];
-    DBGCHECK(vilf_copy_sync(h, pose.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice));
-    std::vector<S2BRes> hr(S, S2BRes{});
-    for (int s = 0; s < S; s++) hr[s].do_opt = 1;
-    DBGCHECK(vilf_copy_sync(h, res.p, hr.data(), hr.size() * sizeof(S2BRes), hipMemcpyHostToDevice));
-    DBGCHECK(hipMemsetAsync(frec.p, 0, nslot * S2M_FREC * 8, h->stream));
-    DBGCHECK(hipMemsetAsync(fkind.p, 0, nslot * 4, h->stream));
-    DBGCHECK(hipMemsetAsync(dtrace.p, 0xff, ntr * 8, h->stream));                  // NaN: a row no iteration wrote
+    const char *who = "vilf_debug_s2m_solve";
+    S2BDbgStage g;
+    DBuf &pose = g.pose, &res = g.res, &frec = g.frec, &fkind = g.fkind, &dtrace = g.out[0];
+    const int rc = s2b_dbg_stage(h, who, stream, pose_qt, nn, g);
+    if (rc != VILF_OK) return rc;
+    const int S = g.c->S, capq = g.c->capq(), sid = g.sid;
+    const size_t ntr = (size_t)trace_rows * S2M_TR;
+    if (!dtrace.ensure(ntr * 8)) return VILF_ERR_DEVICE;
+    DBGCHECK(who, hipMemsetAsync(dtrace.p, 0xff, ntr * 8, h->stream));                  // NaN: a row no iteration wrote
     if (nq) {
         std::vector<double> hrec((size_t)nq * S2M_FREC, 0.0);
         for (int i = 0; i < nq; i++) {
@@ -2985,22 +2989,17 @@ extern "C" int vilf_debug_s2m_solve(vilf_handle *h, int stream, const double *po
             std::memcpy(r + 6, &a, 8); std::memcpy(r + 7, &b, 8);
         }
         const size_t o = (size_t)sid * capq;
-        DBGCHECK(vilf_copy_sync(h, frec.as<double>() + o * S2M_FREC, hrec.data(), hrec.size() * 8, hipMemcpyHostToDevice));
-        DBGCHECK(vilf_copy_sync(h, fkind.as<int>() + o, kind, (size_t)nq * 4, hipMemcpyHostToDevice));
+        DBGCHECK(who, vilf_copy_sync(h, frec.as<double>() + o * S2M_FREC, hrec.data(), hrec.size() * 8, hipMemcpyHostToDevice));
+        DBGCHECK(who, vilf_copy_sync(h, fkind.as<int>() + o, kind, (size_t)nq * 4, hipMemcpyHostToDevice));
     }
-    hipLaunchKernelGGL(b_solve_dbg, dim3(S), dim3(S2M_NT), 0, h->stream, pose.as<double>(), frec.as<double>(), fkind.as<int>(), capq, nq_d[0].as<int>(), nq_d[1].as<int>(), huber_a, max_it, pass,
+    hipLaunchKernelGGL(b_solve_dbg, dim3(S), dim3(S2M_NT), 0, h->stream, pose.as<double>(), frec.as<double>(), fkind.as<int>(), capq, g.nq[0].as<int>(), g.nq[1].as<int>(), huber_a, max_it, pass,
                        res.as<S2BRes>(), dtrace.as<double>(), sid);
-    DBGCHECK(hipGetLastError());
-    DBGCHECK(hipStreamSynchronize(h->stream));
+    DBGCHECK(who, hipGetLastError());
+    DBGCHECK(who, hipStreamSynchronize(h->stream));
     S2BRes r1;
-    std::vector<double> htr(ntr);
-    double hpose[7];
-    DBGCHECK(vilf_copy_sync(h, &r1, res.as<S2BRes>() + sid, sizeof(S2BRes), hipMemcpyDeviceToHost));
-    DBGCHECK(vilf_copy_sync(h, hpose, pose.as<double>() + 24 * (size_t)sid, 7 * 8, hipMemcpyDeviceToHost));
-    DBGCHECK(vilf_copy_sync(h, htr.data(), dtrace.p, ntr * 8, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 7; k++) pose_out[k] = hpose[k];
+    DBGCHECK(who, vilf_copy_sync(h, &r1, res.as<S2BRes>() + sid, sizeof(S2BRes), hipMemcpyDeviceToHost));
+    DBGCHECK(who, vilf_copy_sync(h, pose_out, pose.as<double>() + 24 * (size_t)sid, 7 * 8, hipMemcpyDeviceToHost));
+    DBGCHECK(who, vilf_copy_sync(h, trace, dtrace.p, ntr * 8, hipMemcpyDeviceToHost));
     *cost_out = r1.cost[pass]; *its_out = r1.its[pass]; *nfe_out = r1.nfe[pass]; *nfs_out = r1.nfs[pass];
-    std::memcpy(trace, htr.data(), ntr * 8);
-#undef DBGCHECK
-    return done(VILF_OK);
+    return VILF_OK;
 }
