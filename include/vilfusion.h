@@ -425,7 +425,9 @@ int vilf_get_profile_sc(vilf_handle *h, double ms_out[4], long launches_out[4]);
  *                no RANSAC. Fewer than 3 accepted: not converged, stop (criterion 5). Step = rigid Umeyama without scale (TransformationEstimationSVD) in fp64:
  *                n, sum s, sum t, sum s t^T over the accepted pairs accumulated in fp64 in a fixed tree (xor butterfly 32, 16, .. 1 within 64 consecutive source
  *                points, then the 4 groups of 64 of a block of 256 in order, then the blocks in order), H = sum t s^T / n - mean_t mean_s^T, H = U D V^T by
- *                one-sided Jacobi, R = U diag(1, 1, det U det V) V^T, t = mean_t - R mean_s; the 4 x 4 rounded to float = T_k. source <- T_k source (float,
+ *                one-sided Jacobi, R = U diag(1, 1, det U det V) V^T, t = mean_t - R mean_s; the 4 x 4 rounded to float = T_k. Below rank two (collinear
+ *                correspondences, or a single target point) R is a proper rotation that maps mean_s to mean_t (with t) and the source's principal direction
+ *                onto the target's, and nothing more is pinned. source <- T_k source (float,
  *                as above, on the already moved source: incrementally, as PCL does), final <- T_k final (float, entry = ((a0*b0 + a1*b1) + a2*b2) + a3*b3).
  *                DefaultConvergenceCriteria after every step, in this order: 1 iterations reached max_iterations; 2 cos = 0.5 (trace R_k - 1) >=
  *                rotation_threshold and |t_k|^2 <= transformation_epsilon (fp64 of the float entries); with mse = mean of the accepted d2 of this round (fp64):

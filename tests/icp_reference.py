@@ -127,8 +127,9 @@ class Target:
         return idx, best
 
 
-def umeyama(S, T, reverse=False):
-    """rigid, no scale, from the raw fp64 sums n, sum s, sum t, sum s t^T (the header's formula); reverse: the sums in reversed order"""
+def umeyama64(S, T, reverse=False):
+    """rigid, no scale, from the raw fp64 sums n, sum s, sum t, sum s t^T (the header's formula); reverse: the sums in reversed order.
+    Returns (R, t) in fp64, before the rounding to float."""
     S, T = S.astype(np.float64), T.astype(np.float64)
     if reverse:
         S, T = S[::-1], T[::-1]
@@ -138,9 +139,15 @@ def umeyama(S, T, reverse=False):
     H = seq(T[:, :, None] * S[:, None, :]) / n - np.outer(mt, ms)
     U, _, Vt = np.linalg.svd(H)
     R = U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U) * np.linalg.det(Vt)) or 1.0]) @ Vt
+    return R, mt - R @ ms
+
+
+def umeyama(S, T, reverse=False):
+    """umeyama64 rounded to float: the step T_k as a float 4 x 4"""
+    R, t = umeyama64(S, T, reverse)
     M = np.eye(4, dtype=F)
     M[:3, :3] = R.astype(F)
-    M[:3, 3] = (mt - R @ ms).astype(F)
+    M[:3, 3] = t.astype(F)
     return M
 
 
@@ -191,7 +198,10 @@ def align(source, target, p=None, guess_qt=None, reverse=False):
     rounds, margin = [], np.inf
     converged, criterion, iterations, mse_prev, mse, ncorr = False, NONE, 0, DBL_MAX, 0.0, 0
     first_search = None
-    rel = lambda v, thr, scale: abs(v - thr) / scale
+
+    def rel(v, thr, scale):                                 # |v - thr| / |scale|; a threshold of zero has no scale: inf, or 0 at equality
+        d, sc = abs(v - thr), abs(scale)
+        return d / sc if sc > 0 else (0.0 if d == 0 else np.inf)
     for r in range(p.max_iterations):
         src = transform(pend[:3], src)
         idx, d2 = tg.nearest(src)
@@ -229,9 +239,11 @@ def align(source, target, p=None, guess_qt=None, reverse=False):
                 if dm < p.euclidean_fitness_epsilon:
                     crit = ABS_MSE
                 else:
-                    m4 = rel(dm / mse_prev, p.mse_relative, p.mse_relative)
-                    margin = min(margin, m4)
-                    if dm / mse_prev < p.mse_relative:
+                    with np.errstate(all="ignore"):
+                        ratio = float(np.float64(dm) / np.float64(mse_prev))      # IEEE: 0 / 0 is NaN, and NaN is not < anything (the device's arithmetic)
+                    if not math.isnan(ratio):
+                        margin = min(margin, rel(ratio, p.mse_relative, p.mse_relative))
+                    if ratio < p.mse_relative:
                         crit = REL_MSE
         mse_prev = mse
         rounds.append(dict(n_correspondences=ncorr, criterion=crit, mse=mse, cos_angle=cosa, translation_sqr=tsq))
