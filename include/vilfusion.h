@@ -746,6 +746,91 @@ int vilf_track_detect_masked(vilf_handle *h, const unsigned char *img, const uns
 /* vilf_set_profiling: the erosion, and the probe with rejectWithF_mask (probe, lift, hypotheses, score, apply), of the last vilf_track_read_image_mask; 0 for a
  * plain frame. In the five stages of vilf_track_profile the mask's upload and the erosion fall into the first, the probe and the rejection into the second. */
 int vilf_track_profile_mask(vilf_handle *h, double ms_out[2], long launches_out[2]);
+
+/* ---- Visual start-up: relativePose (≙ Estimator::relativePose, estimator.cpp:461-490, with FeatureManager::getCorresponding, feature_manager.cpp:129-148, and
+ *      MotionEstimator::solveRelativeRT, initial/solve_5pts.cpp:193-227; device) ----
+ * The first stage of initialStructure: the frame l of the window whose correspondences with the newest frame carry enough parallax, and the relative pose of the
+ * two. The reference calls cv::findFundamentalMat(FM_RANSAC, 0.3 / 460, 0.99) on normalised coordinates and cv::recoverPose; OpenCV is not available, so this text
+ * fixes the arithmetic itself (deviations: DESIGN.md §3n), tests/startup_reference.py restates it in numpy and the kernels agree with that to the bit. GlobalSFM and
+ * the per-frame PnP are not part of it. "fp64, each operation rounded" is as in the tracker's text; a NaN compares false everywhere.
+ *   window       n_frames frames 0 .. newest = n_frames - 1 and n_features features in feature order; feature f was first seen in frame start_frame[f] and has
+ *                n_obs(f) = first_obs[f + 1] - first_obs[f] observations in consecutive frames, observation o at row first_obs[f] + o of pts: the normalised image
+ *                point (x, y) of frame start_frame[f] + o, fp64.
+ *   correspondences of the pair (i, newest), i = 0 .. n_frames - 2: feature f belongs to it iff start_frame[f] <= i and start_frame[f] + n_obs(f) - 1 >= newest.
+ *                The members are taken in feature order, j = 0 .. m - 1; a_j = the point of frame i, b_j = the point of frame newest, both coordinates rounded
+ *                to float32 (the reference goes through cv::Point2f). Everything below is fp64 on these float32 values.
+ *   gates        count: m > min_count (20, estimator.cpp:468). parallax: d_j = sqrt(dx dx + dy dy), (dx, dy) = a_j - b_j, fp64, each operation rounded. The sum:
+ *                64 partial sums, p_t = the sum from 0.0 of d_j over j = t, t + 64, t + 128, .. < m in ascending order, t = 0 .. 63; then for o = 32, 16, 8, 4, 2, 1:
+ *                every p_t <- p_t + p_(t xor o), all t at once (addition commutes, so all 64 end equal). parallax = (p_0 / m) * focal_length (460); 0 if m = 0;
+ *                the gate is parallax > min_parallax (30, :481). solve count: m >= min_solve_count (15, solve_5pts.cpp:195; dead behind the count gate with the
+ *                defaults, kept because both are parameters) and m >= 8. A pair that fails a gate is not searched: best_k = chosen = -1 and score, F, R, T and the counts of its row are 0.
+ *   search       the tracker's rejectWithF paragraphs "sample", "8-point solve" and "score" word for word, with n = m, x = a_j, x' = b_j, K = n_hypotheses
+ *                (1 .. VILF_TRACK_MAX_HYPOTHESES, default 512), the seed of pair i = seed + i (uint32, wrapping) and F_THRESHOLD = ransac_threshold (0.3 / 460.0); the
+ *                squared threshold is the fp64 product ransac_threshold * ransac_threshold. Winner = the valid hypothesis of the highest score, ties to the lower
+ *                k; its inlier mask is the RANSAC mask; no refit (FM_RANSAC has none). No valid hypothesis: the pair fails, best_k = -1.
+ *   recoverPose  E = the winner's F as it is (the coordinates are normalised: x'^T E x = 0 with x in frame i, x' in frame newest). G = E^T E, g_pq = sum_r E_rp E_rq
+ *                from 0 over r = 0, 1, 2; Jacobi(G, 3) of the tracker's text -> eigenvalues g_ii, eigenvectors the columns of V. i3 = the index of the smallest
+ *                g_ii (compared with <, ties and NaNs leave the lower index); r0 < r1 the two other indices; i1 = r1 if g_r1r1 > g_r0r0, else r0; i2 = the other.
+ *                v1, v2 = columns i1, i2 of V; v3 = v1 x v2 (c_0 = p_1 q_2 - p_2 q_1, c_1 = p_2 q_0 - p_0 q_2, c_2 = p_0 q_1 - p_1 q_0 for c = p x q, two products
+ *                and a subtraction each). For j = 1, 2: w_r = (E_r0 v_j0 + E_r1 v_j1) + E_r2 v_j2, u_j = w / sqrt((w_0 w_0 + w_1 w_1) + w_2 w_2); u3 = u1 x u2.
+ *                With U = [u1 u2 u3], V = [v1 v2 v3] both determinants are +1 by construction. R1 = U W V^T: R1_rc = (u2_r v1_c - u1_r v2_c) + u3_r v3_c;
+ *                R2 = U W^T V^T: R2_rc = (u1_r v2_c - u2_r v1_c) + u3_r v3_c; t = u3. If any entry of R1, R2 or t is not finite the pair fails (counts 0,
+ *                chosen -1, R and T 0). The four candidates in OpenCV's order: 0 (R1, t), 1 (R2, t), 2 (R1, -t), 3 (R2, -t).
+ *   cheirality   for candidate (R, t) and pair j, with a = a_j, b = b_j: r_k = (R_k0 a_x + R_k1 a_y) + R_k2; rr = (r_0 r_0 + r_1 r_1) + r_2 r_2;
+ *                xx = (b_x b_x + b_y b_y) + 1.0; rx = (r_0 b_x + r_1 b_y) + r_2; rt = (r_0 t_0 + r_1 t_1) + r_2 t_2; xt = (b_x t_0 + b_y t_1) + t_2;
+ *                det = rr xx - rx rx; z1 = (rx xt - xx rt) / det; z2 = (rr xt - rx rt) / det: the depths along the two rays that minimise
+ *                |z1 R (a, 1) + t - z2 (b, 1)|, in closed form (this replaces OpenCV's 4 x 4 DLT triangulation: a deviation). The pair is good iff
+ *                0 < z1 < distance_threshold and 0 < z2 < distance_threshold (50, OpenCV's default in this overload). count_c = the number of good pairs among
+ *                the RANSAC inliers. chosen = the first c in the order above with the largest count (OpenCV's >= chain). inlier_cnt = count_chosen; the pair
+ *                passes iff inlier_cnt > min_inliers (12, solve_5pts.cpp:221).
+ *   output       with (R, t) the chosen candidate, the reference's convention (solve_5pts.cpp:219-220): Rotation = R^T, Translation_r = -((R_0r t_0 + R_1r t_1) + R_2r t_2).
+ *                Point of pair j: (z1 a_x, z1 a_y, z1) in the camera of frame i if j is a RANSAC inlier and good under the chosen candidate, else (0, 0, 0).
+ *   l            the lowest i whose pair passes every gate, -1 if none does. The reference stops at the first passing i; the pairs do not depend on each other,
+ *                so all of them are evaluated and the table of pairs comes with the answer. */
+#define VILF_SU_COUNT 1          /* flags of a pair: m > min_count */
+#define VILF_SU_PARALLAX 2       /* parallax > min_parallax */
+#define VILF_SU_SOLVE_COUNT 4    /* m >= min_solve_count and m >= 8 */
+#define VILF_SU_HYPOTHESIS 8     /* a valid hypothesis exists */
+#define VILF_SU_FINITE 16        /* the decomposition is finite */
+#define VILF_SU_INLIERS 32       /* inlier_cnt > min_inliers */
+#define VILF_SU_PASS 63
+#define VILF_STARTUP_MAX_WINDOWS 256
+typedef struct vilf_startup_params {
+    int n_hypotheses; unsigned seed;                                              /* 512, 0 */
+    int min_count, min_solve_count, min_inliers, pad_;                            /* 20, 15, 12 */
+    double ransac_threshold, focal_length, min_parallax, distance_threshold;      /* 0.3 / 460.0, 460, 30, 50 */
+} vilf_startup_params;
+void vilf_startup_default_params(vilf_startup_params *p);
+typedef struct vilf_startup_window {
+    int n_frames, n_features;        /* 2 .. VILF_MAX_FRAMES, 0 .. VILF_MAX_FEATURES */
+    const int *start_frame;          /* [n_features] */
+    const int *first_obs;            /* [n_features + 1], first_obs[0] = 0, non-decreasing */
+    const double *pts;               /* [first_obs[n_features]][2] */
+} vilf_startup_window;
+typedef struct vilf_startup_result {
+    int l, inlier_cnt;               /* l = -1: no pair passes, everything else 0 */
+    double R[9], T[3];               /* relative_R (row-major), relative_T of pair l */
+} vilf_startup_result;
+typedef struct vilf_startup_pair {
+    int count, flags, best_k, score; /* m, VILF_SU_*, the winning k or -1, its inliers */
+    int cheirality[4];               /* the four candidates' counts */
+    int chosen, inlier_cnt;          /* the chosen candidate or -1, its count */
+    double parallax;                 /* the number the parallax gate compares */
+    double F[9], R[9], T[3];         /* the winner (row-major), Rotation, Translation */
+} vilf_startup_pair;
+/* relativePose for n_windows independent windows: one chain of launches on the handle's stream (gather, hypotheses, score, pose), the host waits once, one download.
+ * out [n_windows]; pairs_out [n_windows][VILF_MAX_FRAMES - 1] or NULL (rows of pairs the window does not have are 0 with best_k = chosen = -1). Invalid argument,
+ * nothing written: a null pointer, n_windows < 1 or > VILF_STARTUP_MAX_WINDOWS, n_frames < 2 or > VILF_MAX_FRAMES, n_features < 0 or > VILF_MAX_FEATURES, first_obs
+ * that does not start at 0 or decreases, start_frame < 0, start_frame + n_obs > n_frames, a coordinate that is not finite, n_hypotheses outside
+ * 1 .. VILF_TRACK_MAX_HYPOTHESES, a threshold, focal length or distance that is not positive and finite, a min_parallax that is not finite, a negative count gate. */
+int vilf_startup_relative_pose(vilf_handle *h, const vilf_startup_params *p, int n_windows, const vilf_startup_window *windows, vilf_startup_result *out,
+                               vilf_startup_pair *pairs_out);
+/* the per-correspondence outputs of the last vilf_startup_relative_pose, each [n_windows][VILF_MAX_FRAMES - 1][VILF_MAX_FEATURES] in correspondence order, 0 behind
+ * the pair's count (any may be NULL): the feature index, the mask (bit 0: RANSAC inlier, bit 1: good under the chosen candidate), the points [..][3].
+ * n_windows other than the last call's, or no call yet: invalid argument, nothing written. */
+int vilf_startup_get_correspondences(vilf_handle *h, int n_windows, int *feature_out, unsigned char *mask_out, double *points_out);
+/* vilf_set_profiling: su_gather, su_hypotheses, su_score, su_pose of the calls since the switch was set */
+int vilf_startup_profile(vilf_handle *h, double ms_out[4], long launches_out[4]);
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,35 @@ class TrackMaskParams(C.Structure):
 VILF_TRACK_MAX_ERODE = 16
 
 
+class StartupParams(C.Structure):
+    """vilf_startup_params: K and seed of the search, the gates of relativePose / solveRelativeRT, the RANSAC threshold, FOCAL_LENGTH, recoverPose's distance"""
+    _fields_ = [("n_hypotheses", C.c_int), ("seed", C.c_uint), ("min_count", C.c_int), ("min_solve_count", C.c_int), ("min_inliers", C.c_int), ("pad_", C.c_int),
+                ("ransac_threshold", C.c_double), ("focal_length", C.c_double), ("min_parallax", C.c_double), ("distance_threshold", C.c_double)]
+
+
+class StartupWindow(C.Structure):
+    """vilf_startup_window: the feature table relativePose reads"""
+    _fields_ = [("n_frames", C.c_int), ("n_features", C.c_int), ("start_frame", C.POINTER(C.c_int32)), ("first_obs", C.POINTER(C.c_int32)), ("pts", c_double_p)]
+
+
+class StartupResult(C.Structure):
+    """vilf_startup_result: l, relative_R, relative_T"""
+    _fields_ = [("l", C.c_int), ("inlier_cnt", C.c_int), ("R", C.c_double * 9), ("T", C.c_double * 3)]
+
+
+class StartupPair(C.Structure):
+    """vilf_startup_pair: one row of the table of pairs (i, newest)"""
+    _fields_ = [("count", C.c_int), ("flags", C.c_int), ("best_k", C.c_int), ("score", C.c_int), ("cheirality", C.c_int * 4), ("chosen", C.c_int),
+                ("inlier_cnt", C.c_int), ("parallax", C.c_double), ("F", C.c_double * 9), ("R", C.c_double * 9), ("T", C.c_double * 3)]
+
+
+VILF_SU_COUNT, VILF_SU_PARALLAX, VILF_SU_SOLVE_COUNT, VILF_SU_HYPOTHESIS, VILF_SU_FINITE, VILF_SU_INLIERS, VILF_SU_PASS = 1, 2, 4, 8, 16, 32, 63
+VILF_STARTUP_MAX_WINDOWS = 256
+# the C name of every mirror of the start-up, for the layout check (tests/test_startup_relative_pose.py compiles the header as tests/test_abi.py does)
+STARTUP_LAYOUTS = {"vilf_startup_params": StartupParams, "vilf_startup_window": StartupWindow, "vilf_startup_result": StartupResult,
+                   "vilf_startup_pair": StartupPair}
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

@@ -56,6 +56,7 @@ struct LwCtx;
 struct ScCtx;
 struct IcpCtx;
 struct TrackCtx;
+struct StartupCtx;
 
 // deep copy of a window snapshot (estimate_extrinsic / estimate_td: the batched entry points run the general single-window solve per slot and need the inputs again)
 struct OwnedWindow {
@@ -125,6 +126,7 @@ struct vilf_handle {
     ScCtx *sc = nullptr;                     // Scan Context descriptor database and search workspace (vilf_sc.hip)
     IcpCtx *icp = nullptr;                   // key-frame cloud store and ICP workspace of the loop verification (vilf_icp.hip)
     TrackCtx *trk = nullptr;                 // image feature tracker: pyramids, feature list, detection workspace (vilf_track.hip)
+    StartupCtx *su = nullptr;                // visual start-up: the pairs' correspondences, hypotheses and result rows (vilf_startup.hip)
 };
 
 // a copy ordered on the handle's stream and waited for: the library's streams are non-blocking (they do not synchronise with the legacy default stream), so a plain
@@ -155,6 +157,8 @@ void vilf_icp_release(vilf_handle *h);
 void vilf_icp_profile_reset(vilf_handle *h);
 void vilf_track_release(vilf_handle *h);
 void vilf_track_profile_reset(vilf_handle *h);
+void vilf_startup_release(vilf_handle *h);
+void vilf_startup_profile_reset(vilf_handle *h);
 void vilf_sc_profile_reset(vilf_handle *h);                                 // vilf_set_profiling: the Scan Context spans start from zero
 int vilf_lw_chol_max_n();                                                      // largest n vilf_lw_chol_solve takes (its back substitution keeps the solution in LDS)
 int vilf_lw_chol_solve(vilf_handle *h, int n, double *S, double *y, int *info);   // blocked Cholesky solve on the handle's stream (vilf_lw.hip): S = [(n + 1) x n] row-major, row n = rhs

@@ -33,6 +33,7 @@
 #include "vilf_device.hpp"
 #include "vilf_kernels.hpp"
 #include "vilf_sort.hpp"
+#include "vilf_fmat.hpp"
 
 #define TK_WIN 21
 #define TK_NPOS (TK_WIN * TK_WIN)
@@ -44,7 +45,6 @@
 #define TK_FE_STAGES 2                      // CLAHE, rejectWithF
 #define TK_MK_STAGES 2                      // erode, probe + rejectWithF_mask
 #define TK_ER_MAX VILF_TRACK_MAX_ERODE
-#define TK_F_SWEEPS 10
 #define TK_F_MAXK VILF_TRACK_MAX_HYPOTHESES
 
 struct TkPyr { unsigned char *lv[TK_LEVELS]; int w[TK_LEVELS], h[TK_LEVELS], lmax; };      // rows are tight (stride = width)
@@ -84,7 +84,7 @@ __global__ void tk_candidates(const double *lam, const unsigned char *mask, int 
 __global__ void tk_keys(const double *lam, const unsigned *cidx, const int *ctl, int cap, unsigned long long *key, int *val);
 __global__ void tk_corners(const int *val, int W, int cap, int *ctl, TkList l, long long md2);
 __global__ void tk_finish(TkList l, int *ctl, int *prev_ids, float2 *prev_un, TkCam cam, double dt, int has_prev);
-#define TK_F_LANES 64                   // tk_f_hypotheses: block 64 (one wave), grid = ceil(K / 64), a lane per hypothesis, its matrices a column of the LDS arrays; no barrier
+// TK_F_LANES (vilf_fmat.hpp)              tk_f_hypotheses: block 64 (one wave), grid = ceil(K / 64), a lane per hypothesis, its matrices a column of the LDS arrays; no barrier
 #define TK_F_WAVES 4                    // tk_f_score: block 256, grid = ceil(K / 4), a wave per hypothesis; no workgroup barrier
 __global__ void tk_clahe_lut(const unsigned char *img, int W, int H, int tw, int th, int limit, float scale, unsigned char *lut);      // grid (tx, ty), block TK_NT
 __global__ void tk_clahe_remap(const unsigned char *img, int W, int H, int tx, int ty, float inv_tw, float inv_th, const unsigned char *lut, unsigned char *out);   // block (32, 8), tiles of the image
@@ -565,72 +565,11 @@ __global__ __launch_bounds__(TK_TW * TK_TH) void tk_clahe_remap(const unsigned c
 
 // ---- rejectWithF ------------------------------------------------------------------------------------------------------------------------------
 namespace {
-VD unsigned tk_mix(unsigned x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
-VD int tk_iu(int N, int p, int q) { return p * N - p * (p - 1) / 2 + (q - p); }      // upper triangle, p <= q
-VD int tk_is(int N, int p, int q) { return p <= q ? tk_iu(N, p, q) : tk_iu(N, q, p); }
-// cyclic Jacobi of the symmetric N x N matrix in column `lane` of M (upper triangle) -> eigenvectors in the columns of V (row-major N x N in column `lane`)
-template <int N> VD void tk_jacobi(double (*M)[TK_F_LANES], double (*V)[TK_F_LANES], int lane) {
-    for (int r = 0; r < N; r++) for (int c = 0; c < N; c++) V[r * N + c][lane] = r == c ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < TK_F_SWEEPS; sweep++)
-        for (int p = 0; p < N - 1; p++)
-            for (int q = p + 1; q < N; q++) {
-                const int ipq = tk_iu(N, p, q), ipp = tk_iu(N, p, p), iqq = tk_iu(N, q, q);
-                const double apq = M[ipq][lane];
-                if (apq == 0.0) continue;
-                const double app = M[ipp][lane], aqq = M[iqq][lane];
-                const double theta = __ddiv_rn(__dsub_rn(aqq, app), __dmul_rn(2.0, apq));
-                const double t = __ddiv_rn(theta < 0.0 ? -1.0 : 1.0, __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
-                const double c = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0))), s = __dmul_rn(t, c);
-                for (int r = 0; r < N; r++) {
-                    if (r == p || r == q) continue;
-                    const int irp = tk_is(N, r, p), irq = tk_is(N, r, q);
-                    const double arp = M[irp][lane], arq = M[irq][lane];
-                    M[irp][lane] = __dsub_rn(__dmul_rn(c, arp), __dmul_rn(s, arq));
-                    M[irq][lane] = __dadd_rn(__dmul_rn(s, arp), __dmul_rn(c, arq));
-                }
-                const double tap = __dmul_rn(t, apq);
-                M[ipp][lane] = __dsub_rn(app, tap); M[iqq][lane] = __dadd_rn(aqq, tap); M[ipq][lane] = 0.0;
-                for (int r = 0; r < N; r++) {
-                    const double vrp = V[r * N + p][lane], vrq = V[r * N + q][lane];
-                    V[r * N + p][lane] = __dsub_rn(__dmul_rn(c, vrp), __dmul_rn(s, vrq));
-                    V[r * N + q][lane] = __dadd_rn(__dmul_rn(s, vrp), __dmul_rn(c, vrq));
-                }
-            }
-}
-template <int N> VD int tk_smallest(double (*M)[TK_F_LANES], int lane) {
-    int at = 0;
-    double best = M[0][lane];
-    for (int i = 1; i < N; i++) { const double a = M[tk_iu(N, i, i)][lane]; if (a < best) { best = a; at = i; } }
-    return at;
-}
-// Hartley normalisation of the eight points (x in P[0 .. 7], y in P[8 .. 15], column `lane`), in place -> centroid and scale
-VD void tk_hartley(double (*P)[TK_F_LANES], int lane, double &cx, double &cy, double &s) {
-    double sx = 0.0, sy = 0.0, md = 0.0;
-    for (int j = 0; j < 8; j++) { sx = __dadd_rn(sx, P[j][lane]); sy = __dadd_rn(sy, P[8 + j][lane]); }
-    cx = __ddiv_rn(sx, 8.0); cy = __ddiv_rn(sy, 8.0);
-    for (int j = 0; j < 8; j++) {
-        const double dx = __dsub_rn(P[j][lane], cx), dy = __dsub_rn(P[8 + j][lane], cy);
-        md = __dadd_rn(md, __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy))));
-    }
-    md = __ddiv_rn(md, 8.0);
-    s = __ddiv_rn(__dsqrt_rn(2.0), md);
-    for (int j = 0; j < 8; j++) { P[j][lane] = __dmul_rn(__dsub_rn(P[j][lane], cx), s); P[8 + j][lane] = __dmul_rn(__dsub_rn(P[8 + j][lane], cy), s); }
-}
 // the lift of rejectWithF: liftProjective in fp64, then the virtual camera's pixel, rounded to float32
 VD float2 tk_f_liftpt(const TkCam &cam, float2 p, double focal, double half_w, double half_h) {
     double ux, uy;
     tk_undistort(cam, p, ux, uy);
     return make_float2((float)__dadd_rn(__dmul_rn(focal, ux), half_w), (float)__dadd_rn(__dmul_rn(focal, uy), half_h));
-}
-// the score's inlier rule for the point pair (a, b) under F (row-major)
-VD bool tk_f_inlier(const double *F, float2 a, float2 b, double thr2) {
-    const double x = (double)a.x, y = (double)a.y, xp = (double)b.x, yp = (double)b.y;
-    const double lp0 = __dadd_rn(__dadd_rn(__dmul_rn(F[0], x), __dmul_rn(F[1], y)), F[2]), lp1 = __dadd_rn(__dadd_rn(__dmul_rn(F[3], x), __dmul_rn(F[4], y)), F[5]);
-    const double lp2 = __dadd_rn(__dadd_rn(__dmul_rn(F[6], x), __dmul_rn(F[7], y)), F[8]);
-    const double l0 = __dadd_rn(__dadd_rn(__dmul_rn(F[0], xp), __dmul_rn(F[3], yp)), F[6]), l1 = __dadd_rn(__dadd_rn(__dmul_rn(F[1], xp), __dmul_rn(F[4], yp)), F[7]);
-    const double d = __dadd_rn(__dadd_rn(__dmul_rn(xp, lp0), __dmul_rn(yp, lp1)), lp2), d2 = __dmul_rn(d, d);
-    const double e1 = __ddiv_rn(d2, __dadd_rn(__dmul_rn(lp0, lp0), __dmul_rn(lp1, lp1))), e2 = __ddiv_rn(d2, __dadd_rn(__dmul_rn(l0, l0), __dmul_rn(l1, l1)));
-    return e1 <= thr2 && e2 <= thr2;
 }
 }  // namespace
 
@@ -661,83 +600,10 @@ __global__ __launch_bounds__(TK_F_LANES) void tk_f_hypotheses(TkF f, int K, unsi
     __shared__ double s_M[45][TK_F_LANES], s_V[81][TK_F_LANES];          // 64 512 bytes: a column per lane, so a lane's accesses never meet another's
     const int lane = threadIdx.x, k = blockIdx.x * TK_F_LANES + lane, n = f.fctl[FC_M];
     if (n < 8 || k >= K) return;
-    // sample: slot j in registers (every loop over the slots is unrolled, so S is never indexed by a run-time value)
-    int S[8];
-    const unsigned base = tk_mix(tk_mix(seed + 0x9e3779b9u) + (unsigned)k);
+    double F[9];
+    const bool ok = tk_f_hypothesis(f.ua, f.ub, n, k, seed, s_M, s_V, lane, F);      // sample indices < n <= TK_MAXN, the rows of ua, ub
 #pragma unroll
-    for (int j = 0; j < 8; j++) {
-        int i = (int)(((unsigned long long)tk_mix(base + (unsigned)j) * (unsigned long long)n) >> 32);
-#pragma unroll
-        for (int step = 0; step < j; step++) {
-            bool dup = false;
-#pragma unroll
-            for (int e = 0; e < j; e++) dup |= S[e] == i;
-            i = dup ? (i + 1 == n ? 0 : i + 1) : i;
-        }
-        S[j] = i;
-    }
-    // the sample's points: side 1 in s_V[0 .. 15], side 2 in s_V[16 .. 31] (V is not needed before the Jacobi)
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const float2 a = f.ua[S[j]], b = f.ub[S[j]];         // S[j] < n <= TK_MAXN
-        s_V[j][lane] = (double)a.x; s_V[8 + j][lane] = (double)a.y; s_V[16 + j][lane] = (double)b.x; s_V[24 + j][lane] = (double)b.y;
-    }
-    double cx1, cy1, s1, cx2, cy2, s2;
-    tk_hartley(s_V, lane, cx1, cy1, s1);
-    tk_hartley(s_V + 16, lane, cx2, cy2, s2);
-    for (int e = 0; e < 45; e++) s_M[e][lane] = 0.0;
-    for (int j = 0; j < 8; j++) {
-        const double x = s_V[j][lane], y = s_V[8 + j][lane], xp = s_V[16 + j][lane], yp = s_V[24 + j][lane];
-        const double r[9] = {__dmul_rn(xp, x), __dmul_rn(xp, y), xp, __dmul_rn(yp, x), __dmul_rn(yp, y), yp, x, y, 1.0};
-        int e = 0;
-#pragma unroll
-        for (int p = 0; p < 9; p++)
-#pragma unroll
-            for (int q = p; q < 9; q++, e++) s_M[e][lane] = __dadd_rn(s_M[e][lane], __dmul_rn(r[p], r[q]));
-    }
-    tk_jacobi<9>(s_M, s_V, lane);
-    double Fh[9];
-    {
-        const int at = tk_smallest<9>(s_M, lane);
-#pragma unroll
-        for (int c = 0; c < 9; c++) Fh[c] = s_V[c * 9 + at][lane];
-    }
-    // rank 2: the same Jacobi at size 3 on G = Fh^T Fh
-#pragma unroll
-    for (int p = 0; p < 3; p++)
-#pragma unroll
-        for (int q = p; q < 3; q++) {
-            double acc = 0.0;
-#pragma unroll
-            for (int r = 0; r < 3; r++) acc = __dadd_rn(acc, __dmul_rn(Fh[r * 3 + p], Fh[r * 3 + q]));
-            s_M[tk_iu(3, p, q)][lane] = acc;
-        }
-    tk_jacobi<3>(s_M, s_V, lane);
-    {
-        const int at = tk_smallest<3>(s_M, lane);
-        const double v0 = s_V[at][lane], v1 = s_V[3 + at][lane], v2 = s_V[6 + at][lane];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const double w = __dadd_rn(__dadd_rn(__dmul_rn(Fh[r * 3], v0), __dmul_rn(Fh[r * 3 + 1], v1)), __dmul_rn(Fh[r * 3 + 2], v2));
-            Fh[r * 3] = __dsub_rn(Fh[r * 3], __dmul_rn(w, v0)); Fh[r * 3 + 1] = __dsub_rn(Fh[r * 3 + 1], __dmul_rn(w, v1)); Fh[r * 3 + 2] = __dsub_rn(Fh[r * 3 + 2], __dmul_rn(w, v2));
-        }
-    }
-    // F = T'^T Fh T
-    const double t1x = __dmul_rn(s1, cx1), t1y = __dmul_rn(s1, cy1), t2x = __dmul_rn(s2, cx2), t2y = __dmul_rn(s2, cy2);
-    double B[9], F[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        B[r * 3] = __dmul_rn(Fh[r * 3], s1); B[r * 3 + 1] = __dmul_rn(Fh[r * 3 + 1], s1);
-        B[r * 3 + 2] = __dsub_rn(__dsub_rn(Fh[r * 3 + 2], __dmul_rn(Fh[r * 3], t1x)), __dmul_rn(Fh[r * 3 + 1], t1y));
-    }
-    bool ok = isfinite(s1) && isfinite(s2);
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        F[c] = __dmul_rn(s2, B[c]); F[3 + c] = __dmul_rn(s2, B[3 + c]);
-        F[6 + c] = __dsub_rn(__dsub_rn(B[6 + c], __dmul_rn(t2x, B[c])), __dmul_rn(t2y, B[3 + c]));
-    }
-#pragma unroll
-    for (int e = 0; e < 9; e++) { ok = ok && isfinite(F[e]); f.F[(size_t)k * 9 + e] = F[e]; }      // k < K <= TK_F_MAXK rows
+    for (int e = 0; e < 9; e++) f.F[(size_t)k * 9 + e] = F[e];      // k < K <= TK_F_MAXK rows
     f.valid[k] = ok ? 1 : 0;
 }
 

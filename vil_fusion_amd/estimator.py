@@ -321,6 +321,68 @@ def visual_imu_alignment(solver, noise, frame_R, frame_T, acc_0, gyr_0, lin_ba, 
     return dict(ok=bool(ok.value), delta_bg=dbg, g=g, x=x[:nx.value].copy(), pre=pre[:n - 1])
 
 
+def startup_default_params(**over):
+    """vilf_startup_params with the reference's constants (estimator.cpp:468-481, solve_5pts.cpp:195-221); keyword arguments replace fields (n_hypotheses=64, seed=3, ...)"""
+    p = abi.StartupParams()
+    lib().vilf_startup_default_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise TypeError(f"vilf_startup_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def relative_pose(solver, windows, correspondences=False, **params):
+    """≙ Estimator::relativePose (estimator.cpp:461-490) for every window at once on the device (vilf_startup_relative_pose). windows: an iterable of
+    dict(n_frames, start_frame [n], first_obs [n + 1], pts [total][2]): the feature table in feature order, normalised image points. params: fields of
+    vilf_startup_params. Returns a list of dict(ok, l, R, T, inlier_cnt, pairs) per window; pairs = the rows of the pairs (i, newest), i = 0 .. n_frames - 2, as
+    dicts. correspondences=True adds to every row feature [count], mask [count] (bit 0 RANSAC inlier, bit 1 good under the chosen candidate), points [count][3]."""
+    L = lib()
+    p = startup_default_params(**params)
+    windows = list(windows)
+    n = len(windows)
+    W = (abi.StartupWindow * max(n, 1))()
+    keep = []
+    for k, w in enumerate(windows):
+        start = np.ascontiguousarray(w["start_frame"], dtype=np.int32)
+        first = np.ascontiguousarray(w["first_obs"], dtype=np.int32)
+        pts = np.ascontiguousarray(w["pts"], dtype=np.float64).reshape(-1, 2)
+        keep.append((start, first, pts))
+        W[k].n_frames, W[k].n_features = int(w["n_frames"]), len(start)
+        W[k].start_frame = start.ctypes.data_as(C.POINTER(C.c_int32))
+        W[k].first_obs = first.ctypes.data_as(C.POINTER(C.c_int32))
+        W[k].pts = abi.dptr(pts)
+    NP, NF = abi.VILF_MAX_FRAMES - 1, abi.VILF_MAX_FEATURES
+    out = (abi.StartupResult * max(n, 1))()
+    rows = (abi.StartupPair * (max(n, 1) * NP))()
+    solver._check(L.vilf_startup_relative_pose(solver._h, C.byref(p), n, W, out, rows), "vilf_startup_relative_pose")
+    if correspondences:
+        feat = np.zeros((n, NP, NF), dtype=np.int32); mask = np.zeros((n, NP, NF), dtype=np.uint8); points = np.zeros((n, NP, NF, 3))
+        solver._check(L.vilf_startup_get_correspondences(solver._h, n, feat.ctypes.data_as(C.POINTER(C.c_int)), mask.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                         abi.dptr(points)), "vilf_startup_get_correspondences")
+    res = []
+    for k, w in enumerate(windows):
+        pairs = []
+        for i in range(int(w["n_frames"]) - 1):
+            r = rows[k * NP + i]
+            row = dict(count=r.count, flags=r.flags, best_k=r.best_k, score=r.score, cheirality=[int(v) for v in r.cheirality], chosen=r.chosen,
+                       inlier_cnt=r.inlier_cnt, parallax=float(r.parallax), F=np.array(r.F), R=np.array(r.R).reshape(3, 3), T=np.array(r.T),
+                       ok=r.flags == abi.VILF_SU_PASS)
+            if correspondences:
+                row.update(feature=feat[k, i, :r.count].copy(), mask=mask[k, i, :r.count].copy(), points=points[k, i, :r.count].copy())
+            pairs.append(row)
+        o = out[k]
+        res.append(dict(ok=o.l >= 0, l=o.l, R=np.array(o.R).reshape(3, 3), T=np.array(o.T), inlier_cnt=o.inlier_cnt, pairs=pairs))
+    return res
+
+
+def startup_profile(solver):
+    """ms and launches of su_gather, su_hypotheses, su_score, su_pose since vilf_set_profiling"""
+    ms, cnt = (C.c_double * 4)(), (C.c_long * 4)()
+    solver._check(lib().vilf_startup_profile(solver._h, ms, cnt), "vilf_startup_profile")
+    return list(ms), list(cnt)
+
+
 def posegraph_optimize(solver, poses_qt, prior_sigma, edges, max_iterations=30, tol=1e-9):
     """≙ the gtsam graph + isam update of global_fusion (poseGraphOptimization.cpp:349-374, :560-587, :433-436) on the device
     (vilf_posegraph_optimize). poses_qt (n, 7) [qx qy qz qw tx ty tz]; edges: iterable of (i, j, q[4], t[3], sigma[6], robust).

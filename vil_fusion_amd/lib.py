@@ -27,6 +27,7 @@ EXPORTED = [
     "vilf_track_configure", "vilf_track_clahe", "vilf_track_reject_f", "vilf_track_profile_frontend",
     "vilf_track_configure_mask", "vilf_track_set_fisheye_mask", "vilf_track_read_image_mask", "vilf_track_erode", "vilf_track_probe", "vilf_track_reject_f_mask",
     "vilf_track_detect_masked", "vilf_track_profile_mask",
+    "vilf_startup_default_params", "vilf_startup_relative_pose", "vilf_startup_get_correspondences", "vilf_startup_profile",
 ]
 
 
@@ -159,6 +160,11 @@ def lib():
     L.vilf_track_reject_f_mask.argtypes = [vp, fpp, fpp, u8p, C.c_int, u8p, abi.c_double_p, ip, ip]
     L.vilf_track_detect_masked.argtypes = [vp, u8p, u8p, fpp, C.c_int, C.c_int, fpp, ip]
     L.vilf_track_profile_mask.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_startup_default_params.argtypes = [C.POINTER(abi.StartupParams)]
+    L.vilf_startup_default_params.restype = None
+    L.vilf_startup_relative_pose.argtypes = [vp, C.POINTER(abi.StartupParams), C.c_int, C.POINTER(abi.StartupWindow), C.POINTER(abi.StartupResult), C.POINTER(abi.StartupPair)]
+    L.vilf_startup_get_correspondences.argtypes = [vp, C.c_int, ip, u8p, abi.c_double_p]
+    L.vilf_startup_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 

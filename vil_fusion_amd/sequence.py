@@ -432,6 +432,30 @@ class SlidingWindowEstimator:
             self.Ps[i] = R0 @ self.Ps[i]; self.Rs[i] = R0 @ self.Rs[i]; self.Vs[i] = R0 @ self.Vs[i]
         return True
 
+    # estimator.cpp:461-490 (relativePose) on the device. Nothing calls it by default: the window still fills from init_state or make_sfm_frames
+    def relative_pose_table(self):
+        """the feature table of vilf_startup_relative_pose from the feature manager, the newest frame = frame_count. getCorresponding walks every feature; those
+        that end before the newest frame belong to no pair and are left out, which keeps the order of the others"""
+        newest = min(self.frame_count, WINDOW_SIZE)
+        feats = [it for it in self.f.feature if it.end_frame() >= newest]
+        first, pts = [0], []
+        for it in feats:
+            pts.extend(fp.point[:2] / fp.point[2] for fp in it.feature_per_frame[:newest + 1 - it.start_frame])
+            first.append(len(pts))
+        return dict(n_frames=newest + 1, start_frame=np.array([it.start_frame for it in feats], dtype=np.int32), first_obs=np.array(first, dtype=np.int32),
+                    pts=np.array(pts, dtype=np.float64).reshape(-1, 2))
+
+    def relative_pose(self, **params):
+        """-> (ok, l, relative_R, relative_T, table). The work is done by backend.relative_pose([table], **params) if the back-end has one, else on the handle of
+        the BackendSolver it keeps as `s`; there is no host path"""
+        table = self.relative_pose_table()
+        if hasattr(self.backend, "relative_pose"):
+            r = self.backend.relative_pose([table], **params)[0]
+        else:
+            from .estimator import relative_pose
+            r = relative_pose(self.backend.s, [table], **params)[0]
+        return r["ok"], r["l"], r["R"], r["T"], table
+
     def _used_f(self, it):
         return self.f._used(it)
 
