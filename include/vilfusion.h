@@ -831,6 +831,105 @@ int vilf_startup_relative_pose(vilf_handle *h, const vilf_startup_params *p, int
 int vilf_startup_get_correspondences(vilf_handle *h, int n_windows, int *feature_out, unsigned char *mask_out, double *points_out);
 /* vilf_set_profiling: su_gather, su_hypotheses, su_score, su_pose of the calls since the switch was set */
 int vilf_startup_profile(vilf_handle *h, double ms_out[4], long launches_out[4]);
+
+/* ---- Visual start-up: GlobalSFM frame chain (≙ GlobalSFM::construct, initial/initial_sfm.cpp:117-217, with triangulatePoint :5-19, solveFrameByPnP :22-72 and
+ *      triangulateTwoFrames :74-110; device) ----
+ * The second stage of initialStructure: from l, relative_R and relative_T of the first stage, the poses of all frames of the window and the positions of its
+ * features in the camera of frame l, the starting value of the full bundle adjustment (:232-310), which is not part of it, as the PnP of the non-key frames
+ * (estimator.cpp:305-372) is not. The reference calls Eigen's jacobiSvd and cv::solvePnP; neither is available, so this text fixes the arithmetic (deviations:
+ * DESIGN.md §3o), tests/sfm_reference.py restates it in numpy and the kernels agree with that to the bit. Everything is fp64, each operation rounded; a NaN
+ * compares false everywhere; "-(x)" negates the rounded x. The window is vilf_startup_window; feature f is seen in frame k iff
+ * start_frame[f] <= k < start_frame[f] + n_obs(f), and its point there, p(f, k), is row first_obs[f] + k - start_frame[f] of pts.
+ *   poses        (:125-153) c_R[k] (row-major 3 x 3) and c_t[k] are the camera-from-world pose of frame k, world = the camera of frame l; P[k] = [c_R[k] | c_t[k]],
+ *                3 x 4. c_R[l] = I, c_t[l] = 0. With R = relative_R and T = relative_T: c_R[newest]_rc = R_cr, c_t[newest]_r = -((R_0r T_0 + R_1r T_1) + R_2r T_2).
+ *                (With l = newest - 1 .. 0 < newest the two frames always differ.)
+ *   triangulatePoint (:5-19) of the poses P, P' and the points (x, y), (x', y'), fp64 as they are in pts (the reference uses Vector2d): the 4 x 4 matrix A,
+ *                A_0c = x P_2c - P_0c, A_1c = y P_2c - P_1c, A_2c = x' P'_2c - P'_0c, A_3c = y' P'_2c - P'_1c (a product and a subtraction each); G = A^T A,
+ *                g_pq = the sum from 0.0 of A_rp A_rq over r = 0, 1, 2, 3 in this order, p <= q; Jacobi(G, 4) of the tracker's text; at = the index of the smallest
+ *                g_ii (compared with <, ties and NaNs leave the lower index); v = column at of V; the position is (v_0 / v_3, v_1 / v_3, v_2 / v_3). If one of the
+ *                three is not finite the feature stays untriangulated at this step (state 0, position 0); a later step may triangulate it. There is no test of
+ *                the depth's sign, as in the reference.
+ *   triangulateTwoFrames(a, b) (:74-110) for every feature that is not yet triangulated and is seen in both frames: triangulatePoint(P[a], P[b], p(f, a), p(f, b)).
+ *   solveFrameByPnP(i, R0, t0) (:22-72) the members are the triangulated features seen in frame i, in feature order, j = 0 .. m - 1; X_j = the position, u_j = p(f, i),
+ *                every coordinate of both rounded to float32 and back (the reference goes through cv::Point3f / cv::Point2f). m < warn_pnp_count (15, :45) only
+ *                sets a flag; m < min_pnp_count (10, :48) fails the frame, nothing is solved. Otherwise a Levenberg-Marquardt of pnp_iterations (default 10,
+ *                1 .. 64) iterations from (R, t) = (R0, t0), lambda = lambda0 (1e-3):
+ *     residual   of member j under (R, t): q_r = (R_r0 X_0 + R_r1 X_1) + R_r2 X_2; p_r = q_r + t_r; iz = 1.0 / p_2; xn = p_0 iz; yn = p_1 iz; e_0 = xn - u_x; e_1 = yn - u_y.
+ *     Jacobian   for the left perturbation R <- exp(w) R, t <- t + d, the unknowns ordered (w_0, w_1, w_2, d_0, d_1, d_2): c_0 = xn iz, c_1 = yn iz,
+ *                J_0 = (-(c_0 q_1), iz q_2 + c_0 q_0, -(iz q_1), iz, 0.0, -c_0), J_1 = (-(iz q_2 + c_1 q_1), c_1 q_0, iz q_0, 0.0, iz, -c_1).
+ *     terms      of member j, 28 of them: h_ab = J_0a J_0b + J_1a J_1b for a <= b (a = 0 .. 5, b = a .. 5, in this order: 21), g_a = J_0a e_0 + J_1a e_1 (6),
+ *                c = e_0 e_0 + e_1 e_1; two products and an addition each, the structural zeros multiplied like any other number.
+ *     sums       each of the 28 separately: 256 partial sums, s_t = the sum from 0.0 of the terms of the members j = t, t + 256, .. < m in ascending order; then
+ *                within every group of 64 consecutive t, for o = 32, 16, 8, 4, 2, 1: every s_t <- s_t + s_(t xor o), all at once; then the sum is
+ *                ((s_0 + s_64) + s_128) + s_192. H, g and cost are these sums.
+ *     solve      Hd = H with every diagonal entry replaced by H_aa + lambda H_aa; b_a = -g_a. LDL^T without pivoting: for j = 0 .. 5: d_j = Hd_jj minus
+ *                u_jk L_jk for k = 0 .. j - 1 in ascending order (one subtraction of a rounded product at a time); the step is rejected iff not d_j > 0 for some j
+ *                (the candidate is then not evaluated); for i = j + 1 .. 5: u_ij = Hd_ji minus u_ik L_jk for k = 0 .. j - 1 in the same way, L_ij = u_ij / d_j.
+ *                y_i = b_i minus L_ik y_k for k = 0 .. i - 1 ascending, i = 0 .. 5; z_i = y_i / d_i; x_i = z_i minus L_ki x_k for k = i + 1 .. 5 ascending,
+ *                i = 5 .. 0. (w, d) = (x_0 .. x_2, x_3 .. x_5).
+ *     candidate  a_i = 0.5 w_i; n = sqrt(((1.0 + a_0 a_0) + a_1 a_1) + a_2 a_2); the quaternion (s, x, y, z) = (1.0 / n, a_0 / n, a_1 / n, a_2 / n); Q = R(q):
+ *                Q_00 = 1.0 - 2.0 (y y + z z), Q_01 = 2.0 (x y - s z), Q_02 = 2.0 (x z + s y), Q_10 = 2.0 (x y + s z), Q_11 = 1.0 - 2.0 (x x + z z),
+ *                Q_12 = 2.0 (y z - s x), Q_20 = 2.0 (x z - s y), Q_21 = 2.0 (y z + s x), Q_22 = 1.0 - 2.0 (x x + y y); R'_rc = (Q_r0 R_0c + Q_r1 R_1c) + Q_r2 R_2c;
+ *                t'_r = t_r + d_r. Only + - * / sqrt: no sin / cos, so that the restatement and the device can agree to the bit.
+ *     accept     cost' = the sum c of the candidate in the order above. The step is accepted iff it was not rejected by a pivot and cost' < cost (a NaN rejects):
+ *                (R, t, cost) <- (R', t', cost'), lambda <- lambda / 10.0, accepted + 1. Otherwise lambda <- lambda * 10.0. Every iteration linearises anew at
+ *                the current (R, t); there is no convergence test.
+ *     result     cost0 = the cost of the first iteration, cost1 = the cost after the last. The frame fails iff an entry of (R, t) or cost1 is not finite
+ *                (a cost that is not a number accepts no step, so the pose would be the guess).
+ *     row        count = m; flags = VILF_SFM_PNP, with VILF_SFM_FEW iff m < warn_pnp_count, and one of VILF_SFM_FAIL_COUNT (accepted, cost0, cost1 = 0),
+ *                VILF_SFM_FAIL_FINITE (accepted, cost0, cost1 as they came out) or VILF_SFM_POSE; the pose in both conventions, 0 unless VILF_SFM_POSE. The rows
+ *                of l and newest: count 0, VILF_SFM_FIXED | VILF_SFM_POSE, costs 0, the given pose.
+ *   chain        (:156-217) 1. triangulateTwoFrames(l, newest). 2. for i = l + 1 .. newest - 1: solveFrameByPnP(i, P[i - 1]), then triangulateTwoFrames(i, newest).
+ *                3. for i = l + 1 .. newest - 1: triangulateTwoFrames(l, i). 4. for i = l - 1 .. 0: solveFrameByPnP(i, P[i + 1]), then triangulateTwoFrames(i, l).
+ *                5. every feature that is still untriangulated and has n_obs >= 2: triangulatePoint of its first and last frame and its points there.
+ *                The first failing PnP ends the chain (the reference's return false): fail_frame = its frame, ok = 0, the frames not reached and the failing
+ *                one keep a pose of 0, step 5 is not run; what was triangulated until then is reported.
+ *   output       (:290-303 without the BA in between) Q[k]_rc = c_R[k]_cr, T[k]_r = -((Q_r0 c_t_0 + Q_r1 c_t_1) + Q_r2 c_t_2); per feature state (0 / 1) and the
+ *                position in the camera of frame l (what sfm_tracked_points and the BA start from), 0 where state is 0. */
+#define VILF_SFM_FIXED 1         /* flags of a frame: l or newest, the pose is given */
+#define VILF_SFM_PNP 2           /* solveFrameByPnP was run for this frame */
+#define VILF_SFM_FEW 4           /* m < warn_pnp_count ("unstable features tracking", :45) */
+#define VILF_SFM_FAIL_COUNT 8    /* m < min_pnp_count: the frame fails */
+#define VILF_SFM_FAIL_FINITE 16  /* the pose or cost1 is not finite: the frame fails */
+#define VILF_SFM_POSE 32         /* R, t, Q, T hold a pose */
+#define VILF_STARTUP_MAX_PROBLEMS 4096
+typedef struct vilf_startup_sfm_params {
+    int min_pnp_count, warn_pnp_count, pnp_iterations, pad_;       /* 10, 15, 10 */
+    double lambda0;                                                /* 1e-3 */
+} vilf_startup_sfm_params;
+void vilf_startup_default_sfm_params(vilf_startup_sfm_params *p);
+typedef struct vilf_startup_frame {
+    int count, flags, accepted, pad_;  /* m, VILF_SFM_*, accepted steps */
+    double cost0, cost1;
+    double R[9], t[3];                 /* c_R, c_t */
+    double Q[9], T[3];                 /* the output convention */
+} vilf_startup_frame;
+typedef struct vilf_startup_structure {
+    int ok, fail_frame, n_triangulated, l;   /* fail_frame = -1 unless a PnP failed; l as given */
+} vilf_startup_structure;
+/* GlobalSFM's chain for n_windows independent windows, rel [n_windows] as vilf_startup_relative_pose returned it: one launch on the handle's stream (a workgroup
+ * per window), the host waits once, one download. out [n_windows]; frames_out [n_windows][VILF_MAX_FRAMES] or NULL (rows of frames the window does not have or
+ * did not reach are 0). A window with rel.l = -1 is skipped: ok = 0, fail_frame = -1, everything else 0; that is no error. Invalid argument, nothing written:
+ * what vilf_startup_relative_pose refuses in the windows, and rel.l < -1 or > n_frames - 2, an entry of rel.R or rel.T that is not finite (with l >= 0),
+ * pnp_iterations outside 1 .. 64, a negative count, a lambda0 that is not positive and finite. */
+int vilf_startup_sfm(vilf_handle *h, const vilf_startup_sfm_params *p, int n_windows, const vilf_startup_window *windows, const vilf_startup_result *rel,
+                     vilf_startup_structure *out, vilf_startup_frame *frames_out);
+/* the per-feature outputs of the last vilf_startup_sfm: state [n_windows][VILF_MAX_FEATURES], positions [n_windows][VILF_MAX_FEATURES][3], 0 behind n_features (either
+ * may be NULL). n_windows other than the last call's, or no call yet: invalid argument, nothing written. */
+int vilf_startup_get_structure(vilf_handle *h, int n_windows, unsigned char *state_out, double *positions_out);
+/* solveFrameByPnP alone for n_problems independent problems (1 .. VILF_STARTUP_MAX_PROBLEMS), for the PnP of the non-key frames (estimator.cpp:352 uses a minimum of
+ * 6, hence min_count per problem; the parameters' min_pnp_count is not read): the members are the n points in their order, pts3 [n][3] and pts2 [n][2] fp64 and
+ * rounded to float32 by the call, (R, t) the guess. out [n_problems]: count = n, flags, accepted, cost0, cost1 and the pose in both conventions (0 for a problem that
+ * fails). One launch, a workgroup per problem. Invalid argument, nothing written: a null pointer, n < 0 or > VILF_MAX_FEATURES, min_count < 0, a coordinate or an
+ * entry of the guess that is not finite, the parameters as above. */
+typedef struct vilf_startup_pnp_problem {
+    int n, min_count;
+    const double *pts3, *pts2;
+    double R[9], t[3];
+} vilf_startup_pnp_problem;
+int vilf_startup_pnp(vilf_handle *h, const vilf_startup_sfm_params *p, int n_problems, const vilf_startup_pnp_problem *problems, vilf_startup_frame *out);
+/* vilf_set_profiling: the chain kernel (vilf_startup_sfm) and the PnP kernel (vilf_startup_pnp) of the calls since the switch was set */
+int vilf_startup_sfm_profile(vilf_handle *h, double ms_out[2], long launches_out[2]);
 #ifdef __cplusplus
 }
 #endif

@@ -205,6 +205,34 @@ STARTUP_LAYOUTS = {"vilf_startup_params": StartupParams, "vilf_startup_window": 
                    "vilf_startup_pair": StartupPair}
 
 
+class StartupSfmParams(C.Structure):
+    """vilf_startup_sfm_params: the count gates of solveFrameByPnP, the iterations and the first damping of its Levenberg-Marquardt"""
+    _fields_ = [("min_pnp_count", C.c_int), ("warn_pnp_count", C.c_int), ("pnp_iterations", C.c_int), ("pad_", C.c_int), ("lambda0", C.c_double)]
+
+
+class StartupFrame(C.Structure):
+    """vilf_startup_frame: a frame of GlobalSFM's chain, or a problem of vilf_startup_pnp"""
+    _fields_ = [("count", C.c_int), ("flags", C.c_int), ("accepted", C.c_int), ("pad_", C.c_int), ("cost0", C.c_double), ("cost1", C.c_double),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("Q", C.c_double * 9), ("T", C.c_double * 3)]
+
+
+class StartupStructure(C.Structure):
+    """vilf_startup_structure: a window's result of vilf_startup_sfm"""
+    _fields_ = [("ok", C.c_int), ("fail_frame", C.c_int), ("n_triangulated", C.c_int), ("l", C.c_int)]
+
+
+class StartupPnpProblem(C.Structure):
+    """vilf_startup_pnp_problem: the points in member order, the per-problem minimum count and the guess"""
+    _fields_ = [("n", C.c_int), ("min_count", C.c_int), ("pts3", c_double_p), ("pts2", c_double_p), ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+VILF_SFM_FIXED, VILF_SFM_PNP, VILF_SFM_FEW, VILF_SFM_FAIL_COUNT, VILF_SFM_FAIL_FINITE, VILF_SFM_POSE = 1, 2, 4, 8, 16, 32
+VILF_STARTUP_MAX_PROBLEMS = 4096
+# the mirrors of the second stage, for the layout check of tests/test_startup_sfm.py
+STARTUP_SFM_LAYOUTS = {"vilf_startup_sfm_params": StartupSfmParams, "vilf_startup_frame": StartupFrame, "vilf_startup_structure": StartupStructure,
+                       "vilf_startup_pnp_problem": StartupPnpProblem}
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

@@ -57,6 +57,7 @@ struct ScCtx;
 struct IcpCtx;
 struct TrackCtx;
 struct StartupCtx;
+struct SfmCtx;
 
 // deep copy of a window snapshot (estimate_extrinsic / estimate_td: the batched entry points run the general single-window solve per slot and need the inputs again)
 struct OwnedWindow {
@@ -127,6 +128,7 @@ struct vilf_handle {
     IcpCtx *icp = nullptr;                   // key-frame cloud store and ICP workspace of the loop verification (vilf_icp.hip)
     TrackCtx *trk = nullptr;                 // image feature tracker: pyramids, feature list, detection workspace (vilf_track.hip)
     StartupCtx *su = nullptr;                // visual start-up: the pairs' correspondences, hypotheses and result rows (vilf_startup.hip)
+    SfmCtx *sfm = nullptr;                   // visual start-up, second stage: the windows, the frame rows and the structure (vilf_sfm.hip)
 };
 
 // a copy ordered on the handle's stream and waited for: the library's streams are non-blocking (they do not synchronise with the legacy default stream), so a plain
@@ -159,6 +161,11 @@ void vilf_track_release(vilf_handle *h);
 void vilf_track_profile_reset(vilf_handle *h);
 void vilf_startup_release(vilf_handle *h);
 void vilf_startup_profile_reset(vilf_handle *h);
+#define VILF_SU_WIN_INTS (4 + VILF_MAX_FEATURES + VILF_MAX_FEATURES + 2)      // a start-up window's integers on the device: n_frames, n_features, first row of its points, 0; start_frame; first_obs (+ 1 pad)
+int vilf_startup_check_windows(vilf_handle *h, const char *who, int n_windows, const vilf_startup_window *windows, size_t *total_out);   // what both stages refuse in the windows
+void vilf_startup_pack_windows(int n_windows, const vilf_startup_window *windows, int *ints, double *pts);                            // VILF_SU_WIN_INTS per window, then all points
+void vilf_sfm_release(vilf_handle *h);
+void vilf_sfm_profile_reset(vilf_handle *h);
 void vilf_sc_profile_reset(vilf_handle *h);                                 // vilf_set_profiling: the Scan Context spans start from zero
 int vilf_lw_chol_max_n();                                                      // largest n vilf_lw_chol_solve takes (its back substitution keeps the solution in LDS)
 int vilf_lw_chol_solve(vilf_handle *h, int n, double *S, double *y, int *info);   // blocked Cholesky solve on the handle's stream (vilf_lw.hip): S = [(n + 1) x n] row-major, row n = rhs

@@ -11,6 +11,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include "vilf_internal.hpp"
 #include "vilf_device.hpp"
 #include "vilf_fmat.hpp"
@@ -19,7 +20,7 @@
 #define SU_MAXN VILF_MAX_FEATURES            // correspondences of a pair
 #define SU_MAXK VILF_TRACK_MAX_HYPOTHESES
 #define SU_STAGES 4
-#define SU_WIN_INTS (4 + SU_MAXN + SU_MAXN + 2)      // a window's integers on the device: n_frames, n_features, first row of its points, 0; start_frame; first_obs (+ 1 pad)
+#define SU_WIN_INTS VILF_SU_WIN_INTS               // a window's integers on the device (vilf_internal.hpp)
 static_assert(SU_WIN_INTS % 2 == 0, "the points behind the integers are 8-byte aligned");
 enum { SC_M = 0, SC_FLAGS = 1, SC_BEST = 2 /* unsigned long long at ints 2, 3: (score + 1) << 32 | (K - 1 - k); 0 = no valid hypothesis */, SC_INTS = 8 };
 
@@ -309,6 +310,47 @@ SuOut su_out(int W) {
 bool su_finite_pos(double v) { return std::isfinite(v) && v > 0; }
 }  // namespace
 
+// the checks of the windows that both stages of the start-up make (who = the entry point, for the message) -> *total_out = the rows of all pts
+int vilf_startup_check_windows(vilf_handle *h, const char *who, int n_windows, const vilf_startup_window *windows, size_t *total_out) {
+    size_t total = 0;
+    for (int w = 0; w < n_windows; w++) {
+        const vilf_startup_window &W = windows[w];
+        if (W.n_frames < 2 || W.n_frames > VILF_MAX_FRAMES || W.n_features < 0 || W.n_features > VILF_MAX_FEATURES) {
+            h->err = std::string(who) + ": 2 <= n_frames <= VILF_MAX_FRAMES, 0 <= n_features <= VILF_MAX_FEATURES"; return VILF_ERR_INVALID_ARGUMENT;
+        }
+        if (!W.first_obs || (W.n_features > 0 && !W.start_frame)) { h->err = std::string(who) + ": null pointer in a window"; return VILF_ERR_INVALID_ARGUMENT; }
+        if (W.first_obs[0] != 0) { h->err = std::string(who) + ": first_obs[0] != 0"; return VILF_ERR_INVALID_ARGUMENT; }
+        for (int f = 0; f < W.n_features; f++) {
+            const long long nobs = (long long)W.first_obs[f + 1] - W.first_obs[f];
+            if (nobs < 0 || W.start_frame[f] < 0 || (long long)W.start_frame[f] + nobs > W.n_frames) {
+                h->err = std::string(who) + ": first_obs decreases, start_frame < 0 or start_frame + n_obs > n_frames"; return VILF_ERR_INVALID_ARGUMENT;
+            }
+        }
+        const size_t rows = (size_t)W.first_obs[W.n_features];          // <= n_features * n_frames
+        if (rows > 0 && !W.pts) { h->err = std::string(who) + ": null pointer in a window"; return VILF_ERR_INVALID_ARGUMENT; }
+        for (size_t e = 0; e < rows * 2; e++)
+            if (!std::isfinite(W.pts[e])) { h->err = std::string(who) + ": a coordinate that is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
+        total += rows;
+    }
+    *total_out = total;
+    return VILF_OK;
+}
+// the windows as the kernels read them: SU_WIN_INTS integers per window, then all points
+void vilf_startup_pack_windows(int n_windows, const vilf_startup_window *windows, int *ints, double *pts) {
+    size_t at = 0;
+    for (int w = 0; w < n_windows; w++) {
+        const vilf_startup_window &Wn = windows[w];
+        int *wi = ints + (size_t)w * SU_WIN_INTS;
+        std::memset(wi, 0, (size_t)SU_WIN_INTS * 4);
+        wi[0] = Wn.n_frames; wi[1] = Wn.n_features; wi[2] = (int)at;
+        if (Wn.n_features > 0) std::memcpy(wi + 4, Wn.start_frame, (size_t)Wn.n_features * 4);
+        std::memcpy(wi + 4 + SU_MAXN, Wn.first_obs, (size_t)(Wn.n_features + 1) * 4);
+        const size_t rows = (size_t)Wn.first_obs[Wn.n_features];
+        if (rows > 0) std::memcpy(pts + at * 2, Wn.pts, rows * 16);
+        at += rows;
+    }
+}
+
 extern "C" void vilf_startup_default_params(vilf_startup_params *p) {
     if (!p) return;
     std::memset(p, 0, sizeof(*p));
@@ -327,25 +369,7 @@ extern "C" int vilf_startup_relative_pose(vilf_handle *h, const vilf_startup_par
         return VILF_ERR_INVALID_ARGUMENT;
     }
     size_t total = 0;
-    for (int w = 0; w < n_windows; w++) {
-        const vilf_startup_window &W = windows[w];
-        if (W.n_frames < 2 || W.n_frames > VILF_MAX_FRAMES || W.n_features < 0 || W.n_features > VILF_MAX_FEATURES) {
-            h->err = "vilf_startup_relative_pose: 2 <= n_frames <= VILF_MAX_FRAMES, 0 <= n_features <= VILF_MAX_FEATURES"; return VILF_ERR_INVALID_ARGUMENT;
-        }
-        if (!W.first_obs || (W.n_features > 0 && !W.start_frame)) { h->err = "vilf_startup_relative_pose: null pointer in a window"; return VILF_ERR_INVALID_ARGUMENT; }
-        if (W.first_obs[0] != 0) { h->err = "vilf_startup_relative_pose: first_obs[0] != 0"; return VILF_ERR_INVALID_ARGUMENT; }
-        for (int f = 0; f < W.n_features; f++) {
-            const long long nobs = (long long)W.first_obs[f + 1] - W.first_obs[f];
-            if (nobs < 0 || W.start_frame[f] < 0 || (long long)W.start_frame[f] + nobs > W.n_frames) {
-                h->err = "vilf_startup_relative_pose: first_obs decreases, start_frame < 0 or start_frame + n_obs > n_frames"; return VILF_ERR_INVALID_ARGUMENT;
-            }
-        }
-        const size_t rows = (size_t)W.first_obs[W.n_features];          // <= n_features * n_frames
-        if (rows > 0 && !W.pts) { h->err = "vilf_startup_relative_pose: null pointer in a window"; return VILF_ERR_INVALID_ARGUMENT; }
-        for (size_t e = 0; e < rows * 2; e++)
-            if (!std::isfinite(W.pts[e])) { h->err = "vilf_startup_relative_pose: a coordinate that is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
-        total += rows;
-    }
+    { const int rcw = vilf_startup_check_windows(h, "vilf_startup_relative_pose", n_windows, windows, &total); if (rcw != VILF_OK) return rcw; }
     HIPCHECK(h, hipSetDevice(h->device));
     if (!h->su) h->su = new StartupCtx();
     StartupCtx *c = h->su;
@@ -360,22 +384,7 @@ extern "C" int vilf_startup_relative_pose(vilf_handle *h, const vilf_startup_par
     if (!c->in.ensure(in_bytes) || !c->work.ensure(work_bytes) || !c->out.ensure(o.bytes) || !c->up.ensure(in_bytes) || !c->down.ensure(o.bytes)) {
         h->err = "vilf_startup_relative_pose: out of memory"; return VILF_ERR_DEVICE;
     }
-    {
-        int *ints = (int *)c->up.p;
-        double *pts = (double *)((char *)c->up.p + in_ints);
-        size_t at = 0;
-        for (int w = 0; w < W; w++) {
-            const vilf_startup_window &Wn = windows[w];
-            int *wi = ints + (size_t)w * SU_WIN_INTS;
-            std::memset(wi, 0, (size_t)SU_WIN_INTS * 4);
-            wi[0] = Wn.n_frames; wi[1] = Wn.n_features; wi[2] = (int)at;
-            if (Wn.n_features > 0) std::memcpy(wi + 4, Wn.start_frame, (size_t)Wn.n_features * 4);
-            std::memcpy(wi + 4 + SU_MAXN, Wn.first_obs, (size_t)(Wn.n_features + 1) * 4);
-            const size_t rows = (size_t)Wn.first_obs[Wn.n_features];
-            if (rows > 0) std::memcpy(pts + at * 2, Wn.pts, rows * 16);
-            at += rows;
-        }
-    }
+    vilf_startup_pack_windows(W, windows, (int *)c->up.p, (double *)((char *)c->up.p + in_ints));
     HIPCHECK(h, hipMemcpyAsync(c->in.p, c->up.p, in_bytes, hipMemcpyHostToDevice, h->stream));
     SuDev d;
     char *ib = c->in.as<char>(), *wb = c->work.as<char>(), *ob = c->out.as<char>();

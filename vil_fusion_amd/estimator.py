@@ -332,16 +332,9 @@ def startup_default_params(**over):
     return p
 
 
-def relative_pose(solver, windows, correspondences=False, **params):
-    """≙ Estimator::relativePose (estimator.cpp:461-490) for every window at once on the device (vilf_startup_relative_pose). windows: an iterable of
-    dict(n_frames, start_frame [n], first_obs [n + 1], pts [total][2]): the feature table in feature order, normalised image points. params: fields of
-    vilf_startup_params. Returns a list of dict(ok, l, R, T, inlier_cnt, pairs) per window; pairs = the rows of the pairs (i, newest), i = 0 .. n_frames - 2, as
-    dicts. correspondences=True adds to every row feature [count], mask [count] (bit 0 RANSAC inlier, bit 1 good under the chosen candidate), points [count][3]."""
-    L = lib()
-    p = startup_default_params(**params)
-    windows = list(windows)
-    n = len(windows)
-    W = (abi.StartupWindow * max(n, 1))()
+def _startup_windows(windows):
+    """-> (the ctypes array of vilf_startup_window, the numpy arrays it points into)"""
+    W = (abi.StartupWindow * max(len(windows), 1))()
     keep = []
     for k, w in enumerate(windows):
         start = np.ascontiguousarray(w["start_frame"], dtype=np.int32)
@@ -352,6 +345,19 @@ def relative_pose(solver, windows, correspondences=False, **params):
         W[k].start_frame = start.ctypes.data_as(C.POINTER(C.c_int32))
         W[k].first_obs = first.ctypes.data_as(C.POINTER(C.c_int32))
         W[k].pts = abi.dptr(pts)
+    return W, keep
+
+
+def relative_pose(solver, windows, correspondences=False, **params):
+    """≙ Estimator::relativePose (estimator.cpp:461-490) for every window at once on the device (vilf_startup_relative_pose). windows: an iterable of
+    dict(n_frames, start_frame [n], first_obs [n + 1], pts [total][2]): the feature table in feature order, normalised image points. params: fields of
+    vilf_startup_params. Returns a list of dict(ok, l, R, T, inlier_cnt, pairs) per window; pairs = the rows of the pairs (i, newest), i = 0 .. n_frames - 2, as
+    dicts. correspondences=True adds to every row feature [count], mask [count] (bit 0 RANSAC inlier, bit 1 good under the chosen candidate), points [count][3]."""
+    L = lib()
+    p = startup_default_params(**params)
+    windows = list(windows)
+    n = len(windows)
+    W, keep = _startup_windows(windows)
     NP, NF = abi.VILF_MAX_FRAMES - 1, abi.VILF_MAX_FEATURES
     out = (abi.StartupResult * max(n, 1))()
     rows = (abi.StartupPair * (max(n, 1) * NP))()
@@ -380,6 +386,92 @@ def startup_profile(solver):
     """ms and launches of su_gather, su_hypotheses, su_score, su_pose since vilf_set_profiling"""
     ms, cnt = (C.c_double * 4)(), (C.c_long * 4)()
     solver._check(lib().vilf_startup_profile(solver._h, ms, cnt), "vilf_startup_profile")
+    return list(ms), list(cnt)
+
+
+def startup_default_sfm_params(**over):
+    """vilf_startup_sfm_params with the reference's constants (initial_sfm.cpp:45-48); keyword arguments replace fields (pnp_iterations=1, ...)"""
+    p = abi.StartupSfmParams()
+    lib().vilf_startup_default_sfm_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise TypeError(f"vilf_startup_sfm_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _startup_frame(r):
+    return dict(count=r.count, flags=r.flags, accepted=r.accepted, cost0=float(r.cost0), cost1=float(r.cost1), R=np.array(r.R).reshape(3, 3), t=np.array(r.t),
+                Q=np.array(r.Q).reshape(3, 3), T=np.array(r.T))
+
+
+def global_sfm(solver, windows, rel=None, structure=False, **params):
+    """≙ the frame chain of GlobalSFM::construct (initial/initial_sfm.cpp:117-217) for every window at once on the device (vilf_startup_sfm). windows as in
+    relative_pose; rel: per window a dict with l, R, T (what relative_pose returns) or None, which runs relative_pose first with the fields of vilf_startup_params
+    among params and feeds its results through; the other params are fields of vilf_startup_sfm_params. Returns a list of dict(ok, fail_frame, n_triangulated,
+    l, frames) per window, frames = the rows of the frames 0 .. n_frames - 1 as dicts (count, flags, accepted, cost0, cost1, R, t, Q, T). structure=True adds
+    state [n_features] and positions [n_features][3], in the camera of frame l."""
+    L = lib()
+    windows = list(windows)
+    n = len(windows)
+    stage1 = {k: params.pop(k) for k in list(params) if hasattr(abi.StartupParams, k) and not hasattr(abi.StartupSfmParams, k)}
+    p = startup_default_sfm_params(**params)
+    if rel is None:
+        rel = relative_pose(solver, windows, **stage1)
+    elif stage1:
+        raise TypeError(f"parameters of relative_pose given together with rel: {sorted(stage1)}")
+    W, keep = _startup_windows(windows)
+    rl = (abi.StartupResult * max(n, 1))()
+    for k, r in enumerate(rel):
+        rl[k].l = int(r["l"])
+        rl[k].R[:] = [float(v) for v in np.asarray(r["R"], dtype=np.float64).reshape(9)]
+        rl[k].T[:] = [float(v) for v in np.asarray(r["T"], dtype=np.float64).reshape(3)]
+    NF, NX = abi.VILF_MAX_FRAMES, abi.VILF_MAX_FEATURES
+    out = (abi.StartupStructure * max(n, 1))()
+    rows = (abi.StartupFrame * (max(n, 1) * NF))()
+    solver._check(L.vilf_startup_sfm(solver._h, C.byref(p), n, W, rl, out, rows), "vilf_startup_sfm")
+    if structure:
+        state = np.zeros((n, NX), dtype=np.uint8); pos = np.zeros((n, NX, 3))
+        solver._check(L.vilf_startup_get_structure(solver._h, n, state.ctypes.data_as(C.POINTER(C.c_uint8)), abi.dptr(pos)), "vilf_startup_get_structure")
+    res = []
+    for k, w in enumerate(windows):
+        o = out[k]
+        r = dict(ok=bool(o.ok), fail_frame=o.fail_frame, n_triangulated=o.n_triangulated, l=o.l, frames=[_startup_frame(rows[k * NF + i]) for i in range(int(w["n_frames"]))])
+        if structure:
+            nx = len(keep[k][0])
+            r.update(state=state[k, :nx].copy(), positions=pos[k, :nx].copy())
+        res.append(r)
+    return res
+
+
+def frame_pnp(solver, problems, **params):
+    """≙ solveFrameByPnP (initial_sfm.cpp:22-72) alone for a batch of independent problems on the device (vilf_startup_pnp). problems: an iterable of
+    dict(pts3 [n][3], pts2 [n][2], R [3][3], t [3], min_count): the members in their order, the guess and the problem's minimum count (estimator.cpp:352 uses 6).
+    params: fields of vilf_startup_sfm_params. Returns the rows as dicts, as the frames of global_sfm."""
+    L = lib()
+    p = startup_default_sfm_params(**params)
+    problems = list(problems)
+    n = len(problems)
+    arr = (abi.StartupPnpProblem * max(n, 1))()
+    keep = []
+    for k, q in enumerate(problems):
+        p3 = np.ascontiguousarray(q["pts3"], dtype=np.float64).reshape(-1, 3)
+        p2 = np.ascontiguousarray(q["pts2"], dtype=np.float64).reshape(-1, 2)
+        assert len(p3) == len(p2)
+        keep.append((p3, p2))
+        arr[k].n, arr[k].min_count = len(p3), int(q["min_count"])
+        arr[k].pts3, arr[k].pts2 = abi.dptr(p3), abi.dptr(p2)
+        arr[k].R[:] = [float(v) for v in np.asarray(q["R"], dtype=np.float64).reshape(9)]
+        arr[k].t[:] = [float(v) for v in np.asarray(q["t"], dtype=np.float64).reshape(3)]
+    out = (abi.StartupFrame * max(n, 1))()
+    solver._check(L.vilf_startup_pnp(solver._h, C.byref(p), n, arr, out), "vilf_startup_pnp")
+    return [_startup_frame(out[k]) for k in range(n)]
+
+
+def startup_sfm_profile(solver):
+    """ms and launches of su_sfm_chain and su_pnp_batch since vilf_set_profiling"""
+    ms, cnt = (C.c_double * 2)(), (C.c_long * 2)()
+    solver._check(lib().vilf_startup_sfm_profile(solver._h, ms, cnt), "vilf_startup_sfm_profile")
     return list(ms), list(cnt)
 
 

@@ -28,6 +28,7 @@ EXPORTED = [
     "vilf_track_configure_mask", "vilf_track_set_fisheye_mask", "vilf_track_read_image_mask", "vilf_track_erode", "vilf_track_probe", "vilf_track_reject_f_mask",
     "vilf_track_detect_masked", "vilf_track_profile_mask",
     "vilf_startup_default_params", "vilf_startup_relative_pose", "vilf_startup_get_correspondences", "vilf_startup_profile",
+    "vilf_startup_default_sfm_params", "vilf_startup_sfm", "vilf_startup_get_structure", "vilf_startup_pnp", "vilf_startup_sfm_profile",
 ]
 
 
@@ -165,6 +166,13 @@ def lib():
     L.vilf_startup_relative_pose.argtypes = [vp, C.POINTER(abi.StartupParams), C.c_int, C.POINTER(abi.StartupWindow), C.POINTER(abi.StartupResult), C.POINTER(abi.StartupPair)]
     L.vilf_startup_get_correspondences.argtypes = [vp, C.c_int, ip, u8p, abi.c_double_p]
     L.vilf_startup_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_startup_default_sfm_params.argtypes = [C.POINTER(abi.StartupSfmParams)]
+    L.vilf_startup_default_sfm_params.restype = None
+    L.vilf_startup_sfm.argtypes = [vp, C.POINTER(abi.StartupSfmParams), C.c_int, C.POINTER(abi.StartupWindow), C.POINTER(abi.StartupResult), C.POINTER(abi.StartupStructure),
+                                   C.POINTER(abi.StartupFrame)]
+    L.vilf_startup_get_structure.argtypes = [vp, C.c_int, u8p, abi.c_double_p]
+    L.vilf_startup_pnp.argtypes = [vp, C.POINTER(abi.StartupSfmParams), C.c_int, C.POINTER(abi.StartupPnpProblem), C.POINTER(abi.StartupFrame)]
+    L.vilf_startup_sfm_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 

@@ -456,6 +456,20 @@ class SlidingWindowEstimator:
             r = relative_pose(self.backend.s, [table], **params)[0]
         return r["ok"], r["l"], r["R"], r["T"], table
 
+    # initial_sfm.cpp:117-217 (the frame chain of GlobalSFM::construct) on the device, from the same table. Nothing calls it by default either: its poses are the
+    # starting value of the full BA, which is not built yet, not the window's
+    def global_sfm(self, **params):
+        """-> (result, table): relativePose and the chain in one go; result = dict(ok, fail_frame, n_triangulated, l, frames, state, positions) of the table's
+        features. The work is done by backend.global_sfm([table], structure=True, **params) if the back-end has one, else on the handle of the BackendSolver it
+        keeps as `s`; there is no host path"""
+        table = self.relative_pose_table()
+        if hasattr(self.backend, "global_sfm"):
+            r = self.backend.global_sfm([table], structure=True, **params)[0]
+        else:
+            from .estimator import global_sfm
+            r = global_sfm(self.backend.s, [table], structure=True, **params)[0]
+        return r, table
+
     def _used_f(self, it):
         return self.f._used(it)
 
