@@ -930,6 +930,95 @@ typedef struct vilf_startup_pnp_problem {
 int vilf_startup_pnp(vilf_handle *h, const vilf_startup_sfm_params *p, int n_problems, const vilf_startup_pnp_problem *problems, vilf_startup_frame *out);
 /* vilf_set_profiling: the chain kernel (vilf_startup_sfm) and the PnP kernel (vilf_startup_pnp) of the calls since the switch was set */
 int vilf_startup_sfm_profile(vilf_handle *h, double ms_out[2], long launches_out[2]);
+
+/* ---- Visual start-up: GlobalSFM full BA (≙ initial_sfm.cpp:232-310, ReprojectionError3D initial_sfm.h:25-54; device) ----
+ * The third stage of initialStructure: the bundle adjustment over the poses and the positions the frame chain left. The reference hands the problem to Ceres
+ * (DENSE_SCHUR, 0.2 s); Ceres is not available, so this text fixes the arithmetic (deviations: DESIGN.md §3p), tests/ba_reference.py restates it in numpy and the
+ * kernel agrees with that to the bit. The PnP of the non-key frames (estimator.cpp:305-372) is not part of it. Everything is fp64, each operation rounded; a NaN
+ * compares false everywhere; "-(x)" negates the rounded x. Window, "seen" and p(f, k) as in the chain's text; observations and positions are fp64 as they are (the
+ * reference passes Vector2d and double position[3]: no float32 rounding, unlike the PnP).
+ *   problem      the unknowns are c_R[k], c_t[k] (camera-from-world, world = the camera of l, the chain's convention) and the positions X_f of the features with
+ *                state 1, the members. Constant (:248-255): c_R[l], c_t[l], c_t[newest]; c_R[newest] is free. Frame k has n_k free unknowns in the order
+ *                (w_0, w_1, w_2, d_0, d_1, d_2): n_l = 0, n_newest = 3 (the rotation), n_k = 6 otherwise; its first has the index o_k = the sum of n_j over j < k;
+ *                nc = the sum of all n_k = 6 n_frames - 9 (57 at 11 frames, 3 at 2). Every observation of a member is a residual (:258-273), those in l and newest too.
+ *   residual     of member f in frame k, with (R, t) = (c_R[k], c_t[k]), X = X_f, u = p(f, k): the PnP's paragraph "residual" -> q, p, iz, xn, yn, e_0, e_1.
+ *   Jacobian     the PnP's c_0, c_1 and J_0, J_1 for the left perturbation R <- exp(w) R, t <- t + d; only the first n_k entries of J_0, J_1 exist for frame k (the
+ *                columns of a constant rotation or translation are left out, not multiplied as zeros; frame l has none). The point's: P_0c = iz R_0c - c_0 R_2c,
+ *                P_1c = iz R_1c - c_1 R_2c, c = 0, 1, 2 (two products and a subtraction each).
+ *   sums over features  "the total over the members (seen in ..)" of a term: 256 partial sums, s_t = the sum from 0.0 of the term over the features f = t, t + 256, .. <
+ *                n_features that are members (and seen in ..), ascending; then the butterfly within every 64 consecutive t and ((s_0 + s_64) + s_128) + s_192 as in
+ *                the PnP's paragraph "sums". (The stride runs over the feature index, not over a compacted member list: a deviation from the PnP that saves the ranking.)
+ *   cost         c_k = the total over the members seen in k of e_0 e_0 + e_1 e_1, k = 0 .. n_frames - 1; cost = the sum from 0.0 of c_k in ascending k.
+ *   camera terms of frame k with n_k > 0: U_k,ab = the total over the members seen in k of J_0a J_0b + J_1a J_1b, a <= b < n_k; g_k,a = the total of J_0a e_0 + J_1a e_1.
+ *   point terms  of member f, its own sums over the frames k that see it in ascending k, from 0.0: v_cd = the sum of P_0c P_0d + P_1c P_1d, c <= d; gp_c = the sum of
+ *                P_0c e_0 + P_1c e_1. Damped: Vd_cc = v_cc + lambda v_cc, Vd_cd = v_cd. LDL^T without pivoting: d_0 = Vd_00; L_10 = Vd_01 / d_0; L_20 = Vd_02 / d_0;
+ *                d_1 = Vd_11 - Vd_01 L_10; u = Vd_12 - Vd_02 L_10; L_21 = u / d_1; d_2 = (Vd_22 - Vd_02 L_20) - u L_21. The whole step is rejected iff not d_j > 0 for
+ *                some j of some member. The inverse: i_j = 1.0 / d_j; m_10 = -(L_10); m_21 = -(L_21); m_20 = L_21 L_10 - L_20; Vi_22 = i_2; Vi_12 = m_21 i_2;
+ *                Vi_02 = m_20 i_2; Vi_11 = i_1 + m_21 Vi_12; Vi_01 = m_10 i_1 + m_21 Vi_02; Vi_00 = (i_0 + m_10 (m_10 i_1)) + m_20 Vi_02; Vi is symmetric.
+ *   coupling     of member f and a frame k that sees it: W_ac = J_0a P_0c + J_1a P_1c, a < n_k; Y_ac = (W_a0 Vi_0c + W_a1 Vi_1c) + W_a2 Vi_2c.
+ *   reduced system (dense Schur) for frames j <= k with n_j, n_k > 0, a < n_j, b < n_k (and a <= b if j = k): T = the total over the members seen in both of
+ *                (Y_a0 W'_b0 + Y_a1 W'_b1) + Y_a2 W'_b2, Y of frame j, W' of frame k. S_(o_j + a)(o_k + b) = Ud - T if j = k, with Ud_ab = U_k,ab + lambda U_k,ab
+ *                if a = b, else U_k,ab; -(T) if j < k. r_(o_k + a) = g_k,a minus the total over the members seen in k of (Y_a0 gp_0 + Y_a1 gp_1) + Y_a2 gp_2;
+ *                the right-hand side is b_i = -(r_i).
+ *   solve        the LDL^T without pivoting of the PnP's paragraph "solve" at the size nc, S read in its upper triangle, the same pivot rule (the step is rejected
+ *                iff not d_j > 0 for some j), y and z as there; x_i = z_i minus L_ki x_k for k = nc - 1 .. i + 1 in descending order, i = nc - 1 .. 0 (descending, so
+ *                that a finished x_k can be taken out of every row at once; the PnP's text has ascending).
+ *   back-substitution of member f: s_c = gp_c, then for every frame k that sees f in ascending k and a = 0 .. n_k - 1 ascending: s_c <- s_c + W_ac x_(o_k + a);
+ *                dX_c = -((Vi_c0 s_0 + Vi_c1 s_1) + Vi_c2 s_2).
+ *   candidate    frame k with n_k > 0: (w, d) = (x_(o_k) .. x_(o_k + 2), x_(o_k + 3) .. x_(o_k + 5)), d = 0 if n_k = 3; the PnP's paragraph "candidate" gives R'
+ *                (and t' = t + d if n_k = 6, t' = t as it is if n_k = 3). X'_f = X_f + dX. Only + - * / sqrt.
+ *   iteration    lambda = lambda0 (1e-3). Each of at most ba_iterations (default 20, 1 .. 64) iterations linearises at the current values (cost, camera and point
+ *                terms), solves and evaluates cost' of the candidate. The step is accepted iff no pivot rejected it and cost' < cost: the values become the
+ *                candidate's, lambda <- lambda / 10.0, accepted + 1; else lambda <- lambda * 10.0. After an accepted step with
+ *                cost - cost' <= function_tolerance * cost (1e-6, Ceres's default; cost the one before the step) the loop ends and VILF_BA_CONVERGED is set.
+ *   verdict      (replaces :277-289; there is no wall-clock limit where the reference gives Ceres 0.2 s: a deviation.) cost0 = the cost of the first iteration,
+ *                cost1 = the cost of the values reached; final_cost = 0.5 cost1 (Ceres's convention); VILF_BA_COST iff final_cost < cost_threshold (5e-3);
+ *                VILF_BA_FINITE iff every entry of every c_R[k], c_t[k], every member's position and cost1 are finite. ok iff VILF_BA_FINITE and (VILF_BA_CONVERGED
+ *                or VILF_BA_COST); otherwise the window fails (the reference's return false) and still reports what it reached.
+ *   output       per frame the pose in both conventions, Q and T by the chain's paragraph "output" (:290-303), 0 for the frames the window does not have; per
+ *                feature the state as given and the position, 0 where state is 0. A window with l = -1 or a failed chain (chain_ok = 0) is skipped: everything 0
+ *                but l; that is no error. */
+#define VILF_BA_CONVERGED 1      /* flags of a window: the function tolerance ended the loop */
+#define VILF_BA_COST 2           /* final_cost < cost_threshold */
+#define VILF_BA_FINITE 4         /* poses, positions and cost1 are finite */
+typedef struct vilf_startup_ba_params {
+    int ba_iterations, pad_;                                       /* 20 */
+    double lambda0, function_tolerance, cost_threshold;            /* 1e-3, 1e-6, 5e-3 */
+} vilf_startup_ba_params;
+void vilf_startup_default_ba_params(vilf_startup_ba_params *p);
+typedef struct vilf_startup_ba_start {
+    int l, chain_ok;                 /* l = -1 or chain_ok = 0: the window is skipped */
+    const double *R, *t;             /* [n_frames][9] c_R row-major, [n_frames][3] c_t */
+    const unsigned char *state;      /* [n_features], 0 / 1 */
+    const double *positions;         /* [n_features][3], read where state is 1 */
+} vilf_startup_ba_start;
+typedef struct vilf_startup_ba_result {
+    int ok, flags, iterations, accepted;        /* VILF_BA_*, iterations run, steps accepted */
+    int n_camera, n_members, n_residuals, l;    /* nc, the members, their observations (two residuals each); l as given */
+    double cost0, cost1, lambda;                /* lambda as the last iteration left it */
+} vilf_startup_ba_result;
+typedef struct vilf_startup_ba_frame {
+    double R[9], t[3];                 /* c_R, c_t */
+    double Q[9], T[3];                 /* the output convention */
+} vilf_startup_ba_frame;
+/* The BA alone for n_windows independent windows from a given start: one launch on the handle's stream (a workgroup per window), the host waits once, one download.
+ * out [n_windows]; frames_out [n_windows][VILF_MAX_FRAMES] or NULL. Invalid argument, nothing written: what vilf_startup_relative_pose refuses in the windows, a null
+ * pointer (in a start too, unless the window is skipped or has no features), l < -1 or > n_frames - 2, a state other than 0 / 1, a member with fewer than two
+ * observations, an entry of R or t or a member's position that is not finite (in a window that is not skipped), ba_iterations outside 1 .. 64, a lambda0,
+ * function_tolerance or cost_threshold that is not positive and finite. */
+int vilf_startup_ba(vilf_handle *h, const vilf_startup_ba_params *p, int n_windows, const vilf_startup_window *windows, const vilf_startup_ba_start *start,
+                    vilf_startup_ba_result *out, vilf_startup_ba_frame *frames_out);
+/* GlobalSFM::construct: the chain, then the BA from its poses and structure, on the handle's stream with no host round trip in between (two launches, the host waits
+ * once, one download). out, frames_out as vilf_startup_ba; chain_out [n_windows] and chain_frames_out [n_windows][VILF_MAX_FRAMES] (either may be NULL) as
+ * vilf_startup_sfm returns them, so that a caller sees where a failure came from. Invalid argument, nothing written: what vilf_startup_sfm and vilf_startup_ba refuse
+ * in their parameters, the windows and rel. */
+int vilf_startup_construct(vilf_handle *h, const vilf_startup_sfm_params *sp, const vilf_startup_ba_params *bp, int n_windows, const vilf_startup_window *windows,
+                           const vilf_startup_result *rel, vilf_startup_ba_result *out, vilf_startup_ba_frame *frames_out, vilf_startup_structure *chain_out,
+                           vilf_startup_frame *chain_frames_out);
+/* the per-feature outputs of the last vilf_startup_ba or vilf_startup_construct, as vilf_startup_get_structure */
+int vilf_startup_get_ba_structure(vilf_handle *h, int n_windows, unsigned char *state_out, double *positions_out);
+/* vilf_set_profiling: su_sfm_ba of the calls since the switch was set (the chain of a vilf_startup_construct counts in vilf_startup_sfm_profile) */
+int vilf_startup_ba_profile(vilf_handle *h, double ms_out[1], long launches_out[1]);
 #ifdef __cplusplus
 }
 #endif

@@ -233,6 +233,34 @@ STARTUP_SFM_LAYOUTS = {"vilf_startup_sfm_params": StartupSfmParams, "vilf_startu
                        "vilf_startup_pnp_problem": StartupPnpProblem}
 
 
+class StartupBaParams(C.Structure):
+    """vilf_startup_ba_params: the iterations and the first damping of the BA's Levenberg-Marquardt, the function tolerance that ends it, the verdict's cost"""
+    _fields_ = [("ba_iterations", C.c_int), ("pad_", C.c_int), ("lambda0", C.c_double), ("function_tolerance", C.c_double), ("cost_threshold", C.c_double)]
+
+
+class StartupBaStart(C.Structure):
+    """vilf_startup_ba_start: l, whether the chain succeeded, the poses and the structure the BA starts from"""
+    _fields_ = [("l", C.c_int), ("chain_ok", C.c_int), ("R", c_double_p), ("t", c_double_p), ("state", C.POINTER(C.c_uint8)), ("positions", c_double_p)]
+
+
+class StartupBaResult(C.Structure):
+    """vilf_startup_ba_result: a window's result of vilf_startup_ba / vilf_startup_construct"""
+    _fields_ = [("ok", C.c_int), ("flags", C.c_int), ("iterations", C.c_int), ("accepted", C.c_int), ("n_camera", C.c_int), ("n_members", C.c_int),
+                ("n_residuals", C.c_int), ("l", C.c_int), ("cost0", C.c_double), ("cost1", C.c_double), ("lambda_", C.c_double)]
+
+
+class StartupBaFrame(C.Structure):
+    """vilf_startup_ba_frame: a frame's pose after the BA, in both conventions"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("Q", C.c_double * 9), ("T", C.c_double * 3)]
+
+
+VILF_BA_CONVERGED, VILF_BA_COST, VILF_BA_FINITE = 1, 2, 4
+# the mirrors of the third stage and the C names of their fields where they differ (lambda is a Python keyword), for the layout check of tests/test_startup_ba.py
+STARTUP_BA_LAYOUTS = {"vilf_startup_ba_params": StartupBaParams, "vilf_startup_ba_start": StartupBaStart, "vilf_startup_ba_result": StartupBaResult,
+                      "vilf_startup_ba_frame": StartupBaFrame}
+STARTUP_BA_C_NAMES = {"lambda_": "lambda"}
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

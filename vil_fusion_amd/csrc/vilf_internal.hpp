@@ -58,6 +58,7 @@ struct IcpCtx;
 struct TrackCtx;
 struct StartupCtx;
 struct SfmCtx;
+struct BaCtx;
 
 // deep copy of a window snapshot (estimate_extrinsic / estimate_td: the batched entry points run the general single-window solve per slot and need the inputs again)
 struct OwnedWindow {
@@ -129,6 +130,7 @@ struct vilf_handle {
     TrackCtx *trk = nullptr;                 // image feature tracker: pyramids, feature list, detection workspace (vilf_track.hip)
     StartupCtx *su = nullptr;                // visual start-up: the pairs' correspondences, hypotheses and result rows (vilf_startup.hip)
     SfmCtx *sfm = nullptr;                   // visual start-up, second stage: the windows, the frame rows and the structure (vilf_sfm.hip)
+    BaCtx *ba = nullptr;                     // visual start-up, third stage: the start values, the BA's frames and structure (vilf_ba.hip)
 };
 
 // a copy ordered on the handle's stream and waited for: the library's streams are non-blocking (they do not synchronise with the legacy default stream), so a plain
@@ -166,6 +168,18 @@ int vilf_startup_check_windows(vilf_handle *h, const char *who, int n_windows, c
 void vilf_startup_pack_windows(int n_windows, const vilf_startup_window *windows, int *ints, double *pts);                            // VILF_SU_WIN_INTS per window, then all points
 void vilf_sfm_release(vilf_handle *h);
 void vilf_sfm_profile_reset(vilf_handle *h);
+// the chain without its wait and download, for vilf_startup_construct (vilf_ba.hip): validation, upload and launch as vilf_startup_sfm into the caller's buffers; out is
+// sized for the chain's download (out_bytes) and extra_out bytes behind it
+struct VilfSfmBufs { DBuf *in, *out; PinBuf *up, *down; };
+struct VilfSfmQueued {
+    const int *win; const double *pts; const int *l;                                                                    // on the device, as su_sfm_chain reads them
+    const vilf_startup_structure *res; const vilf_startup_frame *rows; const unsigned char *state; const double *pos;   // on the device, where su_sfm_chain writes them
+    size_t o_res, o_rows, o_state, o_pos, out_bytes;                                                                    // the same four within out, and the chain's bytes
+};
+int vilf_sfm_enqueue(vilf_handle *h, const char *who, const vilf_startup_sfm_params *p, int n_windows, const vilf_startup_window *windows, const vilf_startup_result *rel,
+                     VilfSfmBufs bufs, size_t extra_out, VilfSfmQueued *q);
+void vilf_ba_release(vilf_handle *h);
+void vilf_ba_profile_reset(vilf_handle *h);
 void vilf_sc_profile_reset(vilf_handle *h);                                 // vilf_set_profiling: the Scan Context spans start from zero
 int vilf_lw_chol_max_n();                                                      // largest n vilf_lw_chol_solve takes (its back substitution keeps the solution in LDS)
 int vilf_lw_chol_solve(vilf_handle *h, int n, double *S, double *y, int *info);   // blocked Cholesky solve on the handle's stream (vilf_lw.hip): S = [(n + 1) x n] row-major, row n = rhs

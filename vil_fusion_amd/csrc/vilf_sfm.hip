@@ -421,33 +421,34 @@ extern "C" void vilf_startup_default_sfm_params(vilf_startup_sfm_params *p) {
     p->min_pnp_count = 10; p->warn_pnp_count = 15; p->pnp_iterations = 10; p->lambda0 = 1e-3;
 }
 
-extern "C" int vilf_startup_sfm(vilf_handle *h, const vilf_startup_sfm_params *p, int n_windows, const vilf_startup_window *windows, const vilf_startup_result *rel,
-                                vilf_startup_structure *out, vilf_startup_frame *frames_out) {
-    if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    if (!p || !windows || !rel || !out) { h->err = "vilf_startup_sfm: null pointer"; return VILF_ERR_INVALID_ARGUMENT; }
-    if (n_windows < 1 || n_windows > VILF_STARTUP_MAX_WINDOWS) { h->err = "vilf_startup_sfm: 1 <= n_windows <= VILF_STARTUP_MAX_WINDOWS"; return VILF_ERR_INVALID_ARGUMENT; }
-    if (!sf_params_ok(p)) { h->err = std::string("vilf_startup_sfm") + SF_PARAMS_TEXT; return VILF_ERR_INVALID_ARGUMENT; }
+// validation, upload and launch of the chain into the buffers given; nothing is waited for and nothing comes back (vilf_startup_sfm, vilf_startup_construct)
+int vilf_sfm_enqueue(vilf_handle *h, const char *who, const vilf_startup_sfm_params *p, int n_windows, const vilf_startup_window *windows, const vilf_startup_result *rel,
+                     VilfSfmBufs bufs, size_t extra_out, VilfSfmQueued *q) {
+    const std::string name(who);
+    if (n_windows < 1 || n_windows > VILF_STARTUP_MAX_WINDOWS) { h->err = name + ": 1 <= n_windows <= VILF_STARTUP_MAX_WINDOWS"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (!sf_params_ok(p)) { h->err = name + SF_PARAMS_TEXT; return VILF_ERR_INVALID_ARGUMENT; }
     size_t total = 0;
-    { const int rcw = vilf_startup_check_windows(h, "vilf_startup_sfm", n_windows, windows, &total); if (rcw != VILF_OK) return rcw; }
+    { const int rcw = vilf_startup_check_windows(h, who, n_windows, windows, &total); if (rcw != VILF_OK) return rcw; }
     for (int w = 0; w < n_windows; w++) {
-        if (rel[w].l < -1 || rel[w].l > windows[w].n_frames - 2) { h->err = "vilf_startup_sfm: -1 <= l <= n_frames - 2"; return VILF_ERR_INVALID_ARGUMENT; }
+        if (rel[w].l < -1 || rel[w].l > windows[w].n_frames - 2) { h->err = name + ": -1 <= l <= n_frames - 2"; return VILF_ERR_INVALID_ARGUMENT; }
         if (rel[w].l < 0) continue;
         bool fin = true;
         for (int e = 0; e < 9; e++) fin = fin && std::isfinite(rel[w].R[e]);
         for (int e = 0; e < 3; e++) fin = fin && std::isfinite(rel[w].T[e]);
-        if (!fin) { h->err = "vilf_startup_sfm: a relative_R or relative_T that is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
+        if (!fin) { h->err = name + ": a relative_R or relative_T that is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
     }
     HIPCHECK(h, hipSetDevice(h->device));
     if (!h->sfm) h->sfm = new SfmCtx();
     SfmCtx *c = h->sfm;
-    c->last_windows = 0;
     const int W = n_windows;
     // upload: the windows' integers, l of every window (padded to 8 bytes), the relative poses, then all points
     const size_t o_l = (size_t)W * SF_WIN_INTS * 4, o_rel = o_l + (size_t)((W + 1) & ~1) * 4, o_pts = o_rel + (size_t)W * 96, in_bytes = o_pts + std::max<size_t>(total, 1) * 16;
     const SfOut o = sf_out(W);
-    if (!c->in.ensure(in_bytes) || !c->out.ensure(o.bytes) || !c->up.ensure(in_bytes) || !c->down.ensure(o.bytes)) { h->err = "vilf_startup_sfm: out of memory"; return VILF_ERR_DEVICE; }
+    if (!bufs.in->ensure(in_bytes) || !bufs.out->ensure(o.bytes + extra_out) || !bufs.up->ensure(in_bytes) || !bufs.down->ensure(o.bytes + extra_out)) {
+        h->err = name + ": out of memory"; return VILF_ERR_DEVICE;
+    }
     {
-        char *ub = (char *)c->up.p;
+        char *ub = (char *)bufs.up->p;
         vilf_startup_pack_windows(W, windows, (int *)ub, (double *)(ub + o_pts));
         int *lw = (int *)(ub + o_l);
         double *rl = (double *)(ub + o_rel);
@@ -462,9 +463,9 @@ extern "C" int vilf_startup_sfm(vilf_handle *h, const vilf_startup_sfm_params *p
         HIPCHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(su_sfm_chain), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SF_LDS_BYTES));
         c->attr = true;
     }
-    HIPCHECK(h, hipMemcpyAsync(c->in.p, c->up.p, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, hipMemcpyAsync(bufs.in->p, bufs.up->p, in_bytes, hipMemcpyHostToDevice, h->stream));
     SfDev d;
-    char *ib = c->in.as<char>(), *ob = c->out.as<char>();
+    char *ib = bufs.in->as<char>(), *ob = bufs.out->as<char>();
     d.win = (const int *)ib; d.l = (const int *)(ib + o_l); d.rel = (const double *)(ib + o_rel); d.pts = (const double *)(ib + o_pts);
     d.res = (vilf_startup_structure *)(ob + o.res); d.rows = (vilf_startup_frame *)(ob + o.rows); d.state = (unsigned char *)(ob + o.state); d.pos = (double *)(ob + o.pos);
     const bool prof = h->profiling != 0;
@@ -473,10 +474,27 @@ extern "C" int vilf_startup_sfm(vilf_handle *h, const vilf_startup_sfm_params *p
     hipLaunchKernelGGL(su_sfm_chain, dim3(W), dim3(SF_NT), SF_LDS_BYTES, h->stream, d, sf_par(p));
     if (prof) { ev[1] = vilf_prof_event(h); vilf_prof_span(h, ev[0], ev[1], &c->ms[0], &c->launches[0]); }
     HIPCHECK(h, hipGetLastError());
-    HIPCHECK(h, vilf_copy_sync(h, c->down.p, c->out.p, o.bytes, hipMemcpyDeviceToHost));
+    q->win = d.win; q->pts = d.pts; q->l = d.l; q->res = d.res; q->rows = d.rows; q->state = d.state; q->pos = d.pos;
+    q->o_res = o.res; q->o_rows = o.rows; q->o_state = o.state; q->o_pos = o.pos; q->out_bytes = o.bytes;
+    return VILF_OK;
+}
+
+extern "C" int vilf_startup_sfm(vilf_handle *h, const vilf_startup_sfm_params *p, int n_windows, const vilf_startup_window *windows, const vilf_startup_result *rel,
+                                vilf_startup_structure *out, vilf_startup_frame *frames_out) {
+    if (!h) return VILF_ERR_INVALID_ARGUMENT;
+    if (!p || !windows || !rel || !out) { h->err = "vilf_startup_sfm: null pointer"; return VILF_ERR_INVALID_ARGUMENT; }
+    if (!h->sfm) h->sfm = new SfmCtx();
+    SfmCtx *c = h->sfm;
+    const int kept = c->last_windows;
+    c->last_windows = 0;
+    VilfSfmBufs bufs = {&c->in, &c->out, &c->up, &c->down};
+    VilfSfmQueued q;
+    { const int rcq = vilf_sfm_enqueue(h, "vilf_startup_sfm", p, n_windows, windows, rel, bufs, 0, &q); if (rcq != VILF_OK) { if (rcq == VILF_ERR_INVALID_ARGUMENT) c->last_windows = kept; return rcq; } }
+    const int W = n_windows;
+    HIPCHECK(h, vilf_copy_sync(h, c->down.p, c->out.p, q.out_bytes, hipMemcpyDeviceToHost));
     const char *hb = (const char *)c->down.p;
-    std::memcpy(out, hb + o.res, (size_t)W * sizeof(vilf_startup_structure));
-    if (frames_out) std::memcpy(frames_out, hb + o.rows, (size_t)W * SF_MAXF * sizeof(vilf_startup_frame));
+    std::memcpy(out, hb + q.o_res, (size_t)W * sizeof(vilf_startup_structure));
+    if (frames_out) std::memcpy(frames_out, hb + q.o_rows, (size_t)W * SF_MAXF * sizeof(vilf_startup_frame));
     c->last_windows = W;
     return VILF_OK;
 }

@@ -475,6 +475,109 @@ def startup_sfm_profile(solver):
     return list(ms), list(cnt)
 
 
+def startup_default_ba_params(**over):
+    """vilf_startup_ba_params with the reference's constants (initial_sfm.cpp:277-289, Ceres's function tolerance); keyword arguments replace fields (ba_iterations=1, ...)"""
+    p = abi.StartupBaParams()
+    lib().vilf_startup_default_ba_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise TypeError(f"vilf_startup_ba_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _startup_ba_results(solver, windows, keep, out, rows):
+    """the BA's rows and its structure (vilf_startup_get_ba_structure) as dicts per window"""
+    n = len(windows)
+    NF, NX = abi.VILF_MAX_FRAMES, abi.VILF_MAX_FEATURES
+    state = np.zeros((n, NX), dtype=np.uint8); pos = np.zeros((n, NX, 3))
+    solver._check(lib().vilf_startup_get_ba_structure(solver._h, n, state.ctypes.data_as(C.POINTER(C.c_uint8)), abi.dptr(pos)), "vilf_startup_get_ba_structure")
+    res = []
+    for k, w in enumerate(windows):
+        o, nx = out[k], len(keep[k][0])
+        frames = [dict(R=np.array(r.R).reshape(3, 3), t=np.array(r.t), Q=np.array(r.Q).reshape(3, 3), T=np.array(r.T)) for r in rows[k * NF:k * NF + int(w["n_frames"])]]
+        res.append(dict(ok=bool(o.ok), flags=o.flags, iterations=o.iterations, accepted=o.accepted, n_camera=o.n_camera, n_members=o.n_members, n_residuals=o.n_residuals,
+                        l=o.l, cost0=float(o.cost0), cost1=float(o.cost1), lam=float(o.lambda_), frames=frames, state=state[k, :nx].copy(), positions=pos[k, :nx].copy()))
+    return res
+
+
+def bundle_adjust(solver, windows, starts, **params):
+    """≙ the full bundle adjustment of GlobalSFM::construct (initial/initial_sfm.cpp:232-310) alone, for every window at once on the device (vilf_startup_ba). windows
+    as in relative_pose; starts: per window a dict(l, R [n_frames][3][3], t [n_frames][3], state [n_features], positions [n_features][3]) and optionally chain_ok
+    (default True), the poses in the chain's convention. params: fields of vilf_startup_ba_params. Returns a list of dict(ok, flags, iterations, accepted, n_camera,
+    n_members, n_residuals, l, cost0, cost1, lam, frames (dicts of R, t, Q, T), state, positions) per window."""
+    L = lib()
+    p = startup_default_ba_params(**params)
+    windows = list(windows)
+    n = len(windows)
+    W, keep = _startup_windows(windows)
+    st = (abi.StartupBaStart * max(n, 1))()
+    hold = []
+    for k, s in enumerate(starts):
+        st[k].l, st[k].chain_ok = int(s["l"]), int(bool(s.get("chain_ok", True)))
+        R = np.ascontiguousarray(s["R"], dtype=np.float64).reshape(-1, 9)
+        t = np.ascontiguousarray(s["t"], dtype=np.float64).reshape(-1, 3)
+        state = np.ascontiguousarray(s["state"], dtype=np.uint8)
+        pos = np.ascontiguousarray(s["positions"], dtype=np.float64).reshape(-1, 3)
+        assert len(R) >= int(windows[k]["n_frames"]) and len(t) >= int(windows[k]["n_frames"]) and len(state) >= len(keep[k][0]) and len(pos) >= len(keep[k][0])
+        hold.append((R, t, state, pos))
+        st[k].R, st[k].t, st[k].state, st[k].positions = abi.dptr(R), abi.dptr(t), state.ctypes.data_as(C.POINTER(C.c_uint8)), abi.dptr(pos)
+    out = (abi.StartupBaResult * max(n, 1))()
+    rows = (abi.StartupBaFrame * (max(n, 1) * abi.VILF_MAX_FRAMES))()
+    solver._check(L.vilf_startup_ba(solver._h, C.byref(p), n, W, st, out, rows), "vilf_startup_ba")
+    return _startup_ba_results(solver, windows, keep, out, rows)
+
+
+def construct(solver, windows, rel=None, **params):
+    """≙ GlobalSFM::construct (initial/initial_sfm.cpp:117-310): the frame chain, then the full bundle adjustment from its poses and structure, for every window at
+    once and without a host round trip in between (vilf_startup_construct). windows and rel as in global_sfm (rel=None runs relative_pose first); params: fields of
+    vilf_startup_params (only with rel=None), vilf_startup_sfm_params and vilf_startup_ba_params (lambda0 sets both, sfm_lambda0 / ba_lambda0 one of them). Returns
+    the BA's dicts as bundle_adjust does, each with chain = dict(ok, fail_frame, n_triangulated, l, frames) as global_sfm returns it."""
+    L = lib()
+    windows = list(windows)
+    n = len(windows)
+    stage1 = {k: params.pop(k) for k in list(params) if hasattr(abi.StartupParams, k) and not hasattr(abi.StartupSfmParams, k) and not hasattr(abi.StartupBaParams, k)}
+    sfm = {k: params[k] for k in params if hasattr(abi.StartupSfmParams, k)}
+    ba = {k: params[k] for k in params if hasattr(abi.StartupBaParams, k)}
+    if "sfm_lambda0" in params:
+        sfm["lambda0"] = params.pop("sfm_lambda0")
+    if "ba_lambda0" in params:
+        ba["lambda0"] = params.pop("ba_lambda0")
+    unknown = [k for k in params if k not in sfm and k not in ba]
+    if unknown:
+        raise TypeError(f"no start-up parameter is called {sorted(unknown)}")
+    sp, bp = startup_default_sfm_params(**sfm), startup_default_ba_params(**ba)
+    if rel is None:
+        rel = relative_pose(solver, windows, **stage1)
+    elif stage1:
+        raise TypeError(f"parameters of relative_pose given together with rel: {sorted(stage1)}")
+    W, keep = _startup_windows(windows)
+    rl = (abi.StartupResult * max(n, 1))()
+    for k, r in enumerate(rel):
+        rl[k].l = int(r["l"])
+        rl[k].R[:] = [float(v) for v in np.asarray(r["R"], dtype=np.float64).reshape(9)]
+        rl[k].T[:] = [float(v) for v in np.asarray(r["T"], dtype=np.float64).reshape(3)]
+    NF = abi.VILF_MAX_FRAMES
+    out = (abi.StartupBaResult * max(n, 1))()
+    rows = (abi.StartupBaFrame * (max(n, 1) * NF))()
+    chain = (abi.StartupStructure * max(n, 1))()
+    crow = (abi.StartupFrame * (max(n, 1) * NF))()
+    solver._check(L.vilf_startup_construct(solver._h, C.byref(sp), C.byref(bp), n, W, rl, out, rows, chain, crow), "vilf_startup_construct")
+    res = _startup_ba_results(solver, windows, keep, out, rows)
+    for k, w in enumerate(windows):
+        o = chain[k]
+        res[k]["chain"] = dict(ok=bool(o.ok), fail_frame=o.fail_frame, n_triangulated=o.n_triangulated, l=o.l,
+                               frames=[_startup_frame(crow[k * NF + i]) for i in range(int(w["n_frames"]))])
+    return res
+
+
+def startup_ba_profile(solver):
+    """ms and launches of su_sfm_ba since vilf_set_profiling"""
+    ms, cnt = (C.c_double * 1)(), (C.c_long * 1)()
+    solver._check(lib().vilf_startup_ba_profile(solver._h, ms, cnt), "vilf_startup_ba_profile")
+    return list(ms), list(cnt)
+
+
 def posegraph_optimize(solver, poses_qt, prior_sigma, edges, max_iterations=30, tol=1e-9):
     """≙ the gtsam graph + isam update of global_fusion (poseGraphOptimization.cpp:349-374, :560-587, :433-436) on the device
     (vilf_posegraph_optimize). poses_qt (n, 7) [qx qy qz qw tx ty tz]; edges: iterable of (i, j, q[4], t[3], sigma[6], robust).

@@ -29,6 +29,7 @@ EXPORTED = [
     "vilf_track_detect_masked", "vilf_track_profile_mask",
     "vilf_startup_default_params", "vilf_startup_relative_pose", "vilf_startup_get_correspondences", "vilf_startup_profile",
     "vilf_startup_default_sfm_params", "vilf_startup_sfm", "vilf_startup_get_structure", "vilf_startup_pnp", "vilf_startup_sfm_profile",
+    "vilf_startup_default_ba_params", "vilf_startup_ba", "vilf_startup_construct", "vilf_startup_get_ba_structure", "vilf_startup_ba_profile",
 ]
 
 
@@ -173,6 +174,14 @@ def lib():
     L.vilf_startup_get_structure.argtypes = [vp, C.c_int, u8p, abi.c_double_p]
     L.vilf_startup_pnp.argtypes = [vp, C.POINTER(abi.StartupSfmParams), C.c_int, C.POINTER(abi.StartupPnpProblem), C.POINTER(abi.StartupFrame)]
     L.vilf_startup_sfm_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_startup_default_ba_params.argtypes = [C.POINTER(abi.StartupBaParams)]
+    L.vilf_startup_default_ba_params.restype = None
+    L.vilf_startup_ba.argtypes = [vp, C.POINTER(abi.StartupBaParams), C.c_int, C.POINTER(abi.StartupWindow), C.POINTER(abi.StartupBaStart), C.POINTER(abi.StartupBaResult),
+                                  C.POINTER(abi.StartupBaFrame)]
+    L.vilf_startup_construct.argtypes = [vp, C.POINTER(abi.StartupSfmParams), C.POINTER(abi.StartupBaParams), C.c_int, C.POINTER(abi.StartupWindow), C.POINTER(abi.StartupResult),
+                                         C.POINTER(abi.StartupBaResult), C.POINTER(abi.StartupBaFrame), C.POINTER(abi.StartupStructure), C.POINTER(abi.StartupFrame)]
+    L.vilf_startup_get_ba_structure.argtypes = [vp, C.c_int, u8p, abi.c_double_p]
+    L.vilf_startup_ba_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 

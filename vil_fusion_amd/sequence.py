@@ -7,8 +7,9 @@ A Python mirror of the reference's per-frame host logic, so whole multi-frame se
                                 setDepth :150-168, removeFailures :170-180, getDepthVector :194-216, triangulate :218-276,
                                 removeBackShiftDepth :292-349, removeBack :351-366, removeFront :368-388, compensatedParallax2 :390-423)
     SlidingWindowEstimator    ≙ vins_estimator/estimator.cpp: clearState :36-88, processOdometry :90-101, processIMU :103-137, processImage :139-234
-                                (NON_LINEAR branch incl. the failureDetection reboot :212-220; the SfM initialisation :237-459 is out of scope —
-                                the window is bootstrapped from given states), solveOdometry :492-503, vector2double :505-547,
+                                (NON_LINEAR branch incl. the failureDetection reboot :212-220; the window is bootstrapped from given states
+                                or a stand-in of the SfM initialisation :237-459 unless initial_structure is asked for: relativePose, GlobalSFM::construct
+                                and the hand-off :263-303 on the device, without the PnP of non-key frames :305-372), solveOdometry :492-503, vector2double :505-547,
                                 failureDetection :640-686, slideWindow :1052-1186
     run_sequences_lockstep    several independent estimators (sequence segments) stepped frame by frame as ONE batch on the device
                                 (vilf_batch_upload / _solve / _marginalize per frame; every segment's prior stays in its slot)
@@ -309,7 +310,9 @@ class SlidingWindowEstimator:
     # estimator.cpp:139-234. `init_state` = (P, R, V, ba, bg) of this frame while the window is being filled (replaces the SfM start-up)
     def process_image(self, image, stamp, init_state=None, sfm_frames=None):
         """`sfm_frames` (only looked at when the window has just filled): the output of initialStructure's SfM + PnP stage (estimator.cpp:237-371),
-        a time-ordered list of dict(stamp, R = c0_R_bk, T = c0_T_ck up to scale, pre = that frame's Integration) -> visualInitialAlign runs first.
+        a time-ordered list of dict(stamp, R = c0_R_bk, T = c0_T_ck up to scale, pre = that frame's Integration) -> visualInitialAlign runs first. A callable
+        is called once this image's features are in the feature manager and returns that list, or None where the structure failed (the window then slides
+        and the next frame tries again, as for a failed alignment).
         Returns the WindowResult of a solved frame, None while the window fills, "reboot" when failureDetection() fired."""
         win = self.begin_image(image, stamp, init_state, sfm_frames)
         if win is None:
@@ -334,7 +337,8 @@ class SlidingWindowEstimator:
                 self.events.append("fill")
                 return None
             if sfm_frames is not None:
-                self.initial_ok = self.visual_initial_align(sfm_frames)
+                frames = sfm_frames() if callable(sfm_frames) else sfm_frames
+                self.initial_ok = frames is not None and self.visual_initial_align(frames)
                 if not self.initial_ok:             # the reference slides the window and retries on the next frame (:201-216)
                     self.slide_window()
                     self.events.append("fill")
@@ -432,7 +436,7 @@ class SlidingWindowEstimator:
             self.Ps[i] = R0 @ self.Ps[i]; self.Rs[i] = R0 @ self.Rs[i]; self.Vs[i] = R0 @ self.Vs[i]
         return True
 
-    # estimator.cpp:461-490 (relativePose) on the device. Nothing calls it by default: the window still fills from init_state or make_sfm_frames
+    # estimator.cpp:461-490 (relativePose) on the device. Nothing calls it by default (initial_structure runs it through construct): the window fills from init_state or make_sfm_frames
     def relative_pose_table(self):
         """the feature table of vilf_startup_relative_pose from the feature manager, the newest frame = frame_count. getCorresponding walks every feature; those
         that end before the newest frame belong to no pair and are left out, which keeps the order of the others"""
@@ -457,7 +461,7 @@ class SlidingWindowEstimator:
         return r["ok"], r["l"], r["R"], r["T"], table
 
     # initial_sfm.cpp:117-217 (the frame chain of GlobalSFM::construct) on the device, from the same table. Nothing calls it by default either: its poses are the
-    # starting value of the full BA, which is not built yet, not the window's
+    # starting value of the full BA (initial_structure below runs both), not the window's
     def global_sfm(self, **params):
         """-> (result, table): relativePose and the chain in one go; result = dict(ok, fail_frame, n_triangulated, l, frames, state, positions) of the table's
         features. The work is done by backend.global_sfm([table], structure=True, **params) if the back-end has one, else on the handle of the BackendSolver it
@@ -469,6 +473,26 @@ class SlidingWindowEstimator:
             from .estimator import global_sfm
             r = global_sfm(self.backend.s, [table], structure=True, **params)[0]
         return r, table
+
+    # estimator.cpp:263-303 (relativePose, GlobalSFM::construct with its full BA, the poses handed on) on the device, from the same table. Opt-in: run_sequence
+    # calls it with startup=dict(source="device"). The PnP of the non-key frames (:305-372) has nothing to do where every frame of the window is a key frame,
+    # which is the case here; a caller with other frames solves them with vilf_startup_pnp
+    def initial_structure(self, **params):
+        """-> the frames visual_initial_align takes (dict(stamp, R = Q[k] RIC^T, T = T[k], pre) per frame of the window), or None where relativePose, the chain
+        or the BA failed; `structure` keeps the result of the construct call and `structure_table` its table either way. The work is done by
+        backend.construct([table], **params) if the back-end has one, else on the handle of the BackendSolver it keeps as `s`; there is no host path"""
+        import copy
+        table = self.relative_pose_table()
+        if hasattr(self.backend, "construct"):
+            r = self.backend.construct([table], **params)[0]
+        else:
+            from .estimator import construct
+            r = construct(self.backend.s, [table], **params)[0]
+        self.structure, self.structure_table = r, table
+        if not r["ok"]:
+            return None
+        return [dict(stamp=self.stamps[k], R=np.asarray(f["Q"]) @ self.ric.T, T=np.array(f["T"], dtype=np.float64), pre=copy.deepcopy(self.pre[k]))
+                for k, f in enumerate(r["frames"])]
 
     def _used_f(self, it):
         return self.f._used(it)
@@ -680,14 +704,22 @@ def run_sequence(seq, opts, backend, n_frames=None, startup=None):
     """Feed a make_sequence() dict through SlidingWindowEstimator; returns the estimator (trajectory, flags, summaries).
     startup=None: while the estimator is INITIAL (the first WINDOW_SIZE + 1 frames, and again after a failureDetection reboot) the frames take
     seq["init"] (a state already initialised). startup=dict(make_sfm_frames kwargs): the window fills from a zero state and visualInitialAlign
-    (SfM stand-in + VisualIMUAlignment on the back-end) initialises it."""
+    (SfM stand-in + VisualIMUAlignment on the back-end) initialises it. startup=dict(source="device", construct kwargs): the same, but the frames come from
+    the estimator's initial_structure (relativePose, the frame chain and the full BA on the device) and not from the stand-in that reads ground truth; a
+    failed structure or alignment slides the window and the next frame tries again."""
     est = SlidingWindowEstimator(opts, backend)
+    device = startup is not None and startup.get("source", "truth") == "device"
+    if startup is not None:
+        startup = {k: v for k, v in startup.items() if k != "source"}
     n = len(seq["images"]) if n_frames is None else n_frames
     est.process_imu(0.0, *seq["imu0"])                 # first sample: only latches acc_0 / gyr_0 (frame_count == 0)
     for k in range(n):
         _feed_measurements(est, seq, k)
         if startup is None:
             est.process_image(seq["images"][k], seq["stamps"][k], seq["init"][k] if est.solver_flag == est.INITIAL else None)
+        elif device:
+            retry = k >= WINDOW_SIZE and est.solver_flag == est.INITIAL
+            est.process_image(seq["images"][k], seq["stamps"][k], None, sfm_frames=(lambda: est.initial_structure(**startup)) if retry else None)
         elif k == WINDOW_SIZE:
             est.stamps[k] = seq["stamps"][k]
             est.process_image(seq["images"][k], seq["stamps"][k], None, sfm_frames=make_sfm_frames(seq, opts, est, **startup))
