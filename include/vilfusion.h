@@ -1019,6 +1019,65 @@ int vilf_startup_construct(vilf_handle *h, const vilf_startup_sfm_params *sp, co
 int vilf_startup_get_ba_structure(vilf_handle *h, int n_windows, unsigned char *state_out, double *positions_out);
 /* vilf_set_profiling: su_sfm_ba of the calls since the switch was set (the chain of a vilf_startup_construct counts in vilf_startup_sfm_profile) */
 int vilf_startup_ba_profile(vilf_handle *h, double ms_out[1], long launches_out[1]);
+
+/* ---- Feature manager: triangulate (≙ FeatureManager::triangulate, feature_manager.cpp:218-274, with getDepthVector :194-216; device) ----
+ * The first half of solveOdometry (estimator.cpp:492-503): the depth of every feature of the window that has none yet, from all its observations. The reference
+ * takes the right singular vector of the smallest singular value from Eigen::JacobiSVD; Eigen is not available, so this text fixes the arithmetic as the CPU oracle
+ * has it (oracle/sequence.cpp, a one-sided Hestenes Jacobi: the one deliberate deviation; agreement with Eigen is neither measured nor claimed),
+ * tests/tri_reference.py restates it and the kernel agrees with that to the bit. Everything is fp64, each operation rounded (no fused multiply-add); a NaN compares
+ * false everywhere; "-(x)" negates the rounded x; "the sum from 0.0 of" terms starts at +0.0 and adds the terms in the stated order, the first one too (so that a
+ * lone -0.0 becomes +0.0). Matrices are row-major, M_rc = M[3 r + c].
+ *   window       n_frames frames with the body positions Ps[k] and rotations Rs[k], the extrinsics tic, ric, and ALL features of f_manager.feature in list order:
+ *                feature f was first seen in frame start_frame[f] and has n_obs(f) = first_obs[f + 1] - first_obs[f] observations in consecutive frames,
+ *                observation o at row first_obs[f] + o of points: feature_per_frame[o].point = (x, y, z) of frame start_frame[f] + o. z need not be 1.
+ *   used         n_obs(f) >= 2 and start_frame[f] < options.window_size - 2 (:223). Only used features are ever touched.
+ *   candidate    used and not depth_in[f] > 0 (:226): a depth of 0, a negative one and a NaN are all candidates. Every other feature keeps depth_in, bit for bit.
+ *   camera       of frame k: tc_k = Ps[k] + Rs[k] tic, Rc_k = Rs[k] ric, with M v: (M v)_r = (M_r0 v_0 + M_r1 v_1) + M_r2 v_2; u + v by component;
+ *                (M N)_rc = the sum from 0.0 of M_rk N_kc over k = 0, 1, 2. The same numbers for every feature of the window.
+ *   design matrix of candidate f with i = start_frame[f] (:229-258): for o = 0 .. n_obs(f) - 1, j = i + o (observation 0 goes through the same products; it is not
+ *                replaced by the identity): d = tc_j - tc_i; t_r = (Rc_i,0r d_0 + Rc_i,1r d_1) + Rc_i,2r d_2 (= Rc_i^T d); R_rc = the sum from 0.0 of
+ *                Rc_i,kr Rc_j,kc over k = 0, 1, 2 (= Rc_i^T Rc_j); P_rc = R_cr for c < 3, P_r3 = -((R_0r t_0 + R_1r t_1) + R_2r t_2) (= [R^T | -(R^T t)]).
+ *                n = sqrt((x x + y y) + z z); (f_0, f_1, f_2) = (x / n, y / n, z / n). Rows 2 o and 2 o + 1 of A (2 n_obs(f) x 4, at most 22 x 4):
+ *                A_(2o)c = f_0 P_2c - f_2 P_0c, A_(2o+1)c = f_1 P_2c - f_2 P_1c, c = 0 .. 3 (two products and a subtraction each).
+ *   right singular vector  V = the 4 x 4 identity. At most 60 sweeps; a sweep visits the pairs (p, q) in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3). A pair:
+ *                alpha, beta, gamma = the sums from 0.0 of A_rp A_rp, A_rq A_rq, A_rp A_rq over the rows r in ascending order. The pair is skipped iff
+ *                |gamma| <= 1e-17 sqrt(alpha beta) or gamma == 0.0. Else zeta = (beta - alpha) / (2.0 gamma); t = sg / (|zeta| + sqrt(1.0 + zeta zeta)) with
+ *                sg = 1.0 if zeta >= 0, else -1.0 (a NaN gives -1.0); c = 1.0 / sqrt(1.0 + t t); s = c t; then every row r in ascending order:
+ *                (A_rp, A_rq) <- (c A_rp - s A_rq, s A_rp + c A_rq) from the old pair, and the four rows of V the same way. The loop stops after the first sweep
+ *                that rotated nothing; sweeps = the sweeps run, that one included (1 .. 60). Winner: n_c = the sum from 0.0 of A_rc A_rc over the rows in ascending
+ *                order, c = 0 .. 3; best = 0, bound = +inf; for c = 0 .. 3: if n_c < bound then bound = n_c, best = c (strict: the first wins a tie, a NaN never wins).
+ *   result       depth = V_2,best / V_3,best. If depth < 0.1 the depth becomes options.init_depth (:268-271) and VILF_TRI_RESET is set; an inf or a NaN stays as
+ *                it is, as in the reference, and VILF_TRI_NONFINITE is set.
+ *   getDepthVector  for the used features in feature order, compacted: 1.0 / depth if depth > 0, else 1.0 / options.init_depth, over the depths after triangulation. */
+#define VILF_TRI_MAX_WINDOWS 4096
+#define VILF_TRI_USED 1          /* flags of a feature: the used rule holds */
+#define VILF_TRI_DONE 2          /* it was a candidate: depth_out is the triangulation's */
+#define VILF_TRI_RESET 4         /* its depth was < 0.1 and became init_depth */
+#define VILF_TRI_NONFINITE 8     /* its depth is inf or NaN and was kept */
+typedef struct vilf_tri_window {
+    int n_frames, n_features;        /* 2 .. VILF_MAX_FRAMES, 0 .. VILF_MAX_FEATURES */
+    const double *Ps, *Rs;           /* [n_frames][3], [n_frames][9] row-major */
+    double tic[3], ric[9];
+    const int *start_frame;          /* [n_features] */
+    const int *first_obs;            /* [n_features + 1], first_obs[0] = 0, non-decreasing */
+    const double *points;            /* [first_obs[n_features]][3] */
+    const double *depth_in;          /* [n_features] estimated_depth */
+    double *depth_out;               /* [n_features]; a feature that is no candidate gets depth_in back, bit for bit */
+    double *inv_depth_out;           /* [n_used] getDepthVector, or NULL */
+    unsigned char *flags_out;        /* [n_features] VILF_TRI_*, or NULL */
+    unsigned char *sweeps_out;       /* [n_features] the sweeps run (1 .. 60), 0 for a feature that is no candidate, or NULL */
+} vilf_tri_window;
+typedef struct vilf_tri_result { int n_used, n_candidates, n_reset, n_nonfinite; } vilf_tri_result;
+/* triangulate + getDepthVector for n_windows independent windows: the host applies the used and the candidate rule while it packs and hands the device ONE dense list
+ * of the candidates of all windows; one upload, one chain of two launches on the handle's stream (tri_cameras: the cameras of every window once; tri_solve: a lane
+ * per candidate), the host waits once, one download; a call without any candidate launches nothing. out [n_windows]. A feature's result does not depend on the batch it is in or on its place in it, to the bit.
+ * Invalid argument, nothing written: a null handle, windows or out, n_windows < 1 or > VILF_TRI_MAX_WINDOWS, n_frames < 2 or > VILF_MAX_FRAMES, n_features < 0 or
+ * > VILF_MAX_FEATURES, a null Ps, Rs or first_obs, a null start_frame, depth_in or depth_out with n_features > 0, a first_obs that does not start at 0 or decreases,
+ * a used feature with start_frame < 0 or start_frame + n_obs > n_frames, a null points with first_obs[n_features] > 0, an entry of Ps, Rs, tic or ric
+ * that is not finite. The points are not screened: what a point that is not finite gives is what the text gives. */
+int vilf_features_triangulate(vilf_handle *h, int n_windows, const vilf_tri_window *windows, vilf_tri_result *out);
+/* vilf_set_profiling: the time and the number of the kernel launches (two per call that has a candidate) since the switch was set */
+int vilf_features_profile(vilf_handle *h, double ms_out[1], long launches_out[1]);
 #ifdef __cplusplus
 }
 #endif

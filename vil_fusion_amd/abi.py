@@ -261,6 +261,24 @@ STARTUP_BA_LAYOUTS = {"vilf_startup_ba_params": StartupBaParams, "vilf_startup_b
 STARTUP_BA_C_NAMES = {"lambda_": "lambda"}
 
 
+class TriWindow(C.Structure):
+    """vilf_tri_window: the poses, the extrinsics and the whole feature list FeatureManager::triangulate reads, and where its outputs go"""
+    _fields_ = [("n_frames", C.c_int), ("n_features", C.c_int), ("Ps", c_double_p), ("Rs", c_double_p), ("tic", C.c_double * 3), ("ric", C.c_double * 9),
+                ("start_frame", C.POINTER(C.c_int32)), ("first_obs", C.POINTER(C.c_int32)), ("points", c_double_p), ("depth_in", c_double_p),
+                ("depth_out", c_double_p), ("inv_depth_out", c_double_p), ("flags_out", C.POINTER(C.c_uint8)), ("sweeps_out", C.POINTER(C.c_uint8))]
+
+
+class TriResult(C.Structure):
+    """vilf_tri_result: a window's counts"""
+    _fields_ = [("n_used", C.c_int), ("n_candidates", C.c_int), ("n_reset", C.c_int), ("n_nonfinite", C.c_int)]
+
+
+VILF_TRI_USED, VILF_TRI_DONE, VILF_TRI_RESET, VILF_TRI_NONFINITE = 1, 2, 4, 8
+VILF_TRI_MAX_WINDOWS = 4096
+# the mirrors of the feature triangulation, for the layout check of tests/test_feature_triangulate.py
+TRI_LAYOUTS = {"vilf_tri_window": TriWindow, "vilf_tri_result": TriResult}
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

@@ -24,8 +24,13 @@ class BackendSolver:
         self._h = h
         self._keep = None
         self._n = 0
+        self._device = int(device)
+        self._tri = None
 
     def close(self):
+        if getattr(self, "_tri", None) is not None:
+            self._tri.close()
+            self._tri = None
         if getattr(self, "_h", None):
             self._L.vilf_destroy(self._h)
             self._h = None
@@ -268,6 +273,23 @@ class BackendSolver:
         fn = self._L.vilf_se3_plus if se3 else self._L.vilf_pose_plus
         self._check(fn(self._h, f(x), f(d), abi.dptr(out)), "vilf_pose_plus")
         return out
+
+    # ---- feature manager ------------------------------------------------------------------------------------------
+    def triangulate_features(self, tables):
+        """≙ f_manager.triangulate + getDepthVector for every table at once (triangulate_features below), on a handle of its own with these options: its stream
+        and its buffers are not those of the window solve. This is what SlidingWindowEstimator and run_sequences_lockstep take as `triangulate`."""
+        if self._tri is None:
+            self._tri = BackendSolver(self.options, self._device)
+        return triangulate_features(self._tri, tables)
+
+    def features_profile(self):
+        """ms and kernel launches of triangulate_features since set_profiling_features"""
+        return features_profile(self._tri) if self._tri is not None else ([0.0], [0])
+
+    def set_profiling_features(self, on=True):
+        if self._tri is None:
+            self._tri = BackendSolver(self.options, self._device)
+        self._tri.set_profiling(on)
 
 
 def imu_preintegrate(noise, acc_0, gyr_0, ba, bg, dt, acc, gyr):
@@ -575,6 +597,55 @@ def startup_ba_profile(solver):
     """ms and launches of su_sfm_ba since vilf_set_profiling"""
     ms, cnt = (C.c_double * 1)(), (C.c_long * 1)()
     solver._check(lib().vilf_startup_ba_profile(solver._h, ms, cnt), "vilf_startup_ba_profile")
+    return list(ms), list(cnt)
+
+
+def triangulate_features(solver, tables):
+    """≙ FeatureManager::triangulate (feature_manager.cpp:218-274) and getDepthVector (:194-216) for every window at once on the device
+    (vilf_features_triangulate). tables: an iterable of dict(n_frames, Ps [n_frames][3], Rs [n_frames][3][3], tic [3], ric [3][3], start_frame [n], first_obs [n + 1],
+    points [total][3], depth [n]): ALL features of the feature manager in list order (FeatureManager.triangulation_table). Returns per table a dict(depth [n]: the
+    depths after triangulation, inv_depth [n_used]: getDepthVector, flags [n]: VILF_TRI_*, sweeps [n], result: dict(n_used, n_candidates, n_reset, n_nonfinite))."""
+    L = lib()
+    tables = list(tables)
+    n = len(tables)
+    W = (abi.TriWindow * max(n, 1))()
+    keep = []
+    i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    for k, t in enumerate(tables):
+        nf = int(t["n_frames"])
+        Ps = np.ascontiguousarray(t["Ps"], dtype=np.float64).reshape(-1)[:3 * nf].copy()
+        Rs = np.ascontiguousarray(t["Rs"], dtype=np.float64).reshape(-1)[:9 * nf].copy()
+        start = np.ascontiguousarray(t["start_frame"], dtype=np.int32)
+        first = np.ascontiguousarray(t["first_obs"], dtype=np.int32)
+        pts = np.ascontiguousarray(t["points"], dtype=np.float64).reshape(-1, 3)
+        din = np.ascontiguousarray(t["depth"], dtype=np.float64)
+        m = len(start)
+        dout, inv, flags, sweeps = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros(max(m, 1), dtype=np.uint8), np.zeros(max(m, 1), dtype=np.uint8)
+        keep.append((Ps, Rs, start, first, pts, din, dout, inv, flags, sweeps))
+        w = W[k]
+        w.n_frames, w.n_features = nf, m
+        w.Ps, w.Rs = abi.dptr(Ps), abi.dptr(Rs)
+        w.tic[:] = [float(v) for v in np.asarray(t["tic"], dtype=np.float64).reshape(3)]
+        w.ric[:] = [float(v) for v in np.asarray(t["ric"], dtype=np.float64).reshape(9)]
+        w.start_frame, w.first_obs = start.ctypes.data_as(i32p), first.ctypes.data_as(i32p)
+        w.points, w.depth_in = abi.dptr(pts), abi.dptr(din)
+        w.depth_out, w.inv_depth_out = abi.dptr(dout), abi.dptr(inv)
+        w.flags_out, w.sweeps_out = flags.ctypes.data_as(u8p), sweeps.ctypes.data_as(u8p)
+    out = (abi.TriResult * max(n, 1))()
+    solver._check(L.vilf_features_triangulate(solver._h, n, W, out), "vilf_features_triangulate")
+    res = []
+    for k in range(n):
+        m = len(keep[k][2])
+        o = out[k]
+        res.append(dict(depth=keep[k][6][:m], inv_depth=keep[k][7][:o.n_used], flags=keep[k][8][:m], sweeps=keep[k][9][:m],
+                        result=dict(n_used=o.n_used, n_candidates=o.n_candidates, n_reset=o.n_reset, n_nonfinite=o.n_nonfinite)))
+    return res
+
+
+def features_profile(solver):
+    """ms and kernel launches (tri_cameras + tri_solve: two per call that has a candidate) of vilf_features_triangulate since vilf_set_profiling"""
+    ms, cnt = (C.c_double * 1)(), (C.c_long * 1)()
+    solver._check(lib().vilf_features_profile(solver._h, ms, cnt), "vilf_features_profile")
     return list(ms), list(cnt)
 
 

@@ -30,6 +30,7 @@ EXPORTED = [
     "vilf_startup_default_params", "vilf_startup_relative_pose", "vilf_startup_get_correspondences", "vilf_startup_profile",
     "vilf_startup_default_sfm_params", "vilf_startup_sfm", "vilf_startup_get_structure", "vilf_startup_pnp", "vilf_startup_sfm_profile",
     "vilf_startup_default_ba_params", "vilf_startup_ba", "vilf_startup_construct", "vilf_startup_get_ba_structure", "vilf_startup_ba_profile",
+    "vilf_features_triangulate", "vilf_features_profile",
 ]
 
 
@@ -182,6 +183,8 @@ def lib():
                                          C.POINTER(abi.StartupBaResult), C.POINTER(abi.StartupBaFrame), C.POINTER(abi.StartupStructure), C.POINTER(abi.StartupFrame)]
     L.vilf_startup_get_ba_structure.argtypes = [vp, C.c_int, u8p, abi.c_double_p]
     L.vilf_startup_ba_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_features_triangulate.argtypes = [vp, C.c_int, C.POINTER(abi.TriWindow), C.POINTER(abi.TriResult)]
+    L.vilf_features_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 

@@ -16,7 +16,9 @@ A Python mirror of the reference's per-frame host logic, so whole multi-frame se
     write_tum                 ≙ utility/visualization.cpp:159-172 (t x y z qx qy qz qw, time relative to the first frame)
 
 The back-end is pluggable: `backend.solve(window) -> WindowResult` and `backend.marginalize(window, result)`; see HipBackend /
-adapters in tests. Everything here is host bookkeeping — no arithmetic of the hot path lives in this file.
+adapters in tests. Everything here is host bookkeeping — no arithmetic of the hot path lives in this file. FeatureManager.triangulate is the
+host loop of the reference (an SVD per feature); given `triangulate=` (BackendSolver.triangulate_features), the estimator, run_sequence and
+run_sequences_lockstep hand the feature table to vilf_features_triangulate instead (triangulation_table / apply_triangulation).
 """
 import numpy as np
 
@@ -130,6 +132,25 @@ class FeatureManager:
             it.estimated_depth = v[2] / v[3]
             if it.estimated_depth < 0.1:
                 it.estimated_depth = INIT_DEPTH
+
+    def triangulation_table(self, Ps, Rs, tic, ric):
+        """what triangulate reads, as the table of vilf_features_triangulate: the poses, the extrinsics and ALL features in list order (the library applies the used
+        and the candidate rule itself)"""
+        first, pts = [0], []
+        for it in self.feature:
+            pts.extend(fp.point for fp in it.feature_per_frame)
+            first.append(len(pts))
+        return dict(n_frames=len(Ps), Ps=np.array(Ps, dtype=np.float64), Rs=np.array(Rs, dtype=np.float64), tic=np.array(tic, dtype=np.float64),
+                    ric=np.array(ric, dtype=np.float64), start_frame=np.array([it.start_frame for it in self.feature], dtype=np.int32),
+                    first_obs=np.array(first, dtype=np.int32), points=np.array(pts, dtype=np.float64).reshape(-1, 3),
+                    depth=np.array([it.estimated_depth for it in self.feature], dtype=np.float64))
+
+    def apply_triangulation(self, depth):
+        """the depths vilf_features_triangulate returned for the table, back into the list (a feature that was no candidate gets its own depth back, bit for bit)"""
+        assert len(depth) == len(self.feature)
+        for it, d in zip(self.feature, depth):
+            it.used_num = len(it.feature_per_frame)         # as triangulate's walk leaves it (:222)
+            it.estimated_depth = float(d)
 
     def remove_back_shift_depth(self, marg_R, marg_P, new_R, new_P):
         keep = []
@@ -250,8 +271,10 @@ class SlidingWindowEstimator:
 
     INITIAL, NON_LINEAR = 0, 1
 
-    def __init__(self, opts, backend):
-        self.o, self.backend = opts, backend
+    def __init__(self, opts, backend, triangulate=None):
+        """`triangulate`: an optional callable tables -> results (BackendSolver.triangulate_features); both places that call f_manager.triangulate (solveOdometry,
+        visualInitialAlign) then go through it with one table. Without it the host loop FeatureManager.triangulate runs, as before."""
+        self.o, self.backend, self.triangulate = opts, backend, triangulate
         self.trajectory = []            # (stamp, P[3], q[4] xyzw) of the newest frame after every solved frame
         self.flags = []
         self.summaries = []
@@ -323,6 +346,22 @@ class SlidingWindowEstimator:
 
     def begin_image(self, image, stamp, init_state=None, sfm_frames=None):
         """processImage up to the solve: returns the window description (vector2double + the factor walk) or None when this frame only fills the window"""
+        if not self.prepare_image(image, stamp, init_state, sfm_frames):
+            return None
+        # solveOdometry (:492-503)
+        self.triangulate_features(self.tic)
+        return self.make_window()
+
+    def triangulate_features(self, tic):
+        """f_manager.triangulate(Ps, tic, ric): the host loop, or one table through the callable the estimator was given"""
+        if self.triangulate is None:
+            self.f.triangulate(self.Ps, self.Rs, tic, self.ric)
+        else:
+            self.f.apply_triangulation(self.triangulate([self.f.triangulation_table(self.Ps, self.Rs, tic, self.ric)])[0]["depth"])
+
+    def prepare_image(self, image, stamp, init_state=None, sfm_frames=None):
+        """processImage up to solveOdometry's triangulation: True when this frame is solved (the caller triangulates, then make_window), False when it only fills
+        the window"""
         j = self.frame_count
         keyframe = self.f.add_feature_check_parallax(j, dict(sorted(image.items())), self.td)
         self.marginalization_flag = MARGIN_OLD if keyframe else MARGIN_SECOND_NEW
@@ -335,21 +374,19 @@ class SlidingWindowEstimator:
             if j < WINDOW_SIZE:
                 self.frame_count += 1
                 self.events.append("fill")
-                return None
+                return False
             if sfm_frames is not None:
                 frames = sfm_frames() if callable(sfm_frames) else sfm_frames
                 self.initial_ok = frames is not None and self.visual_initial_align(frames)
                 if not self.initial_ok:             # the reference slides the window and retries on the next frame (:201-216)
                     self.slide_window()
                     self.events.append("fill")
-                    return None
+                    return False
             self._initial_frame = True              # initialStructure() succeeded (:188-206): no failureDetection on this frame
             self.solver_flag = self.NON_LINEAR
         else:
             self._initial_frame = False
-        # solveOdometry (:492-503)
-        self.f.triangulate(self.Ps, self.Rs, self.tic, self.ric)
-        return self.make_window()
+        return True
 
     def end_image(self, res):
         """processImage after optimization(): double2vector's state, failureDetection -> reboot, slideWindow, removeFailures, the trajectory row"""
@@ -412,7 +449,7 @@ class SlidingWindowEstimator:
         for it in self.f.feature:                                             # clearDepth(-1) (:405-408, feature_manager.cpp:181-192)
             if self._used_f(it):
                 it.estimated_depth, it.lidar_depth_flag = -1.0, False
-        self.f.triangulate(self.Ps, self.Rs, np.zeros(3), self.ric)           # on the camera positions, no tic (:410-416)
+        self.triangulate_features(np.zeros(3))                                # on the camera positions, no tic (:410-416)
         s = x[-1]
         for i in range(WINDOW_SIZE + 1):                                      # :419-422
             if self.pre[i] is not None:
@@ -700,14 +737,14 @@ def _feed_measurements(est, seq, k):
         est.process_odometry(*seq["lidar"][k])
 
 
-def run_sequence(seq, opts, backend, n_frames=None, startup=None):
+def run_sequence(seq, opts, backend, n_frames=None, startup=None, triangulate=None):
     """Feed a make_sequence() dict through SlidingWindowEstimator; returns the estimator (trajectory, flags, summaries).
     startup=None: while the estimator is INITIAL (the first WINDOW_SIZE + 1 frames, and again after a failureDetection reboot) the frames take
     seq["init"] (a state already initialised). startup=dict(make_sfm_frames kwargs): the window fills from a zero state and visualInitialAlign
     (SfM stand-in + VisualIMUAlignment on the back-end) initialises it. startup=dict(source="device", construct kwargs): the same, but the frames come from
     the estimator's initial_structure (relativePose, the frame chain and the full BA on the device) and not from the stand-in that reads ground truth; a
-    failed structure or alignment slides the window and the next frame tries again."""
-    est = SlidingWindowEstimator(opts, backend)
+    failed structure or alignment slides the window and the next frame tries again. triangulate: the estimator's (a callable tables -> results)."""
+    est = SlidingWindowEstimator(opts, backend, triangulate)
     device = startup is not None and startup.get("source", "truth") == "device"
     if startup is not None:
         startup = {k: v for k, v in startup.items() if k != "source"}
@@ -738,14 +775,16 @@ class _SlotBackend:
         self.drop_prior = True
 
 
-def run_sequences_lockstep(seqs, opts, solver, n_frames=None, on_frame=None):
+def run_sequences_lockstep(seqs, opts, solver, n_frames=None, on_frame=None, triangulate=None):
     """len(seqs) independent sequence segments, one SlidingWindowEstimator each, stepped frame by frame as ONE device batch: per frame one
     vilf_batch_upload of the segments' windows (slot i = segment i, so every segment's prior stays in its slot on the device), one
     vilf_batch_solve, one vilf_batch_marginalize, one download. A segment that has no window to solve in a frame (its window is still
     filling, at the start or after a failureDetection reboot) contributes its previous window as a placeholder whose result is dropped; its
-    slot's prior is cleared before its next real solve. Returns the estimators; `solver.lockstep_stats` counts the marginalization paths."""
+    slot's prior is cleared before its next real solve. triangulate (a callable tables -> results, BackendSolver.triangulate_features): the segments that solve
+    in a frame are triangulated by ONE call of it, in front of the one upload; without it every segment runs the host loop. Returns the estimators;
+    `solver.lockstep_stats` counts the marginalization paths."""
     S = len(seqs)
-    ests = [SlidingWindowEstimator(opts, _SlotBackend(solver, i)) for i in range(S)]
+    ests = [SlidingWindowEstimator(opts, _SlotBackend(solver, i), triangulate) for i in range(S)]
     n = min(len(q["images"]) for q in seqs) if n_frames is None else n_frames
     for est, seq in zip(ests, seqs):
         est.process_imu(0.0, *seq["imu0"])
@@ -753,9 +792,19 @@ def run_sequences_lockstep(seqs, opts, solver, n_frames=None, on_frame=None):
     stats = dict(frames=0, new_prior=0, amm_cholesky=0, kept_cholesky=0, unchanged=0)
     for k in range(n):
         wins = [None] * S
+        ready = []
         for i, (est, seq) in enumerate(zip(ests, seqs)):
             _feed_measurements(est, seq, k)
-            wins[i] = est.begin_image(seq["images"][k], seq["stamps"][k], seq["init"][k] if est.solver_flag == est.INITIAL else None)
+            init = seq["init"][k] if est.solver_flag == est.INITIAL else None
+            if triangulate is None:
+                wins[i] = est.begin_image(seq["images"][k], seq["stamps"][k], init)
+            elif est.prepare_image(seq["images"][k], seq["stamps"][k], init):
+                ready.append(i)
+        if ready:                                       # solveOdometry's triangulation of every segment that solves in this frame: one call
+            res = triangulate([ests[i].f.triangulation_table(ests[i].Ps, ests[i].Rs, ests[i].tic, ests[i].ric) for i in ready])
+            for i, r in zip(ready, res):
+                ests[i].f.apply_triangulation(r["depth"])
+                wins[i] = ests[i].make_window()
         live = [i for i in range(S) if wins[i] is not None]
         if not live:
             continue
