@@ -37,6 +37,23 @@ int class_plan(const vilf_window_in &in, int *cls, int *cstart, int *ccount) {
     return VB_CHUNK * std::max(1, (longest + VB_CLS - 1) / VB_CLS);
 }
 
+// Row map of W: one row per feature whose depth is a variable, none for a constant one (its row would be all zeros). The reduce of k_solve_sb deals the k-steps of
+// four rows to its three waves in turn (k-step s on wave s % 3). Feature f stays on the wave it had when rows were features, (f >> 2) % 3, and every wave keeps its
+// features in ascending order, now packed four to a k-step: the j-th variable feature of wave c gets k-step c + 3 (j >> 2), k-slot j & 3. Where the waves' lists differ
+// in length the shorter ones end in padding rows (row_feat = -1: never written, zero). n_rows = 4 x k-steps; never more than F rounded up to 4, so the rows fit the
+// Fmax rows W always had. The kernels know nothing of this rule: they read f_wrow / row_feat / n_rows.
+int w_row_map(int F, int cap, const unsigned char *fconst, int *f_wrow, int *row_feat) {
+    int cnt[3] = {0, 0, 0}, nsteps = 0;
+    for (int k = 0; k < cap; k++) row_feat[k] = -1;
+    for (int f = 0; f < F; f++) {
+        if (fconst[f]) { f_wrow[f] = -1; continue; }
+        const int c = (f >> 2) % 3, j = cnt[c]++, s = c + 3 * (j >> 2);
+        f_wrow[f] = 4 * s + (j & 3); row_feat[4 * s + (j & 3)] = f;
+        nsteps = std::max(nsteps, s + 1);
+    }
+    return 4 * nsteps;
+}
+
 void quat_from_R(const double *m, double *q /*xyzw*/) {   // Eigen Quaterniond(Matrix3d)
     double t = m[0] + m[4] + m[8];
     if (t > 0) {
@@ -342,12 +359,13 @@ constexpr ArrayRow kBatchArrays[] = {
     // uploaded per window, in the order their copies are enqueued
     {D_POSE, 8, VB_POSE_LD, 0, 0, 0, A_WINDOW, D_POSE0}, {D_SB, 8, VB_SB_LD, 0, 0, 0, A_WINDOW, D_SB0}, {D_FEAT, 8, 0, 1, 0, 0, A_WINDOW, D_FEAT0},
     {D_FSTART, 4, 0, 1, 0, 0, A_WINDOW}, {D_FNOBS, 4, 0, 1, 0, 0, A_WINDOW}, {D_FFAC0, 4, 0, 1, 0, 0, A_WINDOW}, {D_FCONST, 1, 0, 1, 0, 0, A_WINDOW}, {D_PSSLOT, 4, 0, 0, 0, 1, A_WINDOW},
+    {D_FWROW, 4, 0, 1, 0, 0, A_WINDOW}, {D_ROWFEAT, 4, 0, 1, 0, 0, A_WINDOW},      // the row map of W (w_row_map)
     {D_FOBS0, 4, 0, 1, 0, 0, A_WINDOW_TD}, {D_PSOBS, 4, 0, 0, 0, 1, A_WINDOW_TD},      // observation indices: only the td factors of k_marg_prepare look an observation up
     {D_FACREC, 8, 0, 0, 0, 8, A_WINDOW}, {D_IMU, 8, VB_IMU_LD, 0, 0, 0, A_WINDOW}, {D_LIDAR, 8, VB_LIDAR_LD, 0, 0, 0, A_WINDOW}, {D_COV, 8, VB_COV_LD, 0, 0, 0, A_WINDOW},
     {D_OBSV, 8, 0, 0, 2, 0, A_WINDOW_TD}, {D_OBSTD, 8, 0, 0, 1, 0, A_WINDOW_TD}, {D_OBSROW, 8, 0, 0, 1, 0, A_WINDOW_TD},
     // uploaded whole, in that order
     {D_NFEAT, 4, 1, 0, 0, 0, A_SMALL}, {D_NFAC, 4, 1, 0, 0, 0, A_SMALL}, {D_EX, 8, VB_EX_LD, 0, 0, 0, A_SMALL}, {D_GR0, 8, 9, 0, 0, 0, A_SMALL}, {D_GP0, 8, 3, 0, 0, 0, A_SMALL},
-    {D_PAIROFF, 4, VB_PTAB, 0, 0, 0, A_SMALL}, {D_MFLAG, 4, 1, 0, 0, 0, A_SMALL}, {D_TD, 8, 1, 0, 0, 0, A_SMALL},
+    {D_PAIROFF, 4, VB_PTAB, 0, 0, 0, A_SMALL}, {D_MFLAG, 4, 1, 0, 0, 0, A_SMALL}, {D_TD, 8, 1, 0, 0, 0, A_SMALL}, {D_NROWS, 4, 1, 0, 0, 0, A_SMALL},
     // the two prior sets: live, and as uploaded (restored by vilf_batch_rewind after a marginalization)
     {D_PHDR, 4, VB_PRIOR_HDR, 0, 0, 0, A_PRIOR, D_PHDR0}, {D_PX0, 8, VB_PRIOR_X0_LD, 0, 0, 0, A_PRIOR, D_PX00}, {D_PJ, 8, VB_PRIOR_LD * VB_PRIOR_LD, 0, 0, 0, A_PRIOR, D_PJ0},
     {D_PR, 8, VB_PRIOR_LD, 0, 0, 0, A_PRIOR, D_PR0}, {D_PH, 8, VB_PRIOR_LD * VB_PRIOR_LD, 0, 0, 0, A_PRIOR, D_PH0}, {D_PG, 8, VB_PRIOR_LD, 0, 0, 0, A_PRIOR, D_PG0},
@@ -400,6 +418,7 @@ static void bind_batch_arrays(vilf_handle *h, const BatchDims &dm) {
     b.pose_init = d[D_POSE0].as<double>(); b.sb_init = d[D_SB0].as<double>(); b.feat_init = d[D_FEAT0].as<double>();
     b.ex = d[D_EX].as<double>(); b.gauge_R0 = d[D_GR0].as<double>(); b.gauge_P0 = d[D_GP0].as<double>(); b.td = d[D_TD].as<double>();
     b.f_start = d[D_FSTART].as<int>(); b.f_nobs = d[D_FNOBS].as<int>(); b.f_obs0 = d[D_FOBS0].as<int>(); b.f_fac0 = d[D_FFAC0].as<int>(); b.f_const = d[D_FCONST].as<uint8_t>();
+    b.f_wrow = d[D_FWROW].as<int>(); b.row_feat = d[D_ROWFEAT].as<int>(); b.n_rows = d[D_NROWS].as<int>();
     b.obs_vel = d[D_OBSV].as<double>(); b.obs_ctd = d[D_OBSTD].as<double>(); b.obs_row = d[D_OBSROW].as<double>(); b.ps_obs = d[D_PSOBS].as<int>(); b.ps_slot = d[D_PSSLOT].as<int>();
     b.pair_off = d[D_PAIROFF].as<int>(); b.facrec = d[D_FACREC].as<double>(); b.imu = d[D_IMU].as<double>(); b.lidar = d[D_LIDAR].as<double>();
     bind_prior_pointers(h);
@@ -544,11 +563,15 @@ void pack_window(const Upload &u, int w) {
     int *psobs = u.dims.est_td ? u.row<int>(D_PSOBS, w) : nullptr, *fobs0 = u.dims.est_td ? u.row<int>(D_FOBS0, w) : nullptr;
     uint8_t *fconst = u.row<uint8_t>(D_FCONST, w);
     const unsigned long long nul = 1ULL << 17;
+    // the flags and the feature maps first: a factor record carries its feature's row of W (bits 18 and up of the second flag word)
+    for (int f = 0; f < F; f++) fconst[f] = in.feature_const[f] ? 1 : 0;
+    int *fwrow = u.row<int>(D_FWROW, w);
+    *u.row<int>(D_NROWS, w) = w_row_map(F, (int)u.dims.F, fconst, fwrow, u.row<int>(D_ROWFEAT, w));
     for (int g = 0; g < pl.nslot; g++) { double *rec = &facrec[(size_t)g * 8]; for (int k = 0; k < 7; k++) rec[k] = 0.0; std::memcpy(&rec[7], &nul, 8); psslot[g] = 0; if (psobs) psobs[g] = 0; }
     int q = 0;                                            // factor index in feature-major order
     for (int f = 0; f < F; f++) {
         const int o0 = in.feature_obs_offset[f], o1 = in.feature_obs_offset[f + 1], s = in.feature_start_frame[f], cst = in.feature_const[f] ? 1 : 0;
-        feat[f] = in.para_feature[f]; fconst[f] = (uint8_t)cst; fstart[f] = s; fnobs[f] = o1 - o0; ffac0[f] = q;
+        feat[f] = in.para_feature[f]; fstart[f] = s; fnobs[f] = o1 - o0; ffac0[f] = q;
         if (fobs0) fobs0[f] = o0;
         const double *pi = in.obs_point + 3 * (size_t)o0;
         for (int t = o0 + 1; t < o1; t++, q++) {
@@ -558,7 +581,7 @@ void pack_window(const Upload &u, int w) {
             double *rec = &facrec[(size_t)pos * 8]; const double *pj = in.obs_point + 3 * (size_t)t;
             for (int k = 0; k < 3; k++) { rec[k] = pi[k]; rec[3 + k] = pj[k]; }
             const unsigned long long a = (unsigned long long)(unsigned)f | ((unsigned long long)(unsigned)q << 32);
-            const unsigned long long b2 = (unsigned long long)s | ((unsigned long long)j << 8) | ((unsigned long long)cst << 16);
+            const unsigned long long b2 = (unsigned long long)s | ((unsigned long long)j << 8) | ((unsigned long long)cst << 16) | (cst ? 0ULL : (unsigned long long)fwrow[f] << 18);
             std::memcpy(&rec[6], &a, 8); std::memcpy(&rec[7], &b2, 8);
         }
     }
@@ -696,6 +719,12 @@ extern "C" int vilf_batch_upload(vilf_handle *h, int B, const vilf_window_in *wi
     return VILF_OK;
 }
 
+// the row map of W as the upload builds it (w_row_map), for a window of F features with the given constant flags: f_wrow[F], row_feat[cap], returns n_rows. A test
+// hook (no handle, no device); not part of include/vilfusion.h.
+extern "C" int vilf_debug_w_row_map(int F, int cap, const unsigned char *feature_const, int *f_wrow, int *row_feat) {
+    if (F < 0 || cap < ((F + 3) & ~3) || !f_wrow || !row_feat || (F && !feature_const)) return VILF_ERR_INVALID_ARGUMENT;
+    return w_row_map(F, cap, feature_const, f_wrow, row_feat);
+}
 // the library's radix sort (vilf_sort.hip) through host buffers — a test hook (tests/test_scan2map.py compares it with a stable host sort); not part of include/vilfusion.h.
 // keys: n values of 4 (key64 == 0) or 8 bytes; the low `bits` bits are sorted, equal keys keep their order.
 extern "C" int vilf_debug_sort_pairs(vilf_handle *h, const void *keys, const int *vals, size_t n, int bits, int key64, void *keys_out, int *vals_out) {

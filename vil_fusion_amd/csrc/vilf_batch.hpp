@@ -3,6 +3,7 @@
 // Memory layout in HBM (all per-window arrays are [B][stride] with strides fixed per upload; the host's table of them, with sizes: kBatchArrays, vilf_api.hip):
 //   state      pose[B][11*7]  sb[B][11*9]  feat[B][Fmax]  ex[B][7]  td[B]   (+ *_init copies for rewind, cand_* trial point)
 //   features   f_start/f_nobs/f_fac0/f_const [B][Fmax]             (feature_manager order)
+//              f_wrow/row_feat [B][Fmax] n_rows[B]                  (the row of W of every feature whose depth is a variable, and back; constant ones have no row)
 //   factors    facrec[B][FACmax][8] / ps_slot[B][FACmax]           (one slot per (feature, later observation); the factors of a frame pair (i<j) are contiguous inside
 //                                                                   the list of the pair's wave class, the four class lists interleaved 56 slots at a time (VB_SLOT);
 //                                                                   unused slots carry a null record; ps_slot = index in feature-major order. The observation points
@@ -14,8 +15,8 @@
 //   lidar      lidar[B][10][7]
 //   prior      hdr[B][80] x0[B][24][9] J[B][160*160] r[B][160] H=J^T J [B][160*160] g=J^T r [B][160]   (two sets: live / as uploaded)
 //   workspace  facw[B][8][FACmax] (per factor: Ji^T Jf (6), Jf^T Jf, Jf^T r)  Hpp[B][66][36] (visual pose-pose blocks)
-//              W[B][Fmax][80] (H_pf rows zero-initialised at upload; the feature's frame range + column 66 = g_f are
-//              rewritten every linearization) hf gf [B][Fmax]
+//              W[B][Fmax][80] (one H_pf row per feature with a variable depth, at row f_wrow[f]; zero-initialised at every upload; the feature's frame
+//              range + column 66 = g_f are rewritten every linearization) hf gf [B][Fmax]
 //              imuH[B][10][900] imug[B][10][30] lidH[B][10][144] lidg[B][10][12] g[B][165]
 //              scale/diag/grad/gn[B][165+Fmax] st[B]
 #pragma once
@@ -184,18 +185,20 @@ struct VbBatch {
     // problem description
     const int *f_start, *f_nobs, *f_obs0, *f_fac0;
     const uint8_t *f_const;
+    const int *f_wrow, *row_feat, *n_rows;   // [B][Fmax], [B][Fmax], [B]: row of W of a feature (-1: constant depth, no row), feature of a row (-1: padding row), rows in use
+                                             // (a multiple of 4). Built by the upload (w_row_map, vilf_api.hip); the kernels rely on the tables alone
     const double *obs;      // unused, NULL: nothing is resident behind it (the points travel inside facrec); kept so that the kernel-argument layout stays
     const double *obs_vel, *obs_ctd, *obs_row;   // estimate_td only: [B][Omax][2] pixel velocity, [B][Omax] td at capture, [B][Omax] image row (ProjectionTdFactor, projection_td_factor.cpp:6-21)
     double *td;             // [B] para_Td
     int est_td; double tr_over_row, row_half;
     const int *ps_feat, *ps_obs, *ps_slot;   // ps_feat: unused, NULL (the feature index is part of facrec); ps_obs: estimate_td only
     const int *pair_off;
-    const double *facrec;   // [B][FACmax][8]: per pair-sorted factor {pts_i[3], pts_j[3], (feature | slot << 32), (frame_i | frame_j << 8 | const << 16)} — one
+    const double *facrec;   // [B][FACmax][8]: per pair-sorted factor {pts_i[3], pts_j[3], (feature | slot << 32), (frame_i | frame_j << 8 | const << 16 | null << 17 | row of W << 18)} — one
                             // coalesced 64-byte record instead of five dependent gathers
     const double *imu, *lidar;
     const int *sb_tab;      // k_solve_sb's gather index table (k_sb_table, built once per handle): SB_TAB_ROWS int4 rows x 256 threads
     const int *lut_imu, *lut_lid, *lut_vis;   // static scatter tables: source element -> LDS tile offset (or -1)
-    double *cf;             // [B][Fmax] per-feature Schur coefficient s_f / sqrt(h~_f'), then W_f . (S y)_p (k_solve_sb)
+    double *cf;             // [B][Fmax] per ROW of W: the Schur coefficient s_f / sqrt(h~_f') of the row's feature (0 for a padding row), then W_f . (S y)_p (k_solve_sb)
     const int *prior_hdr;
     const double *prior_x0, *prior_J, *prior_r, *prior_H, *prior_g;
     // workspace

@@ -714,7 +714,7 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
         if (tid >= VB_CHUNK) {
         } else if (q < nfac && !((ib >> 17) & 1)) {
             const double pts_i[3] = {ra[0], ra[1], ra[2]}, pts_j[3] = {ra[3], rb[0], rb[1]};
-            const int f = (int)(ia & 0xffffffffu), slot = (int)(ia >> 32), fi = (int)(ib & 0xff), fj = (int)((ib >> 8) & 0xff);
+            const int slot = (int)(ia >> 32), fi = (int)(ib & 0xff), fj = (int)((ib >> 8) & 0xff);
             const bool fc = ((ib >> 16) & 1) != 0;
             double r[2], Ji[12], Jj[12], Jf[2];
             projection_eval_pair<true>(s_pt + PT_LD * pair_index(fi, fj), s_ric, s_tic, pts_i, pts_j, fv, b.sqrt_info, r, Ji, Jj, Jf);
@@ -728,7 +728,7 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
                 const double jf0 = sw * Jf[0], jf1 = sw * Jf[1];
                 // 16-byte stores (the row's six doubles start at a multiple of 48 bytes, a record at a multiple of 64): 7 store instructions per lane instead of 14 —
                 // every lane of a wave writes to lines of its own, so the instruction count is what the memory pipeline sees
-                double2_t *Wr = reinterpret_cast<double2_t *>(W + (size_t)f * VB_WLD + 6 * fj);
+                double2_t *Wr = reinterpret_cast<double2_t *>(W + (size_t)(ib >> 18) * VB_WLD + 6 * fj);        // the feature's row of W rides in the record (f_wrow[f])
                 double2_t *fw = reinterpret_cast<double2_t *>(facw + (size_t)slot * VB_FACW);
 #pragma unroll
                 for (int c = 0; c < 6; c += 2) {
@@ -900,7 +900,7 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
     LSTAMP(6);
     // ---- per-feature Schur vectors: H_ff, g_f, anchor block of the H_pf row -------------------------------------------
     {
-        const int *f_nobs = b.f_nobs + (size_t)w * FM, *f_fac0 = b.f_fac0 + (size_t)w * FM;
+        const int *f_nobs = b.f_nobs + (size_t)w * FM, *f_fac0 = b.f_fac0 + (size_t)w * FM, *f_wrow = b.f_wrow + (size_t)w * FM;
         double *hf = b.hf + ww * FM, *gf = b.gf + ww * FM;
         for (int f = tid; f < F; f += NT) {
             if (f_const[f]) { hf[f] = 0; gf[f] = 0; continue; }
@@ -920,7 +920,7 @@ __device__ __forceinline__ int linearize_body(const VbBatch &b, int iteration_ze
                     for (int c = 0; c < 8; c++) acc[c] += v[u][c];
                 }
             }
-            double *Wr = W + (size_t)f * VB_WLD;
+            double *Wr = W + (size_t)f_wrow[f] * VB_WLD;
 #pragma unroll
             for (int c = 0; c < 6; c++) Wr[6 * f_start[f] + c] = acc[c];
             Wr[VB_NPOSE] = acc[7];                      // column 66 carries g_f through the Schur MFMA
@@ -1118,15 +1118,15 @@ __device__ __forceinline__ double block_sum_s(double v, double *s_red) {
 // U row f: columns 0..65 = c_f * S_p * W_f[p], column 66 = c_f * g_f (the rhs rides along as one more column), 67..79 = 0.
 // K (the features) is split over 4 wave groups; the two waves of a group (HALF = 0 / 1) own 8 / 7 of the 15 tile pairs — tile
 // indices are compile-time, so operands are plain register picks. Loads are unconditional, coalesced (zero-padded 80-wide rows,
-// rows >= F are zero) and prefetched three k-steps ahead with no arithmetic on them until they are consumed. Group results are
+// padding rows are zero) and prefetched three k-steps ahead with no arithmetic on them until they are consumed. Group results are
 // subtracted in fixed group order (bit-reproducible).
 template <int HALF>
-__device__ __forceinline__ void schur_mfma(const double *W, int F, const double *s_cf, const double *s_scale, double *s_T, double *s_y, int lane, int wave) {
+__device__ __forceinline__ void schur_mfma(const double *W, int NR, const double *s_cf, const double *s_scale, double *s_T, double *s_y, int lane, int wave) {
     constexpr int TA[15] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 4};
     constexpr int TB[15] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 3, 4};
     constexpr int NP = HALF ? 7 : 8, PB = HALF ? 8 : 0;
     const int c16 = lane & 15, grp = wave >> 1, g4 = lane >> 4;
-    const int nsteps = ((F + 3) & ~3) / 4;
+    const int nsteps = NR / 4;                    // NR rows of W (VbBatch::n_rows, a multiple of 4), s_cf per row
     double *s_t = s_T + SOLVE_OFF_RED;            // s_red of k_solve (free between its block sums): row 67 of the reduce
     double sc5[5];
 #pragma unroll
@@ -1157,7 +1157,7 @@ __device__ __forceinline__ void schur_mfma(const double *W, int F, const double 
         _Pragma("unroll") for (int i = 0; i < NP; i++) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(u[TA[PB + i]], u[TB[PB + i]], acc[i], 0, 0, 0); \
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          // nothing of the compiler's own in flight: the counts below are exact
-    SCHUR_ISSUE(grp, ra) SCHUR_ISSUE(grp + 4, rb)
+    if (nsteps > 0) { SCHUR_ISSUE(grp, ra) SCHUR_ISSUE(grp + 4, rb) }         // (no row at all: every feature constant — no load, the clamp has nothing to clamp to)
     for (int st = grp; st < nsteps; st += 12) {
         SCHUR_ISSUE(st + 8, rc) SCHUR_WAIT(10, ra) SCHUR_STEP(st, ra)
         if (st + 4 < nsteps) { SCHUR_ISSUE(st + 12, ra) SCHUR_WAIT(10, rb) SCHUR_STEP(st + 4, rb) }
@@ -1188,20 +1188,20 @@ __device__ __forceinline__ void schur_mfma(const double *W, int F, const double 
     }
 }
 
-// dot(W~_f[0..65], vec) for every feature, 16 lanes per feature (4 features per wave per round), coalesced 80-wide rows;
-// result per feature is written to out[f] (the caller ignores the entries of constant features). vec lives in LDS (>= 80 entries, 66.. = 0).
+// dot(W~[0..65], vec) for every row of W (NR = VbBatch::n_rows of them), 16 lanes per row (4 rows per wave per round), coalesced 80-wide rows;
+// the result of row k is written to out[k] (a feature's: out[f_wrow[f]]). vec lives in LDS (>= 80 entries, 66.. = 0).
 // Three rounds of rows in flight per wave, inline-asm loads with explicit vmcnt waits like the Schur reduce (plain loads are sunk to their uses
 // by the compiler and every round then waits out a global-load latency).
-__device__ __forceinline__ void feature_dots(const double *W, int F, const double *s_sv /*scale .* vec, 80 entries*/, double *out, int tid) {
+__device__ __forceinline__ void feature_dots(const double *W, int NR, const double *s_sv /*scale .* vec, 80 entries*/, double *out, int tid) {
+    if (NR <= 0) return;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c16 = lane & 15, g = lane >> 4;
     double sv[5];
 #pragma unroll
     for (int t5 = 0; t5 < 5; t5++) sv[t5] = s_sv[16 * t5 + c16];
-    const int Fk4 = (F + 3) & ~3;                       // rows F..Fk4-1 of W are zero (never written)
     double ra[5], rb[5], rc[5];
 #define FD_ISSUE(F0, R)                                                                                                            \
     {                                                                                                                              \
-        const double *Wr_ = W + (size_t)min((F0) + g, Fk4 - 1) * VB_WLD + c16;                                                    \
+        const double *Wr_ = W + (size_t)min((F0) + g, NR - 1) * VB_WLD + c16;                                                    \
         asm volatile("global_load_dwordx2 %0, %5, off\n\tglobal_load_dwordx2 %1, %5, off offset:128\n\t"                           \
                      "global_load_dwordx2 %2, %5, off offset:256\n\tglobal_load_dwordx2 %3, %5, off offset:384\n\t"                \
                      "global_load_dwordx2 %4, %5, off offset:512"                                                                  \
@@ -1210,20 +1210,19 @@ __device__ __forceinline__ void feature_dots(const double *W, int F, const doubl
 #define FD_WAIT(N, R) asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(R[0]), "+v"(R[1]), "+v"(R[2]), "+v"(R[3]), "+v"(R[4]) : : "memory");
 #define FD_STEP(F0, R)                                                                                                             \
     {                                                                                                                              \
-        const int f = (F0) + g;                                                                                                    \
+        const int k = (F0) + g;                                                                                                    \
         double acc = 0;                                                                                                            \
         _Pragma("unroll") for (int t5 = 0; t5 < 5; t5++) acc += R[t5] * sv[t5];                                                    \
-        if (!(f < F)) acc = 0;                                                                                                     \
         _Pragma("unroll") for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);                                           \
-        if (c16 == 0 && f < F) out[f] = acc;                                                                                       \
+        if (c16 == 0 && k < NR) out[k] = acc;                                                                                       \
     }
     constexpr int RS = 4 * SNW;                          // features per round of the workgroup
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     FD_ISSUE(4 * wave, ra) FD_ISSUE(4 * wave + RS, rb)
-    for (int f0 = 4 * wave; f0 < F; f0 += 3 * RS) {
+    for (int f0 = 4 * wave; f0 < NR; f0 += 3 * RS) {
         FD_ISSUE(f0 + 2 * RS, rc) FD_WAIT(10, ra) FD_STEP(f0, ra)
-        if (f0 + RS < F) { FD_ISSUE(f0 + 3 * RS, ra) FD_WAIT(10, rb) FD_STEP(f0 + RS, rb) }
-        if (f0 + 2 * RS < F) { FD_ISSUE(f0 + 4 * RS, rb) FD_WAIT(10, rc) FD_STEP(f0 + 2 * RS, rc) }
+        if (f0 + RS < NR) { FD_ISSUE(f0 + 3 * RS, ra) FD_WAIT(10, rb) FD_STEP(f0 + RS, rb) }
+        if (f0 + 2 * RS < NR) { FD_ISSUE(f0 + 4 * RS, rb) FD_WAIT(10, rc) FD_STEP(f0 + 2 * RS, rc) }
     }
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(ra[4]), "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]), "+v"(rb[4]),
                                         "+v"(rc[0]), "+v"(rc[1]), "+v"(rc[2]), "+v"(rc[3]), "+v"(rc[4]) : : "memory");
@@ -1239,7 +1238,7 @@ extern "C" __global__ __launch_bounds__(SNT) void k_solve(VbBatch b) {
     extern __shared__ double s_dyn[];
     double *s_T = s_dyn + SOLVE_OFF_T, *s_g = s_dyn + SOLVE_OFF_G, *s_diag = s_dyn + SOLVE_OFF_DIAG, *s_scale = s_dyn + SOLVE_OFF_SCALE;   // layout: vilf_kernels.hpp
     double *s_y = s_dyn + SOLVE_OFF_Y, *s_invd = s_dyn + SOLVE_OFF_INVD, *s_v = s_dyn + SOLVE_OFF_V, *s_red = s_dyn + SOLVE_OFF_RED;
-    double *s_cf = s_dyn + SOLVE_OFF_CF;      // 0 for constant features
+    double *s_cf = s_dyn + SOLVE_OFF_CF;      // per row of W; 0 for padding rows
     int *s_rng = (int *)(s_dyn + SOLVE_OFF_RNG);
     __shared__ int s_pcol[VB_P], s_pinv[VB_PRIOR_LD];
     __shared__ double s_dx[VB_PRIOR_LD];
@@ -1273,6 +1272,8 @@ extern "C" __global__ __launch_bounds__(SNT) void k_solve(VbBatch b) {
     const double *hf = b.hf + ww * FM, *gf = b.gf + ww * FM;
     const uint8_t *f_const = b.f_const + (size_t)w * FM;
     const int *f_start = b.f_start + (size_t)w * FM, *f_nobs = b.f_nobs + (size_t)w * FM;
+    const int *f_wrow = b.f_wrow + (size_t)w * FM, *row_feat = b.row_feat + (size_t)w * FM;
+    const int NR = b.n_rows[w];                                             // rows of W in use: one per feature whose depth is a variable, + padding rows (a multiple of 4)
     double *scale_g = b.scale + (size_t)w * (VB_P + FM), *diag_g = b.diag + (size_t)w * (VB_P + FM);
     double *grad_g = b.grad + (size_t)w * (VB_P + FM), *gn_g = b.gn + (size_t)w * (VB_P + FM);
     const double *g_in = b.g + ww * VB_P;
@@ -1410,15 +1411,11 @@ extern "C" __global__ __launch_bounds__(SNT) void k_solve(VbBatch b) {
 #pragma unroll
             for (int u = 0; u < 2; u++) {          // the per-feature scalars are re-read (this thread wrote them above): nothing stays live across the assembly
                 const int f = tid + u * SNT;
-                if (f < F) {
-                    double xf = 0.0;
-                    if (!f_const[f]) {
-                        const double sf = scale_g[VB_P + f], df = diag_g[VB_P + f], hfv = hf[f], gfv = gf[f];
-                        const double vf = sf * gfv / (df * df);
-                        part += sf * sf * hfv * vf * vf;
-                        xf = vf * (sf * sf * hfv + mu * df * df) / sf;
-                    }
-                    W[(size_t)f * VB_WLD + VB_NPOSE + 1] = xf;
+                if (f < F && !f_const[f]) {        // (a constant feature has no row of W; a padding row's column 67 is the zero of the upload)
+                    const double sf = scale_g[VB_P + f], df = diag_g[VB_P + f], hfv = hf[f], gfv = gf[f];
+                    const double vf = sf * gfv / (df * df);
+                    part += sf * sf * hfv * vf * vf;
+                    W[(size_t)f_wrow[f] * VB_WLD + VB_NPOSE + 1] = vf * (sf * sf * hfv + mu * df * df) / sf;
                 }
             }
             __threadfence_block();                 // the MFMA loader of every wave of this workgroup reads column 67 back from global memory after the barriers below
@@ -1432,17 +1429,17 @@ extern "C" __global__ __launch_bounds__(SNT) void k_solve(VbBatch b) {
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const int f = tid + u * SNT;
-            if (f < F) { double c = 0; if (!f_const[f]) { const double sf = scale_g[VB_P + f], df = diag_g[VB_P + f]; c = sf * rsqrt_nr(sf * sf * hf[f] + mu * df * df); } s_cf[f] = c; }
+            if (f < F && !f_const[f]) { const double sf = scale_g[VB_P + f], df = diag_g[VB_P + f]; s_cf[f_wrow[f]] = sf * rsqrt_nr(sf * sf * hf[f] + mu * df * df); }      // per ROW of W
         }
         if (tid < VB_NPAD) s_y[tid] = s_g[tid];
         __syncthreads();
         STAMP(1, 4);
         // ---- MFMA Schur reduce: H~_pp -= U^T U and rhs_p -= U^T t over the 5x5 pose tile block -------------------------
-        for (int f = F + tid; f < ((F + 3) & ~3); f += SNT) s_cf[f] = 0.0;
+        for (int k = tid; k < NR; k += SNT) if (row_feat[k] < 0) s_cf[k] = 0.0;       // padding rows
         if (tid < 80) s_red[tid] = 0.0;           // row 67 of the reduce: -(U^T U)[p][67] (s_red is free between the block sums)
         __syncthreads();
         __threadfence_block();
-        if (wave & 1) schur_mfma<1>(W, F, s_cf, s_scale, s_T, s_y, lane, wave); else schur_mfma<0>(W, F, s_cf, s_scale, s_T, s_y, lane, wave);
+        if (wave & 1) schur_mfma<1>(W, NR, s_cf, s_scale, s_T, s_y, lane, wave); else schur_mfma<0>(W, NR, s_cf, s_scale, s_T, s_y, lane, wave);
         if (tries == 0) {                         // every wave adds the cross term itself (same order in every wave: uniform and identical)
             double cr = ((lane < VB_NPOSE) ? s_v[lane] * s_red[lane] : 0.0) + ((lane + 64 < VB_NPOSE) ? s_v[lane + 64] * s_red[lane + 64] : 0.0);
             cr = vilf_wave_sum64(cr);
@@ -1582,7 +1579,7 @@ extern "C" __global__ __launch_bounds__(SNT) void k_solve(VbBatch b) {
     }
     if (tid < 80) s_v[tid] = (tid < VB_NPOSE) ? s_scale[tid] * s_y[tid] : 0.0;
     __syncthreads();
-    feature_dots(W, F, s_v, s_cf, tid);                                                      // s_cf <- W_f . (S y)_p
+    feature_dots(W, NR, s_v, s_cf, tid);                                                     // s_cf[row] <- W_row . (S y)_p
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < 2; u++) {
@@ -1591,7 +1588,7 @@ extern "C" __global__ __launch_bounds__(SNT) void k_solve(VbBatch b) {
         const double sf = scale_g[VB_P + f], df = diag_g[VB_P + f];
         const double hp = sf * sf * hf[f] + mu * df * df;
         const double gt = sf * gf[f];
-        const double y = (gt - sf * s_cf[f]) / hp;
+        const double y = (gt - sf * s_cf[f_wrow[f]]) / hp;
         gn_g[VB_P + f] = -df * y;
         gy += gt * y;
         gn2 += df * df * y * y;
@@ -1617,7 +1614,8 @@ extern "C" __global__ __launch_bounds__(SNT) void k_solve(VbBatch b) {
 //                     L_a = chol(D_a), B_a = L_a^-1 E_(a-1), D_(a-1) -= B_a^T B_a                      (the longest dependent chain of the kernel)
 //          waves 0-2: gather assembly of the dense block and the band — one thread per DESTINATION entry sums its <= 6 source elements in a fixed order
 //                     (the source index of every entry is arithmetic in the thread id; raw buffer loads, out of range = 0), scales, adds the LM term and stores: no atomics, no zero fill; v^T H~ v of the Cauchy point rides along —
-//                     then the MFMA Schur reduce of the inverse depths, K split over the three waves (15 lower 16x16 tiles of the 80-wide dense block each)
+//                     then the MFMA Schur reduce of the inverse depths, K split over the three waves (15 lower 16x16 tiles of the 80-wide dense block each).
+//                     K = the n_rows rows of W: a feature with constant depth has no row (VbBatch::f_wrow / row_feat / n_rows)
 //   P2b    the three partial U^T U are subtracted in wave order (fixed summation order); M_a = L_a^-1 and N_a = M_a B_(a+1)^T replace L_a / B_(a+1): every
 //          later use of the chain is a product, not a substitution
 //   P3     for a = 10..1: Y_a = M_a band_a - N_a Y_(a+1), all four waves, each owning a 16-column strip of the 76 band columns: the D layout of the fp64
@@ -1628,8 +1626,8 @@ extern "C" __global__ __launch_bounds__(SNT) void k_solve(VbBatch b) {
 //          to LDS, one thread per row factors the 4 x 4 diagonal block redundantly and solves its own strip, and the rank-4 update is ONE MFMA per
 //          tile; the inverted diagonal blocks are kept for P6
 //   P6     wave 0: block back substitution of the dense part, then the chain: u_a = M_a r_a - N_a u_(a+1), w_(a+1) = u_(a+1) - N_a^T w_a, x_a = M_a^T w_a;
-//          waves 1-3: W_f . (S y)_p of every feature meanwhile
-//   P7     feature back-substitution, Gauss-Newton step, dogleg scalars (as k_solve)
+//          waves 1-3: W_k . (S y)_p of every row of W meanwhile
+//   P7     feature back-substitution (a feature's dot through f_wrow), Gauss-Newton step, dogleg scalars (as k_solve)
 // Same arithmetic as a Cholesky of the whole system under another elimination order: results equal k_solve's to rounding.
 typedef unsigned int uint2_t __attribute__((ext_vector_type(2)));
 // raw buffer load of one double: ONE address register per load (32-bit byte offset against an SGPR descriptor) instead of a 64-bit pair, and an offset past the
@@ -1684,9 +1682,10 @@ __device__ __forceinline__ constexpr int sb_y_pb(int wv, int i) { constexpr int 
 
 // waves 0..2: U^T U of the feature rows, K split: wave wv takes the k-steps wv, wv + 3, ...
 //   dense columns 0..65 = W columns 0..65 (poses); 66..74 (SpeedBias[0]) = 0; 75 (rhs) = W column 66 (g_f); 76 (Cauchy row) = W column 67
-__device__ __forceinline__ void sb_feature_reduce(const double *W, const double *cf, int F, int wv, const double *s_scale, double4_t (&acc)[15], int lane) {
+//   NR rows of W (VbBatch::n_rows, a multiple of 4; cf per row): 15 MFMA per k-step of four rows, 15 NR / 4 per window over the three waves
+__device__ __forceinline__ void sb_feature_reduce(const double *W, const double *cf, int NR, int wv, const double *s_scale, double4_t (&acc)[15], int lane) {
     const int c16 = lane & 15, g4 = lane >> 4;
-    const int nsteps = ((F + 3) & ~3) / 4;
+    const int nsteps = NR / 4;
     if (wv >= nsteps) return;
     double sc5[5];
 #pragma unroll
@@ -1934,6 +1933,8 @@ __device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w) {
     double *cf = b.cf + (size_t)w * FM;
     const double *hf = b.hf + ww * FM, *gf = b.gf + ww * FM;
     const uint8_t *f_const = b.f_const + (size_t)w * FM;
+    const int *f_wrow = b.f_wrow + (size_t)w * FM, *row_feat = b.row_feat + (size_t)w * FM;
+    const int NR = b.n_rows[w];                                            // rows of W in use (a multiple of 4, <= Fmax): the features whose depth is a variable + padding rows
     double *scale_g = b.scale + (size_t)w * (VB_P + FM), *diag_g = b.diag + (size_t)w * (VB_P + FM);
     double *grad_g = b.grad + (size_t)w * (VB_P + FM), *gn_g = b.gn + (size_t)w * (VB_P + FM);
     const double *g_in = b.g + ww * VB_P;
@@ -2143,20 +2144,33 @@ __device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w) {
             if (td >= 96 && td < 96 + 9 * SB_NCH) { const int q = td - 96, a = q / 9 + 1, i = q - 9 * (a - 1); s_band[SB_BOFF(a) + i * SB_BSTR(a) + SB_BRHS(a)] = s_g[VB_NPOSE + 9 + q]; }
             // per-feature Schur coefficient and (first try) the Cauchy-point terms. Every wave writes ALL features (identical values): each wave then reads
             // back what it wrote itself — no cross-wave synchronisation while wave 3 runs the chain
-            for (int f = ln; f < ((F + 3) & ~3); f += 64) {
-                double c = 0.0, xf = 0.0;
-                if (f < F && !f_const[f]) {
-                    const double sf = scale_g[VB_P + f], df = diag_g[VB_P + f], hfv = hf[f], gfv = gf[f];
-                    const double hp = sf * sf * hfv + mu * df * df;
-                    c = sf * rsqrt_nr(hp);
-                    if (tries == 0) {
-                        const double vf = sf * gfv / (df * df);
-                        if (wave == 0) part += sf * sf * hfv * vf * vf;
-                        xf = vf * hp / sf;              // column 67 of W: c_f x_f with c_f^2 x_f = s_f v_f  =>  (U^T U)[p][76] = sum_f s_f v_f W~_f[p]
+            // By ROW of W (row_feat): a constant feature has none; a padding row keeps c = 0 and its column 67 stays the zero of the upload. Four rows of a lane per
+            // trip: their row_feat in one round trip, then the sixteen gathers through it in one more (unconditional, a padding row reads feature 0 and drops it)
+            for (int k0 = ln; k0 < NR; k0 += 256) {
+                int rf[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) rf[u] = row_feat[min(k0 + 64 * u, NR - 1)];
+                double sfu[4], dfu[4], hfu[4], gfu[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) { const int f = max(rf[u], 0); sfu[u] = scale_g[VB_P + f]; dfu[u] = diag_g[VB_P + f]; hfu[u] = hf[f]; gfu[u] = gf[f]; }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int k = k0 + 64 * u;
+                    if (k >= NR) break;
+                    double c = 0.0, xf = 0.0;
+                    if (rf[u] >= 0) {
+                        const double sf = sfu[u], df = dfu[u], hfv = hfu[u], gfv = gfu[u];
+                        const double hp = sf * sf * hfv + mu * df * df;
+                        c = sf * rsqrt_nr(hp);
+                        if (tries == 0) {
+                            const double vf = sf * gfv / (df * df);
+                            if (wave == 0) part += sf * sf * hfv * vf * vf;
+                            xf = vf * hp / sf;              // column 67 of W: c_f x_f with c_f^2 x_f = s_f v_f  =>  (U^T U)[p][76] = sum_f s_f v_f W~_f[p]
+                        }
                     }
+                    cf[k] = c;
+                    if (tries == 0 && rf[u] >= 0) W[(size_t)k * VB_WLD + VB_NPOSE + 1] = xf;
                 }
-                cf[f] = c;
-                if (tries == 0 && f < F) W[(size_t)f * VB_WLD + VB_NPOSE + 1] = xf;
             }
             __threadfence_block();
         }
@@ -2165,7 +2179,7 @@ __device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w) {
         double4_t acc15[15];
 #pragma unroll
         for (int i = 0; i < 15; i++) acc15[i] = double4_t{0, 0, 0, 0};
-        if (wave < 3) sb_feature_reduce(W, cf, F, wave, s_scale, acc15, ln);
+        if (wave < 3) sb_feature_reduce(W, cf, NR, wave, s_scale, acc15, ln);
 #ifdef VILF_STAMPS
         if (b.dbg && blockIdx.x == 0 && (tid & 63) == 0) b.dbg[32 + 16 + (tid >> 6)] = __builtin_readcyclecounter();
 #endif
@@ -2463,17 +2477,17 @@ __device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w) {
 #ifdef VILF_STAMPS
         if (b.dbg && blockIdx.x == 0 && tid == 0) b.dbg[32 + 9] = __builtin_readcyclecounter();
 #endif
-    } else if (F > 0) {
-        // waves 1..3: W~_f[0..65] . (S y)_p for every feature, 16 lanes per feature, three rounds of rows in flight (as feature_dots of k_solve)
+    } else if (NR > 0) {
+        // waves 1..3: W~[0..65] . (S y)_p for every ROW of W (cf[row]: P7 looks a feature's up through f_wrow), 16 lanes per row, three rounds of rows in
+        // flight (as feature_dots of k_solve)
         const int c16 = lane & 15, g = lane >> 4, w3 = wave - 1;
         double sv[5];
 #pragma unroll
         for (int t5 = 0; t5 < 5; t5++) sv[t5] = s_v[16 * t5 + c16];
-        const int Fk4 = (F + 3) & ~3;
         double ra[5], rb[5], rc[5];
 #define FD_ISSUE(F0, R)                                                                                                            \
         {                                                                                                                          \
-            const double *Wr_ = W + (size_t)min((F0) + g, Fk4 - 1) * VB_WLD + c16;                                                \
+            const double *Wr_ = W + (size_t)min((F0) + g, NR - 1) * VB_WLD + c16;                                                \
             asm volatile("global_load_dwordx2 %0, %5, off\n\tglobal_load_dwordx2 %1, %5, off offset:128\n\t"                       \
                          "global_load_dwordx2 %2, %5, off offset:256\n\tglobal_load_dwordx2 %3, %5, off offset:384\n\t"            \
                          "global_load_dwordx2 %4, %5, off offset:512"                                                              \
@@ -2482,20 +2496,19 @@ __device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w) {
 #define FD_WAIT(N, R) asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(R[0]), "+v"(R[1]), "+v"(R[2]), "+v"(R[3]), "+v"(R[4]) : : "memory");
 #define FD_STEP(F0, R)                                                                                                             \
         {                                                                                                                          \
-            const int f = (F0) + g;                                                                                                \
+            const int k = (F0) + g;                                                                                                \
             double dacc = 0;                                                                                                       \
             _Pragma("unroll") for (int t5 = 0; t5 < 5; t5++) dacc += R[t5] * sv[t5];                                               \
-            if (!(f < F)) dacc = 0;                                                                                                \
             _Pragma("unroll") for (int o = 8; o > 0; o >>= 1) dacc += __shfl_xor(dacc, o, 64);                                     \
-            if (c16 == 0 && f < F) cf[f] = dacc;                                                                                   \
+            if (c16 == 0 && k < NR) cf[k] = dacc;                                                                                   \
         }
         constexpr int RS = 4 * 3;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         FD_ISSUE(4 * w3, ra) FD_ISSUE(4 * w3 + RS, rb)
-        for (int f0 = 4 * w3; f0 < F; f0 += 3 * RS) {
+        for (int f0 = 4 * w3; f0 < NR; f0 += 3 * RS) {
             FD_ISSUE(f0 + 2 * RS, rc) FD_WAIT(10, ra) FD_STEP(f0, ra)
-            if (f0 + RS < F) { FD_ISSUE(f0 + 3 * RS, ra) FD_WAIT(10, rb) FD_STEP(f0 + RS, rb) }
-            if (f0 + 2 * RS < F) { FD_ISSUE(f0 + 4 * RS, rb) FD_WAIT(10, rc) FD_STEP(f0 + 2 * RS, rc) }
+            if (f0 + RS < NR) { FD_ISSUE(f0 + 3 * RS, ra) FD_WAIT(10, rb) FD_STEP(f0 + RS, rb) }
+            if (f0 + 2 * RS < NR) { FD_ISSUE(f0 + 4 * RS, rb) FD_WAIT(10, rc) FD_STEP(f0 + 2 * RS, rc) }
         }
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(ra[4]), "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]), "+v"(rb[4]),
                                             "+v"(rc[0]), "+v"(rc[1]), "+v"(rc[2]), "+v"(rc[3]), "+v"(rc[4]) : : "memory");
@@ -2523,11 +2536,12 @@ __device__ __forceinline__ void solve_sb_body(const VbBatch &b, int w) {
         gn2 += d * d * y * y;
     }
     for (int f = tid; f < F; f += SBT) {
-        if (f_const[f]) continue;
+        const int k = f_wrow[f];
+        if (k < 0) continue;                       // constant depth: no row of W, no step
         const double sf = scale_g[VB_P + f], df = diag_g[VB_P + f];
         const double hp = sf * sf * hf[f] + mu * df * df;
         const double gt = sf * gf[f];
-        const double y = (gt - sf * cf[f]) / hp;
+        const double y = (gt - sf * cf[k]) / hp;
         gn_g[VB_P + f] = -df * y;
         gy += gt * y;
         gn2 += df * df * y * y;
