@@ -287,6 +287,14 @@ int vilf_eval_projection(vilf_handle *h, const double *const *parameters, const 
 int vilf_eval_projection_td(vilf_handle *h, const double *const *parameters, const double pts_i[3], const double pts_j[3],
                             const double velocity_i[2], const double velocity_j[2], double td_i, double td_j, double row_i, double row_j,
                             double *residuals, double **jacobians);                          /* projection_td_factor.cpp:34 */
+/* IMUFactor::Evaluate. Contract of the inputs, for vilf_eval_imu, vilf_eval_imu_raw and the IMU factors of a window alike: the quaternions of the
+ * two poses are unit to within rounding, as Ceres delivers them after the local parameterization (a quaternion is inverted as the reference inverts
+ * it, conjugate / squaredNorm, and rotates as Eigen's does; nothing is re-normalised and no sign is flipped: q and -q give residuals of opposite
+ * sign in the rotation rows, a residual rotation past 180 degrees is taken as it comes). pre->covariance must have an inverse. It has none for an
+ * interval of no samples or with zero noise (the covariance is exactly zero) and for an interval of ONE sample (integration_base.h:109-118: the position
+ * rows of V are dt / 2 times its velocity rows, rank 12). sqrt_info of such a covariance is not defined: no error is returned, the 15 fixed elimination
+ * steps run, and the entries are not finite or not meaningful (an all-zero covariance gives NaN in the whole upper triangle), as are the whitened
+ * residual and Jacobians; the parts before sqrt_info (vilf_eval_imu_raw's residuals and jacobians) do not depend on it. */
 int vilf_eval_imu(vilf_handle *h, const double *const *parameters, const vilf_imu_preint *pre,
                   double *residuals, double **jacobians);                                   /* imu_factor.h:19 */
 /* the two parts of that product on their own (test hook): residuals / jacobians BEFORE the multiplication by sqrt_info (imu_factor.h:60-62, 86-173 without the

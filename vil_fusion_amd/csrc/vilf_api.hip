@@ -744,6 +744,26 @@ extern "C" int vilf_debug_sort_pairs(vilf_handle *h, const void *keys, const int
     hipFree(dk); hipFree(dk2); hipFree(dv); hipFree(dv2); hipFree(dt);
     return rc;
 }
+// k_imu_prep for n covariances through host buffers, launched as vilf_batch_upload launches it (four factors of 16 lanes per block) — a test hook (tests/test_imu_exact.py
+// compares every lane group and the tail with an exact sqrt_info); not part of include/vilfusion.h. cov: [n][225] row-major in, out: [n][225] = the IMU_SQRT block of each record.
+extern "C" int vilf_debug_imu_sqrt_info(vilf_handle *h, int n, const double *cov, double *out) {
+    if (!h || n <= 0 || !cov || !out) return VILF_ERR_INVALID_ARGUMENT;
+    HIPCHECK(h, hipSetDevice(h->device));
+    const size_t sn = (size_t)n;
+    double *d_cov = nullptr, *d_rec = nullptr;
+    int rc = VILF_OK;
+    if (hipMalloc(&d_cov, sn * 225 * 8) != hipSuccess || hipMalloc(&d_rec, sn * IMU_REC * 8) != hipSuccess) rc = VILF_ERR_DEVICE;
+    if (rc == VILF_OK && (hipMemcpyAsync(d_cov, cov, sn * 225 * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess || hipMemsetAsync(d_rec, 0, sn * IMU_REC * 8, h->stream) != hipSuccess)) rc = VILF_ERR_DEVICE;
+    if (rc == VILF_OK) {
+        hipLaunchKernelGGL(k_imu_prep, dim3((unsigned)((n + 3) / 4)), dim3(IMU_PREP_NT), 0, h->stream, n, d_cov, (double *)nullptr, d_rec);
+        if (hipGetLastError() != hipSuccess) rc = VILF_ERR_DEVICE;
+    }
+    std::vector<double> rec(sn * IMU_REC);
+    if (rc == VILF_OK && (hipMemcpyAsync(rec.data(), d_rec, sn * IMU_REC * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)) rc = VILF_ERR_DEVICE;
+    if (rc == VILF_OK) for (size_t i = 0; i < sn; i++) std::memcpy(out + i * 225, &rec[i * IMU_REC + IMU_SQRT], 225 * 8);
+    hipFree(d_cov); hipFree(d_rec);
+    return rc;
+}
 // dynamic LDS the window kernels are launched with (bytes): [0] k_linearize / k_linearize_split / k_linearize_last, [1] k_solve_sb; [2], the larger of the two, is
 // kept for callers that read three values. Diagnostic (bench.py quotes them beside the registers it reads from the code objects); not part of include/vilfusion.h.
 extern "C" int vilf_debug_lds_bytes(vilf_handle *h, int out3[3]) {
