@@ -1086,6 +1086,101 @@ typedef struct vilf_tri_result { int n_used, n_candidates, n_reset, n_nonfinite;
 int vilf_features_triangulate(vilf_handle *h, int n_windows, const vilf_tri_window *windows, vilf_tri_result *out);
 /* vilf_set_profiling: the time and the number of the kernel launches (two per call that has a candidate) since the switch was set */
 int vilf_features_profile(vilf_handle *h, double ms_out[1], long launches_out[1]);
+
+/* ---- Camera-IMU rotation calibration (≙ InitialEXRotation::CalibrationExRotation, initial/initial_ex_rotation.cpp:11-67, with solveRelativeR :69-99,
+ *      testTriangulation :101-125 and decomposeE :127-142; called from estimator.cpp:159-175 while ESTIMATE_EXTRINSIC is 2; device) ----
+ * The on-line calibration of the camera-IMU rotation ric before any structure exists: every new frame hands in the correspondences of the last two frames and the
+ * pre-integrated rotation between them; the calibrator keeps the history of all frames and solves q_c (x) q_ic = q_ic (x) q_imu for q_ic over the whole history.
+ * The reference calls cv::findFundamentalMat, cv::SVD, cv::triangulatePoints and Eigen's JacobiSVD; none is available, so this text fixes the arithmetic
+ * (deviations: DESIGN.md §3r), tests/exrot_reference.py restates it in numpy and the kernels agree with that to the bit. Everything is fp64, each operation
+ * rounded on its own; a NaN compares false everywhere; "-(x)" negates the rounded x. Matrices are row-major; quaternion coefficients are ordered (x, y, z, w).
+ * A slot is one calibrator (one sequence, for example): its frame_count (the pushes so far), its ric (I after a reset) and the three histories Rc, Rimu, Rc_g, entry
+ * i = 1 .. frame_count. (The reference's entry 0, three identities, is never read.) A push into slot s with the correspondences (a_j, b_j), j = 0 .. m - 1, of the
+ * frames (frame_count - 1, frame_count) of the estimator, a_j in the older one, and delta_q:
+ *   solveRelativeR (:69-99) every coordinate of a_j and b_j is rounded to float32 (the reference goes through cv::Point2f); all that follows is fp64 on these values.
+ *                m < min_corres (9, :71) or m < 8: Rc = I, nothing is searched (VILF_EXROT_COUNT is not set). Otherwise the tracker's rejectWithF paragraphs
+ *                "sample", "8-point solve" and "score" word for word, as relativePose does, with n = m, x = a_j, x' = b_j, K = n_hypotheses (1 ..
+ *                VILF_TRACK_MAX_HYPOTHESES, default 512), the seed of the push = seed + (the slot's frame_count before the push) (uint32, wrapping) and
+ *                F_THRESHOLD = ransac_threshold, its square the fp64 product ransac_threshold * ransac_threshold. Winner = the valid hypothesis of the highest score,
+ *                ties to the lower k. The default ransac_threshold is 3.0: the reference calls cv::findFundamentalMat(ll, rr) with its default arguments (FM_RANSAC,
+ *                3.0, 0.99) on NORMALISED coordinates, where 3.0 is larger than any epipolar distance. Nearly every valid hypothesis then scores m and the lowest
+ *                valid k wins, which is what OpenCV's RANSAC does there too: the first valid sample has every point as an inlier and the iteration stops. A
+ *                caller who wants a search that rejects outliers passes something like 0.3 / 460. No valid hypothesis: Rc = I (VILF_EXROT_HYPOTHESIS is not set).
+ *                decomposition: E = the winner's F as it is; the recoverPose paragraph of relativePose up to R1, R2 and t = u3. Both determinants are +1 by
+ *                construction, so the reference's branch determinant(R1) + 1 < 1e-9 (E <- -E, :83-87) is dead here. An entry of R1, R2 or t that is not finite:
+ *                Rc = I (VILF_EXROT_FINITE is not set).
+ *   testTriangulation (:101-125) for (R, t') and pair j the depths z1, z2 of relativePose's cheirality paragraph (they replace cv::triangulatePoints on float
+ *                matrices: the same deviation as there). The pair is in front iff z1 > 0 and z2 > 0; there is no distance bound. The count runs over ALL m
+ *                correspondences, not over the inliers of the search (the reference passes ll, rr whole). front = (c(R1, t), c(R1, -t), c(R2, t), c(R2, -t));
+ *                under -t both depths are those under t, negated exactly. ans = R1 (chosen 0) iff max(front_0, front_1) > max(front_2, front_3), else R2
+ *                (chosen 1): the reference compares the ratios count / m, which share the denominator. Rc = ans^T (:92-95).
+ *   history      Rimu = R(delta_q) by the Q = R(q) formula of the PnP's paragraph "candidate" with (x, y, z, s) = delta_q; no normalisation, as in Eigen's
+ *                toRotationMatrix. Rc_g = ric^T Rimu ric with the slot's ric BEFORE this push, two products in this order: T_rc = (ric_0r Rimu_0c + ric_1r Rimu_1c)
+ *                + ric_2r Rimu_2c; Rc_g_rc = (T_r0 ric_0c + T_r1 ric_1c) + T_r2 ric_2c. (The reference writes ric.inverse(); ric is R(x)^T of a quaternion that is
+ *                unit to rounding, so the transpose is its inverse to rounding: a deviation.) frame_count + 1; (Rc, Rimu, Rc_g) become entry frame_count. Rc_g of
+ *                earlier pushes is never recomputed, as in the reference.
+ *   quat(M)      Eigen's matrix-to-quaternion (Quaterniond(Matrix3d)): tr = (M_00 + M_11) + M_22. If tr > 0: s = sqrt(tr + 1.0); w = 0.5 s; u = 0.5 / s;
+ *                x = (M_21 - M_12) u; y = (M_02 - M_20) u; z = (M_10 - M_01) u. Else i = 0; if M_11 > M_00: i = 1; if M_22 > M_ii: i = 2; j = (i + 1) mod 3,
+ *                k = (j + 1) mod 3; s = sqrt(((M_ii - M_jj) - M_kk) + 1.0); q_i = 0.5 s; u = 0.5 / s; w = (M_kj - M_jk) u; q_j = (M_ji + M_ij) u; q_k = (M_ki + M_ik) u,
+ *                with (q_0, q_1, q_2) = (x, y, z).
+ *   atan2p(y, x) for y, x >= 0, in + - * / sqrt only (see the PnP's "no sin / cos"): swapped = y > x; lo = swapped ? x : y, hi = swapped ? y : x; q = lo / hi, or 0.0
+ *                if hi == 0; three times q <- q / (1.0 + sqrt(1.0 + q q)); z = q q; s = c_15; then for n = 13, 11, 9, 7, 5, 3: s <- c_n - z s, with c_n the
+ *                fp64 quotient 1.0 / n; s <- 1.0 - z s; r = (q s) 8.0; the result is swapped ? 1.5707963267948966 - r : r.
+ *   weights      (:21-31) for EVERY entry i = 1 .. frame_count, every push: r1 = quat(Rc_i), r2 = quat(Rc_g_i), c = conj(r2) = (-x2, -y2, -z2, w2),
+ *                d = r1 * c: d_w = ((w1 w_c - x1 x_c) - y1 y_c) - z1 z_c; d_x = ((w1 x_c + x1 w_c) + y1 z_c) - z1 y_c; d_y = ((w1 y_c + y1 w_c) + z1 x_c) - x1 z_c;
+ *                d_z = ((w1 z_c + z1 w_c) + x1 y_c) - y1 x_c. angle_i = 57.29577951308232 (2.0 atan2p(sqrt((d_x d_x + d_y d_y) + d_z d_z), |d_w|)), Eigen 3.3's
+ *                angularDistance in degrees. weight_i = angle_i > huber_deg (5.0) ? huber_deg / angle_i : 1.0.
+ *   system       (:32-59) with (x, y, z, w) = quat(Rc_i): L = [w -z y x; z w -x y; -y x w z; -x -y -z w]; with (x, y, z, w) = quat(Rimu_i):
+ *                R = [w z -y x; -z w x y; y -x w z; -x -y -z w]; B_i = weight_i (L - R), a subtraction then a product per entry. G = A^T A of the 4 frame_count x 4
+ *                matrix A of the blocks B_i: g_pq, p <= q, is the sum from 0.0 over i ascending and within i over the rows r = 0 .. 3 of B_rp B_rq, a product and
+ *                an addition per term. Jacobi(G, 4) of the tracker's text. sigma_k = sqrt(g_kk) if g_kk > 0, else 0.0; they are reported sorted in descending
+ *                order. x = the column of V under the smallest g_kk (compared with <, ties and NaNs leave the lower index): the reference's svd.matrixV().col(3).
+ *                ric <- R(x)^T, ric_rc = Q_cr of the "candidate" formula with (x, y, z, s) = x, not normalised.
+ *   success      ok iff frame_count >= min_frames (10 = WINDOW_SIZE) and the third of the sorted sigmas > min_sigma (0.25): ric_cov(1) of :58-60. The slot keeps
+ *                its ric either way; calib_ric is the result's ric where ok is set.
+ *   bounds       at most VILF_EXROT_MAX_SLOTS slots; a slot's history holds at most VILF_EXROT_MAX_HISTORY entries. The reference's history grows without bound;
+ *                here a push into a full slot is an invalid argument and nothing is written: the caller resets. */
+#define VILF_EXROT_COUNT 1        /* flags of a push: m >= min_corres and m >= 8, the pair was searched */
+#define VILF_EXROT_HYPOTHESIS 2   /* a valid hypothesis exists */
+#define VILF_EXROT_FINITE 4       /* the decomposition is finite: Rc is solveRelativeR's, not the identity */
+#define VILF_EXROT_SOLVED 7
+#define VILF_EXROT_SKIPPED 8      /* the slot's pair had n = -1: nothing was pushed, the row only reports the slot's frame_count and ric */
+#define VILF_EXROT_MAX_SLOTS 256
+#define VILF_EXROT_MAX_HISTORY 256
+typedef struct vilf_exrot_params {
+    int n_hypotheses; unsigned seed;                          /* 512, 0 */
+    int min_corres, min_frames;                               /* 9, 10 */
+    double ransac_threshold, huber_deg, min_sigma;            /* 3.0, 5.0, 0.25 */
+} vilf_exrot_params;
+void vilf_exrot_default_params(vilf_exrot_params *p);
+typedef struct vilf_exrot_pair {
+    int n, pad_;                     /* the correspondences, 0 .. VILF_MAX_FEATURES; -1 skips the slot */
+    const double *a, *b;             /* [n][2] normalised image points of the older and of the newer frame (may be NULL with n <= 0) */
+    double delta_q[4];               /* the pre-integrated rotation between the two frames (x, y, z, w) */
+} vilf_exrot_pair;
+typedef struct vilf_exrot_result {
+    int frame_count, flags, count, best_k, score;   /* the slot's pushes after this one, VILF_EXROT_*, m (-1 skipped), the winning k or -1, its inliers */
+    int front[4];                    /* c(R1, t), c(R1, -t), c(R2, t), c(R2, -t) over all m */
+    int chosen, ok, pad_;            /* 0 = R1, 1 = R2, -1 = Rc is the identity; the success rule */
+    double Rc[9];                    /* what solveRelativeR returns */
+    double angle, weight;            /* of the newest entry, degrees */
+    double sigma[4], x[4], ric[9];   /* sorted in descending order; (x, y, z, w); the slot's ric after the push */
+} vilf_exrot_result;
+/* (re)creates n_slots calibrators on the handle: frame_count 0, ric = I, empty histories. Invalid argument, the existing calibrators kept: n_slots outside
+ * 1 .. VILF_EXROT_MAX_SLOTS. */
+int vilf_exrot_reset(vilf_handle *h, int n_slots);
+/* one push into every slot whose pair has n >= 0: one upload, one chain of three launches on the handle's stream (ex_hypotheses, ex_score, ex_solve: a workgroup
+ * per slot), the host waits once, one download. out [n_slots]. A slot's result does not depend on the other slots of the call, to the bit. Invalid argument, nothing
+ * written and no state changed: a null pointer (a or b with n > 0 included), n_slots outside 1 .. VILF_EXROT_MAX_SLOTS or other than the last vilf_exrot_reset's
+ * (or no reset yet), n < -1 or > VILF_MAX_FEATURES, a coordinate or a delta_q entry that is not finite, a pushed slot that already holds VILF_EXROT_MAX_HISTORY
+ * entries, n_hypotheses outside 1 .. VILF_TRACK_MAX_HYPOTHESES, a threshold, huber_deg or min_sigma that is not positive and finite, min_corres or min_frames < 0. */
+int vilf_exrot_push(vilf_handle *h, const vilf_exrot_params *p, int n_slots, const vilf_exrot_pair *pairs, vilf_exrot_result *out);
+/* the history of a slot: *count_out = frame_count, Rc, Rimu, Rc_g [count][9] and the angles and weights [count] of the slot's last push, entry i at row i - 1.
+ * Every array holds VILF_EXROT_MAX_HISTORY rows at the caller's and may be NULL. Invalid argument, nothing written: a null handle or count_out, no reset yet, a slot
+ * outside 0 .. n_slots - 1. */
+int vilf_exrot_get_history(vilf_handle *h, int slot, int *count_out, double *Rc_out, double *Rimu_out, double *Rcg_out, double *angle_out, double *weight_out);
+/* vilf_set_profiling: ex_hypotheses, ex_score, ex_solve of the pushes since the switch was set */
+int vilf_exrot_profile(vilf_handle *h, double ms_out[3], long launches_out[3]);
 #ifdef __cplusplus
 }
 #endif

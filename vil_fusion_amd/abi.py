@@ -279,6 +279,30 @@ VILF_TRI_MAX_WINDOWS = 4096
 TRI_LAYOUTS = {"vilf_tri_window": TriWindow, "vilf_tri_result": TriResult}
 
 
+class ExrotParams(C.Structure):
+    """vilf_exrot_params: K and seed of the search, the gates of solveRelativeR and CalibrationExRotation, the RANSAC threshold, the Huber angle, the sigma gate"""
+    _fields_ = [("n_hypotheses", C.c_int), ("seed", C.c_uint), ("min_corres", C.c_int), ("min_frames", C.c_int),
+                ("ransac_threshold", C.c_double), ("huber_deg", C.c_double), ("min_sigma", C.c_double)]
+
+
+class ExrotPair(C.Structure):
+    """vilf_exrot_pair: a slot's correspondences of the last two frames and the pre-integrated rotation between them; n = -1 skips the slot"""
+    _fields_ = [("n", C.c_int), ("pad_", C.c_int), ("a", c_double_p), ("b", c_double_p), ("delta_q", C.c_double * 4)]
+
+
+class ExrotResult(C.Structure):
+    """vilf_exrot_result: a slot's row of one push"""
+    _fields_ = [("frame_count", C.c_int), ("flags", C.c_int), ("count", C.c_int), ("best_k", C.c_int), ("score", C.c_int), ("front", C.c_int * 4),
+                ("chosen", C.c_int), ("ok", C.c_int), ("pad_", C.c_int), ("Rc", C.c_double * 9), ("angle", C.c_double), ("weight", C.c_double),
+                ("sigma", C.c_double * 4), ("x", C.c_double * 4), ("ric", C.c_double * 9)]
+
+
+VILF_EXROT_COUNT, VILF_EXROT_HYPOTHESIS, VILF_EXROT_FINITE, VILF_EXROT_SOLVED, VILF_EXROT_SKIPPED = 1, 2, 4, 7, 8
+VILF_EXROT_MAX_SLOTS, VILF_EXROT_MAX_HISTORY = 256, 256
+# the mirrors of the camera-IMU rotation calibration, for the layout check of tests/test_exrot_reference.py
+EXROT_LAYOUTS = {"vilf_exrot_params": ExrotParams, "vilf_exrot_pair": ExrotPair, "vilf_exrot_result": ExrotResult}
+
+
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""
     if a is None:

@@ -176,6 +176,7 @@ extern "C" void vilf_destroy(vilf_handle *h) {
     vilf_sfm_release(h);
     vilf_ba_release(h);
     vilf_tri_release(h);
+    vilf_exrot_release(h);
     for (auto &b : h->d) b.release();
     h->pin_up.release(); h->pin_down.release();
     if (h->ev0) hipEventDestroy(h->ev0);
@@ -932,6 +933,7 @@ extern "C" int vilf_set_profiling(vilf_handle *h, int on) {
     vilf_sfm_profile_reset(h);
     vilf_ba_profile_reset(h);
     vilf_tri_profile_reset(h);
+    vilf_exrot_profile_reset(h);
     return VILF_OK;
 }
 extern "C" int vilf_get_profile(vilf_handle *h, double ms_out[4], long launches_out[4]) {

@@ -649,6 +649,75 @@ def features_profile(solver):
     return list(ms), list(cnt)
 
 
+def exrot_default_params(**over):
+    """vilf_exrot_params with the reference's constants (initial_ex_rotation.cpp:30, :60, :71); keyword arguments replace fields (n_hypotheses=64, seed=3, ...)"""
+    p = abi.ExrotParams()
+    lib().vilf_exrot_default_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise TypeError(f"vilf_exrot_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def exrot_result_dict(r):
+    return dict(frame_count=r.frame_count, flags=r.flags, count=r.count, best_k=r.best_k, score=r.score, front=[int(v) for v in r.front], chosen=r.chosen,
+                ok=bool(r.ok), Rc=np.array(r.Rc).reshape(3, 3), angle=np.float64(r.angle), weight=np.float64(r.weight), sigma=np.array(r.sigma), x=np.array(r.x),
+                ric=np.array(r.ric).reshape(3, 3))
+
+
+class ExRotation:
+    """≙ InitialEXRotation (initial/initial_ex_rotation.cpp) for n_slots independent calibrators whose state lives on the device, in the handle of a BackendSolver
+    (vilf_exrot_*). params: fields of vilf_exrot_params. A handle holds one set of calibrators: creating a second ExRotation on the same solver resets the first."""
+
+    def __init__(self, solver, n_slots=1, **params):
+        self.s, self.n_slots = solver, int(n_slots)
+        self.params = exrot_default_params(**params)
+        self.reset()
+
+    def reset(self):
+        """frame_count 0, ric = I and an empty history in every slot"""
+        self.s._check(lib().vilf_exrot_reset(self.s._h, self.n_slots), "vilf_exrot_reset")
+
+    def push(self, pairs):
+        """pairs: per slot (a [m][2], b [m][2], delta_q [4] xyzw), the normalised points of the older and of the newer frame, or None to skip the slot.
+        Returns per slot a dict of the fields of vilf_exrot_result (ok: the calibration succeeded and ric is calib_ric)."""
+        pairs = list(pairs)
+        n = len(pairs)
+        arr = (abi.ExrotPair * max(n, 1))()
+        keep = []
+        for k, pr in enumerate(pairs):
+            if pr is None:
+                arr[k].n = -1
+                continue
+            a = np.ascontiguousarray(np.asarray(pr[0], dtype=np.float64).reshape(-1, 2))
+            b = np.ascontiguousarray(np.asarray(pr[1], dtype=np.float64).reshape(-1, 2))
+            if len(a) != len(b):
+                raise ValueError("a and b of a pair differ in length")
+            keep.append((a, b))
+            arr[k].n, arr[k].a, arr[k].b = len(a), abi.dptr(a), abi.dptr(b)
+            arr[k].delta_q[:] = [float(v) for v in np.asarray(pr[2], dtype=np.float64).reshape(4)]
+        out = (abi.ExrotResult * max(n, 1))()
+        self.s._check(lib().vilf_exrot_push(self.s._h, C.byref(self.params), n, arr, out), "vilf_exrot_push")
+        return [exrot_result_dict(out[k]) for k in range(n)]
+
+    def history(self, slot=0):
+        """dict(count, Rc, Rimu, Rcg [count][3][3], angle, weight [count]: of the slot's last push)"""
+        H = abi.VILF_EXROT_MAX_HISTORY
+        Rc, Rimu, Rcg, ang, wgt = np.zeros((H, 3, 3)), np.zeros((H, 3, 3)), np.zeros((H, 3, 3)), np.zeros(H), np.zeros(H)
+        cnt = C.c_int(0)
+        self.s._check(lib().vilf_exrot_get_history(self.s._h, int(slot), C.byref(cnt), abi.dptr(Rc), abi.dptr(Rimu), abi.dptr(Rcg), abi.dptr(ang), abi.dptr(wgt)),
+                      "vilf_exrot_get_history")
+        c = cnt.value
+        return dict(count=c, Rc=Rc[:c].copy(), Rimu=Rimu[:c].copy(), Rcg=Rcg[:c].copy(), angle=ang[:c].copy(), weight=wgt[:c].copy())
+
+    def profile(self):
+        """ms and launches of ex_hypotheses, ex_score, ex_solve since vilf_set_profiling"""
+        ms, cnt = (C.c_double * 3)(), (C.c_long * 3)()
+        self.s._check(lib().vilf_exrot_profile(self.s._h, ms, cnt), "vilf_exrot_profile")
+        return list(ms), list(cnt)
+
+
 def posegraph_optimize(solver, poses_qt, prior_sigma, edges, max_iterations=30, tol=1e-9):
     """≙ the gtsam graph + isam update of global_fusion (poseGraphOptimization.cpp:349-374, :560-587, :433-436) on the device
     (vilf_posegraph_optimize). poses_qt (n, 7) [qx qy qz qw tx ty tz]; edges: iterable of (i, j, q[4], t[3], sigma[6], robust).

@@ -31,6 +31,7 @@ EXPORTED = [
     "vilf_startup_default_sfm_params", "vilf_startup_sfm", "vilf_startup_get_structure", "vilf_startup_pnp", "vilf_startup_sfm_profile",
     "vilf_startup_default_ba_params", "vilf_startup_ba", "vilf_startup_construct", "vilf_startup_get_ba_structure", "vilf_startup_ba_profile",
     "vilf_features_triangulate", "vilf_features_profile",
+    "vilf_exrot_default_params", "vilf_exrot_reset", "vilf_exrot_push", "vilf_exrot_get_history", "vilf_exrot_profile",
 ]
 
 
@@ -185,6 +186,12 @@ def lib():
     L.vilf_startup_ba_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     L.vilf_features_triangulate.argtypes = [vp, C.c_int, C.POINTER(abi.TriWindow), C.POINTER(abi.TriResult)]
     L.vilf_features_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_exrot_default_params.argtypes = [C.POINTER(abi.ExrotParams)]
+    L.vilf_exrot_default_params.restype = None
+    L.vilf_exrot_reset.argtypes = [vp, C.c_int]
+    L.vilf_exrot_push.argtypes = [vp, C.POINTER(abi.ExrotParams), C.c_int, C.POINTER(abi.ExrotPair), C.POINTER(abi.ExrotResult)]
+    L.vilf_exrot_get_history.argtypes = [vp, C.c_int, ip, abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p]
+    L.vilf_exrot_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 

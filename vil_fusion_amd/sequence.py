@@ -99,6 +99,17 @@ class FeatureManager:
         du, dv = pi[0] / pi[2] - pj[0], pi[1] / pi[2] - pj[1]
         return max(0.0, float(np.sqrt(du * du + dv * dv)))
 
+    # feature_manager.cpp:129-148
+    def get_corresponding(self, l, r):
+        """getCorresponding(l, r): the features with start_frame <= l and end_frame >= r, in feature order -> (a [m][3], b [m][3]), their points at frame l and at
+        frame r"""
+        a, b = [], []
+        for it in self.feature:
+            if it.start_frame <= l and it.end_frame() >= r:
+                a.append(it.feature_per_frame[l - it.start_frame].point)
+                b.append(it.feature_per_frame[r - it.start_frame].point)
+        return np.array(a, dtype=np.float64).reshape(-1, 3), np.array(b, dtype=np.float64).reshape(-1, 3)
+
     def set_depth(self, x):
         k = -1
         for it in self.feature:
@@ -282,6 +293,13 @@ class SlidingWindowEstimator:
         self.n_reboots = 0
         self.initial_ok, self.alignment = None, None
         self.last_R = self.last_P = self.last_R0 = self.last_P0 = None
+        # ESTIMATE_EXTRINSIC (parameters.cpp): 2 = the camera-IMU rotation is calibrated on line before any structure exists (estimator.cpp:159-175). Like the
+        # reference's global it survives clearState, as do the calibrator and the calibrated rotation (RIC[0] = calib_ric, :171)
+        self.estimate_extrinsic = int(opts.estimate_extrinsic)
+        self.calib_ric = None
+        self.ex_calibrated = None       # (index of the process_image call, frame_count) at which the calibration succeeded
+        self.ex_rows = []               # the calibrator's row of every push
+        self._exrot = None
         self.clear_state()
 
     # estimator.cpp:36-88 (+ setParameter :24-34)
@@ -294,7 +312,8 @@ class SlidingWindowEstimator:
         self.pre = [None] * n
         self.lidar = [(np.array([0, 0, 0, 1.0]), np.zeros(3)) for _ in range(n)]
         self.g = np.array(opts.G[:])
-        self.ric = np.array(opts.RIC[:]).reshape(3, 3); self.tic = np.array(opts.TIC[:])
+        self.ric = np.array(opts.RIC[:]).reshape(3, 3) if self.calib_ric is None else self.calib_ric.copy()
+        self.tic = np.array(opts.TIC[:])
         self.td = 0.0
         self.f = FeatureManager()
         self.frame_count = 0
@@ -370,9 +389,15 @@ class SlidingWindowEstimator:
             self.Ps[j], self.Rs[j], self.Vs[j], self.Bas[j], self.Bgs[j] = [np.array(x, dtype=np.float64) for x in init_state]
             if self.pre[j] is not None:       # ≙ repropagate() with the start-up biases (initial_aligment.cpp / estimator.cpp:437-440)
                 self.pre[j].ba, self.pre[j].bg = self.Bas[j].copy(), self.Bgs[j].copy()
+        if self.estimate_extrinsic == 2 and j != 0:
+            self.calibrate_ex_rotation()
         if self.solver_flag == self.INITIAL:
             if j < WINDOW_SIZE:
                 self.frame_count += 1
+                self.events.append("fill")
+                return False
+            if self.estimate_extrinsic == 2:        # no initialStructure before the rotation is calibrated (:182): the window slides
+                self.slide_window()
                 self.events.append("fill")
                 return False
             if sfm_frames is not None:
@@ -472,6 +497,30 @@ class SlidingWindowEstimator:
         for i in range(fc + 1):
             self.Ps[i] = R0 @ self.Ps[i]; self.Rs[i] = R0 @ self.Rs[i]; self.Vs[i] = R0 @ self.Vs[i]
         return True
+
+    # estimator.cpp:159-175 (ESTIMATE_EXTRINSIC == 2): one push of the calibrator per image
+    def ex_rotation(self, pairs):
+        """the push: backend.ex_rotation(pairs) if the back-end has one, else an ExRotation (one slot) on the handle of the BackendSolver the back-end keeps as `s`;
+        there is no host path"""
+        if hasattr(self.backend, "ex_rotation"):
+            return self.backend.ex_rotation(pairs)
+        if self._exrot is None:
+            from .estimator import ExRotation
+            self._exrot = ExRotation(self.backend.s, 1)
+        return self._exrot.push(pairs)
+
+    def calibrate_ex_rotation(self):
+        j = self.frame_count
+        a, b = self.f.get_corresponding(j - 1, j)
+        off = synth.IMU_OFF["delta_q"][0]
+        dq = self.pre[j].row()[off:off + 4].copy() if self.pre[j] is not None else np.array([0.0, 0.0, 0.0, 1.0])
+        r = self.ex_rotation([(a[:, :2], b[:, :2], dq)])[0]      # solveRelativeR reads the first two coordinates (:76-77)
+        self.ex_rows.append(r)
+        if r["ok"]:
+            self.calib_ric = np.array(r["ric"], dtype=np.float64).reshape(3, 3)
+            self.ric = self.calib_ric.copy()
+            self.estimate_extrinsic = 1
+            self.ex_calibrated = (len(self.events), j)
 
     # estimator.cpp:461-490 (relativePose) on the device. Nothing calls it by default (initial_structure runs it through construct): the window fills from init_state or make_sfm_frames
     def relative_pose_table(self):
