@@ -1181,6 +1181,90 @@ int vilf_exrot_push(vilf_handle *h, const vilf_exrot_params *p, int n_slots, con
 int vilf_exrot_get_history(vilf_handle *h, int slot, int *count_out, double *Rc_out, double *Rimu_out, double *Rcg_out, double *angle_out, double *weight_out);
 /* vilf_set_profiling: ex_hypotheses, ex_score, ex_solve of the pushes since the switch was set */
 int vilf_exrot_profile(vilf_handle *h, double ms_out[3], long launches_out[3]);
+
+/* ---- Visual loop closure, first stage: key-frame BRIEF and matching (≙ KeyFrame::computeWindowBRIEFPoint, computeBRIEFPoint, searchByBRIEFDes and searchInAera,
+ * pose_graph/keyframe.cpp:75-171, with BRIEF::compute, pose_graph/ThirdParty/DVision/BRIEF.cpp:39-106; device) ----
+ * What a KeyFrame computes from its image, and the brute-force descriptor search between key frames, over a store of key frames that stays on the device. OpenCV is
+ * not available, so this text fixes the arithmetic itself, as the tracker's text does; tests/kf_reference.py restates it in numpy and the kernels agree with that
+ * on every integer and every float bit. Agreement with OpenCV's own rasters (GaussianBlur's fixed-point rounding, FAST's pixel order) is neither measured nor
+ * claimed. Candidate retrieval (detectLoop's DBoW2 query), PnP-RANSAC, the 4-DoF graph and the relocalisation factors are not part of this stage:
+ * the caller names the old key frames.
+ *   conventions  images are 8-bit, row-major, W x H, both sides > 21. R(i, n) is the tracker's reflect-101. Points are float32 (x, y) pixel coordinates, finite and
+ *                within 1e6 pixels of the origin (anything else is an invalid argument). >> is arithmetic. No floating point in blur, FAST or the search.
+ *   pattern      VILF_KF_BITS = 256 tests (x1_i, y1_i, x2_i, y2_i), int, given by the caller in the parameters (the reference reads config/brief_pattern.yml
+ *                through BriefExtractor). An entry with |v| > 64 is an invalid argument.
+ *   blur         stands for cv::GaussianBlur(9 x 9, sigma = 2) on 8-bit (BRIEF.cpp:60): integer and separable. Taps q = {7, 17, 32, 46, 52, 46, 32, 17, 7}
+ *                = rint(256 g_i) of the normalised Gaussian; they sum to 256. h(x, y) = sum_i q_i I(R(x + i - 4, W), y) (at most 65280: 16 bits);
+ *                v(x, y) = sum_i q_i h(x, R(y + i - 4, H)); blur(x, y) = (v + 32768) >> 16.
+ *   FAST         stands for cv::FAST(image, keypoints, 20, true) (keyframe.cpp:92), type 9-16, on the unblurred image; the threshold t is a parameter, 1 .. 254,
+ *                default 20. Circle c_k, k = 0 .. 15: (0,3) (1,3) (2,2) (3,1) (3,0) (3,-1) (2,-2) (1,-3) (0,-3) (-1,-3) (-2,-2) (-3,-1) (-3,0) (-3,1) (-2,2) (-1,3).
+ *                Tested pixels p: 3 <= x < W - 3, 3 <= y < H - 3. d_k = I(p) - I(p + c_k). A = the maximum over the 16 cyclic arcs of 9 consecutive k of the
+ *                minimum of d_k on the arc; B the same with -d_k. p is a corner iff max(A, B) > t; its score is max(A, B) - 1, the largest threshold at which it
+ *                is still a corner (1 .. 254). Every other pixel scores 0. A corner is kept iff its score is strictly greater than the scores of all eight
+ *                neighbours: two equal adjacent maxima both go. Key points are emitted in row-major order (y, then x), pt = (x, y) as float32.
+ *   descriptor   (BRIEF::compute) for a float32 point (px, py), on the blurred image. For test i: X1 = (int)(px + (float)x1_i), the addition in float32, the
+ *                conversion truncating toward zero (so -0.5 gives 0 and passes the range check, as in the reference); Y1, X2, Y2 likewise. Bit i is set iff
+ *                0 <= X1, X2 < W and 0 <= Y1, Y2 < H and blur(X1, Y1) < blur(X2, Y2). Layout: four uint64 words per descriptor, bit i in word i / 64 at
+ *                position i % 64. The window descriptors are those of the caller's point_2d_uv (sub-pixel points, any position); the key-point descriptors
+ *                are those of the FAST points.
+ *   lift         (keyframe.cpp:105-112) each FAST point through the tracker's undistortion text with the store's camera, rounded to float32: keypoints_norm.
+ *   match        (searchInAera, keyframe.cpp:121-150) for a window descriptor w of the current key frame and an old key frame with descriptors D_0 .. D_(m-1):
+ *                (dist, j) = the lexicographic minimum of (popcount(w ^ D_j), j) over the j with popcount(w ^ D_j) < match_max_dist (128: the reference's loop
+ *                with bestDist = 128 and a strict <). No such j (m = 0 included): index -1, distance match_max_dist, status 0. Otherwise status = 1 iff
+ *                dist < match_accept_dist (80). Outputs per (old key frame, window point): status, the old key point's pt and its lifted point ((0, 0) when
+ *                status is 0), j, dist; per old key frame the number of status 1. */
+#define VILF_KF_BITS 256
+#define VILF_KF_WORDS 4              /* uint64 words of a descriptor */
+#define VILF_KF_MAX_OFFSET 64        /* largest |v| of a pattern entry */
+#define VILF_KF_MATCH_CHUNK 256      /* kf_match: old descriptors per pass through LDS, 64 for each of the four waves (tests place their edge cases by it) */
+#define VILF_KF_MAX_CANDIDATES 256   /* old key frames of one vilf_kf_match */
+typedef struct vilf_kf_params {
+    int width, height;               /* COL, ROW */
+    int fast_threshold;              /* 1 .. 254; 20 (keyframe.cpp:90) */
+    int match_max_dist;              /* 0 .. 257; 128 (bestDist, keyframe.cpp:129) */
+    int match_accept_dist;           /* 0 .. 257; 80 (keyframe.cpp:142) */
+    int pad_;
+    double fx, fy, cx, cy;           /* PinholeCamera::Parameters, as vilf_track_params */
+    double k1, k2, p1, p2;
+    int x1[VILF_KF_BITS], y1[VILF_KF_BITS], x2[VILF_KF_BITS], y2[VILF_KF_BITS];
+} vilf_kf_params;
+/* the three thresholds at their defaults, everything else 0: the image size, the camera and the pattern are the caller's */
+void vilf_kf_default_params(vilf_kf_params *p);
+/* the store, hung off the handle and sized here: cap_keyframes key frames, cap_keypoints FAST points over all of them; every key frame has room for
+ * VILF_MAX_FEATURES window points. Invalid argument, the handle and an existing store untouched: a null pointer, a side <= 21, a capacity < 1, cap_keypoints > 2^30,
+ * a threshold outside its range, a pattern entry with |v| > VILF_KF_MAX_OFFSET, a focal length that is not positive, a camera parameter that is not finite.
+ * A second call drops the store and sizes a new one. */
+int vilf_kf_create(vilf_handle *h, const vilf_kf_params *p, int cap_keyframes, long cap_keypoints);
+/* a key frame from its image (rows row_stride bytes apart) and its window points window_uv [n_window][2] (point_2d_uv), 0 <= n_window <= VILF_MAX_FEATURES: blur,
+ * FAST, both sets of descriptors and the lift, all kept on the device. The host reads the number of FAST points once. *index_out = its index,
+ * *n_keypoints_out = its FAST points (either may be NULL). Invalid argument, the store as it was: no store, a null image, row_stride < width, n_window out of
+ * range, a null window_uv with n_window > 0, a window point outside the conventions, no free key frame, more FAST points than the free key points (never truncated). */
+int vilf_kf_add_keyframe(vilf_handle *h, const unsigned char *img, int row_stride, const float *window_uv, int n_window, int *index_out, int *n_keypoints_out);
+/* the "load previous keyframe" constructor (keyframe.cpp:44-72): a key frame from stored data, no image. keypoints, keypoints_norm [n_kp][2], descriptors
+ * [n_kp][4], window_uv [n_window][2], window_descriptors [n_window][4]; the values are stored as they are. Invalid argument, the store as it was: as above, n_kp < 0,
+ * a null array whose count is > 0. */
+int vilf_kf_add_loaded(vilf_handle *h, int n_kp, const float *keypoints, const float *keypoints_norm, const unsigned long long *descriptors,
+                       int n_window, const float *window_uv, const unsigned long long *window_descriptors, int *index_out);
+/* a stored key frame: *n_kp_out, *n_window_out and the arrays in the layouts above (any output may be NULL). cap_kp < its key points with a key-point array asked
+ * for, or cap_window < its window points with a window array asked for: invalid argument, nothing written. */
+int vilf_kf_get(vilf_handle *h, int index, int cap_kp, float *keypoints, float *keypoints_norm, unsigned long long *descriptors, int *n_kp_out,
+                int cap_window, float *window_uv, unsigned long long *window_descriptors, int *n_window_out);
+int vilf_kf_size(vilf_handle *h, int *n_out);
+/* searchByBRIEFDes (keyframe.cpp:152-171) of key frame cur's window descriptors in the key-point descriptors of n_old key frames (1 .. VILF_KF_MAX_CANDIDATES; an
+ * index may repeat and may be cur), all in one launch. With n = the window points of cur: status [n_old][n], pt_old, pt_old_norm [n_old][n][2], best_index,
+ * best_dist [n_old][n], n_matched [n_old] (any output may be NULL). Invalid argument, nothing written: no store, cur or an old index out of range, n_old out of
+ * range, a null old_index. */
+int vilf_kf_match(vilf_handle *h, int cur, int n_old, const int *old_index, unsigned char *status, float *pt_old, float *pt_old_norm, int *best_index,
+                  int *best_dist, int *n_matched);
+/* stateless pieces (they need the store's parameters and leave its key frames alone): the blurred image, rows tight; */
+int vilf_kf_blur(vilf_handle *h, const unsigned char *img, int row_stride, unsigned char *out);
+/* the FAST key points of an image in their order, pts_out [cap][2], score_out [cap] (the score byte of each; may be NULL), *n_out of them; more than cap points:
+ * invalid argument, nothing written (*n_out included); */
+int vilf_kf_fast(vilf_handle *h, const unsigned char *img, int row_stride, int cap, float *pts_out, unsigned char *score_out, int *n_out);
+/* the descriptors of n points [n][2] (0 .. 2^20) on the blur of an image -> desc_out [n][4] */
+int vilf_kf_brief(vilf_handle *h, const unsigned char *img, int row_stride, const float *pts, int n, unsigned long long *desc_out);
+/* vilf_set_profiling: upload + blur, FAST (score, row counts, scan, placement), descriptors + lift, match, download, summed over the calls since the switch was set */
+int vilf_kf_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
 #ifdef __cplusplus
 }
 #endif

@@ -302,6 +302,20 @@ VILF_EXROT_MAX_SLOTS, VILF_EXROT_MAX_HISTORY = 256, 256
 # the mirrors of the camera-IMU rotation calibration, for the layout check of tests/test_exrot_reference.py
 EXROT_LAYOUTS = {"vilf_exrot_params": ExrotParams, "vilf_exrot_pair": ExrotPair, "vilf_exrot_result": ExrotResult}
 
+VILF_KF_BITS, VILF_KF_WORDS, VILF_KF_MAX_OFFSET, VILF_KF_MATCH_CHUNK, VILF_KF_MAX_CANDIDATES = 256, 4, 64, 256, 256
+
+
+class KfParams(C.Structure):
+    """vilf_kf_params: the image size, FAST and match thresholds, the pinhole camera and the BRIEF pattern of the key-frame store"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("fast_threshold", C.c_int), ("match_max_dist", C.c_int), ("match_accept_dist", C.c_int), ("pad_", C.c_int),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double),
+                ("x1", C.c_int * VILF_KF_BITS), ("y1", C.c_int * VILF_KF_BITS), ("x2", C.c_int * VILF_KF_BITS), ("y2", C.c_int * VILF_KF_BITS)]
+
+
+# the mirror of the key-frame store, for the layout check of tests/test_keyframe_reference.py
+KF_LAYOUTS = {"vilf_kf_params": KfParams}
+
 
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""

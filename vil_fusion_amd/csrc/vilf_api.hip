@@ -177,6 +177,7 @@ extern "C" void vilf_destroy(vilf_handle *h) {
     vilf_ba_release(h);
     vilf_tri_release(h);
     vilf_exrot_release(h);
+    vilf_kf_release(h);
     for (auto &b : h->d) b.release();
     h->pin_up.release(); h->pin_down.release();
     if (h->ev0) hipEventDestroy(h->ev0);
@@ -934,6 +935,7 @@ extern "C" int vilf_set_profiling(vilf_handle *h, int on) {
     vilf_ba_profile_reset(h);
     vilf_tri_profile_reset(h);
     vilf_exrot_profile_reset(h);
+    vilf_kf_profile_reset(h);
     return VILF_OK;
 }
 extern "C" int vilf_get_profile(vilf_handle *h, double ms_out[4], long launches_out[4]) {

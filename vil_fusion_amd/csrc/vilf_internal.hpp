@@ -62,6 +62,7 @@ struct SfmCtx;
 struct BaCtx;
 struct TriCtx;
 struct ExrotCtx;
+struct KfCtx;
 
 // deep copy of a window snapshot (estimate_extrinsic / estimate_td: the batched entry points run the general single-window solve per slot and need the inputs again)
 struct OwnedWindow {
@@ -135,6 +136,7 @@ struct vilf_handle {
     SfmCtx *sfm = nullptr;                   // visual start-up, second stage: the windows, the frame rows and the structure (vilf_sfm.hip)
     BaCtx *ba = nullptr;                     // visual start-up, third stage: the start values, the BA's frames and structure (vilf_ba.hip)
     ExrotCtx *exrot = nullptr;               // camera-IMU rotation calibration: the slots' frame counts, ric and histories (vilf_exrot.hip)
+    KfCtx *kf = nullptr;                     // visual loop closure: the key-frame store (key points, lifted points, descriptors, window points) and its workspace (vilf_kf.hip)
     TriCtx *tri = nullptr;                   // feature triangulation: the packed candidates, the cameras and the depths (vilf_tri.hip)
 };
 
@@ -189,6 +191,8 @@ void vilf_tri_release(vilf_handle *h);
 void vilf_tri_profile_reset(vilf_handle *h);
 void vilf_exrot_release(vilf_handle *h);
 void vilf_exrot_profile_reset(vilf_handle *h);
+void vilf_kf_release(vilf_handle *h);
+void vilf_kf_profile_reset(vilf_handle *h);
 void vilf_sc_profile_reset(vilf_handle *h);                                 // vilf_set_profiling: the Scan Context spans start from zero
 int vilf_lw_chol_max_n();                                                      // largest n vilf_lw_chol_solve takes (its back substitution keeps the solution in LDS)
 int vilf_lw_chol_solve(vilf_handle *h, int n, double *S, double *y, int *info);   // blocked Cholesky solve on the handle's stream (vilf_lw.hip): S = [(n + 1) x n] row-major, row n = rhs

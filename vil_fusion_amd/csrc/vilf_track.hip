@@ -34,6 +34,7 @@
 #include "vilf_kernels.hpp"
 #include "vilf_sort.hpp"
 #include "vilf_fmat.hpp"
+#include "vilf_image.hpp"                 // tk_r, TkCam, tk_undistort: the reflected index and the undistortion text, shared with vilf_kf.hip
 
 #define TK_WIN 21
 #define TK_NPOS (TK_WIN * TK_WIN)
@@ -60,7 +61,6 @@ static inline TkList tk_list(void *base, int cap) {
 }
 // control words of one tracker (device): written by the kernels, never read by the host
 enum { TC_N = 0, TC_KEPT, TC_NMAX, TC_NCAND, TC_NID, TC_PREVN, TC_LAMMAX = 8 /* unsigned long long at ints 8, 9 */, TC_INTS = 16 };
-struct TkCam { double i11, i13, i22, i23, k1, k2, p1, p2; int distort; };
 // rejectWithF on the device: the lifted survivors and their rows in the list, control words (FC_*), F and valid flag per hypothesis, the result record
 // (best, inliers, F as 11 doubles)
 enum { FC_M = 0, FC_BEST = 2 /* unsigned long long at ints 2, 3: (score + 1) << 32 | (K - 1 - k); 0 = no valid hypothesis */, FC_INTS = 4 };
@@ -139,14 +139,6 @@ void vilf_track_release(vilf_handle *h) { if (h->trk) { h->trk->release(); delet
 namespace {
 #define TK_WSYNC __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier()
 
-// R(i, n): reflect-101, periodic with period 2 (n - 1); n >= 2
-VD int tk_r(int i, int n) {
-    if ((unsigned)i < (unsigned)n) return i;
-    const int p = 2 * (n - 1);
-    int m = i % p;
-    m += m < 0 ? p : 0;
-    return m < n ? m : p - m;
-}
 VD long long tk_wave_sum(long long v) {          // exact, so the order is free; every lane gets the total
     for (int o = 32; o > 0; o >>= 1) {
         const int lo = __shfl_xor((int)(unsigned)(v & 0xffffffffll), o), hi = __shfl_xor((int)(v >> 32), o);
@@ -174,20 +166,6 @@ VD int tk_bilinear(const unsigned char *I, int W, int H, int x, int y, const TkC
     const int x0 = tk_r(x, W), x1 = tk_r(x + 1, W);
     const unsigned char *r0 = I + (size_t)tk_r(y, H) * W, *r1 = I + (size_t)tk_r(y + 1, H) * W;
     return (c.w00 * (int)r0[x0] + c.w01 * (int)r0[x1] + c.w10 * (int)r1[x0] + c.w11 * (int)r1[x1] + 256) >> 9;
-}
-// the undistortion text in fp64: liftProjective of the float32 pixel p, before any rounding to float32
-VD void tk_undistort(const TkCam &cam, float2 p, double &ux, double &uy) {
-    const double mx = __dadd_rn(__dmul_rn(cam.i11, (double)p.x), cam.i13), my = __dadd_rn(__dmul_rn(cam.i22, (double)p.y), cam.i23);
-    ux = mx; uy = my;
-    if (cam.distort) {
-        for (int r = 0; r < 8; r++) {                // PinholeCamera::distortion (PinholeCamera.cc:646-662), every operation rounded on its own
-            const double x2 = __dmul_rn(ux, ux), y2 = __dmul_rn(uy, uy), xy = __dmul_rn(ux, uy), rho2 = __dadd_rn(x2, y2);
-            const double rad = __dadd_rn(__dmul_rn(cam.k1, rho2), __dmul_rn(__dmul_rn(cam.k2, rho2), rho2));
-            const double ddx = __dadd_rn(__dadd_rn(__dmul_rn(ux, rad), __dmul_rn(__dmul_rn(2.0, cam.p1), xy)), __dmul_rn(cam.p2, __dadd_rn(rho2, __dmul_rn(2.0, x2))));
-            const double ddy = __dadd_rn(__dadd_rn(__dmul_rn(uy, rad), __dmul_rn(__dmul_rn(2.0, cam.p2), xy)), __dmul_rn(cam.p1, __dadd_rn(rho2, __dmul_rn(2.0, y2))));
-            ux = __dsub_rn(mx, ddx); uy = __dsub_rn(my, ddy);
-        }
-    }
 }
 }  // namespace
 
@@ -767,13 +745,7 @@ TkF tk_f(TrackCtx *c) {
     f.F = (double *)(b + TKF_F); f.valid = (int *)(b + TKF_VALID); f.res = (double *)(b + TKF_RES);
     return f;
 }
-TkCam tk_cam(const vilf_track_params &p) {
-    TkCam cam;
-    cam.i11 = 1.0 / p.fx; cam.i13 = -p.cx / p.fx; cam.i22 = 1.0 / p.fy; cam.i23 = -p.cy / p.fy;
-    cam.k1 = p.k1; cam.k2 = p.k2; cam.p1 = p.p1; cam.p2 = p.p2;
-    cam.distort = (p.k1 != 0.0 || p.k2 != 0.0 || p.p1 != 0.0 || p.p2 != 0.0) ? 1 : 0;
-    return cam;
-}
+TkCam tk_cam(const vilf_track_params &p) { return ::tk_cam(p.fx, p.fy, p.cx, p.cy, p.k1, p.k2, p.p1, p.p2); }
 // rejectWithF on the pairs (cur[i], fwd[i]) whose status is set (the count on the device, or n_host): the outliers' status bytes are cleared. Fixed grids; the
 // kernels read the survivors' count themselves and leave at once when it is below 8
 int tk_reject(vilf_handle *h, TrackCtx *c, const float2 *cur, const float2 *fwd, unsigned char *status, const int *n_dev, int n_host) {

@@ -822,6 +822,142 @@ class ScanContext:
         return dict(zip(("sc_descriptor", "sc_ringkey_topk", "sc_distance", "sc_reduce"), ((ms[i], cnt[i]) for i in range(4))))
 
 
+KF_STAGES = ("upload_blur", "fast", "brief_lift", "match", "download")
+
+
+def kf_default_params(width, height, camera, pattern, **over):
+    """vilf_kf_params: camera = (fx, fy, cx, cy, k1, k2, p1, p2); pattern = (x1, y1, x2, y2), 256 integers each (the reference reads them from
+    config/brief_pattern.yml); keyword arguments replace fields (fast_threshold=20, match_max_dist=128, match_accept_dist=80)"""
+    p = abi.KfParams()
+    lib().vilf_kf_default_params(C.byref(p))
+    p.width, p.height = int(width), int(height)
+    assert len(camera) == 8, "camera = (fx, fy, cx, cy, k1, k2, p1, p2)"
+    p.fx, p.fy, p.cx, p.cy, p.k1, p.k2, p.p1, p.p2 = (float(v) for v in camera)
+    assert len(pattern) == 4 and all(len(a) == abi.VILF_KF_BITS for a in pattern), "pattern = (x1, y1, x2, y2), 256 entries each"
+    for name, a in zip(("x1", "y1", "x2", "y2"), pattern):
+        setattr(p, name, (C.c_int * abi.VILF_KF_BITS)(*(int(v) for v in a)))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"vilf_kf_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+class KeyFrameStore:
+    """Host mirror of what pose_graph's KeyFrame computes from an image (keyframe.cpp:75-118) and of searchByBRIEFDes (:121-171), over the device store of a
+    BackendSolver handle (vilf_kf_*). Images are (height, width) uint8 arrays, points (n, 2) float32 pixels, descriptors (n, 4) uint64 (bit i in word i // 64 at
+    position i % 64). The arithmetic is the contract in include/vilfusion.h. Candidate retrieval (DBoW2) is not here: the caller names the old key frames."""
+
+    def __init__(self, solver, width, height, camera, pattern, cap_keyframes=1024, cap_keypoints=1 << 20, params=None, **over):
+        self.s, self._L = solver, solver._L
+        self.params = params if params is not None else kf_default_params(width, height, camera, pattern, **over)
+        self.width, self.height = self.params.width, self.params.height
+        self.s._check(self._L.vilf_kf_create(self.s._h, C.byref(self.params), int(cap_keyframes), int(cap_keypoints)), "vilf_kf_create")
+
+    def _img(self, img):
+        a = np.asarray(img)
+        assert a.dtype == np.uint8 and a.ndim == 2 and a.shape == (self.height, self.width) and a.strides[1] == 1 and a.strides[0] >= self.width, (a.dtype, a.shape, a.strides)
+        return a
+
+    @staticmethod
+    def _u8(a):
+        return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    @staticmethod
+    def _fp(a):
+        return a.ctypes.data_as(C.POINTER(C.c_float))
+
+    @staticmethod
+    def _ip(a):
+        return a.ctypes.data_as(C.POINTER(C.c_int))
+
+    @staticmethod
+    def _u64(a):
+        return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+    @staticmethod
+    def _pts(p):
+        return np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 2)
+
+    @staticmethod
+    def _desc(d):
+        return np.ascontiguousarray(d, dtype=np.uint64).reshape(-1, abi.VILF_KF_WORDS)
+
+    def __len__(self):
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_kf_size(self.s._h, C.byref(n)), "vilf_kf_size")
+        return n.value
+
+    def add_keyframe(self, img, window_uv):
+        """computeWindowBRIEFPoint and computeBRIEFPoint for one image and its window points (point_2d_uv) -> (index, number of FAST key points)"""
+        a, w = self._img(img), self._pts(window_uv)
+        idx, nkp = C.c_int(-1), C.c_int(0)
+        self.s._check(self._L.vilf_kf_add_keyframe(self.s._h, self._u8(a), int(a.strides[0]), self._fp(w), len(w), C.byref(idx), C.byref(nkp)), "vilf_kf_add_keyframe")
+        return idx.value, nkp.value
+
+    def add_loaded(self, keypoints, keypoints_norm, descriptors, window_uv, window_descriptors):
+        """the "load previous keyframe" constructor (keyframe.cpp:44-72): a key frame from stored data -> index"""
+        kp, kn, d, w, wd = self._pts(keypoints), self._pts(keypoints_norm), self._desc(descriptors), self._pts(window_uv), self._desc(window_descriptors)
+        assert len(kp) == len(kn) == len(d) and len(w) == len(wd)
+        idx = C.c_int(-1)
+        self.s._check(self._L.vilf_kf_add_loaded(self.s._h, len(kp), self._fp(kp), self._fp(kn), self._u64(d), len(w), self._fp(w), self._u64(wd), C.byref(idx)), "vilf_kf_add_loaded")
+        return idx.value
+
+    def get(self, index):
+        """a stored key frame as a dict: keypoints, keypoints_norm (n, 2) float32, descriptors (n, 4) uint64, window_uv (m, 2) float32, window_descriptors (m, 4) uint64"""
+        nk, nw = C.c_int(0), C.c_int(0)
+        self.s._check(self._L.vilf_kf_get(self.s._h, int(index), 0, None, None, None, C.byref(nk), 0, None, None, C.byref(nw)), "vilf_kf_get")
+        k, m = nk.value, nw.value
+        kp, kn, w = (np.zeros((max(n, 1), 2), dtype=np.float32) for n in (k, k, m))
+        d, wd = (np.zeros((max(n, 1), abi.VILF_KF_WORDS), dtype=np.uint64) for n in (k, m))
+        self.s._check(self._L.vilf_kf_get(self.s._h, int(index), k, self._fp(kp), self._fp(kn), self._u64(d), None, m, self._fp(w), self._u64(wd), None), "vilf_kf_get")
+        return dict(keypoints=kp[:k], keypoints_norm=kn[:k], descriptors=d[:k], window_uv=w[:m], window_descriptors=wd[:m])
+
+    def searchByBRIEFDes(self, cur, olds):
+        """:152-171 for key frame cur against every old key frame of `olds`, in one launch -> dict of status (n_old, n) uint8, pt_old, pt_old_norm (n_old, n, 2)
+        float32, best_index, best_dist (n_old, n) int32, n_matched (n_old,) int32, with n the window points of cur"""
+        old = np.ascontiguousarray(olds, dtype=np.int32).reshape(-1)
+        nw = C.c_int(0)
+        self.s._check(self._L.vilf_kf_get(self.s._h, int(cur), 0, None, None, None, None, 0, None, None, C.byref(nw)), "vilf_kf_get")
+        n, k = nw.value, len(old)
+        rows = max(n * k, 1)
+        st = np.zeros(rows, dtype=np.uint8)
+        pt, ptn = np.zeros((rows, 2), dtype=np.float32), np.zeros((rows, 2), dtype=np.float32)
+        bi, bd, nm = np.zeros(rows, dtype=np.int32), np.zeros(rows, dtype=np.int32), np.zeros(max(k, 1), dtype=np.int32)
+        self.s._check(self._L.vilf_kf_match(self.s._h, int(cur), k, self._ip(old), self._u8(st), self._fp(pt), self._fp(ptn), self._ip(bi), self._ip(bd), self._ip(nm)), "vilf_kf_match")
+        return dict(status=st[:n * k].reshape(k, n), pt_old=pt[:n * k].reshape(k, n, 2), pt_old_norm=ptn[:n * k].reshape(k, n, 2), best_index=bi[:n * k].reshape(k, n),
+                    best_dist=bd[:n * k].reshape(k, n), n_matched=nm[:k])
+
+    def blur(self, img):
+        """the blurred image BRIEF reads (stateless)"""
+        a = self._img(img)
+        out = np.zeros((self.height, self.width), dtype=np.uint8)
+        self.s._check(self._L.vilf_kf_blur(self.s._h, self._u8(a), int(a.strides[0]), self._u8(out)), "vilf_kf_blur")
+        return out
+
+    def fast(self, img, cap=None):
+        """the FAST key points of an image (stateless) -> (points (n, 2) float32 in row-major order, scores (n,) uint8); more than cap points raise"""
+        a = self._img(img)
+        cap = self.width * self.height if cap is None else int(cap)
+        pts, sc = np.zeros((max(cap, 1), 2), dtype=np.float32), np.zeros(max(cap, 1), dtype=np.uint8)
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_kf_fast(self.s._h, self._u8(a), int(a.strides[0]), cap, self._fp(pts), self._u8(sc), C.byref(n)), "vilf_kf_fast")
+        return pts[:n.value].copy(), sc[:n.value].copy()
+
+    def brief(self, img, pts):
+        """the descriptors of points on the blur of an image (stateless) -> (n, 4) uint64"""
+        a, p = self._img(img), self._pts(pts)
+        out = np.zeros((max(len(p), 1), abi.VILF_KF_WORDS), dtype=np.uint64)
+        self.s._check(self._L.vilf_kf_brief(self.s._h, self._u8(a), int(a.strides[0]), self._fp(p), len(p), self._u64(out)), "vilf_kf_brief")
+        return out[:len(p)]
+
+    def profile(self):
+        """ms and spans of upload + blur, FAST, descriptors + lift, match, download since vilf_set_profiling was switched on"""
+        ms, cnt = (C.c_double * 5)(), (C.c_long * 5)()
+        self.s._check(self._L.vilf_kf_profile(self.s._h, ms, cnt), "vilf_kf_profile")
+        return dict(zip(KF_STAGES, ((ms[i], cnt[i]) for i in range(5))))
+
+
 ICP_MAP_KERNELS = ("gmap_xf_bbox", "gmap_leaf_keys", "radix_sort", "gmap_centroids")
 ICP_KERNELS = ("icp_bbox", "icp_leaf_keys", "radix_sort", "icp_voxel", "icp_cell_table", "icp_search", "icp_step", "unused")
 

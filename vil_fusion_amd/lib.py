@@ -32,6 +32,8 @@ EXPORTED = [
     "vilf_startup_default_ba_params", "vilf_startup_ba", "vilf_startup_construct", "vilf_startup_get_ba_structure", "vilf_startup_ba_profile",
     "vilf_features_triangulate", "vilf_features_profile",
     "vilf_exrot_default_params", "vilf_exrot_reset", "vilf_exrot_push", "vilf_exrot_get_history", "vilf_exrot_profile",
+    "vilf_kf_default_params", "vilf_kf_create", "vilf_kf_add_keyframe", "vilf_kf_add_loaded", "vilf_kf_get", "vilf_kf_size", "vilf_kf_match",
+    "vilf_kf_blur", "vilf_kf_fast", "vilf_kf_brief", "vilf_kf_profile",
 ]
 
 
@@ -192,6 +194,19 @@ def lib():
     L.vilf_exrot_push.argtypes = [vp, C.POINTER(abi.ExrotParams), C.c_int, C.POINTER(abi.ExrotPair), C.POINTER(abi.ExrotResult)]
     L.vilf_exrot_get_history.argtypes = [vp, C.c_int, ip, abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p]
     L.vilf_exrot_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    u64p = C.POINTER(C.c_uint64)
+    L.vilf_kf_default_params.argtypes = [C.POINTER(abi.KfParams)]
+    L.vilf_kf_default_params.restype = None
+    L.vilf_kf_create.argtypes = [vp, C.POINTER(abi.KfParams), C.c_int, C.c_long]
+    L.vilf_kf_add_keyframe.argtypes = [vp, u8p, C.c_int, fpp, C.c_int, ip, ip]
+    L.vilf_kf_add_loaded.argtypes = [vp, C.c_int, fpp, fpp, u64p, C.c_int, fpp, u64p, ip]
+    L.vilf_kf_get.argtypes = [vp, C.c_int, C.c_int, fpp, fpp, u64p, ip, C.c_int, fpp, u64p, ip]
+    L.vilf_kf_size.argtypes = [vp, ip]
+    L.vilf_kf_match.argtypes = [vp, C.c_int, C.c_int, ip, u8p, fpp, fpp, ip, ip, ip]
+    L.vilf_kf_blur.argtypes = [vp, u8p, C.c_int, u8p]
+    L.vilf_kf_fast.argtypes = [vp, u8p, C.c_int, C.c_int, fpp, u8p, ip]
+    L.vilf_kf_brief.argtypes = [vp, u8p, C.c_int, fpp, C.c_int, u64p]
+    L.vilf_kf_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 
