@@ -165,19 +165,7 @@ extern "C" void vilf_destroy(vilf_handle *h) {
     if (!h) return;
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
-    vilf_s2m_release(h);
-    vilf_feat_release(h);
-    vilf_pg_release(h);
-    vilf_lw_release(h);
-    vilf_sc_release(h);
-    vilf_icp_release(h);
-    vilf_track_release(h);
-    vilf_startup_release(h);
-    vilf_sfm_release(h);
-    vilf_ba_release(h);
-    vilf_tri_release(h);
-    vilf_exrot_release(h);
-    vilf_kf_release(h);
+    for (int s = 0; s < VILF_STAGE_COUNT; s++) vilf_stage_drop(h, s);
     for (auto &b : h->d) b.release();
     h->pin_up.release(); h->pin_down.release();
     if (h->ev0) hipEventDestroy(h->ev0);
@@ -904,7 +892,7 @@ extern "C" int vilf_batch_solve(vilf_handle *h, int sync) {
     hipLaunchKernelGGL(k_finalize, grid, dim3(WIN1_NT), 0, h->stream, h->batch);
     if (prof) {
         pev.push_back(vilf_prof_event(h)); ne++;
-        for (size_t i = 0; i < kinds.size(); i++) vilf_prof_span(h, pev[i], pev[i + 1], &h->kernel_ms[kinds[i]], &h->kernel_launches[kinds[i]]);
+        for (size_t i = 0; i < kinds.size(); i++) vilf_prof_span(h, pev[i], pev[i + 1], &h->kernel_prof.ms[kinds[i]], &h->kernel_prof.launches[kinds[i]]);
     }
     hipEventRecord(h->ev1, h->stream);
     HIPCHECK(h, hipGetLastError());
@@ -924,33 +912,13 @@ extern "C" int vilf_set_profiling(vilf_handle *h, int on) {
     // hipEventCreate is slow enough to starve the stream when it happens between launches (measured: 1.9 ms per frame for ~50 events): the pool is filled here
     if (on) { HIPCHECK(h, hipSetDevice(h->device)); while (h->prof_free.size() < 1024) { hipEvent_t e; HIPCHECK(h, hipEventCreate(&e)); h->prof_free.push_back(e); } }
     h->profiling = on;
-    for (int i = 0; i < 4; i++) { h->kernel_ms[i] = 0; h->kernel_launches[i] = 0; }
-    for (int i = 0; i < 8; i++) { h->s2m_ms[i] = 0; h->s2m_launches[i] = 0; }
-    for (int i = 0; i < 4; i++) { h->marg_ms[i] = 0; h->marg_launches[i] = 0; }
-    vilf_sc_profile_reset(h);
-    vilf_icp_profile_reset(h);
-    vilf_track_profile_reset(h);
-    vilf_startup_profile_reset(h);
-    vilf_sfm_profile_reset(h);
-    vilf_ba_profile_reset(h);
-    vilf_tri_profile_reset(h);
-    vilf_exrot_profile_reset(h);
-    vilf_kf_profile_reset(h);
+    h->kernel_prof.reset(); h->s2m_prof.reset(); h->marg_prof.reset();
+    for (VilfStage *s : h->stage) if (s) s->profile_reset();
     return VILF_OK;
 }
-extern "C" int vilf_get_profile(vilf_handle *h, double ms_out[4], long launches_out[4]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < 4; i++) { ms_out[i] = h->kernel_ms[i]; launches_out[i] = h->kernel_launches[i]; }
-    return VILF_OK;
-}
+extern "C" int vilf_get_profile(vilf_handle *h, double ms_out[4], long launches_out[4]) { return vilf_handle_profile(h, &vilf_handle::kernel_prof, ms_out, launches_out); }
 
-extern "C" int vilf_get_profile_marginalize(vilf_handle *h, double ms_out[4], long launches_out[4]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < 4; i++) { ms_out[i] = h->marg_ms[i]; launches_out[i] = h->marg_launches[i]; }
-    return VILF_OK;
-}
+extern "C" int vilf_get_profile_marginalize(vilf_handle *h, double ms_out[4], long launches_out[4]) { return vilf_handle_profile(h, &vilf_handle::marg_prof, ms_out, launches_out); }
 
 // a window whose kernel gave up a bounded device-side wait (VbState::dev_error): no numbers are handed out for it
 static int vb_check_dev_error(vilf_handle *h, const VbState *st, int first, int n) {
@@ -1172,12 +1140,10 @@ extern "C" int vilf_batch_marginalize(vilf_handle *h, int sync) {
     { const int rc = reserve_marg_workspace(h, sPool, to_other_set); if (rc != VILF_OK) return rc; }
     VbMarg &g = h->marg;
     const dim3 grid(h->B), block(VB_NT);
-    const bool prof = h->profiling != 0;
-    hipEvent_t mev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (prof) mev[0] = vilf_prof_event(h);
+    ProfMarks prof(h, h->marg_prof);
     if (h->batch.est_td) hipLaunchKernelGGL(k_marg_prepare_td, grid, block, 0, h->stream, h->batch, g);
     else hipLaunchKernelGGL(k_marg_prepare, grid, block, 0, h->stream, h->batch, g);
-    if (prof) mev[1] = vilf_prof_event(h);
+    prof.mark(0);
     hipLaunchKernelGGL(k_marg_schur, grid, block, MGS_FAST_LDS_BYTES, h->stream, h->batch, g,
                        std::getenv("VILF_MARG_FORCE_EXACT") ? 2 : 0);      // test hook: exercise the Jacobi path on well-conditioned windows too
     g.pool = (int)sPool;
@@ -1186,7 +1152,7 @@ extern "C" int vilf_batch_marginalize(vilf_handle *h, int sync) {
         hipLaunchKernelGGL(k_marg_schur, grid, block, MGS_EXACT_LDS_BYTES, h->stream, h->batch, g, 1);
     }
     g.pool_round = 0;
-    if (prof) mev[2] = vilf_prof_event(h);
+    prof.mark(1);
     // kept block: the Cholesky form of the new prior where the reference's 1e-8 truncation provably removes nothing (k_mf_chol; it marks the windows it has
     // finished, the launches below skip those), otherwise the
     // eigen-solver of the kept block in three launches (tred2 per workgroup, the QL recurrence of every window one lane each, rotation replay +
@@ -1219,14 +1185,11 @@ extern "C" int vilf_batch_marginalize(vilf_handle *h, int sync) {
         swap_prior_sets(h);
         h->prior_backup_valid = true;           // the other set now holds the priors as uploaded
     }
-    if (prof) mev[3] = vilf_prof_event(h);
+    prof.mark(2);
     hipLaunchKernelGGL(k_prior_prep, grid, block, PRIOR_PREP_LDS_BYTES, h->stream, h->batch, h->d[D_PH].as<double>(), h->d[D_PG].as<double>(), (unsigned)PRIOR_PREP_LDS_BYTES, (const int *)g.qlInfo);
-    if (prof) mev[4] = vilf_prof_event(h);
+    prof.mark(3);
     HIPCHECK(h, hipGetLastError());
-    if (prof) {
-        for (int k = 0; k < 4; k++) vilf_prof_span(h, mev[k], mev[k + 1], &h->marg_ms[k], &h->marg_launches[k]);
-        if (sync) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    }
+    if (h->profiling && sync) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
     for (int w = 0; w < h->B; w++) { h->prior_dev_newer[w] = 1; h->prior_dirty[w] = 0; }
     h->prior_restore_needed = true;
     if (sync) {

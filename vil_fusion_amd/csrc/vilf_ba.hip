@@ -50,24 +50,16 @@ static_assert(BA_LDS_BYTES <= 160 * 1024, "the BA's LDS fits a CU");
 static_assert(BA_MAXN <= 4 * BA_NT, "a thread takes at most four features");
 __global__ void su_sfm_ba(BaDev d, BaPar p);
 
-struct BaCtx {
-    DBuf in, out;
-    PinBuf up, down;
+struct BaCtx : VilfStage {
+    StageIO io;
     int last_windows = 0;
     size_t last_state = 0, last_pos = 0;                           // where the last call's download holds the state and the positions
-    double ms[1] = {0};
-    long launches[1] = {0};
+    StageProf<1> prof;
     bool attr = false;
-    void release() { in.release(); out.release(); up.release(); down.release(); }
+    void profile_reset() override { prof.reset(); }
 };
-void vilf_ba_profile_reset(vilf_handle *h) {
-    if (!h->ba) return;
-    h->ba->ms[0] = 0; h->ba->launches[0] = 0;
-}
-void vilf_ba_release(vilf_handle *h) { if (h->ba) { h->ba->release(); delete h->ba; h->ba = nullptr; } }
 
 namespace {
-VD double ba_dot3(double a0, double b0, double a1, double b1, double a2, double b2) { return __dadd_rn(__dadd_rn(__dmul_rn(a0, b0), __dmul_rn(a1, b1)), __dmul_rn(a2, b2)); }
 VD double ba_pair(double a0, double b0, double a1, double b1) { return __dadd_rn(__dmul_rn(a0, b0), __dmul_rn(a1, b1)); }
 
 // the paragraph "sums over features": the butterfly within the wave, then waves 0 + 1 + 2 + 3; red [4][K]. Thread e < K returns with the total of term e, the
@@ -90,7 +82,7 @@ template <int K> VD double ba_total(double (&v)[K], double *red, int tid) {
 VD void ba_obs(const double *P, const double *X, const double *u, double *J0, double *J1, double *P0, double *P1, double &e0, double &e1) {
     double q[3];
 #pragma unroll
-    for (int r = 0; r < 3; r++) q[r] = ba_dot3(P[r * 4], X[0], P[r * 4 + 1], X[1], P[r * 4 + 2], X[2]);
+    for (int r = 0; r < 3; r++) q[r] = vilf_dot3(P[r * 4], X[0], P[r * 4 + 1], X[1], P[r * 4 + 2], X[2]);
     const double p0 = __dadd_rn(q[0], P[3]), p1 = __dadd_rn(q[1], P[7]), p2 = __dadd_rn(q[2], P[11]);
     const double iz = __ddiv_rn(1.0, p2), xn = __dmul_rn(p0, iz), yn = __dmul_rn(p1, iz);
     e0 = __dsub_rn(xn, u[0]); e1 = __dsub_rn(yn, u[1]);
@@ -107,7 +99,7 @@ VD void ba_obs(const double *P, const double *X, const double *u, double *J0, do
 VD double ba_sq(const double *P, const double *X, const double *u) {
     double q[3];
 #pragma unroll
-    for (int r = 0; r < 3; r++) q[r] = ba_dot3(P[r * 4], X[0], P[r * 4 + 1], X[1], P[r * 4 + 2], X[2]);
+    for (int r = 0; r < 3; r++) q[r] = vilf_dot3(P[r * 4], X[0], P[r * 4 + 1], X[1], P[r * 4 + 2], X[2]);
     const double p0 = __dadd_rn(q[0], P[3]), p1 = __dadd_rn(q[1], P[7]), p2 = __dadd_rn(q[2], P[11]);
     const double iz = __ddiv_rn(1.0, p2), e0 = __dsub_rn(__dmul_rn(p0, iz), u[0]), e1 = __dsub_rn(__dmul_rn(p1, iz), u[1]);
     return ba_pair(e0, e0, e1, e1);
@@ -272,12 +264,12 @@ __global__ __launch_bounds__(BA_NT) void su_sfm_ba(BaDev d, BaPar p) {
 #pragma unroll
                         for (int a = 0; a < 6; a++)
 #pragma unroll
-                            for (int c = 0; c < 3; c++) Y[a][c] = ba_dot3(Wj[a][0], V0[c], Wj[a][1], V1[c], Wj[a][2], V2[c]);
+                            for (int c = 0; c < 3; c++) Y[a][c] = vilf_dot3(Wj[a][0], V0[c], Wj[a][1], V1[c], Wj[a][2], V2[c]);
 #pragma unroll
                         for (int a = 0; a < 6; a++) {
 #pragma unroll
-                            for (int b = 0; b < 6; b++) t[a * 6 + b] = __dadd_rn(t[a * 6 + b], ba_dot3(Y[a][0], Wk[b][0], Y[a][1], Wk[b][1], Y[a][2], Wk[b][2]));
-                            t[36 + a] = __dadd_rn(t[36 + a], ba_dot3(Y[a][0], gp[0], Y[a][1], gp[1], Y[a][2], gp[2]));
+                            for (int b = 0; b < 6; b++) t[a * 6 + b] = __dadd_rn(t[a * 6 + b], vilf_dot3(Y[a][0], Wk[b][0], Y[a][1], Wk[b][1], Y[a][2], Wk[b][2]));
+                            t[36 + a] = __dadd_rn(t[36 + a], vilf_dot3(Y[a][0], gp[0], Y[a][1], gp[1], Y[a][2], gp[2]));
                         }
                     }
                     const double tot = ba_total<BA_PAIR>(t, s_red + par * 4 * BA_PAIR, tid);
@@ -345,7 +337,7 @@ __global__ __launch_bounds__(BA_NT) void su_sfm_ba(BaDev d, BaPar p) {
 #pragma unroll
                     for (int r = 0; r < 3; r++) {
 #pragma unroll
-                        for (int c = 0; c < 3; c++) Pn[r * 4 + c] = ba_dot3(Q[r * 3], P[c], Q[r * 3 + 1], P[4 + c], Q[r * 3 + 2], P[8 + c]);
+                        for (int c = 0; c < 3; c++) Pn[r * 4 + c] = vilf_dot3(Q[r * 3], P[c], Q[r * 3 + 1], P[4 + c], Q[r * 3 + 2], P[8 + c]);
                         Pn[r * 4 + 3] = nk == 6 ? __dadd_rn(P[r * 4 + 3], s_x[ok + 3 + r]) : P[r * 4 + 3];
                     }
                 }
@@ -372,9 +364,9 @@ __global__ __launch_bounds__(BA_NT) void su_sfm_ba(BaDev d, BaPar p) {
                     }
                 }
                 const double *vi = s_vi + 6 * f;
-                s_posn[3 * f] = __dadd_rn(X[0], -ba_dot3(vi[0], s[0], vi[1], s[1], vi[2], s[2]));
-                s_posn[3 * f + 1] = __dadd_rn(X[1], -ba_dot3(vi[1], s[0], vi[3], s[1], vi[4], s[2]));
-                s_posn[3 * f + 2] = __dadd_rn(X[2], -ba_dot3(vi[2], s[0], vi[4], s[1], vi[5], s[2]));
+                s_posn[3 * f] = __dadd_rn(X[0], -vilf_dot3(vi[0], s[0], vi[1], s[1], vi[2], s[2]));
+                s_posn[3 * f + 1] = __dadd_rn(X[1], -vilf_dot3(vi[1], s[0], vi[3], s[1], vi[4], s[2]));
+                s_posn[3 * f + 2] = __dadd_rn(X[2], -vilf_dot3(vi[2], s[0], vi[4], s[1], vi[5], s[2]));
             }
             __syncthreads();
             // the candidate's cost
@@ -430,7 +422,7 @@ __global__ __launch_bounds__(BA_NT) void su_sfm_ba(BaDev d, BaPar p) {
 #pragma unroll
             for (int c = 0; c < 3; c++) { o->R[r * 3 + c] = P[r * 4 + c]; o->Q[r * 3 + c] = P[c * 4 + r]; }
             o->t[r] = P[r * 4 + 3];
-            o->T[r] = -ba_dot3(P[r], P[3], P[4 + r], P[7], P[8 + r], P[11]);
+            o->T[r] = -vilf_dot3(P[r], P[3], P[4 + r], P[7], P[8 + r], P[11]);
         }
     }
     for (int f = tid; f < BA_MAXN; f += BA_NT) { state_out[f] = s_state[f]; pos_out[3 * f] = s_pos[3 * f]; pos_out[3 * f + 1] = s_pos[3 * f + 1]; pos_out[3 * f + 2] = s_pos[3 * f + 2]; }
@@ -447,14 +439,13 @@ __global__ __launch_bounds__(BA_NT) void su_sfm_ba(BaDev d, BaPar p) {
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 namespace {
-size_t ba_align(size_t v) { return (v + 255) & ~(size_t)255; }
 // the BA's part of a download: the results, the frames, the state, the positions
 struct BaOut { size_t res, frames, state, pos, bytes; };
 BaOut ba_out(int W, size_t base) {
+    Layout l{base};
     BaOut o;
-    o.res = ba_align(base); o.frames = ba_align(o.res + (size_t)W * sizeof(vilf_startup_ba_result));
-    o.state = ba_align(o.frames + (size_t)W * BA_MAXF * sizeof(vilf_startup_ba_frame)); o.pos = ba_align(o.state + (size_t)W * BA_MAXN);
-    o.bytes = o.pos + (size_t)W * BA_MAXN * 24;
+    o.res = l.take((size_t)W * sizeof(vilf_startup_ba_result)); o.frames = l.take((size_t)W * BA_MAXF * sizeof(vilf_startup_ba_frame)); o.state = l.take((size_t)W * BA_MAXN);
+    o.pos = l.take((size_t)W * BA_MAXN * 24); o.bytes = l.at;
     return o;
 }
 bool ba_pos_fin(double v) { return std::isfinite(v) && v > 0; }
@@ -472,11 +463,9 @@ int ba_launch(vilf_handle *h, BaCtx *c, int W, const BaDev &d, const vilf_startu
         HIPCHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(su_sfm_ba), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BA_LDS_BYTES));
         c->attr = true;
     }
-    const bool prof = h->profiling != 0;
-    hipEvent_t ev[2];
-    if (prof) ev[0] = vilf_prof_event(h);
+    ProfMarks prof(h, c->prof);
     hipLaunchKernelGGL(su_sfm_ba, dim3(W), dim3(BA_NT), BA_LDS_BYTES, h->stream, d, ba_par(p));
-    if (prof) { ev[1] = vilf_prof_event(h); vilf_prof_span(h, ev[0], ev[1], &c->ms[0], &c->launches[0]); }
+    prof.mark(0);
     HIPCHECK(h, hipGetLastError());
     return VILF_OK;
 }
@@ -514,17 +503,18 @@ extern "C" int vilf_startup_ba(vilf_handle *h, const vilf_startup_ba_params *p, 
         if (!fin) { h->err = "vilf_startup_ba: a pose entry or a member's position that is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
     }
     HIPCHECK(h, hipSetDevice(h->device));
-    if (!h->ba) h->ba = new BaCtx();
-    BaCtx *c = h->ba;
+    BaCtx *c = vilf_stage_make<BaCtx>(h, ST_BA);
     c->last_windows = 0;
     const int W = n_windows;
     // upload: the windows' integers, l and chain_ok of every window, the poses, the positions, the state, then all points
-    const size_t o_l = (size_t)W * BA_WIN_INTS * 4, o_ok = o_l + (size_t)W * 4, o_pose = ba_align(o_ok + (size_t)W * 4), o_pos = o_pose + (size_t)W * BA_MAXF * 96,
-                 o_state = o_pos + (size_t)W * BA_MAXN * 24, o_pts = ba_align(o_state + (size_t)W * BA_MAXN), in_bytes = o_pts + std::max<size_t>(total, 1) * 16;
+    Layout li;
+    li.take((size_t)W * BA_WIN_INTS * 4, 4);
+    const size_t o_l = li.take((size_t)W * 4, 4), o_ok = li.take((size_t)W * 4, 4), o_pose = li.take((size_t)W * BA_MAXF * 96), o_pos = li.take((size_t)W * BA_MAXN * 24, 8),
+                 o_state = li.take((size_t)W * BA_MAXN, 1), o_pts = li.take(std::max<size_t>(total, 1) * 16), in_bytes = li.at;
     const BaOut o = ba_out(W, 0);
-    if (!c->in.ensure(in_bytes) || !c->out.ensure(o.bytes) || !c->up.ensure(in_bytes) || !c->down.ensure(o.bytes)) { h->err = "vilf_startup_ba: out of memory"; return VILF_ERR_DEVICE; }
+    if (!c->io.ensure(in_bytes, o.bytes)) { h->err = "vilf_startup_ba: out of memory"; return VILF_ERR_DEVICE; }
     {
-        char *ub = (char *)c->up.p;
+        char *ub = (char *)c->io.up.p;
         vilf_startup_pack_windows(W, windows, (int *)ub, (double *)(ub + o_pts));
         int *lw = (int *)(ub + o_l), *okw = (int *)(ub + o_ok);
         double *pose = (double *)(ub + o_pose), *pos = (double *)(ub + o_pos);
@@ -546,15 +536,15 @@ extern "C" int vilf_startup_ba(vilf_handle *h, const vilf_startup_ba_params *p, 
             }
         }
     }
-    HIPCHECK(h, hipMemcpyAsync(c->in.p, c->up.p, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, c->io.upload(h, in_bytes));
     BaDev d;
-    char *ib = c->in.as<char>(), *ob = c->out.as<char>();
+    char *ib = c->io.in.as<char>(), *ob = c->io.out.as<char>();
     d.win = (const int *)ib; d.l = (const int *)(ib + o_l); d.chain_ok = (const int *)(ib + o_ok); d.chain_stride = 1; d.pose = (const double *)(ib + o_pose); d.pose_stride = 12;
     d.pos = (const double *)(ib + o_pos); d.state = (const unsigned char *)(ib + o_state); d.pts = (const double *)(ib + o_pts);
     d.res = (vilf_startup_ba_result *)(ob + o.res); d.frames = (vilf_startup_ba_frame *)(ob + o.frames); d.state_out = (unsigned char *)(ob + o.state); d.pos_out = (double *)(ob + o.pos);
     { const int rcl = ba_launch(h, c, W, d, p); if (rcl != VILF_OK) return rcl; }
-    HIPCHECK(h, vilf_copy_sync(h, c->down.p, c->out.p, o.bytes, hipMemcpyDeviceToHost));
-    const char *hb = (const char *)c->down.p;
+    HIPCHECK(h, c->io.download(h, o.bytes));
+    const char *hb = (const char *)c->io.down.p;
     std::memcpy(out, hb + o.res, (size_t)W * sizeof(vilf_startup_ba_result));
     if (frames_out) std::memcpy(frames_out, hb + o.frames, (size_t)W * BA_MAXF * sizeof(vilf_startup_ba_frame));
     c->last_windows = W; c->last_state = o.state; c->last_pos = o.pos;
@@ -567,27 +557,25 @@ extern "C" int vilf_startup_construct(vilf_handle *h, const vilf_startup_sfm_par
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
     if (!sp || !bp || !windows || !rel || !out) { h->err = "vilf_startup_construct: null pointer"; return VILF_ERR_INVALID_ARGUMENT; }
     if (!ba_params_ok(bp)) { h->err = std::string("vilf_startup_construct") + BA_PARAMS_TEXT; return VILF_ERR_INVALID_ARGUMENT; }
-    if (!h->ba) h->ba = new BaCtx();
-    BaCtx *c = h->ba;
+    BaCtx *c = vilf_stage_make<BaCtx>(h, ST_BA);
     const int kept = c->last_windows;
     c->last_windows = 0;
     // the chain writes into this call's buffers, the BA's download lies behind the chain's: one copy brings both
     const int W = n_windows;
-    VilfSfmBufs bufs = {&c->in, &c->out, &c->up, &c->down};
     VilfSfmQueued q;
     const size_t extra = W >= 1 && W <= VILF_STARTUP_MAX_WINDOWS ? ba_out(W, 0).bytes + 256 : 0;
-    { const int rcq = vilf_sfm_enqueue(h, "vilf_startup_construct", sp, n_windows, windows, rel, bufs, extra, &q); if (rcq != VILF_OK) { if (rcq == VILF_ERR_INVALID_ARGUMENT) c->last_windows = kept; return rcq; } }   // refused: no buffer was touched
+    { const int rcq = vilf_sfm_enqueue(h, "vilf_startup_construct", sp, n_windows, windows, rel, &c->io, extra, &q); if (rcq != VILF_OK) { if (rcq == VILF_ERR_INVALID_ARGUMENT) c->last_windows = kept; return rcq; } }   // refused: no buffer was touched
     const BaOut o = ba_out(W, q.out_bytes);
     BaDev d;
-    char *ob = c->out.as<char>();
+    char *ob = c->io.out.as<char>();
     d.win = q.win; d.pts = q.pts; d.l = q.l;
     d.chain_ok = (const int *)q.res; d.chain_stride = (int)(sizeof(vilf_startup_structure) / 4);                          // vilf_startup_structure.ok comes first
     d.pose = (const double *)q.rows + offsetof(vilf_startup_frame, R) / 8; d.pose_stride = (int)(sizeof(vilf_startup_frame) / 8);
     d.state = q.state; d.pos = q.pos;
     d.res = (vilf_startup_ba_result *)(ob + o.res); d.frames = (vilf_startup_ba_frame *)(ob + o.frames); d.state_out = (unsigned char *)(ob + o.state); d.pos_out = (double *)(ob + o.pos);
     { const int rcl = ba_launch(h, c, W, d, bp); if (rcl != VILF_OK) return rcl; }
-    HIPCHECK(h, vilf_copy_sync(h, c->down.p, c->out.p, o.bytes, hipMemcpyDeviceToHost));
-    const char *hb = (const char *)c->down.p;
+    HIPCHECK(h, c->io.download(h, o.bytes));
+    const char *hb = (const char *)c->io.down.p;
     std::memcpy(out, hb + o.res, (size_t)W * sizeof(vilf_startup_ba_result));
     if (frames_out) std::memcpy(frames_out, hb + o.frames, (size_t)W * BA_MAXF * sizeof(vilf_startup_ba_frame));
     if (chain_out) std::memcpy(chain_out, hb + q.o_res, (size_t)W * sizeof(vilf_startup_structure));
@@ -601,19 +589,14 @@ static_assert(offsetof(vilf_startup_frame, R) % 8 == 0 && offsetof(vilf_startup_
 
 extern "C" int vilf_startup_get_ba_structure(vilf_handle *h, int n_windows, unsigned char *state_out, double *positions_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    BaCtx *c = h->ba;
+    BaCtx *c = vilf_stage<BaCtx>(h, ST_BA);
     if (!c || c->last_windows < 1 || n_windows != c->last_windows) {
         h->err = "vilf_startup_get_ba_structure: n_windows is not that of the last vilf_startup_ba or vilf_startup_construct"; return VILF_ERR_INVALID_ARGUMENT;
     }
-    const char *hb = (const char *)c->down.p;
+    const char *hb = (const char *)c->io.down.p;
     if (state_out) std::memcpy(state_out, hb + c->last_state, (size_t)n_windows * BA_MAXN);
     if (positions_out) std::memcpy(positions_out, hb + c->last_pos, (size_t)n_windows * BA_MAXN * 24);
     return VILF_OK;
 }
 
-extern "C" int vilf_startup_ba_profile(vilf_handle *h, double ms_out[1], long launches_out[1]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    ms_out[0] = h->ba ? h->ba->ms[0] : 0.0; launches_out[0] = h->ba ? h->ba->launches[0] : 0;
-    return VILF_OK;
-}
+extern "C" int vilf_startup_ba_profile(vilf_handle *h, double ms_out[1], long launches_out[1]) { return vilf_stage_profile(h, ST_BA, &BaCtx::prof, ms_out, launches_out); }

@@ -13,6 +13,9 @@
 
 #define VD __device__ __forceinline__
 
+// a0 b0 + a1 b1 + a2 b2, left to right, every product and sum rounded on its own
+VD double vilf_dot3(double a0, double b0, double a1, double b1, double a2, double b2) { return __dadd_rn(__dadd_rn(__dmul_rn(a0, b0), __dmul_rn(a1, b1)), __dmul_rn(a2, b2)); }
+
 // workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every global load and store in flight (s_waitcnt vmcnt(0)), which ends any prefetch
 // at the next barrier. Use only where nothing in GLOBAL memory written before it is read by another thread after it.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

@@ -42,20 +42,14 @@ __global__ void ex_hypotheses(ExDev d, ExPar p);
 __global__ void ex_score(ExDev d, ExPar p);
 __global__ void ex_solve(ExDev d, ExPar p);
 
-struct ExrotCtx {
-    DBuf state, in, work, out;
-    PinBuf up, down;
+struct ExrotCtx : VilfStage {
+    StageIO io;
+    DBuf state, work;
     int n_slots = 0;
     std::vector<int> fc;                     // host mirror of the slots' frame_count (the full-slot check needs no download)
-    double ms[EX_STAGES] = {0, 0, 0};
-    long launches[EX_STAGES] = {0, 0, 0};
-    void release() { state.release(); in.release(); work.release(); out.release(); up.release(); down.release(); }
+    StageProf<EX_STAGES> prof;
+    void profile_reset() override { prof.reset(); }
 };
-void vilf_exrot_profile_reset(vilf_handle *h) {
-    if (!h->exrot) return;
-    for (int i = 0; i < EX_STAGES; i++) { h->exrot->ms[i] = 0; h->exrot->launches[i] = 0; }
-}
-void vilf_exrot_release(vilf_handle *h) { if (h->exrot) { h->exrot->release(); delete h->exrot; h->exrot = nullptr; } }
 
 namespace {
 VD bool ex_searched(int n, int min_corres) { return n >= min_corres && n >= 8; }
@@ -108,7 +102,7 @@ VD void ex_mat3(const double *A, bool ta, const double *B, double *Cm) {
     for (int r = 0; r < 3; r++)
 #pragma unroll
         for (int c = 0; c < 3; c++)
-            Cm[r * 3 + c] = ta ? su_dot3(A[r], B[c], A[3 + r], B[3 + c], A[6 + r], B[6 + c]) : su_dot3(A[r * 3], B[c], A[r * 3 + 1], B[3 + c], A[r * 3 + 2], B[6 + c]);
+            Cm[r * 3 + c] = ta ? vilf_dot3(A[r], B[c], A[3 + r], B[3 + c], A[6 + r], B[6 + c]) : vilf_dot3(A[r * 3], B[c], A[r * 3 + 1], B[3 + c], A[r * 3 + 2], B[6 + c]);
 }
 }  // namespace
 
@@ -284,14 +278,14 @@ __global__ __launch_bounds__(EX_NT) void ex_solve(ExDev d, ExPar p) {
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 namespace {
-size_t ex_align(size_t v) { return (v + 255) & ~(size_t)255; }
 bool ex_finite_pos(double v) { return std::isfinite(v) && v > 0; }
 // the state: frame_count and ric of every slot first (what a reset uploads), then the histories, the angles and the weights
 struct ExState { size_t fc, ric, hist, ang, wgt, bytes; };
 ExState ex_state(int S) {
+    Layout l;
     ExState o;
-    o.fc = 0; o.ric = ex_align((size_t)S * 4); o.hist = ex_align(o.ric + (size_t)S * 72); o.ang = ex_align(o.hist + (size_t)S * 3 * EX_H * 72);
-    o.wgt = ex_align(o.ang + (size_t)S * EX_H * 8); o.bytes = o.wgt + (size_t)S * EX_H * 8;
+    o.fc = l.take((size_t)S * 4); o.ric = l.take((size_t)S * 72); o.hist = l.take((size_t)S * 3 * EX_H * 72); o.ang = l.take((size_t)S * EX_H * 8);
+    o.wgt = l.take((size_t)S * EX_H * 8); o.bytes = l.at;
     return o;
 }
 }  // namespace
@@ -307,12 +301,11 @@ extern "C" int vilf_exrot_reset(vilf_handle *h, int n_slots) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
     if (n_slots < 1 || n_slots > VILF_EXROT_MAX_SLOTS) { h->err = "vilf_exrot_reset: 1 <= n_slots <= VILF_EXROT_MAX_SLOTS"; return VILF_ERR_INVALID_ARGUMENT; }
     HIPCHECK(h, hipSetDevice(h->device));
-    if (!h->exrot) h->exrot = new ExrotCtx();
-    ExrotCtx *c = h->exrot;
+    ExrotCtx *c = vilf_stage_make<ExrotCtx>(h, ST_EXROT);
     const ExState o = ex_state(n_slots);
     c->n_slots = 0;                               // the layout depends on the number of slots: nothing of the old state survives
-    if (!c->state.ensure(o.bytes) || !c->up.ensure(o.hist)) { h->err = "vilf_exrot_reset: out of memory"; return VILF_ERR_DEVICE; }
-    char *ub = (char *)c->up.p;
+    if (!c->state.ensure(o.bytes) || !c->io.up.ensure(o.hist)) { h->err = "vilf_exrot_reset: out of memory"; return VILF_ERR_DEVICE; }
+    char *ub = (char *)c->io.up.p;
     std::memset(ub, 0, o.hist);
     for (int s = 0; s < n_slots; s++) { double *r = (double *)(ub + o.ric) + (size_t)s * 9; r[0] = r[4] = r[8] = 1.0; }
     HIPCHECK(h, vilf_copy_sync(h, c->state.p, ub, o.hist, hipMemcpyHostToDevice));
@@ -324,7 +317,7 @@ extern "C" int vilf_exrot_reset(vilf_handle *h, int n_slots) {
 extern "C" int vilf_exrot_push(vilf_handle *h, const vilf_exrot_params *p, int n_slots, const vilf_exrot_pair *pairs, vilf_exrot_result *out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
     if (!p || !pairs || !out) { h->err = "vilf_exrot_push: null pointer"; return VILF_ERR_INVALID_ARGUMENT; }
-    ExrotCtx *c = h->exrot;
+    ExrotCtx *c = vilf_stage<ExrotCtx>(h, ST_EXROT);
     if (n_slots < 1 || n_slots > VILF_EXROT_MAX_SLOTS || !c || n_slots != c->n_slots) {
         h->err = "vilf_exrot_push: n_slots is outside 1 .. VILF_EXROT_MAX_SLOTS or not that of the last vilf_exrot_reset"; return VILF_ERR_INVALID_ARGUMENT;
     }
@@ -350,14 +343,15 @@ extern "C" int vilf_exrot_push(vilf_handle *h, const vilf_exrot_params *p, int n
     const int S = n_slots, K = p->n_hypotheses;
     const size_t rows = std::max<size_t>(total, 1);
     // upload: the slots' integers, delta_q, then the points of both sides as float32
-    const size_t i_hdr = 0, i_dq = ex_align((size_t)S * EH_INTS * 4), i_ua = ex_align(i_dq + (size_t)S * 32), i_ub = ex_align(i_ua + rows * 8), in_bytes = i_ub + rows * 8;
-    const size_t o_F = 0, o_valid = ex_align(o_F + (size_t)S * K * 72), o_best = ex_align(o_valid + (size_t)S * K * 4), work_bytes = o_best + (size_t)S * 8;
+    Layout li, lw;
+    const size_t i_hdr = li.take((size_t)S * EH_INTS * 4), i_dq = li.take((size_t)S * 32), i_ua = li.take(rows * 8), i_ub = li.take(rows * 8), in_bytes = li.at;
+    const size_t o_F = lw.take((size_t)S * K * 72), o_valid = lw.take((size_t)S * K * 4), o_best = lw.take((size_t)S * 8), work_bytes = lw.at;
     const size_t out_bytes = (size_t)S * sizeof(vilf_exrot_result);
-    if (!c->in.ensure(in_bytes) || !c->work.ensure(work_bytes) || !c->out.ensure(out_bytes) || !c->up.ensure(in_bytes) || !c->down.ensure(out_bytes)) {
+    if (!c->io.ensure(in_bytes, out_bytes) || !c->work.ensure(work_bytes)) {
         h->err = "vilf_exrot_push: out of memory"; return VILF_ERR_DEVICE;
     }
     {
-        char *ub = (char *)c->up.p;
+        char *ub = (char *)c->io.up.p;
         int *hdr = (int *)(ub + i_hdr);
         double *dq = (double *)(ub + i_dq);
         float *ua = (float *)(ub + i_ua), *ubp = (float *)(ub + i_ub);
@@ -373,38 +367,36 @@ extern "C" int vilf_exrot_push(vilf_handle *h, const vilf_exrot_params *p, int n
             if (P.n > 0) at += (size_t)P.n;
         }
     }
-    HIPCHECK(h, hipMemcpyAsync(c->in.p, c->up.p, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, c->io.upload(h, in_bytes));
     // the result rows start from 0: a kernel writes only what the text gives a value
-    HIPCHECK(h, hipMemsetAsync(c->out.p, 0, out_bytes, h->stream));
+    HIPCHECK(h, hipMemsetAsync(c->io.out.p, 0, out_bytes, h->stream));
     const ExState o = ex_state(S);
     ExDev d;
-    char *ib = c->in.as<char>(), *wb = c->work.as<char>(), *sb = c->state.as<char>();
+    char *ib = c->io.in.as<char>(), *wb = c->work.as<char>(), *sb = c->state.as<char>();
     d.hdr = (const int *)(ib + i_hdr); d.dq = (const double *)(ib + i_dq); d.ua = (const float2 *)(ib + i_ua); d.ub = (const float2 *)(ib + i_ub);
     d.fc = (int *)(sb + o.fc); d.ric = (double *)(sb + o.ric); d.hist = (double *)(sb + o.hist); d.ang = (double *)(sb + o.ang); d.wgt = (double *)(sb + o.wgt);
     d.F = (double *)(wb + o_F); d.valid = (int *)(wb + o_valid); d.best = (unsigned long long *)(wb + o_best);
-    d.rows = c->out.as<vilf_exrot_result>();
+    d.rows = c->io.out.as<vilf_exrot_result>();
     ExPar ep;
     ep.K = K; ep.seed = p->seed; ep.min_corres = p->min_corres; ep.min_frames = p->min_frames;
     ep.thr2 = p->ransac_threshold * p->ransac_threshold; ep.huber = p->huber_deg; ep.min_sigma = p->min_sigma;
-    const bool prof = h->profiling != 0;
-    hipEvent_t ev[EX_STAGES + 1];
-    if (prof) ev[0] = vilf_prof_event(h);
+    ProfMarks prof(h, c->prof);
     hipLaunchKernelGGL(ex_hypotheses, dim3((K + TK_F_LANES - 1) / TK_F_LANES, S), dim3(TK_F_LANES), 0, h->stream, d, ep);
-    if (prof) ev[1] = vilf_prof_event(h);
+    prof.mark(0);
     hipLaunchKernelGGL(ex_score, dim3((K + EX_SCORE_WAVES - 1) / EX_SCORE_WAVES, S), dim3(64 * EX_SCORE_WAVES), 0, h->stream, d, ep);
-    if (prof) ev[2] = vilf_prof_event(h);
+    prof.mark(1);
     hipLaunchKernelGGL(ex_solve, dim3(S), dim3(EX_NT), 0, h->stream, d, ep);
-    if (prof) { ev[3] = vilf_prof_event(h); for (int k = 0; k < EX_STAGES; k++) vilf_prof_span(h, ev[k], ev[k + 1], &c->ms[k], &c->launches[k]); }
+    prof.mark(2);
     HIPCHECK(h, hipGetLastError());
-    HIPCHECK(h, vilf_copy_sync(h, c->down.p, c->out.p, out_bytes, hipMemcpyDeviceToHost));
-    std::memcpy(out, c->down.p, out_bytes);
+    HIPCHECK(h, c->io.download(h, out_bytes));
+    std::memcpy(out, c->io.down.p, out_bytes);
     for (int s = 0; s < S; s++) if (pairs[s].n >= 0) c->fc[s] += 1;
     return VILF_OK;
 }
 
 extern "C" int vilf_exrot_get_history(vilf_handle *h, int slot, int *count_out, double *Rc_out, double *Rimu_out, double *Rcg_out, double *angle_out, double *weight_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    ExrotCtx *c = h->exrot;
+    ExrotCtx *c = vilf_stage<ExrotCtx>(h, ST_EXROT);
     if (!count_out || !c || c->n_slots < 1 || slot < 0 || slot >= c->n_slots) {
         h->err = "vilf_exrot_get_history: a null count_out, no vilf_exrot_reset yet or a slot outside 0 .. n_slots - 1"; return VILF_ERR_INVALID_ARGUMENT;
     }
@@ -412,8 +404,8 @@ extern "C" int vilf_exrot_get_history(vilf_handle *h, int slot, int *count_out, 
     const ExState o = ex_state(c->n_slots);
     const int cnt = std::min(c->fc[(size_t)slot], EX_H);
     const size_t hb = (size_t)EX_H * 72, bytes = 3 * hb + 2 * (size_t)EX_H * 8;
-    if (!c->down.ensure(bytes)) { h->err = "vilf_exrot_get_history: out of memory"; return VILF_ERR_DEVICE; }
-    char *db = (char *)c->down.p;
+    if (!c->io.down.ensure(bytes)) { h->err = "vilf_exrot_get_history: out of memory"; return VILF_ERR_DEVICE; }
+    char *db = (char *)c->io.down.p;
     const char *sb = c->state.as<char>();
     if (cnt > 0) {
         HIPCHECK(h, hipMemcpyAsync(db, sb + o.hist + (size_t)slot * 3 * hb, 3 * hb, hipMemcpyDeviceToHost, h->stream));
@@ -430,9 +422,4 @@ extern "C" int vilf_exrot_get_history(vilf_handle *h, int slot, int *count_out, 
     return VILF_OK;
 }
 
-extern "C" int vilf_exrot_profile(vilf_handle *h, double ms_out[3], long launches_out[3]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < EX_STAGES; i++) { ms_out[i] = h->exrot ? h->exrot->ms[i] : 0.0; launches_out[i] = h->exrot ? h->exrot->launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_exrot_profile(vilf_handle *h, double ms_out[3], long launches_out[3]) { return vilf_stage_profile(h, ST_EXROT, &ExrotCtx::prof, ms_out, launches_out); }

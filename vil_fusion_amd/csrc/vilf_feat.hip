@@ -26,7 +26,7 @@
 #define FE_HALO 5
 #define FE_NT 256
 
-struct FeatCtx {
+struct FeatCtx : VilfStage {
     DBuf pts, keys, keys2, vals, vals2, temp, rpts, curv, rstart, etmp, stmp, ecnt, scnt, eoff, soff, oute, outs, tot;
     DBuf dcloud, dunit, dfeat, dout;          // getFeatureDepth
     size_t temp_bytes = 0;
@@ -238,15 +238,6 @@ __global__ __launch_bounds__(256) void fd_depth(const float4 *u, int n, const fl
     out[f] = res;
 }
 
-void vilf_feat_release(vilf_handle *h) {
-    if (!h->feat) return;
-    FeatCtx *c = h->feat;
-    DBuf *all[] = {&c->pts, &c->keys, &c->keys2, &c->vals, &c->vals2, &c->temp, &c->rpts, &c->curv, &c->rstart, &c->etmp, &c->stmp, &c->ecnt, &c->scnt, &c->eoff, &c->soff, &c->oute, &c->outs, &c->tot, &c->dcloud, &c->dunit, &c->dfeat, &c->dout};
-    for (DBuf *b : all) b->release();
-    delete c;
-    h->feat = nullptr;
-}
-
 extern "C" int vilf_lidar_extract_features(vilf_handle *h, const float *xyzi, int n, int n_scans, double min_range, double max_range, double edge_threshold,
                                            float *edge_out, int cap_edge, int *n_edge, float *surf_out, int cap_surf, int *n_surf) {
     if (!h || n < 0 || (n && !xyzi) || !n_edge || !n_surf || (n_scans != 16 && n_scans != 32 && n_scans != 64)) return VILF_ERR_INVALID_ARGUMENT;
@@ -254,8 +245,7 @@ extern "C" int vilf_lidar_extract_features(vilf_handle *h, const float *xyzi, in
     HIPCHECK(h, hipSetDevice(h->device));
     *n_edge = 0; *n_surf = 0;
     if (n == 0) return VILF_OK;
-    if (!h->feat) h->feat = new FeatCtx();
-    FeatCtx *c = h->feat;
+    FeatCtx *c = vilf_stage_make<FeatCtx>(h, ST_FEAT);
     const int nsec = n_scans * FE_SEC;
     const size_t sn = (size_t)n;
     if (n > c->cap || n_scans != c->scans) {
@@ -325,8 +315,7 @@ extern "C" int vilf_feature_depth(vilf_handle *h, const float *cloud_xyzi, int n
     HIPCHECK(h, hipSetDevice(h->device));
     for (int i = 0; i < m; i++) depth_out[i] = -1.0f;
     if (m == 0 || n < 10) return VILF_OK;                         // "depth cloud is too few" (:97-101)
-    if (!h->feat) h->feat = new FeatCtx();
-    FeatCtx *c = h->feat;
+    FeatCtx *c = vilf_stage_make<FeatCtx>(h, ST_FEAT);
     if (!c->dcloud.ensure((size_t)n * 16) || !c->dunit.ensure((size_t)n * 16) || !c->dfeat.ensure((size_t)m * 12) || !c->dout.ensure((size_t)m * 4)) { h->err = "hipMalloc failed (feature depth)"; return VILF_ERR_DEVICE; }
     const float bin_res = 180.0 / (float)360;
     const float thr = (float)std::pow(std::sin(bin_res / 180.0 * M_PI) * 5.0, 2);

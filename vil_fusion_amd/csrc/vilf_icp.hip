@@ -110,7 +110,7 @@ __global__ void icp_cell_table(IcpDev D);
 __global__ void icp_search(IcpDev D, int round);
 __global__ void icp_step(IcpDev D, int round);
 
-struct IcpCtx {
+struct IcpCtx : VilfStage {
     vilf_icp_params p;
     int cap_kf = 0, size = 0;
     long cap_pts = 0;
@@ -120,26 +120,14 @@ struct IcpCtx {
     std::vector<float> h_mats;
     std::vector<IcpState> h_st;
     int last_n = 0, last_W = 0;        // pairs and work elements of the last align call (vilf_icp_get_history / get_search)
-    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long launches[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    StageProf<8> prof;
     DBuf gm_chunks, gm_part, gm_hdr, gm_bcount, gm_bbase, gm_map;      // the global map: gm_map is its own, no align or sub-map call writes it
     std::vector<int> h_chunks;
     bool gm_built = false;
     long gm_n = 0;
-    double gm_ms[4] = {0, 0, 0, 0};
-    long gm_launches[4] = {0, 0, 0, 0};
-    void release() {
-        DBuf *all[] = {&pts, &doff, &mats, &segs, &tp, &vox, &cur, &tgs, &k1, &k2, &v1, &v2, &temp, &hdr, &st, &cells, &part, &hist, &nn_idx, &nn_d2, &flag,
-                       &gm_chunks, &gm_part, &gm_hdr, &gm_bcount, &gm_bbase, &gm_map};
-        for (DBuf *b : all) b->release();
-    }
+    StageProf<4> gm_prof;
+    void profile_reset() override { prof.reset(); gm_prof.reset(); }
 };
-void vilf_icp_profile_reset(vilf_handle *h) {
-    if (!h->icp) return;
-    for (int i = 0; i < 8; i++) { h->icp->ms[i] = 0; h->icp->launches[i] = 0; }
-    for (int i = 0; i < 4; i++) { h->icp->gm_ms[i] = 0; h->icp->gm_launches[i] = 0; }
-}
-void vilf_icp_release(vilf_handle *h) { if (h->icp) { h->icp->release(); delete h->icp; h->icp = nullptr; } }
 
 namespace {
 // local2global (:185-187): ((m0 x + m1 y) + m2 z) + m3, every operation rounded on its own
@@ -523,22 +511,22 @@ extern "C" int vilf_icp_create(vilf_handle *h, const vilf_icp_params *p, int cap
     }
     HIPCHECK(h, hipSetDevice(h->device));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
-    vilf_icp_release(h);
+    vilf_stage_drop(h, ST_ICP);
     IcpCtx *c = new IcpCtx();
     c->p = d; c->cap_kf = cap_keyframes; c->cap_pts = cap_points;
     c->off.assign(1, 0);
     if (!c->pts.ensure((size_t)cap_points * 16) || !c->doff.ensure(((size_t)cap_keyframes + 1) * 4) || !c->mats.ensure((size_t)cap_keyframes * 48) || !c->flag.ensure(4)) {
-        c->release(); delete c;
+        delete c;
         h->err = "hipMalloc failed (ICP cloud store)";
         return VILF_ERR_DEVICE;
     }
-    h->icp = c;
+    h->stage[ST_ICP] = c;
     return VILF_OK;
 }
 
 extern "C" int vilf_icp_add_clouds(vilf_handle *h, int n, const float *xyzi, const int *offsets, int *first_index_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    IcpCtx *c = h->icp;
+    IcpCtx *c = vilf_stage<IcpCtx>(h, ST_ICP);
     if (!c) { h->err = "vilf_icp_add_clouds: no store (vilf_icp_create)"; return VILF_ERR_INVALID_ARGUMENT; }
     if (n < 0 || !offsets || offsets[0] < 0) { h->err = "vilf_icp_add_clouds: bad arguments"; return VILF_ERR_INVALID_ARGUMENT; }
     for (int i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) { h->err = "vilf_icp_add_clouds: offsets must not decrease"; return VILF_ERR_INVALID_ARGUMENT; }
@@ -570,7 +558,8 @@ extern "C" int vilf_icp_add_cloud(vilf_handle *h, const float *xyzi, int n, int 
 
 extern "C" int vilf_icp_size(vilf_handle *h, int *n_out) {
     if (!h || !n_out) return VILF_ERR_INVALID_ARGUMENT;
-    *n_out = h->icp ? h->icp->size : 0;
+    const IcpCtx *c = vilf_stage<IcpCtx>(h, ST_ICP);
+    *n_out = c ? c->size : 0;
     return VILF_OK;
 }
 
@@ -620,15 +609,13 @@ static int icp_enqueue(vilf_handle *h, IcpCtx *c, const std::vector<IcpSegHost> 
                c->hdr.as<IcpHdr>(), c->st.as<IcpState>(), c->cells.as<int>(), c->part.as<double>(), c->hist.as<vilf_icp_iter>(), c->nn_idx.as<int>(), c->nn_d2.as<float>(), c->flag.as<int>(),
                c->p.own_pose, max_blocks, c->p.max_iterations, (int)W, (float)c->p.leaf_size,
                c->p.max_correspondence_distance * c->p.max_correspondence_distance, c->p.transformation_epsilon, c->p.euclidean_fitness_epsilon, c->p.rotation_threshold, c->p.mse_relative};
-    const bool prof = h->profiling != 0;
-    hipEvent_t e = prof ? vilf_prof_event(h) : nullptr;
-    auto span = [&](int slot) { if (prof) { hipEvent_t e1 = vilf_prof_event(h); vilf_prof_span(h, e, e1, &c->ms[slot], &c->launches[slot]); e = e1; } };
+    ProfMarks prof(h, c->prof);
     const dim3 gw((unsigned)((Wn + ICP_PT_NT - 1) / ICP_PT_NT));
-    hipLaunchKernelGGL(icp_bbox, dim3(nseg), dim3(ICP_SEG_NT), 0, h->stream, D); span(0);
-    hipLaunchKernelGGL(icp_leaf_keys, gw, dim3(ICP_PT_NT), 0, h->stream, D); span(1);
+    hipLaunchKernelGGL(icp_bbox, dim3(nseg), dim3(ICP_SEG_NT), 0, h->stream, D); prof.mark(0);
+    hipLaunchKernelGGL(icp_leaf_keys, gw, dim3(ICP_PT_NT), 0, h->stream, D); prof.mark(1);
     if (W > 0 && vilf_sort_pairs_u64(h->stream, c->temp.p, c->temp.cap, D.k1, D.k2, D.v1, D.v2, (size_t)W, ICP_LEAF_BITS + icp_bits((unsigned long long)nseg)) != 0) { h->err = "vilf_icp: radix sort failed"; return VILF_ERR_DEVICE; }
-    span(2);
-    hipLaunchKernelGGL(icp_voxel, dim3(nseg), dim3(ICP_SEG_NT), 0, h->stream, D); span(3);
+    prof.mark(2);
+    hipLaunchKernelGGL(icp_voxel, dim3(nseg), dim3(ICP_SEG_NT), 0, h->stream, D); prof.mark(3);
     if (with_icp) {
         std::vector<IcpState> &st = c->h_st;
         st.resize((size_t)npair);
@@ -639,17 +626,17 @@ static int icp_enqueue(vilf_handle *h, IcpCtx *c, const std::vector<IcpSegHost> 
             std::memcpy(st[i].pend, st[i].fin, sizeof(st[i].fin));
         }
         HIPCHECK(h, hipMemcpyAsync(c->st.p, st.data(), st.size() * sizeof(IcpState), hipMemcpyHostToDevice, h->stream));
-        if (prof) e = vilf_prof_event(h);
-        hipLaunchKernelGGL(icp_cell_keys, gw, dim3(ICP_PT_NT), 0, h->stream, D); span(4);
+        prof = ProfMarks(h, c->prof);      // the states' upload belongs to no slot
+        hipLaunchKernelGGL(icp_cell_keys, gw, dim3(ICP_PT_NT), 0, h->stream, D); prof.mark(4);
         if (W > 0 && vilf_sort_pairs_u64(h->stream, c->temp.p, c->temp.cap, D.k1, D.k2, D.v1, D.v2, (size_t)W, ICP_CELL_BITS + icp_bits((unsigned long long)nseg)) != 0) { h->err = "vilf_icp: radix sort failed"; return VILF_ERR_DEVICE; }
-        span(2);
-        hipLaunchKernelGGL(icp_cell_table, gw, dim3(ICP_PT_NT), 0, h->stream, D); span(4);
+        prof.mark(2);
+        hipLaunchKernelGGL(icp_cell_table, gw, dim3(ICP_PT_NT), 0, h->stream, D); prof.mark(4);
         for (int r = 0; r < c->p.max_iterations; r++) {
-            hipLaunchKernelGGL(icp_search, dim3(max_blocks, npair), dim3(ICP_SRCH_NT), 0, h->stream, D, r); span(5);
-            hipLaunchKernelGGL(icp_step, dim3(npair), dim3(ICP_STEP_NT), 0, h->stream, D, r); span(6);
+            hipLaunchKernelGGL(icp_search, dim3(max_blocks, npair), dim3(ICP_SRCH_NT), 0, h->stream, D, r); prof.mark(5);
+            hipLaunchKernelGGL(icp_step, dim3(npair), dim3(ICP_STEP_NT), 0, h->stream, D, r); prof.mark(6);
         }
-        hipLaunchKernelGGL(icp_search, dim3(max_blocks, npair), dim3(ICP_SRCH_NT), 0, h->stream, D, -1); span(5);
-        hipLaunchKernelGGL(icp_step, dim3(npair), dim3(ICP_STEP_NT), 0, h->stream, D, -1); span(6);
+        hipLaunchKernelGGL(icp_search, dim3(max_blocks, npair), dim3(ICP_SRCH_NT), 0, h->stream, D, -1); prof.mark(5);
+        hipLaunchKernelGGL(icp_step, dim3(npair), dim3(ICP_STEP_NT), 0, h->stream, D, -1); prof.mark(6);
     }
     HIPCHECK(h, hipGetLastError());
     return VILF_OK;
@@ -665,7 +652,7 @@ static int icp_finish(vilf_handle *h, IcpCtx *c) {
 
 extern "C" int vilf_icp_submap(vilf_handle *h, int key, int submap_size, int root, const double *poses6, float *xyzi_out, int cap, int *n_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    IcpCtx *c = h->icp;
+    IcpCtx *c = vilf_stage<IcpCtx>(h, ST_ICP);
     if (!c || !poses6 || !n_out || cap < 0 || (cap > 0 && !xyzi_out)) { h->err = "vilf_icp_submap: no store (vilf_icp_create) or null argument"; return VILF_ERR_INVALID_ARGUMENT; }
     if (key < 0 || key >= c->size || root < 0 || root >= c->size || submap_size < 0) { h->err = "vilf_icp_submap: key or root outside the store"; return VILF_ERR_INVALID_ARGUMENT; }
     c->last_n = 0;
@@ -684,7 +671,7 @@ extern "C" int vilf_icp_submap(vilf_handle *h, int key, int submap_size, int roo
 
 extern "C" int vilf_icp_align_pairs(vilf_handle *h, int n, const int *prev, const int *curr, const double *poses6, const double *guess_qt, vilf_icp_result *out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    IcpCtx *c = h->icp;
+    IcpCtx *c = vilf_stage<IcpCtx>(h, ST_ICP);
     if (!c) { h->err = "vilf_icp_align: no store (vilf_icp_create)"; return VILF_ERR_INVALID_ARGUMENT; }
     if (n < 0 || (n > 0 && (!prev || !curr || !poses6 || !out))) { h->err = "vilf_icp_align: null argument"; return VILF_ERR_INVALID_ARGUMENT; }
     if (n > 32767) { h->err = "vilf_icp_align_pairs: at most 32767 pairs in one call"; return VILF_ERR_UNSUPPORTED; }
@@ -722,7 +709,7 @@ extern "C" int vilf_icp_align(vilf_handle *h, int prev, int curr, const double *
 
 extern "C" int vilf_icp_get_history(vilf_handle *h, int pair, vilf_icp_iter *out, int cap, int *n_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    IcpCtx *c = h->icp;
+    IcpCtx *c = vilf_stage<IcpCtx>(h, ST_ICP);
     if (!c || !n_out || cap < 0 || (cap > 0 && !out) || pair < 0 || pair >= c->last_n) { h->err = "vilf_icp_get_history: no align call before, or pair out of range"; return VILF_ERR_INVALID_ARGUMENT; }
     HIPCHECK(h, hipSetDevice(h->device));
     IcpState st;
@@ -736,7 +723,7 @@ extern "C" int vilf_icp_get_history(vilf_handle *h, int pair, vilf_icp_iter *out
 
 extern "C" int vilf_icp_get_search(vilf_handle *h, int pair, int which, int *index_out, float *d2_out, int cap, int *n_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    IcpCtx *c = h->icp;
+    IcpCtx *c = vilf_stage<IcpCtx>(h, ST_ICP);
     if (!c || !n_out || cap < 0 || pair < 0 || pair >= c->last_n || which < 0 || which > 1) { h->err = "vilf_icp_get_search: no align call before, or pair out of range"; return VILF_ERR_INVALID_ARGUMENT; }
     HIPCHECK(h, hipSetDevice(h->device));
     IcpHdr H;
@@ -749,12 +736,7 @@ extern "C" int vilf_icp_get_search(vilf_handle *h, int pair, int which, int *ind
     return VILF_OK;
 }
 
-extern "C" int vilf_get_profile_icp(vilf_handle *h, double ms_out[8], long launches_out[8]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < 8; i++) { ms_out[i] = h->icp ? h->icp->ms[i] : 0.0; launches_out[i] = h->icp ? h->icp->launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_get_profile_icp(vilf_handle *h, double ms_out[8], long launches_out[8]) { return vilf_stage_profile(h, ST_ICP, &IcpCtx::prof, ms_out, launches_out); }
 
 // ---- the global map (≙ publishGlobalMap :310-336) -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(GM_XF_NT) void gmap_xf_bbox(GmapDev G) {
@@ -872,7 +854,7 @@ __global__ __launch_bounds__(GM_RUN_NT) void gmap_centroids(GmapDev G) {
 
 extern "C" int vilf_icp_global_map(vilf_handle *h, int first, int count, int skip, const double *poses6, long *n_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    IcpCtx *c = h->icp;
+    IcpCtx *c = vilf_stage<IcpCtx>(h, ST_ICP);
     if (!c || !poses6 || !n_out) { h->err = "vilf_icp_global_map: no store (vilf_icp_create) or null argument"; return VILF_ERR_INVALID_ARGUMENT; }
     if (first < 0 || count < 0 || skip < 1 || (long)first + count > c->size) { h->err = "vilf_icp_global_map: first >= 0, count >= 0, skip >= 1, first + count <= size"; return VILF_ERR_INVALID_ARGUMENT; }
     for (size_t i = 0; i < 6 * (size_t)c->size; i++) if (!std::isfinite(poses6[i])) { h->err = "vilf_icp_global_map: the pose of key frame " + std::to_string(i / 6) + " is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
@@ -901,18 +883,16 @@ extern "C" int vilf_icp_global_map(vilf_handle *h, int first, int count, int ski
     const GmapDev G{c->pts.as<float4>(), c->mats.as<float>(), c->gm_chunks.as<int4>(), c->gm_part.as<float>(), nchunks, c->tp.as<float4>(), c->gm_map.as<float4>(),
                     c->k1.as<unsigned long long>(), c->k2.as<unsigned long long>(), c->v1.as<int>(), c->v2.as<int>(), c->gm_hdr.as<GmapHdr>(), c->gm_bcount.as<int>(),
                     c->gm_bbase.as<int>(), c->flag.as<int>(), (int)W, nblk, (float)c->p.leaf_size};
-    const bool prof = h->profiling != 0;
-    hipEvent_t e = prof ? vilf_prof_event(h) : nullptr;
-    auto span = [&](int slot) { if (prof) { hipEvent_t e1 = vilf_prof_event(h); vilf_prof_span(h, e, e1, &c->gm_ms[slot], &c->gm_launches[slot]); e = e1; } };
+    ProfMarks prof(h, c->gm_prof);
     if (nchunks > 0) hipLaunchKernelGGL(gmap_xf_bbox, dim3(nchunks), dim3(GM_XF_NT), 0, h->stream, G);
-    hipLaunchKernelGGL(gmap_box, dim3(1), dim3(GM_XF_NT), 0, h->stream, G); span(0);
+    hipLaunchKernelGGL(gmap_box, dim3(1), dim3(GM_XF_NT), 0, h->stream, G); prof.mark(0);
     if (W > 0) {
-        hipLaunchKernelGGL(gmap_leaf_keys, dim3((unsigned)((W + ICP_PT_NT - 1) / ICP_PT_NT)), dim3(ICP_PT_NT), 0, h->stream, G); span(1);
+        hipLaunchKernelGGL(gmap_leaf_keys, dim3((unsigned)((W + ICP_PT_NT - 1) / ICP_PT_NT)), dim3(ICP_PT_NT), 0, h->stream, G); prof.mark(1);
         if (vilf_sort_pairs_u64(h->stream, c->temp.p, c->temp.cap, G.k1, G.k2, G.v1, G.v2, (size_t)W, ICP_LEAF_BITS) != 0) { h->err = "vilf_icp_global_map: radix sort failed"; return VILF_ERR_DEVICE; }
-        span(2);
+        prof.mark(2);
         hipLaunchKernelGGL(gmap_count, dim3(nblk), dim3(GM_RUN_NT), 0, h->stream, G);
         hipLaunchKernelGGL(gmap_scan, dim3(1), dim3(GM_RUN_NT), 0, h->stream, G);
-        hipLaunchKernelGGL(gmap_centroids, dim3(nblk), dim3(GM_RUN_NT), 0, h->stream, G); span(3);
+        hipLaunchKernelGGL(gmap_centroids, dim3(nblk), dim3(GM_RUN_NT), 0, h->stream, G); prof.mark(3);
     }
     HIPCHECK(h, hipGetLastError());
     GmapHdr H;
@@ -926,13 +906,14 @@ extern "C" int vilf_icp_global_map(vilf_handle *h, int first, int count, int ski
 
 extern "C" int vilf_icp_global_map_size(vilf_handle *h, long *n_out) {
     if (!h || !n_out) return VILF_ERR_INVALID_ARGUMENT;
-    *n_out = h->icp ? h->icp->gm_n : 0;
+    const IcpCtx *c = vilf_stage<IcpCtx>(h, ST_ICP);
+    *n_out = c ? c->gm_n : 0;
     return VILF_OK;
 }
 
 extern "C" int vilf_icp_global_map_get(vilf_handle *h, long offset, long count, float *xyzi_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    IcpCtx *c = h->icp;
+    IcpCtx *c = vilf_stage<IcpCtx>(h, ST_ICP);
     if (!c || !c->gm_built) { h->err = "vilf_icp_global_map_get: no map (vilf_icp_global_map)"; return VILF_ERR_INVALID_ARGUMENT; }
     if (offset < 0 || count < 0 || offset > c->gm_n || count > c->gm_n - offset || (count > 0 && !xyzi_out)) {
         h->err = "vilf_icp_global_map_get: [" + std::to_string(offset) + ", " + std::to_string(offset) + " + " + std::to_string(count) + ") outside the map of " + std::to_string(c->gm_n) + " points, or null output";
@@ -944,9 +925,4 @@ extern "C" int vilf_icp_global_map_get(vilf_handle *h, long offset, long count, 
     return VILF_OK;
 }
 
-extern "C" int vilf_get_profile_icp_map(vilf_handle *h, double ms_out[4], long launches_out[4]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < 4; i++) { ms_out[i] = h->icp ? h->icp->gm_ms[i] : 0.0; launches_out[i] = h->icp ? h->icp->gm_launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_get_profile_icp_map(vilf_handle *h, double ms_out[4], long launches_out[4]) { return vilf_stage_profile(h, ST_ICP, &IcpCtx::gm_prof, ms_out, launches_out); }

@@ -7,19 +7,36 @@
 #include "../../include/vilfusion.h"
 #include "vilf_batch.hpp"
 
-struct DBuf {
+// ---- what every stage file's host half is built from -------------------------------------------------------------------------------------------------
+//   DBuf / PinBuf   a device / pinned host buffer that grows on demand and frees itself: move-only, release() for the places that free in mid-life
+//   VilfStage       the base of every stage's context; the handle keeps them in stage[] (vilf_stage<C>, vilf_stage_make<C>, vilf_stage_drop), vilf_destroy deletes
+//                   and vilf_set_profiling resets them in one loop. A context's members free themselves; a destructor is written only for raw resources
+//   StageProf<N>    the accumulated times and launch counts of a stage's N slots; ProfMarks books the spans between marks into it, vilf_stage_profile /
+//                   vilf_handle_profile are the body of every vilf_*_profile getter
+//   Layout          the offsets of the arrays packed into one block; StageIO is the in / out / up / down quadruple of a batched stage with its two copies
+template <hipError_t (*Free)(void *)> struct VilfBuf {
     void *p = nullptr;
     size_t cap = 0;
+    VilfBuf() = default;
+    VilfBuf(const VilfBuf &) = delete;
+    VilfBuf &operator=(const VilfBuf &) = delete;
+    VilfBuf(VilfBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    VilfBuf &operator=(VilfBuf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~VilfBuf() { release(); }
+    void release() { if (p) Free(p); p = nullptr; cap = 0; }
+};
+struct DBuf : VilfBuf<hipFree> {
     bool ensure(size_t bytes) {
         if (bytes <= cap) return true;
-        if (p) hipFree(p);
-        p = nullptr; cap = 0;
+        release();
         size_t want = bytes + bytes / 8 + 256;
         if (hipMalloc(&p, want) != hipSuccess) return false;
         cap = want;
         return true;
     }
-    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
     template <typename T> T *as() { return reinterpret_cast<T *>(p); }
 };
 
@@ -35,34 +52,55 @@ enum {
 };
 
 // pinned host staging kept across calls (vilf_batch_upload / download): no allocation, no zero fill, truly asynchronous copies
-struct PinBuf {
-    void *p = nullptr; size_t cap = 0;
+struct PinBuf : VilfBuf<hipHostFree> {
     bool ensure(size_t bytes) {
         if (bytes <= cap) return true;
-        if (p) hipHostFree(p);
-        p = nullptr; cap = 0;
+        release();
         const size_t want = bytes + bytes / 8 + 4096;
         if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) return false;
         std::memset(p, 0, want);
         cap = want;
         return true;
     }
-    void release() { if (p) hipHostFree(p); p = nullptr; cap = 0; }
 };
 
-struct S2B;
-struct FeatCtx;
-struct PgCtx;
-struct LwCtx;
-struct ScCtx;
-struct IcpCtx;
-struct TrackCtx;
-struct StartupCtx;
-struct SfmCtx;
-struct BaCtx;
-struct TriCtx;
-struct ExrotCtx;
-struct KfCtx;
+struct VilfStage {
+    virtual ~VilfStage() = default;
+    virtual void profile_reset() {}
+};
+// the handle's stages, in the order vilf_destroy frees them
+enum {
+    ST_S2M, ST_S2B,      // scan-to-map state: single stream / batched streams (S2B, vilf_s2m.hip)
+    ST_FEAT,             // LiDAR feature extraction workspace (FeatCtx, vilf_feat.hip)
+    ST_PG,               // pose-graph workspace (PgCtx, vilf_pg.hip)
+    ST_LW,               // large-window solve workspace (LwCtx, vilf_lw.hip)
+    ST_SC,               // Scan Context descriptor database and search workspace (ScCtx, vilf_sc.hip)
+    ST_ICP,              // key-frame cloud store and ICP workspace of the loop verification (IcpCtx, vilf_icp.hip)
+    ST_TRACK,            // image feature tracker: pyramids, feature list, detection workspace (TrackCtx, vilf_track.hip)
+    ST_STARTUP,          // visual start-up: the pairs' correspondences, hypotheses and result rows (StartupCtx, vilf_startup.hip)
+    ST_SFM,              // visual start-up, second stage: the windows, the frame rows and the structure (SfmCtx, vilf_sfm.hip)
+    ST_BA,               // visual start-up, third stage: the start values, the BA's frames and structure (BaCtx, vilf_ba.hip)
+    ST_TRI,              // feature triangulation: the packed candidates, the cameras and the depths (TriCtx, vilf_tri.hip)
+    ST_EXROT,            // camera-IMU rotation calibration: the slots' frame counts, ric and histories (ExrotCtx, vilf_exrot.hip)
+    ST_KF,               // visual loop closure: the key-frame store and its workspace (KfCtx, vilf_kf.hip)
+    VILF_STAGE_COUNT
+};
+
+template <int N> struct StageProf {
+    double ms[N] = {};
+    long launches[N] = {};
+    void reset() { for (int i = 0; i < N; i++) { ms[i] = 0; launches[i] = 0; } }
+    void read(double *ms_out, long *launches_out) const { for (int i = 0; i < N; i++) { ms_out[i] = ms[i]; launches_out[i] = launches[i]; } }
+};
+
+struct Layout {
+    size_t at = 0;
+    size_t take(size_t bytes, size_t align = 256) {      // the next array's offset: at, aligned up
+        const size_t o = (at + align - 1) & ~(align - 1);
+        at = o + bytes;
+        return o;
+    }
+};
 
 // deep copy of a window snapshot (estimate_extrinsic / estimate_td: the batched entry points run the general single-window solve per slot and need the inputs again)
 struct OwnedWindow {
@@ -112,32 +150,17 @@ struct vilf_handle {
     std::vector<hipEvent_t> prof_used, prof_free;
     hipEvent_t wait_ev = nullptr;            // vilf_wait_for
     void *stamp_pinned = nullptr; size_t stamp_cap = 0; hipEvent_t stamp_ev = nullptr;   // vilf_batch_newest_poses_device: pinned staging of the caller's stamps
-    double kernel_ms[4] = {0, 0, 0, 0};      // linearize, solve, step, other (accumulated since last reset)
-    long kernel_launches[4] = {0, 0, 0, 0};
+    StageProf<4> kernel_prof;                // linearize, solve, step, other (accumulated since last reset)
     std::vector<hipEvent_t> s2m_ev;         // scan-to-map profiling (same switch): group of launches -> ms
     std::vector<int> s2m_groups;
-    double marg_ms[4] = {0, 0, 0, 0};        // k_marg_prepare, k_marg_schur, k_marg_finish, k_prior_prep
-    long marg_launches[4] = {0, 0, 0, 0};
-    double s2m_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long s2m_launches[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    StageProf<4> marg_prof;                  // k_marg_prepare, k_marg_schur, k_marg_finish, k_prior_prep
+    StageProf<8> s2m_prof;
     std::vector<WindowPlan> plans;
     double last_solve_usec = 0;
     bool solve_time_pending = false;         // the last solve was enqueued with sync == 0: ev0 / ev1 are read by the next call that waits for the stream
     int split_gen = 0;      // generation counter of the k_linearize_split launches of this handle
     bool solve_dense_fallback = false;       // a prior imported from the host holds a speed-bias block other than SpeedBias[0]: k_solve (dense) instead of k_solve_sb
-    FeatCtx *feat = nullptr;                 // LiDAR feature extraction workspace (vilf_feat.hip)
-    S2B *s2m = nullptr, *s2b = nullptr;      // scan-to-map state: single stream / batched streams (vilf_s2m.hip)
-    PgCtx *pg = nullptr;                     // pose-graph workspace (vilf_pg.hip)
-    LwCtx *lw = nullptr;                     // large-window solve workspace (vilf_lw.hip)
-    ScCtx *sc = nullptr;                     // Scan Context descriptor database and search workspace (vilf_sc.hip)
-    IcpCtx *icp = nullptr;                   // key-frame cloud store and ICP workspace of the loop verification (vilf_icp.hip)
-    TrackCtx *trk = nullptr;                 // image feature tracker: pyramids, feature list, detection workspace (vilf_track.hip)
-    StartupCtx *su = nullptr;                // visual start-up: the pairs' correspondences, hypotheses and result rows (vilf_startup.hip)
-    SfmCtx *sfm = nullptr;                   // visual start-up, second stage: the windows, the frame rows and the structure (vilf_sfm.hip)
-    BaCtx *ba = nullptr;                     // visual start-up, third stage: the start values, the BA's frames and structure (vilf_ba.hip)
-    ExrotCtx *exrot = nullptr;               // camera-IMU rotation calibration: the slots' frame counts, ric and histories (vilf_exrot.hip)
-    KfCtx *kf = nullptr;                     // visual loop closure: the key-frame store (key points, lifted points, descriptors, window points) and its workspace (vilf_kf.hip)
-    TriCtx *tri = nullptr;                   // feature triangulation: the packed candidates, the cameras and the depths (vilf_tri.hip)
+    VilfStage *stage[VILF_STAGE_COUNT] = {};   // the stages' contexts (ST_*), created by the first call that needs one
 };
 
 // a copy ordered on the handle's stream and waited for: the library's streams are non-blocking (they do not synchronise with the legacy default stream), so a plain
@@ -159,41 +182,61 @@ static inline hipError_t vilf_copy_sync(vilf_handle *h, void *dst, const void *s
 hipEvent_t vilf_prof_event(vilf_handle *h);                                 // an event recorded on the handle's stream now (from the pool)
 void vilf_prof_span(vilf_handle *h, hipEvent_t a, hipEvent_t b, double *ms, long *cnt);   // elapsed(a, b) is added to *ms at the next flush
 int vilf_prof_flush(vilf_handle *h);                                        // waits for the stream, reads every pending span
-void vilf_s2m_release(vilf_handle *h);
-void vilf_feat_release(vilf_handle *h);
-void vilf_pg_release(vilf_handle *h);
-void vilf_lw_release(vilf_handle *h);
-void vilf_sc_release(vilf_handle *h);
-void vilf_icp_release(vilf_handle *h);
-void vilf_icp_profile_reset(vilf_handle *h);
-void vilf_track_release(vilf_handle *h);
-void vilf_track_profile_reset(vilf_handle *h);
-void vilf_startup_release(vilf_handle *h);
-void vilf_startup_profile_reset(vilf_handle *h);
+
+// a stage's context, typed (null until a call has made it); the same, made by the first call that needs it; a stage freed in mid-life
+template <class C> C *vilf_stage(const vilf_handle *h, int s) { return static_cast<C *>(h->stage[s]); }
+template <class C> C *vilf_stage_make(vilf_handle *h, int s) {
+    if (!h->stage[s]) h->stage[s] = new C();
+    return vilf_stage<C>(h, s);
+}
+static inline void vilf_stage_drop(vilf_handle *h, int s) { delete h->stage[s]; h->stage[s] = nullptr; }
+
+// the body of every vilf_*_profile getter: the pending spans are read, then the record is copied out (zeros while the stage does not exist)
+template <int N> int vilf_profile_read(vilf_handle *h, const StageProf<N> *p, double *ms_out, long *launches_out) {
+    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
+    (p ? *p : StageProf<N>()).read(ms_out, launches_out);
+    return VILF_OK;
+}
+template <class C, int N> int vilf_stage_profile(vilf_handle *h, int s, StageProf<N> C::*prof, double *ms_out, long *launches_out) {
+    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
+    const C *c = vilf_stage<C>(h, s);
+    return vilf_profile_read(h, c ? &(c->*prof) : nullptr, ms_out, launches_out);
+}
+template <int N> int vilf_handle_profile(vilf_handle *h, StageProf<N> vilf_handle::*prof, double *ms_out, long *launches_out) {
+    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
+    return vilf_profile_read(h, &(h->*prof), ms_out, launches_out);
+}
+// the marks of a call: every mark closes the span since the one before it (the first: since the construction) into its slot. Nothing happens while profiling is off
+template <int N> struct ProfMarks {
+    vilf_handle *h; StageProf<N> *p; hipEvent_t e;
+    ProfMarks(vilf_handle *h_, StageProf<N> &p_) : h(h_), p(&p_), e(h_->profiling ? vilf_prof_event(h_) : nullptr) {}
+    void mark(int slot) {
+        if (!h->profiling) return;
+        hipEvent_t b = vilf_prof_event(h);
+        vilf_prof_span(h, e, b, &p->ms[slot], &p->launches[slot]);
+        e = b;
+    }
+};
+// a batched stage's staging: the upload block on the device and its pinned image, the download block and its pinned image
+struct StageIO {
+    DBuf in, out;
+    PinBuf up, down;
+    bool ensure(size_t in_bytes, size_t out_bytes) { return in.ensure(in_bytes) && out.ensure(out_bytes) && up.ensure(in_bytes) && down.ensure(out_bytes); }
+    hipError_t upload(vilf_handle *h, size_t bytes) { return hipMemcpyAsync(in.p, up.p, bytes, hipMemcpyHostToDevice, h->stream); }
+    hipError_t download(vilf_handle *h, size_t bytes) { return vilf_copy_sync(h, down.p, out.p, bytes, hipMemcpyDeviceToHost); }
+};
 #define VILF_SU_WIN_INTS (4 + VILF_MAX_FEATURES + VILF_MAX_FEATURES + 2)      // a start-up window's integers on the device: n_frames, n_features, first row of its points, 0; start_frame; first_obs (+ 1 pad)
 int vilf_startup_check_windows(vilf_handle *h, const char *who, int n_windows, const vilf_startup_window *windows, size_t *total_out);   // what both stages refuse in the windows
 void vilf_startup_pack_windows(int n_windows, const vilf_startup_window *windows, int *ints, double *pts);                            // VILF_SU_WIN_INTS per window, then all points
-void vilf_sfm_release(vilf_handle *h);
-void vilf_sfm_profile_reset(vilf_handle *h);
 // the chain without its wait and download, for vilf_startup_construct (vilf_ba.hip): validation, upload and launch as vilf_startup_sfm into the caller's buffers; out is
 // sized for the chain's download (out_bytes) and extra_out bytes behind it
-struct VilfSfmBufs { DBuf *in, *out; PinBuf *up, *down; };
 struct VilfSfmQueued {
     const int *win; const double *pts; const int *l;                                                                    // on the device, as su_sfm_chain reads them
     const vilf_startup_structure *res; const vilf_startup_frame *rows; const unsigned char *state; const double *pos;   // on the device, where su_sfm_chain writes them
     size_t o_res, o_rows, o_state, o_pos, out_bytes;                                                                    // the same four within out, and the chain's bytes
 };
 int vilf_sfm_enqueue(vilf_handle *h, const char *who, const vilf_startup_sfm_params *p, int n_windows, const vilf_startup_window *windows, const vilf_startup_result *rel,
-                     VilfSfmBufs bufs, size_t extra_out, VilfSfmQueued *q);
-void vilf_ba_release(vilf_handle *h);
-void vilf_ba_profile_reset(vilf_handle *h);
-void vilf_tri_release(vilf_handle *h);
-void vilf_tri_profile_reset(vilf_handle *h);
-void vilf_exrot_release(vilf_handle *h);
-void vilf_exrot_profile_reset(vilf_handle *h);
-void vilf_kf_release(vilf_handle *h);
-void vilf_kf_profile_reset(vilf_handle *h);
-void vilf_sc_profile_reset(vilf_handle *h);                                 // vilf_set_profiling: the Scan Context spans start from zero
+                     StageIO *io, size_t extra_out, VilfSfmQueued *q);
 int vilf_lw_chol_max_n();                                                      // largest n vilf_lw_chol_solve takes (its back substitution keeps the solution in LDS)
 int vilf_lw_chol_solve(vilf_handle *h, int n, double *S, double *y, int *info);   // blocked Cholesky solve on the handle's stream (vilf_lw.hip): S = [(n + 1) x n] row-major, row n = rhs
 int vilf_lw_group_solve(vilf_handle *h, int G, const vilf_window_in *const *ins, vilf_window_out *const *outs, const int *slot1);   // G windows in one chain of launches; slot1[g] = resident batch slot + 1 (0 / nullptr: not resident)

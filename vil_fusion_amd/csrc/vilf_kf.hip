@@ -60,7 +60,7 @@ struct KfMatchOut { unsigned char *status; float2 *pt, *ptn; int *idx, *dist, *n
 __global__ void kf_match(const KfMeta *meta, const unsigned long long *kp_desc, const float2 *kp_pt, const float2 *kp_norm, const unsigned long long *win_desc, int cur,
                          const int *old, int max_dist, int accept_dist, KfMatchOut out);                  // grid (ceil(n_window / 64), n_old), n_window > 0
 
-struct KfCtx {
+struct KfCtx : VilfStage {
     vilf_kf_params p;
     int capK = 0, size = 0;
     long capP = 0, used = 0;
@@ -69,16 +69,9 @@ struct KfCtx {
     DBuf kp_pt, kp_norm, kp_desc, win_pt, win_desc, meta_d, pat;            // the store
     DBuf img, blur, score, rowcnt, rowoff, total, tpts, tscore, tdesc, old_d, res;      // one call's workspace
     PinBuf stage, pin, down;            // the image on its way to the device; counts, a meta row, window points and old indices on theirs; a search's results on their way back
-    double ms[KF_STAGES] = {0, 0, 0, 0, 0};
-    long launches[KF_STAGES] = {0, 0, 0, 0, 0};
-    void release() {
-        DBuf *all[] = {&kp_pt, &kp_norm, &kp_desc, &win_pt, &win_desc, &meta_d, &pat, &img, &blur, &score, &rowcnt, &rowoff, &total, &tpts, &tscore, &tdesc, &old_d, &res};
-        for (DBuf *b : all) b->release();
-        stage.release(); pin.release(); down.release();
-    }
+    StageProf<KF_STAGES> prof;
+    void profile_reset() override { prof.reset(); }
 };
-void vilf_kf_profile_reset(vilf_handle *h) { if (h->kf) for (int i = 0; i < KF_STAGES; i++) { h->kf->ms[i] = 0; h->kf->launches[i] = 0; } }
-void vilf_kf_release(vilf_handle *h) { if (h->kf) { h->kf->release(); delete h->kf; h->kf = nullptr; } }
 
 // ---- kf_blur -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(KF_TW * KF_TH) void kf_blur(const unsigned char *src, int W, int H, unsigned char *dst) {
@@ -282,20 +275,10 @@ __global__ __launch_bounds__(KF_NT) void kf_match(const KfMeta *meta, const unsi
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 namespace {
 KfCtx *kf_ctx(vilf_handle *h, const char *who) {
-    if (!h->kf) h->err = std::string(who) + ": no key-frame store (vilf_kf_create)";
-    return h->kf;
+    KfCtx *c = vilf_stage<KfCtx>(h, ST_KF);
+    if (!c) h->err = std::string(who) + ": no key-frame store (vilf_kf_create)";
+    return c;
 }
-// stage marks of a call: every mark closes the span since the one before it
-struct KfProf {
-    vilf_handle *h; KfCtx *c; hipEvent_t e;
-    KfProf(vilf_handle *h_, KfCtx *c_) : h(h_), c(c_), e(h_->profiling ? vilf_prof_event(h_) : nullptr) {}
-    void mark(int stage) {
-        if (!h->profiling) return;
-        hipEvent_t b = vilf_prof_event(h);
-        vilf_prof_span(h, e, b, &c->ms[stage], &c->launches[stage]);
-        e = b;
-    }
-};
 int kf_end(vilf_handle *h) {                              // a fault of the launches is reported by the call that made them
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipStreamSynchronize(h->stream));
@@ -396,17 +379,17 @@ extern "C" int vilf_kf_create(vilf_handle *h, const vilf_kf_params *p, int cap_k
     if (!c->kp_pt.ensure(P * 8) || !c->kp_norm.ensure(P * 8) || !c->kp_desc.ensure(P * 32) || !c->win_pt.ensure(K * KF_WIN_CAP * 8) || !c->win_desc.ensure(K * KF_WIN_CAP * 32) ||
         !c->meta_d.ensure(K * sizeof(KfMeta)) || !c->pat.ensure(VILF_KF_BITS * 4) || !c->img.ensure(N) || !c->blur.ensure(N) || !c->score.ensure(N) || !c->rowcnt.ensure(Hh * 4) ||
         !c->rowoff.ensure(Hh * 4) || !c->total.ensure(16) || !c->old_d.ensure(VILF_KF_MAX_CANDIDATES * 4) || !c->stage.ensure(N) || !c->pin.ensure(KF_PIN_BYTES)) {
-        c->release(); delete c;
+        delete c;
         h->err = "hipMalloc failed (key-frame store)";
         return VILF_ERR_DEVICE;
     }
     if (vilf_copy_sync(h, c->pat.p, pat.data(), VILF_KF_BITS * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        c->release(); delete c;
+        delete c;
         h->err = "vilf_kf_create: the pattern's upload failed";
         return VILF_ERR_DEVICE;
     }
-    vilf_kf_release(h);
-    h->kf = c;
+    vilf_stage_drop(h, ST_KF);
+    h->stage[ST_KF] = c;
     return VILF_OK;
 }
 
@@ -419,7 +402,7 @@ extern "C" int vilf_kf_add_keyframe(vilf_handle *h, const unsigned char *img, in
     HIPCHECK(h, hipSetDevice(h->device));
     float2 *wpt = c->win_pt.as<float2>() + (size_t)c->size * KF_WIN_CAP;
     unsigned long long *wdesc = c->win_desc.as<unsigned long long>() + (size_t)c->size * KF_WIN_CAP * KF_WORDS;
-    KfProf prof(h, c);
+    ProfMarks prof(h, c->prof);
     { const int rc = kf_upload(h, c, img, row_stride); if (rc != VILF_OK) return rc; }
     if (n_window > 0) {
         float *pw = (float *)((char *)c->pin.p + KF_PIN_DATA);
@@ -467,7 +450,7 @@ extern "C" int vilf_kf_add_loaded(vilf_handle *h, int n_kp, const float *keypoin
     }
     HIPCHECK(h, hipSetDevice(h->device));
     const size_t u = (size_t)c->used, k = (size_t)c->size, nk = (size_t)n_kp, nw = (size_t)n_window;
-    KfProf prof(h, c);
+    ProfMarks prof(h, c->prof);
     if (nk) {
         HIPCHECK(h, hipMemcpyAsync(c->kp_pt.as<float2>() + u, keypoints, nk * 8, hipMemcpyHostToDevice, h->stream));
         HIPCHECK(h, hipMemcpyAsync(c->kp_norm.as<float2>() + u, keypoints_norm, nk * 8, hipMemcpyHostToDevice, h->stream));
@@ -499,7 +482,7 @@ extern "C" int vilf_kf_get(vilf_handle *h, int index, int cap_kp, float *keypoin
     }
     HIPCHECK(h, hipSetDevice(h->device));
     const size_t u = (size_t)m.kp_off, k = (size_t)index, nk = (size_t)m.n_kp, nw = (size_t)m.n_win;
-    KfProf prof(h, c);
+    ProfMarks prof(h, c->prof);
     if (nk && keypoints) HIPCHECK(h, hipMemcpyAsync(keypoints, c->kp_pt.as<float2>() + u, nk * 8, hipMemcpyDeviceToHost, h->stream));
     if (nk && keypoints_norm) HIPCHECK(h, hipMemcpyAsync(keypoints_norm, c->kp_norm.as<float2>() + u, nk * 8, hipMemcpyDeviceToHost, h->stream));
     if (nk && descriptors) HIPCHECK(h, hipMemcpyAsync(descriptors, c->kp_desc.as<unsigned long long>() + u * KF_WORDS, nk * 32, hipMemcpyDeviceToHost, h->stream));
@@ -514,7 +497,8 @@ extern "C" int vilf_kf_get(vilf_handle *h, int index, int cap_kp, float *keypoin
 
 extern "C" int vilf_kf_size(vilf_handle *h, int *n_out) {
     if (!h || !n_out) return VILF_ERR_INVALID_ARGUMENT;
-    *n_out = h->kf ? h->kf->size : 0;
+    const KfCtx *c = vilf_stage<KfCtx>(h, ST_KF);
+    *n_out = c ? c->size : 0;
     return VILF_OK;
 }
 
@@ -531,13 +515,15 @@ extern "C" int vilf_kf_match(vilf_handle *h, int cur, int n_old, const int *old_
     const int nw = c->meta[cur].n_win;
     const size_t rows = (size_t)n_old * nw;
     // the results of one call, one allocation: points, lifted points, indices, distances, counts, status bytes
-    const size_t o_pt = 0, o_ptn = o_pt + rows * 8, o_idx = o_ptn + rows * 8, o_dist = o_idx + rows * 4, o_cnt = o_dist + rows * 4, o_st = o_cnt + (size_t)n_old * 4, bytes = o_st + rows;
+    Layout l;
+    const size_t o_pt = l.take(rows * 8, 8), o_ptn = l.take(rows * 8, 8), o_idx = l.take(rows * 4, 4), o_dist = l.take(rows * 4, 4), o_cnt = l.take((size_t)n_old * 4, 4),
+                 o_st = l.take(rows, 1), bytes = l.at;
     if (!c->res.ensure(bytes) || !c->down.ensure(bytes)) { h->err = "allocation failed (key-frame match)"; return VILF_ERR_DEVICE; }
     char *b = c->res.as<char>();
     const KfMatchOut out{(unsigned char *)(b + o_st), (float2 *)(b + o_pt), (float2 *)(b + o_ptn), (int *)(b + o_idx), (int *)(b + o_dist), (int *)(b + o_cnt)};
     int *po = (int *)((char *)c->pin.p + KF_PIN_DATA);
     std::memcpy(po, old_index, (size_t)n_old * 4);
-    KfProf prof(h, c);
+    ProfMarks prof(h, c->prof);
     HIPCHECK(h, hipMemcpyAsync(c->old_d.p, po, (size_t)n_old * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(h, hipMemsetAsync(out.nmatched, 0, (size_t)n_old * 4, h->stream));
     if (nw > 0) hipLaunchKernelGGL(kf_match, dim3((nw + 63) / 64, n_old), dim3(KF_NT), 0, h->stream, c->meta_d.as<KfMeta>(), c->kp_desc.as<unsigned long long>(), c->kp_pt.as<float2>(),
@@ -563,7 +549,7 @@ extern "C" int vilf_kf_blur(vilf_handle *h, const unsigned char *img, int row_st
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
     if (!img || !out || row_stride < c->p.width) { h->err = "vilf_kf_blur: null pointer or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
     HIPCHECK(h, hipSetDevice(h->device));
-    KfProf prof(h, c);
+    ProfMarks prof(h, c->prof);
     { const int rc = kf_upload(h, c, img, row_stride); if (rc != VILF_OK) return rc; }
     { const int rc = kf_run_blur(h, c); if (rc != VILF_OK) return rc; }
     prof.mark(0);
@@ -578,7 +564,7 @@ extern "C" int vilf_kf_fast(vilf_handle *h, const unsigned char *img, int row_st
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
     if (!img || !pts_out || !n_out || cap < 0 || row_stride < c->p.width) { h->err = "vilf_kf_fast: null pointer, cap < 0 or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
     HIPCHECK(h, hipSetDevice(h->device));
-    KfProf prof(h, c);
+    ProfMarks prof(h, c->prof);
     { const int rc = kf_upload(h, c, img, row_stride); if (rc != VILF_OK) return rc; }
     prof.mark(0);
     int n = 0;
@@ -611,7 +597,7 @@ extern "C" int vilf_kf_brief(vilf_handle *h, const unsigned char *img, int row_s
     if (n == 0) return VILF_OK;
     HIPCHECK(h, hipSetDevice(h->device));
     if (!c->tpts.ensure((size_t)n * 8) || !c->tdesc.ensure((size_t)n * 32)) { h->err = "hipMalloc failed (descriptors)"; return VILF_ERR_DEVICE; }
-    KfProf prof(h, c);
+    ProfMarks prof(h, c->prof);
     { const int rc = kf_upload(h, c, img, row_stride); if (rc != VILF_OK) return rc; }
     HIPCHECK(h, hipMemcpyAsync(c->tpts.p, pts, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
     { const int rc = kf_run_blur(h, c); if (rc != VILF_OK) return rc; }
@@ -623,9 +609,4 @@ extern "C" int vilf_kf_brief(vilf_handle *h, const unsigned char *img, int row_s
     return kf_end(h);
 }
 
-extern "C" int vilf_kf_profile(vilf_handle *h, double ms_out[5], long launches_out[5]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < KF_STAGES; i++) { ms_out[i] = h->kf ? h->kf->ms[i] : 0.0; launches_out[i] = h->kf ? h->kf->launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_kf_profile(vilf_handle *h, double ms_out[5], long launches_out[5]) { return vilf_stage_profile(h, ST_KF, &KfCtx::prof, ms_out, launches_out); }

@@ -103,25 +103,24 @@ __device__ __forceinline__ bool lw_inband(const LwWin &w, int i, int j) {
 #define SY_KS 16                                   // most K splits of the Schur reduce (partials in their own buffers, summed in fixed order by lw_schur_prep); a group uses
                                                    // LwWin::nks of them: 4 when its windows' tiles fill the chip, up to 16 for a single window (60 workgroups of ~12 chunks otherwise)
 
-struct LwCtx {
+struct LwCtx : VilfStage {
     DBuf arena, desc;                  // the group's device memory; its LwWin array
     char *stage = nullptr;             // host image of the arena's input region (pinned: the copy of a group's factors runs at the link's rate)
     size_t stage_cap = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms[4] = {0, 0, 0, 0};       // vilf_set_profiling: factor scatter, Schur SYRK, Cholesky (potrf + potrs), other device work
-    long launches[4] = {0, 0, 0, 0};
-    void release() {
-        arena.release(); desc.release();
-        if (stage) { hipHostFree(stage); stage = nullptr; stage_cap = 0; }
-        for (hipEvent_t &e : ev) if (e) { hipEventDestroy(e); e = nullptr; }
+    StageProf<4> prof;                 // vilf_set_profiling: factor scatter, Schur SYRK, Cholesky (potrf + potrs), other device work. Timed with a wait per group (LwEnq::toc),
+                                       // so nothing is pending at a read; the switch does not reset it (bench.py reads differences)
+    ~LwCtx() override {
+        if (stage) hipHostFree(stage);
+        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
     }
 };
 extern "C" int vilf_get_profile_large_window(vilf_handle *h, double ms_out[4], long launches_out[4]) {
     if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < 4; i++) { ms_out[i] = h->lw ? h->lw->ms[i] : 0.0; launches_out[i] = h->lw ? h->lw->launches[i] : 0; }
+    const LwCtx *c = vilf_stage<LwCtx>(h, ST_LW);
+    (c ? c->prof : StageProf<4>()).read(ms_out, launches_out);
     return VILF_OK;
 }
-void vilf_lw_release(vilf_handle *h) { if (h->lw) { h->lw->release(); delete h->lw; h->lw = nullptr; } }
 
 namespace {
 using namespace vd;
@@ -1578,7 +1577,7 @@ struct LwEnq {
     vilf_handle *h; LwCtx *c; const LwWin *ws; LwDims d; bool ext, prof;
     bool cleared_full = false;         // the first linearisation of a solve clears all of Hpp, the later ones its band
     void tic() { if (prof) hipEventRecord(c->ev[0], h->stream); }
-    void toc(int grp) { if (prof) { hipEventRecord(c->ev[1], h->stream); hipEventSynchronize(c->ev[1]); float t = 0; hipEventElapsedTime(&t, c->ev[0], c->ev[1]); c->ms[grp] += t; c->launches[grp] += 1; } }
+    void toc(int grp) { if (prof) { hipEventRecord(c->ev[1], h->stream); hipEventSynchronize(c->ev[1]); float t = 0; hipEventElapsedTime(&t, c->ev[0], c->ev[1]); c->prof.ms[grp] += t; c->prof.launches[grp] += 1; } }
     dim3 grid(size_t gx, unsigned gy = 1) const { return dim3((unsigned)std::max<size_t>(gx, 1), gy, (unsigned)d.G); }
     // one evaluation at the device state x (which = 0) or cand (1), the prior's dx already in pdx. Cost only (jac = 0): the caller has zeroed scal[0]
     void evaluate(int which, int jac, int sk) {
@@ -1868,8 +1867,7 @@ int vilf_lw_group_solve(vilf_handle *h, int G, const vilf_window_in *const *ins,
     if (G < 1 || G > 65535) return VILF_ERR_INVALID_ARGUMENT;
     const bool est_ex = h->opts.estimate_extrinsic != 0, est_td = h->opts.estimate_td != 0, ext = est_ex || est_td;
     HIPCHECK(h, hipSetDevice(h->device));
-    if (!h->lw) h->lw = new LwCtx();
-    LwCtx *c = h->lw;
+    LwCtx *c = vilf_stage_make<LwCtx>(h, ST_LW);
     const bool prof = h->profiling != 0;
     if (prof && !c->ev[0]) { hipEventCreate(&c->ev[0]); hipEventCreate(&c->ev[1]); }
     std::vector<LwHostWin> hws(G);

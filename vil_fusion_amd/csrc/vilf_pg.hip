@@ -20,14 +20,9 @@
 #include "vilf_internal.hpp"
 #include "vilf_device.hpp"
 
-struct PgCtx {
+struct PgCtx : VilfStage {
     DBuf x, prior, edges, rec, adj_off, adj_item, loop_ij, D, E, C, F, g, Y, Cm, rhs, scal, info;
-    void release() {
-        DBuf *all[] = {&x, &prior, &edges, &rec, &adj_off, &adj_item, &loop_ij, &D, &E, &C, &F, &g, &Y, &Cm, &rhs, &scal, &info};
-        for (DBuf *b : all) b->release();
-    }
 };
-void vilf_pg_release(vilf_handle *h) { if (h->pg) { h->pg->release(); delete h->pg; h->pg = nullptr; } }
 
 namespace {
 using namespace vd;
@@ -298,8 +293,7 @@ extern "C" int vilf_posegraph_optimize(vilf_handle *h, int K, double *poses_qt, 
     if (!h || K < 1 || !poses_qt || !prior_sigma || n_edges < 0 || (n_edges && !edges) || max_iterations < 0) return VILF_ERR_INVALID_ARGUMENT;
     if (n_edges >= (1 << 28) - 1) return VILF_ERR_INVALID_ARGUMENT;
     HIPCHECK(h, hipSetDevice(h->device));
-    if (!h->pg) h->pg = new PgCtx();
-    PgCtx *c = h->pg;
+    PgCtx *c = vilf_stage_make<PgCtx>(h, ST_PG);
     // ---- host: device edge records, adjacency (factor order), loop list
     std::vector<PgEdgeDev> ed(std::max(n_edges, 1));
     std::vector<std::vector<int>> adj(K);

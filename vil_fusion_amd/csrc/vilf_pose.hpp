@@ -12,14 +12,13 @@ VD void su_cross(const double *p, const double *q, double *c) {
     c[1] = __dsub_rn(__dmul_rn(p[2], q[0]), __dmul_rn(p[0], q[2]));
     c[2] = __dsub_rn(__dmul_rn(p[0], q[1]), __dmul_rn(p[1], q[0]));
 }
-VD double su_dot3(double a0, double b0, double a1, double b1, double a2, double b2) { return __dadd_rn(__dadd_rn(__dmul_rn(a0, b0), __dmul_rn(a1, b1)), __dmul_rn(a2, b2)); }
 // the two depths of the cheirality paragraph for (R, t) and the pair (a, b)
 VD void su_depths(const double *R, const double *t, float2 a, float2 b, double &z1, double &z2) {
     const double ax = (double)a.x, ay = (double)a.y, bx = (double)b.x, by = (double)b.y;
     const double r0 = __dadd_rn(__dadd_rn(__dmul_rn(R[0], ax), __dmul_rn(R[1], ay)), R[2]), r1 = __dadd_rn(__dadd_rn(__dmul_rn(R[3], ax), __dmul_rn(R[4], ay)), R[5]);
     const double r2 = __dadd_rn(__dadd_rn(__dmul_rn(R[6], ax), __dmul_rn(R[7], ay)), R[8]);
-    const double rr = su_dot3(r0, r0, r1, r1, r2, r2), xx = __dadd_rn(__dadd_rn(__dmul_rn(bx, bx), __dmul_rn(by, by)), 1.0);
-    const double rx = __dadd_rn(__dadd_rn(__dmul_rn(r0, bx), __dmul_rn(r1, by)), r2), rt = su_dot3(r0, t[0], r1, t[1], r2, t[2]);
+    const double rr = vilf_dot3(r0, r0, r1, r1, r2, r2), xx = __dadd_rn(__dadd_rn(__dmul_rn(bx, bx), __dmul_rn(by, by)), 1.0);
+    const double rx = __dadd_rn(__dadd_rn(__dmul_rn(r0, bx), __dmul_rn(r1, by)), r2), rt = vilf_dot3(r0, t[0], r1, t[1], r2, t[2]);
     const double xt = __dadd_rn(__dadd_rn(__dmul_rn(bx, t[0]), __dmul_rn(by, t[1])), t[2]);
     const double det = __dsub_rn(__dmul_rn(rr, xx), __dmul_rn(rx, rx));
     z1 = __ddiv_rn(__dsub_rn(__dmul_rn(rx, xt), __dmul_rn(xx, rt)), det);
@@ -48,13 +47,13 @@ VD bool su_decompose(const double *E, double (*s_M)[TK_F_LANES], double (*s_V)[T
     {
         double wv[3];
 #pragma unroll
-        for (int r = 0; r < 3; r++) wv[r] = su_dot3(E[r * 3], v1[0], E[r * 3 + 1], v1[1], E[r * 3 + 2], v1[2]);
-        const double nrm = __dsqrt_rn(su_dot3(wv[0], wv[0], wv[1], wv[1], wv[2], wv[2]));
+        for (int r = 0; r < 3; r++) wv[r] = vilf_dot3(E[r * 3], v1[0], E[r * 3 + 1], v1[1], E[r * 3 + 2], v1[2]);
+        const double nrm = __dsqrt_rn(vilf_dot3(wv[0], wv[0], wv[1], wv[1], wv[2], wv[2]));
 #pragma unroll
         for (int r = 0; r < 3; r++) u1[r] = __ddiv_rn(wv[r], nrm);
 #pragma unroll
-        for (int r = 0; r < 3; r++) wv[r] = su_dot3(E[r * 3], v2[0], E[r * 3 + 1], v2[1], E[r * 3 + 2], v2[2]);
-        const double nrm2 = __dsqrt_rn(su_dot3(wv[0], wv[0], wv[1], wv[1], wv[2], wv[2]));
+        for (int r = 0; r < 3; r++) wv[r] = vilf_dot3(E[r * 3], v2[0], E[r * 3 + 1], v2[1], E[r * 3 + 2], v2[2]);
+        const double nrm2 = __dsqrt_rn(vilf_dot3(wv[0], wv[0], wv[1], wv[1], wv[2], wv[2]));
 #pragma unroll
         for (int r = 0; r < 3; r++) u2[r] = __ddiv_rn(wv[r], nrm2);
     }

@@ -2175,7 +2175,6 @@ struct S2BMap {                 // one local map (edge = 0, surf = 1) of every s
     // pts: the current map; alt: where the next step writes its map. The neighbour directory travels with its map: dir pairs with pts, dirAlt with alt (the map update
     // writes the directory of the map it emits). sorted: cell-major copy of an unordered map, afterwards the map update's queue of uncommon points.
     DBuf pts, alt, n, dir, dirAlt, sorted, fixq;
-    void release() { for (DBuf *b : {&pts, &alt, &n, &dir, &dirAlt, &sorted, &fixq}) b->release(); }
     int cap = 0, cs_cfg = 0;    // fixed at reserve time: capacity per stream, cell shift of the cell-major order (s2b_cell_shift), leaf size and its inverse
     float leaf = 0.0f, inv = 0.0f;
     S2BMapState st;
@@ -2191,7 +2190,6 @@ struct S2BScan {                // the scan side of one feature kind: resident s
     DBuf raw, n, ds, nDs;
     DBuf svlist;                // streams b_scan_voxel_runs hands back to b_scan_voxel: [0] count, [1..] stream ids
     DBuf bigmap;                // streams whose scan cloud does not fit the in-LDS voxel grid (b_scan_voxel): the global-sort path takes them as a sub-batch (h_big: as uploaded)
-    void release() { for (DBuf *b : {&raw, &n, &ds, &nDs, &svlist, &bigmap}) b->release(); }
     int cap = 0;
     std::vector<int> h_n, h_big;
     CSet cur() { return CSet{raw.as<float4>(), n.as<int>(), cap}; }
@@ -2203,22 +2201,16 @@ struct S2BScan {                // the scan side of one feature kind: resident s
 struct S2BSnap {
     S2BMapState st[2];
     DBuf pts[2], n[2], dir[2], pose;
-    void release() { for (DBuf *b : {&pts[0], &pts[1], &n[0], &n[1], &dir[0], &dir[1], &pose}) b->release(); }
     bool valid = false, live = false;
     void *live_ptr[2] = {nullptr, nullptr};
 };
-struct S2B {
+struct S2B : VilfStage {
     int S = 0;
     S2BMap m[2];
     S2BScan sc[2];
     S2BSnap snap;
     DBuf tmpB, nTmp, bcnt, nOld, mOld;                   // nOld, mOld: map point counts before the append / surviving the crop (unsorted-map path)
     DBuf keys, keys2, vals, vals2, temp, mm, frec, fkind, pose, res, err, bits, muT, tileHeads;
-    void release() {
-        for (int w = 0; w < 2; w++) { m[w].release(); sc[w].release(); }
-        snap.release();
-        for (DBuf *b : {&tmpB, &nTmp, &bcnt, &nOld, &mOld, &keys, &keys2, &vals, &vals2, &temp, &mm, &frec, &fkind, &pose, &res, &err, &bits, &muT, &tileHeads}) b->release();
-    }
     unsigned epoch = 0;                // directory entries carry (epoch % 255 + 1) << 24: a slot this step did not write reads as empty
     unsigned next_tag() { epoch++; return (epoch % 255u + 1u) << 24; }
     bool scan_dirty = true;
@@ -2228,16 +2220,12 @@ struct S2B {
     int capq() const { return sc[0].cap + sc[1].cap; }
 };
 
-void vilf_s2m_release(vilf_handle *h) {
-    for (S2B **pc : {&h->s2m, &h->s2b}) if (*pc) { (*pc)->release(); delete *pc; *pc = nullptr; }
-}
-
 // profiling (vilf_set_profiling): HIP events between groups of launches on the handle's stream.
 // group 0 voxel grid, 1 radix sort (rocPRIM), 2 neighbour index (cell keys, hash build), 3 associate (5-NN + fits), 4 LM solve,
 // 5 sub-map (append, crop, compact), 6 other
 static void s2m_prof_mark(vilf_handle *h, int group) {       // the launches since the previous mark belong to `group`
     hipEvent_t e = vilf_prof_event(h);
-    if (!h->s2m_groups.empty()) vilf_prof_span(h, h->s2m_ev.back(), e, &h->s2m_ms[group], &h->s2m_launches[group]);
+    if (!h->s2m_groups.empty()) vilf_prof_span(h, h->s2m_ev.back(), e, &h->s2m_prof.ms[group], &h->s2m_prof.launches[group]);
     h->s2m_ev.push_back(e);
     h->s2m_groups.push_back(group);
 }
@@ -2257,8 +2245,7 @@ static int s2b_cell_shift(float leaf, double half) {
 static int s2b_reserve(vilf_handle *h, S2B *c, int S, int capScanE, int capScanS, int capMapE, int capMapS) {
     const int wantScan[2] = {std::max(capScanE, 1), std::max(capScanS, 1)}, wantMap[2] = {std::max(capMapE, 1), std::max(capMapS, 1)};
     if (S != c->S) {
-        c->release();
-        *c = S2B(); c->S = S;
+        *c = S2B(); c->S = S;             // the old buffers go with the old state
         if (!c->pose.ensure((size_t)S * 24 * 8) || !c->res.ensure((size_t)S * sizeof(S2BRes)) || !c->err.ensure((size_t)S * 4) || !c->mm.ensure((size_t)S * sizeof(MinMax)) || !c->nTmp.ensure((size_t)S * 4) || !c->bits.ensure(64) || !c->nOld.ensure((size_t)S * 4) || !c->mOld.ensure((size_t)S * 4) || !c->bcnt.ensure((size_t)S * 4)) return VILF_ERR_DEVICE;
         HIPCHECK(h, hipMemsetAsync(c->bcnt.p, 0, (size_t)S * 4, h->stream));
         for (int w = 0; w < 2; w++) {
@@ -2299,8 +2286,7 @@ static int s2b_reserve(vilf_handle *h, S2B *c, int S, int capScanE, int capScanS
                 HIPCHECK(h, hipMemcpy2DAsync(nb.p, (size_t)nc * 16, m.pts.p, (size_t)oc * 16, (size_t)oc * 16, S, hipMemcpyDeviceToDevice, h->stream));
                 HIPCHECK(h, hipStreamSynchronize(h->stream));
             }
-            m.pts.release();
-            m.pts = nb;
+            m.pts = std::move(nb);
             m.cap = nc; grew = true; c->snap.valid = c->snap.live = false;
             if (!m.sorted.ensure((size_t)S * nc * 16) || !m.alt.ensure((size_t)S * nc * 16) || !m.fixq.ensure((size_t)S * nc * 4)) return VILF_ERR_DEVICE;
         }
@@ -2662,7 +2648,7 @@ static int s2b_upload_map(vilf_handle *h, S2BMap &m, int sid, int old_n, const f
 }
 
 // ---- single-stream ABI (S = 1, capacities grow on demand) ---------------------------------------------------------------
-static S2B *single(vilf_handle *h) { if (!h->s2m) h->s2m = new S2B(); return h->s2m; }
+static S2B *single(vilf_handle *h) { return vilf_stage_make<S2B>(h, ST_S2M); }
 
 extern "C" int vilf_scan2map_init(vilf_handle *h, const float *e, int ne, const float *s, int ns) {
     if (!h || ne < 0 || ns < 0 || (ne && !e) || (ns && !s)) return VILF_ERR_INVALID_ARGUMENT;
@@ -2735,13 +2721,12 @@ extern "C" int vilf_scan2map_step(vilf_handle *h, const float *e, int ne, const 
 extern "C" int vilf_scan2map_batch_create(vilf_handle *h, int n_streams, int cap_scan_edge, int cap_scan_surf, int cap_map_edge, int cap_map_surf) {
     if (!h || n_streams < 1 || n_streams > 65535 || cap_scan_edge < 1 || cap_scan_surf < 1 || cap_map_edge < 1 || cap_map_surf < 1) return VILF_ERR_INVALID_ARGUMENT;
     HIPCHECK(h, hipSetDevice(h->device));
-    if (h->s2b) { h->s2b->release(); delete h->s2b; h->s2b = nullptr; }
-    h->s2b = new S2B();
-    return s2b_reserve(h, h->s2b, n_streams, cap_scan_edge, cap_scan_surf, cap_map_edge, cap_map_surf);
+    vilf_stage_drop(h, ST_S2B);
+    return s2b_reserve(h, vilf_stage_make<S2B>(h, ST_S2B), n_streams, cap_scan_edge, cap_scan_surf, cap_map_edge, cap_map_surf);
 }
 #define S2B_CHECK(h, sid)                                                                   \
-    if (!(h) || !(h)->s2b) return VILF_ERR_INVALID_ARGUMENT;                                \
-    S2B *c = (h)->s2b;                                                                      \
+    S2B *c = (h) ? vilf_stage<S2B>((h), ST_S2B) : nullptr;                                  \
+    if (!c) return VILF_ERR_INVALID_ARGUMENT;                                               \
     if ((sid) < 0 || (sid) >= c->S) return VILF_ERR_INVALID_ARGUMENT;                       \
     HIPCHECK(h, hipSetDevice((h)->device));
 
@@ -2810,12 +2795,7 @@ extern "C" int vilf_scan2map_batch_step(vilf_handle *h, int sync) {
     if (sync) { HIPCHECK(h, hipStreamSynchronize(h->stream)); if ((rc = vilf_prof_flush(h)) != VILF_OK) return rc; }
     return VILF_OK;
 }
-extern "C" int vilf_get_profile_scan2map(vilf_handle *h, double ms_out[8], long launches_out[8]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < 8; i++) { ms_out[i] = h->s2m_ms[i]; launches_out[i] = h->s2m_launches[i]; }
-    return VILF_OK;
-}
+extern "C" int vilf_get_profile_scan2map(vilf_handle *h, double ms_out[8], long launches_out[8]) { return vilf_handle_profile(h, &vilf_handle::s2m_prof, ms_out, launches_out); }
 extern "C" int vilf_scan2map_batch_snapshot(vilf_handle *h) {
     S2B_CHECK(h, 0)
     S2BSnap &sn = c->snap;
@@ -2881,10 +2861,9 @@ struct S2BDbgStage {
     S2B *c = nullptr; int sid = 0;
     DBuf nq[2], pose, res, frec, fkind;
     DBuf q[2], out[3];          // the hook's own: query clouds (associate), neighbour lists (associate) / trace (solve)
-    ~S2BDbgStage() { for (DBuf *b : {&nq[0], &nq[1], &pose, &res, &frec, &fkind, &q[0], &q[1], &out[0], &out[1], &out[2]}) b->release(); }
 };
 static int s2b_dbg_stage(vilf_handle *h, const char *who, int stream, const double *pose_qt, const int nn[2], S2BDbgStage &g) {
-    S2B *c = g.c = stream == -1 ? h->s2m : h->s2b;
+    S2B *c = g.c = vilf_stage<S2B>(h, stream == -1 ? ST_S2M : ST_S2B);
     const int sid = g.sid = stream == -1 ? 0 : stream;
     if (!c || c->S < 1 || c->sc[0].cap < 1 || c->sc[1].cap < 1 || c->m[0].cap < 1 || c->m[1].cap < 1) return VILF_ERR_INVALID_ARGUMENT;
     if (stream < -1 || sid >= c->S || nn[0] > c->sc[0].cap || nn[1] > c->sc[1].cap) return VILF_ERR_INVALID_ARGUMENT;

@@ -61,22 +61,16 @@ __global__ void sc_ringkey_topk(ScDb db, ScQuery Q, int *cand);
 __global__ void sc_distance(ScDb db, ScQuery Q, int shift_radius, const int *cand, double *slot_d, int2 *slot_js);
 __global__ void sc_reduce(ScDb db, ScQuery Q, int nslots, double thres, const int *cand, const double *slot_d, const int2 *slot_js, vilf_sc_result *res);
 
-struct ScCtx {
+struct ScCtx : VilfStage {
     vilf_sc_params p;
     int capacity = 0, size = 0;
     long calls = 0;                    // tree_making_period_conter (:327)
     int snap = 0;                      // size of polarcontext_invkeys_to_search_
     DBuf desc, nrm, rkey, skey, norm, mask, pts, off, cand, slot_d, slot_js, res;
-    double ms[4] = {0, 0, 0, 0};       // vilf_set_profiling: sc_descriptor, sc_ringkey_topk, sc_distance, sc_reduce
-    long launches[4] = {0, 0, 0, 0};
+    StageProf<4> prof;                 // vilf_set_profiling: sc_descriptor, sc_ringkey_topk, sc_distance, sc_reduce
+    void profile_reset() override { prof.reset(); }
     ScDb db() { return ScDb{desc.as<double>(), nrm.as<double>(), rkey.as<float>(), skey.as<double>(), norm.as<double>(), mask.as<unsigned long long>()}; }
-    void release() {
-        DBuf *all[] = {&desc, &nrm, &rkey, &skey, &norm, &mask, &pts, &off, &cand, &slot_d, &slot_js, &res};
-        for (DBuf *b : all) b->release();
-    }
 };
-void vilf_sc_profile_reset(vilf_handle *h) { if (h->sc) for (int i = 0; i < 4; i++) { h->sc->ms[i] = 0; h->sc->launches[i] = 0; } }
-void vilf_sc_release(vilf_handle *h) { if (h->sc) { h->sc->release(); delete h->sc; h->sc = nullptr; } }
 
 namespace {
 #define SC_WSYNC __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier()
@@ -306,23 +300,23 @@ extern "C" int vilf_sc_create(vilf_handle *h, const vilf_sc_params *p, int capac
     }
     HIPCHECK(h, hipSetDevice(h->device));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
-    vilf_sc_release(h);
+    vilf_stage_drop(h, ST_SC);
     ScCtx *c = new ScCtx();
     c->p = d; c->capacity = capacity;
     const size_t n = (size_t)capacity;
     if (!c->desc.ensure(n * SC_BINS * 8) || !c->nrm.ensure(n * SC_NRM * 8) || !c->rkey.ensure(n * SC_RINGS * 4) || !c->skey.ensure(n * SC_SECTORS * 8) ||
         !c->norm.ensure(n * SC_SECTORS * 8) || !c->mask.ensure(n * 8)) {
-        c->release(); delete c;
+        delete c;
         h->err = "hipMalloc failed (scan context database)";
         return VILF_ERR_DEVICE;
     }
-    h->sc = c;
+    h->stage[ST_SC] = c;
     return VILF_OK;
 }
 
 extern "C" int vilf_sc_add_keyframes(vilf_handle *h, int n, const float *xyzi, const int *offsets, int *first_index_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    ScCtx *c = h->sc;
+    ScCtx *c = vilf_stage<ScCtx>(h, ST_SC);
     if (!c) { h->err = "vilf_sc_add_keyframes: no database (vilf_sc_create)"; return VILF_ERR_INVALID_ARGUMENT; }
     if (n < 0 || !offsets || offsets[0] < 0) { h->err = "vilf_sc_add_keyframes: bad arguments"; return VILF_ERR_INVALID_ARGUMENT; }
     for (int i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) { h->err = "vilf_sc_add_keyframes: offsets must not decrease"; return VILF_ERR_INVALID_ARGUMENT; }
@@ -338,10 +332,10 @@ extern "C" int vilf_sc_add_keyframes(vilf_handle *h, int n, const float *xyzi, c
     if (!c->pts.ensure(std::max<size_t>(total, 1) * 16) || !c->off.ensure((size_t)(n + 1) * 4)) { h->err = "hipMalloc failed (scan context clouds)"; return VILF_ERR_DEVICE; }
     if (total > 0) HIPCHECK(h, hipMemcpyAsync(c->pts.p, xyzi, (size_t)total * 16, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(h, hipMemcpyAsync(c->off.p, offsets, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, h->stream));
-    hipEvent_t e0 = h->profiling ? vilf_prof_event(h) : nullptr;
+    ProfMarks prof(h, c->prof);
     hipLaunchKernelGGL(sc_descriptor, dim3(n), dim3(SC_DESC_NT), 0, h->stream, c->pts.as<float4>(), c->off.as<int>(), c->size, c->db(), c->p.max_radius, c->p.lidar_height);
     HIPCHECK(h, hipGetLastError());
-    if (h->profiling) vilf_prof_span(h, e0, vilf_prof_event(h), &c->ms[0], &c->launches[0]);
+    prof.mark(0);
     HIPCHECK(h, hipStreamSynchronize(h->stream));       // the caller's clouds are free again; a fault of the launch is reported by this call
     if (h->profiling) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
     c->size += n;
@@ -367,24 +361,22 @@ static int sc_search(vilf_handle *h, ScCtx *c, int first, int n, int fixed_snap,
         h->err = "hipMalloc failed (scan context search)";
         return VILF_ERR_DEVICE;
     }
-    const bool prof = h->profiling != 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (prof) ev[0] = vilf_prof_event(h);
+    ProfMarks prof(h, c->prof);
     if (Q.k && max_cand > 0) hipLaunchKernelGGL(sc_ringkey_topk, dim3(n), dim3(SC_TOPK_NT), 0, h->stream, c->db(), Q, c->cand.as<int>());
-    if (prof) ev[1] = vilf_prof_event(h);
+    prof.mark(1);
     if (max_cand > 0) hipLaunchKernelGGL(sc_distance, dim3(n, gy), dim3(SC_DIST_NT), 0, h->stream, c->db(), Q, shift_radius, c->cand.as<int>(), c->slot_d.as<double>(), c->slot_js.as<int2>());
-    if (prof) ev[2] = vilf_prof_event(h);
+    prof.mark(2);
     hipLaunchKernelGGL(sc_reduce, dim3(n), dim3(SC_RED_NT), 0, h->stream, c->db(), Q, nslots, c->p.dist_thres, c->cand.as<int>(), c->slot_d.as<double>(), c->slot_js.as<int2>(), c->res.as<vilf_sc_result>());
     HIPCHECK(h, hipGetLastError());
-    if (prof) { ev[3] = vilf_prof_event(h); for (int k = 0; k < 3; k++) vilf_prof_span(h, ev[k], ev[k + 1], &c->ms[1 + k], &c->launches[1 + k]); }
+    prof.mark(3);
     HIPCHECK(h, vilf_copy_sync(h, out, c->res.p, sn * sizeof(vilf_sc_result), hipMemcpyDeviceToHost));
-    if (prof) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
+    if (h->profiling) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
     return VILF_OK;
 }
 
 extern "C" int vilf_sc_detect(vilf_handle *h, vilf_sc_result *out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    ScCtx *c = h->sc;
+    ScCtx *c = vilf_stage<ScCtx>(h, ST_SC);
     if (!c || !out) { h->err = "vilf_sc_detect: no database (vilf_sc_create) or null result"; return VILF_ERR_INVALID_ARGUMENT; }
     if (c->size == 0) { h->err = "vilf_sc_detect: the database is empty"; return VILF_ERR_INVALID_ARGUMENT; }
     if (c->size < c->p.num_exclude_recent + 1) {        // the early return (:221-225): the call is not counted
@@ -399,7 +391,7 @@ extern "C" int vilf_sc_detect(vilf_handle *h, vilf_sc_result *out) {
 
 extern "C" int vilf_sc_detect_range(vilf_handle *h, int first, int n, vilf_sc_result *out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    ScCtx *c = h->sc;
+    ScCtx *c = vilf_stage<ScCtx>(h, ST_SC);
     if (!c) { h->err = "vilf_sc_detect_range: no database (vilf_sc_create)"; return VILF_ERR_INVALID_ARGUMENT; }
     if (first < 0 || n < 0 || (long)first + n > c->size || (n > 0 && !out)) { h->err = "vilf_sc_detect_range: range outside the database or null result"; return VILF_ERR_INVALID_ARGUMENT; }
     if (n == 0) return VILF_OK;
@@ -408,7 +400,7 @@ extern "C" int vilf_sc_detect_range(vilf_handle *h, int first, int n, vilf_sc_re
 
 extern "C" int vilf_sc_get(vilf_handle *h, int index, double *desc, float *ring_key, double *sector_key) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    ScCtx *c = h->sc;
+    ScCtx *c = vilf_stage<ScCtx>(h, ST_SC);
     if (!c || index < 0 || index >= c->size) { h->err = "vilf_sc_get: no database or index out of range"; return VILF_ERR_INVALID_ARGUMENT; }
     HIPCHECK(h, hipSetDevice(h->device));
     const size_t i = (size_t)index;
@@ -421,13 +413,9 @@ extern "C" int vilf_sc_get(vilf_handle *h, int index, double *desc, float *ring_
 
 extern "C" int vilf_sc_size(vilf_handle *h, int *n_out) {
     if (!h || !n_out) return VILF_ERR_INVALID_ARGUMENT;
-    *n_out = h->sc ? h->sc->size : 0;
+    const ScCtx *c = vilf_stage<ScCtx>(h, ST_SC);
+    *n_out = c ? c->size : 0;
     return VILF_OK;
 }
 
-extern "C" int vilf_get_profile_sc(vilf_handle *h, double ms_out[4], long launches_out[4]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < 4; i++) { ms_out[i] = h->sc ? h->sc->ms[i] : 0.0; launches_out[i] = h->sc ? h->sc->launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_get_profile_sc(vilf_handle *h, double ms_out[4], long launches_out[4]) { return vilf_stage_profile(h, ST_SC, &ScCtx::prof, ms_out, launches_out); }

@@ -42,23 +42,15 @@ static_assert(SF_MAXN * 12 + SF_MAXN * 8 <= 4 * SF_JROWS * TK_F_LANES * 8 && (SF
 __global__ void su_sfm_chain(SfDev d, SfPar p);
 __global__ void su_pnp_batch(SfPnpDev d, SfPar p);
 
-struct SfmCtx {
-    DBuf in, out, pin, pout;
-    PinBuf up, down, pup, pdown;
+struct SfmCtx : VilfStage {
+    StageIO io, pnp;                        // the chain's staging, the PnP batch's
     int last_windows = 0;
-    double ms[2] = {0, 0};
-    long launches[2] = {0, 0};
+    StageProf<2> prof;
     bool attr = false;
-    void release() { in.release(); out.release(); pin.release(); pout.release(); up.release(); down.release(); pup.release(); pdown.release(); }
+    void profile_reset() override { prof.reset(); }
 };
-void vilf_sfm_profile_reset(vilf_handle *h) {
-    if (!h->sfm) return;
-    for (int i = 0; i < 2; i++) { h->sfm->ms[i] = 0; h->sfm->launches[i] = 0; }
-}
-void vilf_sfm_release(vilf_handle *h) { if (h->sfm) { h->sfm->release(); delete h->sfm; h->sfm = nullptr; } }
 
 namespace {
-VD double sf_dot3(double a0, double b0, double a1, double b1, double a2, double b2) { return __dadd_rn(__dadd_rn(__dmul_rn(a0, b0), __dmul_rn(a1, b1)), __dmul_rn(a2, b2)); }
 
 // the paragraph "sums": the butterfly within the wave, then waves 0 + 1 + 2 + 3; red [4][K]. Every thread returns with the same K sums.
 template <int K> VD void sf_total(double (&v)[K], double *red, int tid) {
@@ -79,7 +71,7 @@ template <int K> VD void sf_total(double (&v)[K], double *red, int tid) {
 VD void sf_residual(const double *R, const double *t, const float *X, float2 u, double *q, double &iz, double &xn, double &yn, double &e0, double &e1) {
     const double X0 = (double)X[0], X1 = (double)X[1], X2 = (double)X[2];
 #pragma unroll
-    for (int r = 0; r < 3; r++) q[r] = sf_dot3(R[r * 3], X0, R[r * 3 + 1], X1, R[r * 3 + 2], X2);
+    for (int r = 0; r < 3; r++) q[r] = vilf_dot3(R[r * 3], X0, R[r * 3 + 1], X1, R[r * 3 + 2], X2);
     const double p0 = __dadd_rn(q[0], t[0]), p1 = __dadd_rn(q[1], t[1]), p2 = __dadd_rn(q[2], t[2]);
     iz = __ddiv_rn(1.0, p2); xn = __dmul_rn(p0, iz); yn = __dmul_rn(p1, iz);
     e0 = __dsub_rn(xn, (double)u.x); e1 = __dsub_rn(yn, (double)u.y);
@@ -178,7 +170,7 @@ VD bool sf_pnp(const float *sX, const float2 *su, int m, int min_count, const Sf
 #pragma unroll
         for (int r = 0; r < 3; r++) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) Rn[r * 3 + c] = sf_dot3(Q[r * 3], R[c], Q[r * 3 + 1], R[3 + c], Q[r * 3 + 2], R[6 + c]);
+            for (int c = 0; c < 3; c++) Rn[r * 3 + c] = vilf_dot3(Q[r * 3], R[c], Q[r * 3 + 1], R[3 + c], Q[r * 3 + 2], R[6 + c]);
             tn[r] = __dadd_rn(t[r], x[3 + r]);
         }
         const double cn = sf_cost(Rn, tn, sX, su, m, red2, tid);      // evaluated for a rejected pivot too (the barrier inside is met by all); its value is then not used
@@ -212,7 +204,7 @@ VD void sf_write_row(vilf_startup_frame *o, const SfRow &row, const double *R, c
 #pragma unroll
         for (int c = 0; c < 3; c++) { o->R[r * 3 + c] = pose ? R[r * 3 + c] : 0.0; o->Q[r * 3 + c] = pose ? R[c * 3 + r] : 0.0; }
         o->t[r] = pose ? t[r] : 0.0;
-        o->T[r] = pose ? -sf_dot3(R[r], t[0], R[3 + r], t[1], R[6 + r], t[2]) : 0.0;
+        o->T[r] = pose ? -vilf_dot3(R[r], t[0], R[3 + r], t[1], R[6 + r], t[2]) : 0.0;
     }
 }
 }  // namespace
@@ -251,7 +243,7 @@ __global__ __launch_bounds__(SF_NT) void su_sfm_chain(SfDev d, SfPar p) {
 #pragma unroll
                 for (int c = 0; c < 3; c++) { Rl[r * 3 + c] = r == c ? 1.0 : 0.0; Rn[r * 3 + c] = R[c * 3 + r]; }
                 tl[r] = 0.0;
-                tn[r] = -sf_dot3(R[r], T[0], R[3 + r], T[1], R[6 + r], T[2]);
+                tn[r] = -vilf_dot3(R[r], T[0], R[3 + r], T[1], R[6 + r], T[2]);
             }
 #pragma unroll
             for (int r = 0; r < 3; r++) {
@@ -395,13 +387,13 @@ __global__ __launch_bounds__(SF_NT) void su_pnp_batch(SfPnpDev d, SfPar p) {
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 namespace {
-size_t sf_align(size_t v) { return (v + 255) & ~(size_t)255; }
 // the download of a chain call: the results, the rows, the state, the positions
 struct SfOut { size_t res, rows, state, pos, bytes; };
 SfOut sf_out(int W) {
+    Layout l;
     SfOut o;
-    o.res = 0; o.rows = sf_align((size_t)W * sizeof(vilf_startup_structure)); o.state = sf_align(o.rows + (size_t)W * SF_MAXF * sizeof(vilf_startup_frame));
-    o.pos = sf_align(o.state + (size_t)W * SF_MAXN); o.bytes = o.pos + (size_t)W * SF_MAXN * 24;
+    o.res = l.take((size_t)W * sizeof(vilf_startup_structure)); o.rows = l.take((size_t)W * SF_MAXF * sizeof(vilf_startup_frame)); o.state = l.take((size_t)W * SF_MAXN);
+    o.pos = l.take((size_t)W * SF_MAXN * 24); o.bytes = l.at;
     return o;
 }
 bool sf_params_ok(const vilf_startup_sfm_params *p) {
@@ -423,7 +415,7 @@ extern "C" void vilf_startup_default_sfm_params(vilf_startup_sfm_params *p) {
 
 // validation, upload and launch of the chain into the buffers given; nothing is waited for and nothing comes back (vilf_startup_sfm, vilf_startup_construct)
 int vilf_sfm_enqueue(vilf_handle *h, const char *who, const vilf_startup_sfm_params *p, int n_windows, const vilf_startup_window *windows, const vilf_startup_result *rel,
-                     VilfSfmBufs bufs, size_t extra_out, VilfSfmQueued *q) {
+                     StageIO *io, size_t extra_out, VilfSfmQueued *q) {
     const std::string name(who);
     if (n_windows < 1 || n_windows > VILF_STARTUP_MAX_WINDOWS) { h->err = name + ": 1 <= n_windows <= VILF_STARTUP_MAX_WINDOWS"; return VILF_ERR_INVALID_ARGUMENT; }
     if (!sf_params_ok(p)) { h->err = name + SF_PARAMS_TEXT; return VILF_ERR_INVALID_ARGUMENT; }
@@ -438,17 +430,18 @@ int vilf_sfm_enqueue(vilf_handle *h, const char *who, const vilf_startup_sfm_par
         if (!fin) { h->err = name + ": a relative_R or relative_T that is not finite"; return VILF_ERR_INVALID_ARGUMENT; }
     }
     HIPCHECK(h, hipSetDevice(h->device));
-    if (!h->sfm) h->sfm = new SfmCtx();
-    SfmCtx *c = h->sfm;
+    SfmCtx *c = vilf_stage_make<SfmCtx>(h, ST_SFM);
     const int W = n_windows;
     // upload: the windows' integers, l of every window (padded to 8 bytes), the relative poses, then all points
-    const size_t o_l = (size_t)W * SF_WIN_INTS * 4, o_rel = o_l + (size_t)((W + 1) & ~1) * 4, o_pts = o_rel + (size_t)W * 96, in_bytes = o_pts + std::max<size_t>(total, 1) * 16;
+    Layout li;
+    li.take((size_t)W * SF_WIN_INTS * 4, 8);
+    const size_t o_l = li.take((size_t)((W + 1) & ~1) * 4, 8), o_rel = li.take((size_t)W * 96, 8), o_pts = li.take(std::max<size_t>(total, 1) * 16, 8), in_bytes = li.at;
     const SfOut o = sf_out(W);
-    if (!bufs.in->ensure(in_bytes) || !bufs.out->ensure(o.bytes + extra_out) || !bufs.up->ensure(in_bytes) || !bufs.down->ensure(o.bytes + extra_out)) {
+    if (!io->ensure(in_bytes, o.bytes + extra_out)) {
         h->err = name + ": out of memory"; return VILF_ERR_DEVICE;
     }
     {
-        char *ub = (char *)bufs.up->p;
+        char *ub = (char *)io->up.p;
         vilf_startup_pack_windows(W, windows, (int *)ub, (double *)(ub + o_pts));
         int *lw = (int *)(ub + o_l);
         double *rl = (double *)(ub + o_rel);
@@ -463,16 +456,14 @@ int vilf_sfm_enqueue(vilf_handle *h, const char *who, const vilf_startup_sfm_par
         HIPCHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(su_sfm_chain), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SF_LDS_BYTES));
         c->attr = true;
     }
-    HIPCHECK(h, hipMemcpyAsync(bufs.in->p, bufs.up->p, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, io->upload(h, in_bytes));
     SfDev d;
-    char *ib = bufs.in->as<char>(), *ob = bufs.out->as<char>();
+    char *ib = io->in.as<char>(), *ob = io->out.as<char>();
     d.win = (const int *)ib; d.l = (const int *)(ib + o_l); d.rel = (const double *)(ib + o_rel); d.pts = (const double *)(ib + o_pts);
     d.res = (vilf_startup_structure *)(ob + o.res); d.rows = (vilf_startup_frame *)(ob + o.rows); d.state = (unsigned char *)(ob + o.state); d.pos = (double *)(ob + o.pos);
-    const bool prof = h->profiling != 0;
-    hipEvent_t ev[2];
-    if (prof) ev[0] = vilf_prof_event(h);
+    ProfMarks prof(h, c->prof);
     hipLaunchKernelGGL(su_sfm_chain, dim3(W), dim3(SF_NT), SF_LDS_BYTES, h->stream, d, sf_par(p));
-    if (prof) { ev[1] = vilf_prof_event(h); vilf_prof_span(h, ev[0], ev[1], &c->ms[0], &c->launches[0]); }
+    prof.mark(0);
     HIPCHECK(h, hipGetLastError());
     q->win = d.win; q->pts = d.pts; q->l = d.l; q->res = d.res; q->rows = d.rows; q->state = d.state; q->pos = d.pos;
     q->o_res = o.res; q->o_rows = o.rows; q->o_state = o.state; q->o_pos = o.pos; q->out_bytes = o.bytes;
@@ -483,16 +474,14 @@ extern "C" int vilf_startup_sfm(vilf_handle *h, const vilf_startup_sfm_params *p
                                 vilf_startup_structure *out, vilf_startup_frame *frames_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
     if (!p || !windows || !rel || !out) { h->err = "vilf_startup_sfm: null pointer"; return VILF_ERR_INVALID_ARGUMENT; }
-    if (!h->sfm) h->sfm = new SfmCtx();
-    SfmCtx *c = h->sfm;
+    SfmCtx *c = vilf_stage_make<SfmCtx>(h, ST_SFM);
     const int kept = c->last_windows;
     c->last_windows = 0;
-    VilfSfmBufs bufs = {&c->in, &c->out, &c->up, &c->down};
     VilfSfmQueued q;
-    { const int rcq = vilf_sfm_enqueue(h, "vilf_startup_sfm", p, n_windows, windows, rel, bufs, 0, &q); if (rcq != VILF_OK) { if (rcq == VILF_ERR_INVALID_ARGUMENT) c->last_windows = kept; return rcq; } }
+    { const int rcq = vilf_sfm_enqueue(h, "vilf_startup_sfm", p, n_windows, windows, rel, &c->io, 0, &q); if (rcq != VILF_OK) { if (rcq == VILF_ERR_INVALID_ARGUMENT) c->last_windows = kept; return rcq; } }
     const int W = n_windows;
-    HIPCHECK(h, vilf_copy_sync(h, c->down.p, c->out.p, q.out_bytes, hipMemcpyDeviceToHost));
-    const char *hb = (const char *)c->down.p;
+    HIPCHECK(h, c->io.download(h, q.out_bytes));
+    const char *hb = (const char *)c->io.down.p;
     std::memcpy(out, hb + q.o_res, (size_t)W * sizeof(vilf_startup_structure));
     if (frames_out) std::memcpy(frames_out, hb + q.o_rows, (size_t)W * SF_MAXF * sizeof(vilf_startup_frame));
     c->last_windows = W;
@@ -501,12 +490,12 @@ extern "C" int vilf_startup_sfm(vilf_handle *h, const vilf_startup_sfm_params *p
 
 extern "C" int vilf_startup_get_structure(vilf_handle *h, int n_windows, unsigned char *state_out, double *positions_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    SfmCtx *c = h->sfm;
+    SfmCtx *c = vilf_stage<SfmCtx>(h, ST_SFM);
     if (!c || c->last_windows < 1 || n_windows != c->last_windows) {
         h->err = "vilf_startup_get_structure: n_windows is not that of the last vilf_startup_sfm"; return VILF_ERR_INVALID_ARGUMENT;
     }
     const SfOut o = sf_out(n_windows);
-    const char *hb = (const char *)c->down.p;
+    const char *hb = (const char *)c->io.down.p;
     if (state_out) std::memcpy(state_out, hb + o.state, (size_t)n_windows * SF_MAXN);
     if (positions_out) std::memcpy(positions_out, hb + o.pos, (size_t)n_windows * SF_MAXN * 24);
     return VILF_OK;
@@ -531,14 +520,15 @@ extern "C" int vilf_startup_pnp(vilf_handle *h, const vilf_startup_sfm_params *p
         total += (size_t)q.n;
     }
     HIPCHECK(h, hipSetDevice(h->device));
-    if (!h->sfm) h->sfm = new SfmCtx();
-    SfmCtx *c = h->sfm;
+    SfmCtx *c = vilf_stage_make<SfmCtx>(h, ST_SFM);
     const int B = n_problems;
     const size_t rows = std::max<size_t>(total, 1);
-    const size_t o_guess = (size_t)B * 16, o_p3 = o_guess + (size_t)B * 96, o_p2 = o_p3 + rows * 24, in_bytes = o_p2 + rows * 16, out_bytes = (size_t)B * sizeof(vilf_startup_frame);
-    if (!c->pin.ensure(in_bytes) || !c->pout.ensure(out_bytes) || !c->pup.ensure(in_bytes) || !c->pdown.ensure(out_bytes)) { h->err = "vilf_startup_pnp: out of memory"; return VILF_ERR_DEVICE; }
+    Layout li;
+    li.take((size_t)B * 16, 8);
+    const size_t o_guess = li.take((size_t)B * 96, 8), o_p3 = li.take(rows * 24, 8), o_p2 = li.take(rows * 16, 8), in_bytes = li.at, out_bytes = (size_t)B * sizeof(vilf_startup_frame);
+    if (!c->pnp.ensure(in_bytes, out_bytes)) { h->err = "vilf_startup_pnp: out of memory"; return VILF_ERR_DEVICE; }
     {
-        char *ub = (char *)c->pup.p;
+        char *ub = (char *)c->pnp.up.p;
         int *pi = (int *)ub;
         double *g = (double *)(ub + o_guess), *p3 = (double *)(ub + o_p3), *p2 = (double *)(ub + o_p2);
         size_t at = 0;
@@ -550,25 +540,18 @@ extern "C" int vilf_startup_pnp(vilf_handle *h, const vilf_startup_sfm_params *p
             at += (size_t)q.n;
         }
     }
-    HIPCHECK(h, hipMemcpyAsync(c->pin.p, c->pup.p, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, c->pnp.upload(h, in_bytes));
     SfPnpDev d;
-    char *ib = c->pin.as<char>();
+    char *ib = c->pnp.in.as<char>();
     d.prob = (const int *)ib; d.guess = (const double *)(ib + o_guess); d.pts3 = (const double *)(ib + o_p3); d.pts2 = (const double *)(ib + o_p2);
-    d.rows = c->pout.as<vilf_startup_frame>();
-    const bool prof = h->profiling != 0;
-    hipEvent_t ev[2];
-    if (prof) ev[0] = vilf_prof_event(h);
+    d.rows = c->pnp.out.as<vilf_startup_frame>();
+    ProfMarks prof(h, c->prof);
     hipLaunchKernelGGL(su_pnp_batch, dim3(B), dim3(SF_NT), 0, h->stream, d, sf_par(p));
-    if (prof) { ev[1] = vilf_prof_event(h); vilf_prof_span(h, ev[0], ev[1], &c->ms[1], &c->launches[1]); }
+    prof.mark(1);
     HIPCHECK(h, hipGetLastError());
-    HIPCHECK(h, vilf_copy_sync(h, c->pdown.p, c->pout.p, out_bytes, hipMemcpyDeviceToHost));
-    std::memcpy(out, c->pdown.p, out_bytes);
+    HIPCHECK(h, c->pnp.download(h, out_bytes));
+    std::memcpy(out, c->pnp.down.p, out_bytes);
     return VILF_OK;
 }
 
-extern "C" int vilf_startup_sfm_profile(vilf_handle *h, double ms_out[2], long launches_out[2]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < 2; i++) { ms_out[i] = h->sfm ? h->sfm->ms[i] : 0.0; launches_out[i] = h->sfm ? h->sfm->launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_startup_sfm_profile(vilf_handle *h, double ms_out[2], long launches_out[2]) { return vilf_stage_profile(h, ST_SFM, &SfmCtx::prof, ms_out, launches_out); }

@@ -43,19 +43,13 @@ __global__ void su_hypotheses(SuDev d, SuPar p);
 __global__ void su_score(SuDev d, SuPar p);
 __global__ void su_pose(SuDev d, SuPar p);
 
-struct StartupCtx {
-    DBuf in, work, out;
-    PinBuf up, down;
+struct StartupCtx : VilfStage {
+    StageIO io;
+    DBuf work;
     int last_windows = 0;
-    double ms[SU_STAGES] = {0, 0, 0, 0};
-    long launches[SU_STAGES] = {0, 0, 0, 0};
-    void release() { in.release(); work.release(); out.release(); up.release(); down.release(); }
+    StageProf<SU_STAGES> prof;
+    void profile_reset() override { prof.reset(); }
 };
-void vilf_startup_profile_reset(vilf_handle *h) {
-    if (!h->su) return;
-    for (int i = 0; i < SU_STAGES; i++) { h->su->ms[i] = 0; h->su->launches[i] = 0; }
-}
-void vilf_startup_release(vilf_handle *h) { if (h->su) { h->su->release(); delete h->su; h->su = nullptr; } }
 
 namespace {
 VD bool su_searched(int flags) { return (flags & (VILF_SU_COUNT | VILF_SU_PARALLAX | VILF_SU_SOLVE_COUNT)) == (VILF_SU_COUNT | VILF_SU_PARALLAX | VILF_SU_SOLVE_COUNT); }
@@ -229,7 +223,7 @@ __global__ __launch_bounds__(64) void su_pose(SuDev d, SuPar p) {
         for (int r = 0; r < 3; r++) {
 #pragma unroll
             for (int c = 0; c < 3; c++) row->R[r * 3 + c] = Rc[c * 3 + r];             // Rotation = R^T
-            row->T[r] = chosen >= 0 ? -su_dot3(Rc[r], tc[0], Rc[3 + r], tc[1], Rc[6 + r], tc[2]) : 0.0;
+            row->T[r] = chosen >= 0 ? -vilf_dot3(Rc[r], tc[0], Rc[3 + r], tc[1], Rc[6 + r], tc[2]) : 0.0;
         }
         if (flags == VILF_SU_PASS) atomicMin(d.lwin + w, i);
     }
@@ -237,14 +231,14 @@ __global__ __launch_bounds__(64) void su_pose(SuDev d, SuPar p) {
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 namespace {
-size_t su_align(size_t v) { return (v + 255) & ~(size_t)255; }
 // the download: l of every window, the rows, then the per-correspondence arrays
 struct SuOut { size_t lwin, rows, feat, mask, points, bytes; };
 SuOut su_out(int W) {
     const size_t slots = (size_t)W * SU_NP;
+    Layout l;
     SuOut o;
-    o.lwin = 0; o.rows = su_align((size_t)W * 4); o.feat = su_align(o.rows + slots * sizeof(vilf_startup_pair)); o.mask = su_align(o.feat + slots * SU_MAXN * 4);
-    o.points = su_align(o.mask + slots * SU_MAXN); o.bytes = o.points + slots * SU_MAXN * 24;
+    o.lwin = l.take((size_t)W * 4); o.rows = l.take(slots * sizeof(vilf_startup_pair)); o.feat = l.take(slots * SU_MAXN * 4); o.mask = l.take(slots * SU_MAXN);
+    o.points = l.take(slots * SU_MAXN * 24); o.bytes = l.at;
     return o;
 }
 bool su_finite_pos(double v) { return std::isfinite(v) && v > 0; }
@@ -311,23 +305,23 @@ extern "C" int vilf_startup_relative_pose(vilf_handle *h, const vilf_startup_par
     size_t total = 0;
     { const int rcw = vilf_startup_check_windows(h, "vilf_startup_relative_pose", n_windows, windows, &total); if (rcw != VILF_OK) return rcw; }
     HIPCHECK(h, hipSetDevice(h->device));
-    if (!h->su) h->su = new StartupCtx();
-    StartupCtx *c = h->su;
+    StartupCtx *c = vilf_stage_make<StartupCtx>(h, ST_STARTUP);
     c->last_windows = 0;
     const int W = n_windows, K = p->n_hypotheses;
     const size_t slots = (size_t)W * SU_NP;
     // upload: the windows' integers, then all points
     const size_t in_ints = (size_t)W * SU_WIN_INTS * 4, in_bytes = in_ints + std::max<size_t>(total, 1) * 16;
-    const size_t o_ua = 0, o_ub = su_align(o_ua + slots * SU_MAXN * 8), o_ctl = su_align(o_ub + slots * SU_MAXN * 8), o_F = su_align(o_ctl + slots * SC_INTS * 4),
-                 o_valid = su_align(o_F + slots * (size_t)K * 72), work_bytes = o_valid + slots * (size_t)K * 4;
+    Layout lw;
+    const size_t o_ua = lw.take(slots * SU_MAXN * 8), o_ub = lw.take(slots * SU_MAXN * 8), o_ctl = lw.take(slots * SC_INTS * 4), o_F = lw.take(slots * (size_t)K * 72),
+                 o_valid = lw.take(slots * (size_t)K * 4), work_bytes = lw.at;
     const SuOut o = su_out(W);
-    if (!c->in.ensure(in_bytes) || !c->work.ensure(work_bytes) || !c->out.ensure(o.bytes) || !c->up.ensure(in_bytes) || !c->down.ensure(o.bytes)) {
+    if (!c->io.ensure(in_bytes, o.bytes) || !c->work.ensure(work_bytes)) {
         h->err = "vilf_startup_relative_pose: out of memory"; return VILF_ERR_DEVICE;
     }
-    vilf_startup_pack_windows(W, windows, (int *)c->up.p, (double *)((char *)c->up.p + in_ints));
-    HIPCHECK(h, hipMemcpyAsync(c->in.p, c->up.p, in_bytes, hipMemcpyHostToDevice, h->stream));
+    vilf_startup_pack_windows(W, windows, (int *)c->io.up.p, (double *)((char *)c->io.up.p + in_ints));
+    HIPCHECK(h, c->io.upload(h, in_bytes));
     SuDev d;
-    char *ib = c->in.as<char>(), *wb = c->work.as<char>(), *ob = c->out.as<char>();
+    char *ib = c->io.in.as<char>(), *wb = c->work.as<char>(), *ob = c->io.out.as<char>();
     d.win = (const int *)ib; d.pts = (const double *)(ib + in_ints);
     d.ua = (float2 *)(wb + o_ua); d.ub = (float2 *)(wb + o_ub); d.ctl = (int *)(wb + o_ctl); d.F = (double *)(wb + o_F); d.valid = (int *)(wb + o_valid);
     d.lwin = (int *)(ob + o.lwin); d.rows = (vilf_startup_pair *)(ob + o.rows); d.feat = (int *)(ob + o.feat); d.mask = (unsigned char *)(ob + o.mask);
@@ -335,20 +329,18 @@ extern "C" int vilf_startup_relative_pose(vilf_handle *h, const vilf_startup_par
     SuPar sp;
     sp.K = K; sp.seed = p->seed; sp.min_count = p->min_count; sp.min_solve = p->min_solve_count; sp.min_inliers = p->min_inliers;
     sp.thr2 = p->ransac_threshold * p->ransac_threshold; sp.focal = p->focal_length; sp.min_parallax = p->min_parallax; sp.dist = p->distance_threshold;
-    const bool prof = h->profiling != 0;
-    hipEvent_t ev[SU_STAGES + 1];
-    if (prof) ev[0] = vilf_prof_event(h);
+    ProfMarks prof(h, c->prof);
     hipLaunchKernelGGL(su_gather, dim3(SU_NP, W), dim3(SU_NT), 0, h->stream, d, sp);
-    if (prof) ev[1] = vilf_prof_event(h);
+    prof.mark(0);
     hipLaunchKernelGGL(su_hypotheses, dim3((K + TK_F_LANES - 1) / TK_F_LANES, SU_NP, W), dim3(TK_F_LANES), 0, h->stream, d, sp);
-    if (prof) ev[2] = vilf_prof_event(h);
+    prof.mark(1);
     hipLaunchKernelGGL(su_score, dim3((K + SU_SCORE_WAVES - 1) / SU_SCORE_WAVES, SU_NP, W), dim3(64 * SU_SCORE_WAVES), 0, h->stream, d, sp);
-    if (prof) ev[3] = vilf_prof_event(h);
+    prof.mark(2);
     hipLaunchKernelGGL(su_pose, dim3(SU_NP, W), dim3(64), 0, h->stream, d, sp);
-    if (prof) { ev[4] = vilf_prof_event(h); for (int k = 0; k < SU_STAGES; k++) vilf_prof_span(h, ev[k], ev[k + 1], &c->ms[k], &c->launches[k]); }
+    prof.mark(3);
     HIPCHECK(h, hipGetLastError());
-    HIPCHECK(h, vilf_copy_sync(h, c->down.p, c->out.p, o.bytes, hipMemcpyDeviceToHost));
-    const char *hb = (const char *)c->down.p;
+    HIPCHECK(h, c->io.download(h, o.bytes));
+    const char *hb = (const char *)c->io.down.p;
     const int *lwin = (const int *)(hb + o.lwin);
     const vilf_startup_pair *rows = (const vilf_startup_pair *)(hb + o.rows);
     for (int w = 0; w < W; w++) {
@@ -369,22 +361,17 @@ extern "C" int vilf_startup_relative_pose(vilf_handle *h, const vilf_startup_par
 
 extern "C" int vilf_startup_get_correspondences(vilf_handle *h, int n_windows, int *feature_out, unsigned char *mask_out, double *points_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    StartupCtx *c = h->su;
+    StartupCtx *c = vilf_stage<StartupCtx>(h, ST_STARTUP);
     if (!c || c->last_windows < 1 || n_windows != c->last_windows) {
         h->err = "vilf_startup_get_correspondences: n_windows is not that of the last vilf_startup_relative_pose"; return VILF_ERR_INVALID_ARGUMENT;
     }
     const SuOut o = su_out(n_windows);
     const size_t cells = (size_t)n_windows * SU_NP * SU_MAXN;
-    const char *hb = (const char *)c->down.p;
+    const char *hb = (const char *)c->io.down.p;
     if (feature_out) std::memcpy(feature_out, hb + o.feat, cells * 4);
     if (mask_out) std::memcpy(mask_out, hb + o.mask, cells);
     if (points_out) std::memcpy(points_out, hb + o.points, cells * 24);
     return VILF_OK;
 }
 
-extern "C" int vilf_startup_profile(vilf_handle *h, double ms_out[4], long launches_out[4]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < SU_STAGES; i++) { ms_out[i] = h->su ? h->su->ms[i] : 0.0; launches_out[i] = h->su ? h->su->launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_startup_profile(vilf_handle *h, double ms_out[4], long launches_out[4]) { return vilf_stage_profile(h, ST_STARTUP, &StartupCtx::prof, ms_out, launches_out); }

@@ -98,7 +98,7 @@ __global__ void tk_mask_probe(const unsigned char *E, const float2 *fwd, const u
 __global__ void tk_fm_apply(TkF f, int K, const float2 *cur, const float2 *fwd, const int *n_dev, int n_host, TkCam cam, double focal, double half_w, double half_h, double epi, unsigned char *status);   // one workgroup, TK_NT
 __global__ void tk_mask_init(const unsigned char *E, const unsigned char *fish, size_t n, unsigned char *mask);      // 1-D, TK_NT, four pixels per thread
 
-struct TrackCtx {
+struct TrackCtx : VilfStage {
     vilf_track_params p;
     TkPyr pyr[4];                       // [0], [1]: current / next of the tracker (cur says which); [2], [3]: the stateless calls
     int cur = 0, lcur = 0;
@@ -112,29 +112,13 @@ struct TrackCtx {
     PinBuf mstage;                      // a mask on its way to the device
     vilf_track_mask_params mp;          // the defaults after vilf_track_init
     bool has_fish = false;
-    double mk_ms[TK_MK_STAGES] = {0, 0};
-    long mk_launches[TK_MK_STAGES] = {0, 0};
+    StageProf<TK_MK_STAGES> mk_prof;
     vilf_track_frontend fe;             // both off and the defaults after vilf_track_init
-    double fe_ms[TK_FE_STAGES] = {0, 0};
-    long fe_launches[TK_FE_STAGES] = {0, 0};
+    StageProf<TK_FE_STAGES> fe_prof;
     PinBuf pin, stage[4];               // the downloaded list; the image on its way to level 0 of pyramid k
-    double ms[TK_STAGES] = {0, 0, 0, 0, 0};
-    long launches[TK_STAGES] = {0, 0, 0, 0, 0};
-    void release() {
-        DBuf *all[] = {&pyrmem[0], &pyrmem[1], &pyrmem[2], &pyrmem[3], &list[0], &list[1], &tmplist, &ctl, &tmpctl, &prev_ids, &prev_un, &fwd, &status, &lkpts,
-                       &mask, &lam, &cidx, &cidx2, &cval, &key, &key2, &val, &val2, &temp, &raw, &lut, &fmem, &mraw, &er, &fish, &sstatus};
-        for (DBuf *b : all) b->release();
-        pin.release(); mstage.release();
-        for (PinBuf &b : stage) b.release();
-    }
+    StageProf<TK_STAGES> prof;
+    void profile_reset() override { prof.reset(); fe_prof.reset(); mk_prof.reset(); }
 };
-void vilf_track_profile_reset(vilf_handle *h) {
-    if (!h->trk) return;
-    for (int i = 0; i < TK_STAGES; i++) { h->trk->ms[i] = 0; h->trk->launches[i] = 0; }
-    for (int i = 0; i < TK_FE_STAGES; i++) { h->trk->fe_ms[i] = 0; h->trk->fe_launches[i] = 0; }
-    for (int i = 0; i < TK_MK_STAGES; i++) { h->trk->mk_ms[i] = 0; h->trk->mk_launches[i] = 0; }
-}
-void vilf_track_release(vilf_handle *h) { if (h->trk) { h->trk->release(); delete h->trk; h->trk = nullptr; } }
 
 namespace {
 #define TK_WSYNC __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier()
@@ -831,8 +815,9 @@ int tk_detect(vilf_handle *h, TrackCtx *c, const unsigned char *img, const unsig
     return VILF_OK;
 }
 TrackCtx *tk_ctx(vilf_handle *h, const char *who) {
-    if (!h->trk) h->err = std::string(who) + ": no tracker (vilf_track_init)";
-    return h->trk;
+    TrackCtx *c = vilf_stage<TrackCtx>(h, ST_TRACK);
+    if (!c) h->err = std::string(who) + ": no tracker (vilf_track_init)";
+    return c;
 }
 }  // namespace
 
@@ -847,7 +832,7 @@ extern "C" int vilf_track_init(vilf_handle *h, const vilf_track_params *p) {
     if ((long long)p->width * p->height > (1ll << 28)) { h->err = "vilf_track_init: more than 2^28 pixels"; return VILF_ERR_UNSUPPORTED; }
     HIPCHECK(h, hipSetDevice(h->device));
     HIPCHECK(h, hipStreamSynchronize(h->stream));
-    vilf_track_release(h);
+    vilf_stage_drop(h, ST_TRACK);
     TrackCtx *c = new TrackCtx();
     c->p = *p;
     c->fe = tk_fe_defaults();
@@ -875,8 +860,8 @@ extern "C" int vilf_track_init(vilf_handle *h, const vilf_track_params *p) {
          c->key2.ensure(n * 8) && c->val.ensure(n * 4) && c->val2.ensure(n * 4) && c->temp.ensure(std::max(vilf_sort_temp_bytes(n, 8), vilf_sort_temp_bytes(n, 4)) + 256) &&
          c->pin.ensure(tk_list_bytes(TK_MAXN)) && c->raw.ensure(n) && c->lut.ensure((size_t)VILF_TRACK_MAX_TILES * 256) && c->fmem.ensure(TKF_BYTES) &&
          c->mraw.ensure(n) && c->er.ensure(n) && c->fish.ensure(n) && c->sstatus.ensure(TK_MAXN) && c->mstage.ensure(n);
-    if (!ok) { c->release(); delete c; h->err = "hipMalloc failed (feature tracker)"; return VILF_ERR_DEVICE; }
-    h->trk = c;
+    if (!ok) { delete c; h->err = "hipMalloc failed (feature tracker)"; return VILF_ERR_DEVICE; }
+    h->stage[ST_TRACK] = c;
     return vilf_track_reset(h);
 }
 
@@ -897,22 +882,19 @@ namespace {
 // one frame of readImage (mask == null) or readImage_mask: the arguments are checked by the two entry points
 int tk_frame(vilf_handle *h, TrackCtx *c, const unsigned char *img, int row_stride, const unsigned char *mask, int mask_row_stride, double stamp, int *n_out) {
     HIPCHECK(h, hipSetDevice(h->device));
-    const bool prof = h->profiling != 0;
-    if (prof) vilf_track_profile_reset(h);                  // the stages of the last frame
-    hipEvent_t ev[TK_STAGES + 1], fev[2 * TK_FE_STAGES], mev[2 * TK_MK_STAGES];
+    if (h->profiling) c->profile_reset();                   // the stages of the last frame
     const bool eq = c->fe.equalize != 0, rej = !mask && c->fe.reject_f != 0 && c->frames > 0, trk = mask && c->frames > 0;      // the masked entry point has its own rejection
-    auto mark = [&](int k) { if (prof) ev[k] = vilf_prof_event(h); };
     TkPyr &cur = c->pyr[c->cur], &nxt = c->pyr[c->cur ^ 1];
     TkList lc = tk_list(c->list[c->lcur].p, TK_MAXN), ln = tk_list(c->list[c->lcur ^ 1].p, TK_MAXN);
     int *ctl = c->ctl.as<int>();
     const long long md = c->p.min_dist;
-    mark(0);
+    ProfMarks prof(h, c->prof);
     if (eq) {                                                // the raw image into its own buffer, the equalised one straight into level 0
         { const int rc = tk_upload(h, nxt, c->raw.as<unsigned char>(), (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride); if (rc != VILF_OK) return rc; }
         if (mask) { const int rc = tk_upload_mask(h, c, c->mraw.as<unsigned char>(), mask, mask_row_stride); if (rc != VILF_OK) return rc; }
-        if (prof) fev[0] = vilf_prof_event(h);
+        ProfMarks fe(h, c->fe_prof);
         { const int rc = tk_clahe(h, c, c->raw.as<unsigned char>(), nxt.lv[0]); if (rc != VILF_OK) return rc; }
-        if (prof) fev[1] = vilf_prof_event(h);
+        fe.mark(0);
         { const int rc = tk_levels(h, nxt, nxt.lmax); if (rc != VILF_OK) return rc; }
     } else if (mask) {                                       // both uploads in front of the kernels
         { const int rc = tk_upload(h, nxt, nxt.lv[0], (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride); if (rc != VILF_OK) return rc; }
@@ -920,42 +902,37 @@ int tk_frame(vilf_handle *h, TrackCtx *c, const unsigned char *img, int row_stri
         { const int rc = tk_levels(h, nxt, nxt.lmax); if (rc != VILF_OK) return rc; }
     } else { const int rc = tk_build(h, nxt, (unsigned char *)c->stage[c->cur ^ 1].p, img, row_stride, nxt.lmax); if (rc != VILF_OK) return rc; }
     if (mask) {                                              // E serves the probe and the detection, so it is made on the first frame too
-        if (prof) mev[0] = vilf_prof_event(h);
+        ProfMarks mk(h, c->mk_prof);
         { const int rc = tk_erode(h, c, c->mraw.as<unsigned char>(), c->er.as<unsigned char>()); if (rc != VILF_OK) return rc; }
-        if (prof) mev[1] = vilf_prof_event(h);
+        mk.mark(0);
     }
-    mark(1);
+    prof.mark(0);
     if (c->frames > 0)
         hipLaunchKernelGGL(tk_lk, dim3((c->p.max_cnt + TK_LK_WAVES - 1) / TK_LK_WAVES), dim3(64 * TK_LK_WAVES), 0, h->stream, cur, nxt, lc.pts, ctl + TC_N, 0, c->fwd.as<float2>(), c->status.as<unsigned char>(), 1);
     if (rej) {                                               // between the inBorder drop (LK's status) and setMask, which reads the same status bytes
-        if (prof) fev[2] = vilf_prof_event(h);
+        ProfMarks fe(h, c->fe_prof);
         { const int rc = tk_reject(h, c, lc.pts, c->fwd.as<float2>(), c->status.as<unsigned char>(), ctl + TC_N, 0); if (rc != VILF_OK) return rc; }
-        if (prof) fev[3] = vilf_prof_event(h);
+        fe.mark(1);
     }
     if (trk) {                                               // probe -> the static status; the rejection clears LK's status bytes, which tk_setmask reads
-        if (prof) mev[2] = vilf_prof_event(h);
+        ProfMarks mk(h, c->mk_prof);
         hipLaunchKernelGGL(tk_mask_probe, dim3((c->p.max_cnt + TK_NT - 1) / TK_NT), dim3(TK_NT), 0, h->stream, c->er.as<unsigned char>(), c->fwd.as<float2>(), c->status.as<unsigned char>(), ctl + TC_N, 0,
                            c->p.width, c->p.height, c->mp.probe, c->sstatus.as<unsigned char>());
         if (c->mp.reject) { const int rc = tk_reject_mask(h, c, lc.pts, c->fwd.as<float2>(), c->sstatus.as<unsigned char>(), c->status.as<unsigned char>(), ctl + TC_N, 0); if (rc != VILF_OK) return rc; }
-        if (prof) mev[3] = vilf_prof_event(h);
+        mk.mark(1);
     }
-    mark(2);
+    prof.mark(1);
     hipLaunchKernelGGL(tk_setmask, dim3(1), dim3(TK_NT), 0, h->stream, lc, c->fwd.as<float2>(), c->status.as<unsigned char>(), ln, ctl, c->p.max_cnt, md * md,
                        c->has_fish ? c->fish.as<unsigned char>() : (const unsigned char *)nullptr, c->p.width, c->p.height);
     HIPCHECK(h, hipGetLastError());
-    mark(3);
+    prof.mark(2);
     { const int rc = tk_detect(h, c, nxt.lv[0], mask ? c->er.as<unsigned char>() : nullptr, ctl, ln, c->p.max_cnt); if (rc != VILF_OK) return rc; }
-    mark(4);
+    prof.mark(3);
     hipLaunchKernelGGL(tk_finish, dim3(1), dim3(TK_NT), 0, h->stream, ln, ctl, c->prev_ids.as<int>(), c->prev_un.as<float2>(), tk_cam(c->p), stamp - c->t_prev, c->frames > 0 ? 1 : 0);
     HIPCHECK(h, hipGetLastError());
-    mark(5);
-    if (prof) for (int k = 0; k < TK_STAGES; k++) vilf_prof_span(h, ev[k], ev[k + 1], &c->ms[k], &c->launches[k]);
-    if (prof && eq) vilf_prof_span(h, fev[0], fev[1], &c->fe_ms[0], &c->fe_launches[0]);
-    if (prof && rej) vilf_prof_span(h, fev[2], fev[3], &c->fe_ms[1], &c->fe_launches[1]);
-    if (prof && mask) vilf_prof_span(h, mev[0], mev[1], &c->mk_ms[0], &c->mk_launches[0]);
-    if (prof && trk) vilf_prof_span(h, mev[2], mev[3], &c->mk_ms[1], &c->mk_launches[1]);
+    prof.mark(4);
     HIPCHECK(h, vilf_copy_sync(h, c->pin.p, ln.hdr, tk_list_bytes(TK_MAXN), hipMemcpyDeviceToHost));
-    if (prof) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
+    if (h->profiling) { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
     c->cur ^= 1; c->lcur ^= 1; c->frames++; c->t_prev = stamp;
     c->n_host = std::min(std::max(((const int *)c->pin.p)[0], 0), c->p.max_cnt);
     if (n_out) *n_out = c->n_host;
@@ -1068,12 +1045,7 @@ extern "C" int vilf_track_detect_masked(vilf_handle *h, const unsigned char *img
     return tk_detect_call(h, "vilf_track_detect_masked", img, eroded, true, kept_pts, n_kept, n_max, pts_out, n_out);
 }
 
-extern "C" int vilf_track_profile(vilf_handle *h, double ms_out[5], long launches_out[5]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < TK_STAGES; i++) { ms_out[i] = h->trk ? h->trk->ms[i] : 0.0; launches_out[i] = h->trk ? h->trk->launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_track_profile(vilf_handle *h, double ms_out[5], long launches_out[5]) { return vilf_stage_profile(h, ST_TRACK, &TrackCtx::prof, ms_out, launches_out); }
 
 extern "C" int vilf_track_configure(vilf_handle *h, const vilf_track_frontend *fe) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
@@ -1132,12 +1104,7 @@ extern "C" int vilf_track_reject_f(vilf_handle *h, const float *cur_pts, const f
     return VILF_OK;
 }
 
-extern "C" int vilf_track_profile_frontend(vilf_handle *h, double ms_out[2], long launches_out[2]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < TK_FE_STAGES; i++) { ms_out[i] = h->trk ? h->trk->fe_ms[i] : 0.0; launches_out[i] = h->trk ? h->trk->fe_launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_track_profile_frontend(vilf_handle *h, double ms_out[2], long launches_out[2]) { return vilf_stage_profile(h, ST_TRACK, &TrackCtx::fe_prof, ms_out, launches_out); }
 
 extern "C" int vilf_track_configure_mask(vilf_handle *h, const vilf_track_mask_params *mp) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
@@ -1229,9 +1196,4 @@ extern "C" int vilf_track_reject_f_mask(vilf_handle *h, const float *cur_pts, co
     return VILF_OK;
 }
 
-extern "C" int vilf_track_profile_mask(vilf_handle *h, double ms_out[2], long launches_out[2]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    for (int i = 0; i < TK_MK_STAGES; i++) { ms_out[i] = h->trk ? h->trk->mk_ms[i] : 0.0; launches_out[i] = h->trk ? h->trk->mk_launches[i] : 0; }
-    return VILF_OK;
-}
+extern "C" int vilf_track_profile_mask(vilf_handle *h, double ms_out[2], long launches_out[2]) { return vilf_stage_profile(h, ST_TRACK, &TrackCtx::mk_prof, ms_out, launches_out); }

@@ -35,18 +35,14 @@ struct TriDev {
 __global__ void tri_cameras(TriDev d);
 __global__ void tri_solve(TriDev d);
 
-struct TriCtx {
-    DBuf in, cam, out;
-    PinBuf up, down;
-    double ms[1] = {0};
-    long launches[1] = {0};
-    void release() { in.release(); cam.release(); out.release(); up.release(); down.release(); }
+struct TriCtx : VilfStage {
+    StageIO io;
+    DBuf cam;
+    StageProf<1> prof;
+    void profile_reset() override { prof.reset(); }
 };
-void vilf_tri_profile_reset(vilf_handle *h) { if (h->tri) { h->tri->ms[0] = 0; h->tri->launches[0] = 0; } }
-void vilf_tri_release(vilf_handle *h) { if (h->tri) { h->tri->release(); delete h->tri; h->tri = nullptr; } }
 
 namespace {
-VD double tri_dot3(double a0, double b0, double a1, double b1, double a2, double b2) { return __dadd_rn(__dadd_rn(__dmul_rn(a0, b0), __dmul_rn(a1, b1)), __dmul_rn(a2, b2)); }
 // the sum from 0.0 of three products
 VD double tri_sum3(double a0, double b0, double a1, double b1, double a2, double b2) {
     return __dadd_rn(__dadd_rn(__dadd_rn(0.0, __dmul_rn(a0, b0)), __dmul_rn(a1, b1)), __dmul_rn(a2, b2));
@@ -62,7 +58,7 @@ __global__ __launch_bounds__(64) void tri_cameras(TriDev d) {
     double *c = d.cam + (size_t)g * TRI_CAM_DBL;
 #pragma unroll
     for (int r = 0; r < 3; r++) {
-        c[r] = __dadd_rn(P[r], tri_dot3(R[3 * r], tic[0], R[3 * r + 1], tic[1], R[3 * r + 2], tic[2]));
+        c[r] = __dadd_rn(P[r], vilf_dot3(R[3 * r], tic[0], R[3 * r + 1], tic[1], R[3 * r + 2], tic[2]));
 #pragma unroll
         for (int q = 0; q < 3; q++) c[3 + 3 * r + q] = tri_sum3(R[3 * r], ric[q], R[3 * r + 1], ric[3 + q], R[3 * r + 2], ric[6 + q]);
     }
@@ -89,7 +85,7 @@ __global__ __launch_bounds__(TRI_LANES) void tri_solve(TriDev d) {
         for (int e = 0; e < 3; e++) dd[e] = __dsub_rn(cj[e], t0[e]);
 #pragma unroll
         for (int r = 0; r < 3; r++) {
-            t[r] = tri_dot3(R0[r], dd[0], R0[3 + r], dd[1], R0[6 + r], dd[2]);
+            t[r] = vilf_dot3(R0[r], dd[0], R0[3 + r], dd[1], R0[6 + r], dd[2]);
 #pragma unroll
             for (int c = 0; c < 3; c++) R[3 * r + c] = tri_sum3(R0[r], cj[3 + c], R0[3 + r], cj[6 + c], R0[6 + r], cj[9 + c]);
         }
@@ -98,7 +94,7 @@ __global__ __launch_bounds__(TRI_LANES) void tri_solve(TriDev d) {
         for (int r = 0; r < 3; r++) {
 #pragma unroll
             for (int c = 0; c < 3; c++) P[r][c] = R[3 * c + r];
-            P[r][3] = -tri_dot3(R[r], t[0], R[3 + r], t[1], R[6 + r], t[2]);
+            P[r][3] = -vilf_dot3(R[r], t[0], R[3 + r], t[1], R[6 + r], t[2]);
         }
         const double x = pt[3 * o], y = pt[3 * o + 1], z = pt[3 * o + 2];
         const double n = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)), __dmul_rn(z, z)));
@@ -161,7 +157,6 @@ __global__ __launch_bounds__(TRI_LANES) void tri_solve(TriDev d) {
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 namespace {
-size_t tri_align(size_t v) { return (v + 255) & ~(size_t)255; }
 bool tri_used(long long nobs, int start, int window_size) { return nobs >= 2 && start < window_size - 2; }
 bool tri_all_finite(const double *p, int n) { for (int i = 0; i < n; i++) if (!std::isfinite(p[i])) return false; return true; }
 }  // namespace
@@ -200,18 +195,18 @@ extern "C" int vilf_features_triangulate(vilf_handle *h, int n_windows, const vi
         if (cand_here) { n_slots++; n_cand += cand_here; }
     }
     HIPCHECK(h, hipSetDevice(h->device));
-    if (!h->tri) h->tri = new TriCtx();
-    TriCtx *c = h->tri;
+    TriCtx *c = vilf_stage_make<TriCtx>(h, ST_TRI);
     // upload: the poses of the windows that have candidates, the candidate list, the candidates' points. Download: the depths, then flags | sweeps << 8
-    const size_t o_pose = 0, o_cand = tri_align(o_pose + std::max<size_t>(n_slots, 1) * TRI_POSE_DBL * 8), o_pts = tri_align(o_cand + std::max<size_t>(n_cand, 1) * sizeof(int4)),
-                 in_bytes = o_pts + std::max<size_t>(n_rows, 1) * 24;
-    const size_t o_depth = 0, o_meta = tri_align(o_depth + std::max<size_t>(n_cand, 1) * 8), out_bytes = o_meta + std::max<size_t>(n_cand, 1) * 4;
+    Layout li, lo;
+    const size_t o_pose = li.take(std::max<size_t>(n_slots, 1) * TRI_POSE_DBL * 8), o_cand = li.take(std::max<size_t>(n_cand, 1) * sizeof(int4)),
+                 o_pts = li.take(std::max<size_t>(n_rows, 1) * 24), in_bytes = li.at;
+    const size_t o_depth = lo.take(std::max<size_t>(n_cand, 1) * 8), o_meta = lo.take(std::max<size_t>(n_cand, 1) * 4), out_bytes = lo.at;
     const size_t cam_bytes = std::max<size_t>(n_slots, 1) * TRI_NF * TRI_CAM_DBL * 8;
-    if (!c->in.ensure(in_bytes) || !c->cam.ensure(cam_bytes) || !c->out.ensure(out_bytes) || !c->up.ensure(in_bytes) || !c->down.ensure(out_bytes)) {
+    if (!c->io.ensure(in_bytes, out_bytes) || !c->cam.ensure(cam_bytes)) {
         h->err = "vilf_features_triangulate: out of memory"; return VILF_ERR_DEVICE;
     }
     {
-        char *ub = (char *)c->up.p;
+        char *ub = (char *)c->io.up.p;
         double *pose = (double *)(ub + o_pose), *pts = (double *)(ub + o_pts);
         int4 *cand = (int4 *)(ub + o_cand);
         size_t slot = 0, at = 0, row = 0;
@@ -237,25 +232,23 @@ extern "C" int vilf_features_triangulate(vilf_handle *h, int n_windows, const vi
         }
     }
     if (n_cand > 0) {
-        HIPCHECK(h, hipMemcpyAsync(c->in.p, c->up.p, in_bytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(h, c->io.upload(h, in_bytes));
         TriDev d;
-        char *ib = c->in.as<char>(), *ob = c->out.as<char>();
+        char *ib = c->io.in.as<char>(), *ob = c->io.out.as<char>();
         d.pose = (const double *)(ib + o_pose); d.cand = (const int4 *)(ib + o_cand); d.pts = (const double *)(ib + o_pts);
         d.cam = c->cam.as<double>(); d.depth = (double *)(ob + o_depth); d.meta = (unsigned *)(ob + o_meta);
         d.n_slots = (int)n_slots; d.n_cand = (int)n_cand; d.init_depth = init_depth;
-        const bool prof = h->profiling != 0;
-        hipEvent_t ev[3];
-        if (prof) ev[0] = vilf_prof_event(h);
+        ProfMarks prof(h, c->prof);
         hipLaunchKernelGGL(tri_cameras, dim3((unsigned)((n_slots * TRI_NF + 63) / 64)), dim3(64), 0, h->stream, d);
-        if (prof) ev[1] = vilf_prof_event(h);
+        prof.mark(0);
         hipLaunchKernelGGL(tri_solve, dim3((unsigned)((n_cand + TRI_LANES - 1) / TRI_LANES)), dim3(TRI_LANES), 0, h->stream, d);
-        if (prof) { ev[2] = vilf_prof_event(h); vilf_prof_span(h, ev[0], ev[1], &c->ms[0], &c->launches[0]); vilf_prof_span(h, ev[1], ev[2], &c->ms[0], &c->launches[0]); }
+        prof.mark(0);
         HIPCHECK(h, hipGetLastError());
-        HIPCHECK(h, vilf_copy_sync(h, c->down.p, c->out.p, out_bytes, hipMemcpyDeviceToHost));
+        HIPCHECK(h, c->io.download(h, out_bytes));
     }
     // the outputs in feature order: the candidates' from the download, the others' from the host
-    const double *depth = (const double *)((const char *)c->down.p + o_depth);
-    const unsigned *meta = (const unsigned *)((const char *)c->down.p + o_meta);
+    const double *depth = (const double *)((const char *)c->io.down.p + o_depth);
+    const unsigned *meta = (const unsigned *)((const char *)c->io.down.p + o_meta);
     size_t at = 0;
     for (int w = 0; w < n_windows; w++) {
         const vilf_tri_window &W = windows[w];
@@ -284,9 +277,4 @@ extern "C" int vilf_features_triangulate(vilf_handle *h, int n_windows, const vi
     return VILF_OK;
 }
 
-extern "C" int vilf_features_profile(vilf_handle *h, double ms_out[1], long launches_out[1]) {
-    if (!h || !ms_out || !launches_out) return VILF_ERR_INVALID_ARGUMENT;
-    { const int rcf = vilf_prof_flush(h); if (rcf != VILF_OK) return rcf; }
-    ms_out[0] = h->tri ? h->tri->ms[0] : 0.0; launches_out[0] = h->tri ? h->tri->launches[0] : 0;
-    return VILF_OK;
-}
+extern "C" int vilf_features_profile(vilf_handle *h, double ms_out[1], long launches_out[1]) { return vilf_stage_profile(h, ST_TRI, &TriCtx::prof, ms_out, launches_out); }
