@@ -1265,6 +1265,83 @@ int vilf_kf_fast(vilf_handle *h, const unsigned char *img, int row_stride, int c
 int vilf_kf_brief(vilf_handle *h, const unsigned char *img, int row_stride, const float *pts, int n, unsigned long long *desc_out);
 /* vilf_set_profiling: upload + blur, FAST (score, row counts, scan, placement), descriptors + lift, match, download, summed over the calls since the switch was set */
 int vilf_kf_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
+
+/* ---- Visual loop closure, second stage: PnP-RANSAC and the loop decision (≙ KeyFrame::PnPRANSAC and the end of KeyFrame::findConnection,
+ * pose_graph/keyframe.cpp:200-256, 401-520; device, the decision on the host) ----
+ * What findConnection does after searchByBRIEFDes: the pose of the old key frame from the current key frame's world points and the old key frame's matched lifted
+ * points, and the decision whether the two close a loop. cv::solvePnPRansac draws random samples and OpenCV is not available, so the search is a design of this
+ * project, as rejectWithF's is; tests/kfloop_reference.py restates this text in numpy and the kernels agree with it on every integer and every float bit up to the
+ * pose out (deviations from OpenCV: DESIGN.md §3t). Candidate retrieval, optimize4DoF and the relocalisation factors are not part of this stage.
+ *   geometry     of a key frame: point_3d [n_window][3], the world points of its window features rounded to float32 (cv::Point3f), and origin_vio_R [9] (row-major),
+ *                origin_vio_T [3] in fp64; all finite. The extrinsic qic [9], tic [3] is a parameter of the call. Only the current key frame needs a geometry.
+ *   gate         for an old key frame: S = the window points of cur with match status 1 (first stage, paragraph match), in window order, m = |S|. m <= min_loop_num
+ *                (25, keyframe.h:16; :406): no PnP, no loop. Member j of S: X_j = point_3d of cur, u_j = the matched old key point's keypoints_norm, both float32.
+ *   guess        of cur, fp64, every product and sum rounded on its own, three-term sums left to right: R_w_c = origin_vio_R qic (entry (r, c) =
+ *                (R_r0 q_0c + R_r1 q_1c) + R_r2 q_2c); T_w_c_r = origin_vio_T_r + ((R_r0 tic_0 + R_r1 tic_1) + R_r2 tic_2); R0 = R_w_c^T;
+ *                t0_r = -((R0_r0 T_w_c_0 + R0_r1 T_w_c_1) + R0_r2 T_w_c_2) (:212-216).
+ *   hypotheses   K = n_hypotheses (1 .. VILF_TRACK_MAX_HYPOTHESES, default 256), no adaptive stopping. The sample of hypothesis k is the tracker's rejectWithF
+ *                paragraph "sample" with 5 slots in place of 8 and n = m; the seed of an old key frame is seed + (its key-frame index) (uint32, wrapping): the
+ *                index, not the position in the call, so a candidate's result does not depend on its neighbours in the call. Each hypothesis solves the start-up's
+ *                paragraph solveFrameByPnP ("residual", "Jacobian", "terms", "solve", "candidate", "accept") on its 5 members in slot order, from (R0, t0), with
+ *                lambda0 and hyp_iterations iterations (default 5, 1 .. 64), with one difference: each of the 28 sums, and the candidate's cost, is a plain sum
+ *                from 0.0 in slot order (no 256 partial sums, no butterfly). There is no count gate and a hypothesis is invalid (score -1) unless the nine R and
+ *                three t it ends with are finite. This is OpenCV 2.4's solvePnPRansac (iterative solvePnP on 5-point samples from the extrinsic guess), which the
+ *                reference's CV_MAJOR_VERSION < 3 branch calls; OpenCV 3.x runs EPnP on the sample instead.
+ *   score        with (p_2, e_0, e_1) of the paragraph "residual" (p_2 = q_2 + t_2): member j is an inlier of (R, t) iff p_2 > 0 and e_0 e_0 + e_1 e_1 <= thr2,
+ *                thr2 = reproj_threshold * reproj_threshold in fp64 (default 10.0 / 460.0, :232); a NaN compares false. (OpenCV has no p_2 > 0 test: it is added
+ *                on purpose.) Score = the number of inliers over S. The winner is the valid hypothesis of the highest score, ties to the lower k. No valid
+ *                hypothesis: best_k = -1, every status 0, no loop.
+ *   refit        the status mask is the winner's (OpenCV 3.x reports the model's inliers and refits; so does this). The refit is solveFrameByPnP word for word, 256
+ *                partial sums and butterfly included, with no count gate, on the inliers in S order, from the winner's pose, with lambda0 and refine_iterations (10,
+ *                1 .. 64). If it ends not finite (its cost, R or t), the pose is the winner's and VILF_KFL_REFIT_DROPPED says so; cost0, cost1 and accepted are the
+ *                refit's either way.
+ *   pose out     (:245-254) R_w_c_old = R^T; T_w_c_old_r = -((R_0r t_0 + R_1r t_1) + R_2r t_2); PnP_R_old = R_w_c_old qic^T (entry (r, c) =
+ *                (W_r0 q_c0 + W_r1 q_c1) + W_r2 q_c2); PnP_T_old_r = T_w_c_old_r - ((P_r0 tic_0 + P_r1 tic_1) + P_r2 tic_2), P = PnP_R_old. On the device, fp64,
+ *                each operation rounded.
+ *   decision     (:472-487) on the host in fp64 after the download, only if the inlier count is > min_loop_num. relative_t = PnP_R_old^T (origin_vio_T - PnP_T_old);
+ *                relative_q = the quaternion of PnP_R_old^T origin_vio_R by Eigen's rule (trace > 0: from sqrt(trace + 1); else around the largest diagonal
+ *                entry), as (w, x, y, z); relative_yaw = normalizeAngle(yaw(origin_vio_R) - yaw(PnP_R_old)) in degrees, yaw(R) = atan2(R_10, R_00) * 180 / pi
+ *                (Utility::R2ypr), normalizeAngle(a) = a - 360 floor((a + 180) / 360) for a > 0, else a + 360 floor((-a + 180) / 360). Loop iff
+ *                |relative_yaw| < max_yaw (30.0) and |relative_t| < max_dist (20.0). atan2 is the host's libm: bit agreement with numpy is not claimed here. */
+#define VILF_KFL_GATE 1              /* m <= min_loop_num: no PnP; the row is 0 apart from n_matched and this flag */
+#define VILF_KFL_NO_HYPOTHESIS 2     /* no valid hypothesis */
+#define VILF_KFL_REFIT 4             /* the pose is the refit's */
+#define VILF_KFL_REFIT_DROPPED 8     /* the refit ended not finite: the pose is the winner's */
+#define VILF_KFL_LOOP 16             /* has_loop */
+typedef struct vilf_kf_loop_params {
+    int n_hypotheses;                /* 1 .. VILF_TRACK_MAX_HYPOTHESES; 256 */
+    unsigned seed;
+    int hyp_iterations;              /* 1 .. 64; 5 */
+    int refine_iterations;           /* 1 .. 64; 10 */
+    int min_loop_num;                /* >= 5; 25 (MIN_LOOP_NUM) */
+    int pad_;
+    double lambda0;                  /* 1e-3 */
+    double reproj_threshold;         /* 10.0 / 460.0 */
+    double max_yaw, max_dist;        /* 30.0 degrees, 20.0 */
+    double qic[9], tic[3];           /* the camera-IMU extrinsic; identity and 0 by default */
+} vilf_kf_loop_params;
+typedef struct vilf_kf_loop_result {
+    int n_matched, n_inliers, best_k, flags, has_loop, accepted;
+    double R[9], t[3];               /* the camera pose of the old key frame (world to camera) */
+    double PnP_R_old[9], PnP_T_old[3];
+    double relative_t[3], relative_q[4], relative_yaw;      /* with more than min_loop_num inliers, else 0; q as (w, x, y, z) */
+    double cost0, cost1;             /* the refit's first and last cost */
+} vilf_kf_loop_result;
+void vilf_kf_default_loop_params(vilf_kf_loop_params *p);
+/* the geometry of stored key frame `index` (from vilf_kf_add_keyframe or vilf_kf_add_loaded): point_3d [n_window][3] of its window points, origin_vio_R [9],
+ * origin_vio_T [3]. A second call replaces the geometry. Invalid argument, the store as it was: no store, index out of range, a null point_3d with n_window > 0, a
+ * null vio_R or vio_T, a value that is not finite. */
+int vilf_kf_set_geometry(vilf_handle *h, int index, const float *point_3d, const double vio_R[9], const double vio_T[3]);
+/* findConnection of key frame cur against n_old old key frames (as vilf_kf_match: an index may repeat): one upload, one chain of launches on the handle's stream
+ * (match, gather, hypotheses, score, refine), one wait, one download, then the decision on the host. out [n_old]; with n = the window points of cur, status_out
+ * [n_old][n] (the inlier mask, over the window points) and pt_old_norm_out [n_old][n][2] (the first stage's matched lifted points) may be NULL. Old key frames need
+ * no geometry. Invalid argument, nothing written: anything vilf_kf_match refuses, a null p or out, cur without geometry, a parameter outside its range or not finite,
+ * a threshold, lambda0, max_yaw or max_dist that is not positive, min_loop_num < 5 (the sample needs m > min_loop_num >= 5). */
+int vilf_kf_find_connection(vilf_handle *h, const vilf_kf_loop_params *p, int cur, int n_old, const int *old_index, vilf_kf_loop_result *out,
+                            unsigned char *status_out, float *pt_old_norm_out);
+/* vilf_set_profiling: gather, hypotheses, score, refine, download of the vilf_kf_find_connection calls since the switch was set (their match is booked in
+ * vilf_kf_profile's slot) */
+int vilf_kf_loop_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
 #ifdef __cplusplus
 }
 #endif

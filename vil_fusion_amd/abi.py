@@ -316,6 +316,26 @@ class KfParams(C.Structure):
 # the mirror of the key-frame store, for the layout check of tests/test_keyframe_reference.py
 KF_LAYOUTS = {"vilf_kf_params": KfParams}
 
+VILF_KFL_GATE, VILF_KFL_NO_HYPOTHESIS, VILF_KFL_REFIT, VILF_KFL_REFIT_DROPPED, VILF_KFL_LOOP = 1, 2, 4, 8, 16
+
+
+class KfLoopParams(C.Structure):
+    """vilf_kf_loop_params: the PnP-RANSAC search, the loop gates and the camera-IMU extrinsic of a vilf_kf_find_connection"""
+    _fields_ = [("n_hypotheses", C.c_int), ("seed", C.c_uint), ("hyp_iterations", C.c_int), ("refine_iterations", C.c_int), ("min_loop_num", C.c_int), ("pad_", C.c_int),
+                ("lambda0", C.c_double), ("reproj_threshold", C.c_double), ("max_yaw", C.c_double), ("max_dist", C.c_double),
+                ("qic", C.c_double * 9), ("tic", C.c_double * 3)]
+
+
+class KfLoopResult(C.Structure):
+    """vilf_kf_loop_result: one old key frame's row of a vilf_kf_find_connection"""
+    _fields_ = [("n_matched", C.c_int), ("n_inliers", C.c_int), ("best_k", C.c_int), ("flags", C.c_int), ("has_loop", C.c_int), ("accepted", C.c_int),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("PnP_R_old", C.c_double * 9), ("PnP_T_old", C.c_double * 3),
+                ("relative_t", C.c_double * 3), ("relative_q", C.c_double * 4), ("relative_yaw", C.c_double), ("cost0", C.c_double), ("cost1", C.c_double)]
+
+
+# the mirrors of the second stage, for the layout check of tests/test_keyframe_loop_reference.py
+KFL_LAYOUTS = {"vilf_kf_loop_params": KfLoopParams, "vilf_kf_loop_result": KfLoopResult}
+
 
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""

@@ -24,15 +24,10 @@
 #include "vilf_device.hpp"
 #include "vilf_kernels.hpp"
 #include "vilf_image.hpp"
+#include "vilf_kf.hpp"
 
-#define KF_STAGES 5                     // upload + blur, FAST, descriptors + lift, match, download
-#define KF_WORDS VILF_KF_WORDS
-#define KF_WIN_CAP VILF_MAX_FEATURES    // window points of a key frame: slot k of the window arrays starts at k * KF_WIN_CAP
 #define KF_MAX_POINTS (1 << 20)         // vilf_kf_brief
 
-// a key frame's place in the store: its key points are rows kp_off .. kp_off + n_kp - 1 of the key-point arrays
-struct KfMeta { int kp_off, n_kp, n_win, pad_; };
-static_assert(sizeof(KfMeta) == 16, "kf_match reads a row as one int4");
 // the packed pattern: test i as (x1 + 64) | (y1 + 64) << 8 | (x2 + 64) << 16 | (y2 + 64) << 24, every byte 0 .. 128
 static_assert(VILF_KF_MAX_OFFSET == 64 && VILF_KF_BITS == 256 && KF_WORDS * 64 == VILF_KF_BITS, "a byte per offset; four tests per lane");
 
@@ -45,8 +40,6 @@ static_assert(VILF_KF_MAX_OFFSET == 64 && VILF_KF_BITS == 256 && KF_WORDS * 64 =
 #define KF_FAST_R 3
 #define KF_FAST_LW (KF_TW + 2 * KF_FAST_R)
 #define KF_FAST_LH (KF_TH + 2 * KF_FAST_R)
-#define KF_NT 256                       // every 1-D kernel; kf_nms_count, kf_nms_place, kf_brief: four waves = four rows / points per workgroup
-#define KF_WAVES (KF_NT / 64)
 #define KF_CHUNK VILF_KF_MATCH_CHUNK    // kf_match: 256 descriptors = 8 KB of LDS
 static_assert(KF_CHUNK == 64 * KF_WAVES, "kf_match: a wave takes 64 entries of a chunk");
 __global__ void kf_blur(const unsigned char *src, int W, int H, unsigned char *dst);
@@ -56,22 +49,7 @@ __global__ void kf_nms_scan(const int *rowcnt, int H, int *rowoff, int *total); 
 __global__ void kf_nms_place(const unsigned char *score, int W, int H, const int *rowoff, int limit, float2 *pts, unsigned char *pscore);   // grid = ceil(H / 4); pscore may be null
 __global__ void kf_brief(const unsigned char *blur, int W, int H, const unsigned *pat, const float2 *pts, int n, unsigned long long *desc);   // grid = ceil(n / 4)
 __global__ void kf_lift(const float2 *pts, int n, TkCam cam, float2 *out);                                 // grid = ceil(n / 256)
-struct KfMatchOut { unsigned char *status; float2 *pt, *ptn; int *idx, *dist, *nmatched; };
-__global__ void kf_match(const KfMeta *meta, const unsigned long long *kp_desc, const float2 *kp_pt, const float2 *kp_norm, const unsigned long long *win_desc, int cur,
-                         const int *old, int max_dist, int accept_dist, KfMatchOut out);                  // grid (ceil(n_window / 64), n_old), n_window > 0
-
-struct KfCtx : VilfStage {
-    vilf_kf_params p;
-    int capK = 0, size = 0;
-    long capP = 0, used = 0;
-    size_t ncell = 0;                   // W * H
-    std::vector<KfMeta> meta;           // host mirror of meta_d
-    DBuf kp_pt, kp_norm, kp_desc, win_pt, win_desc, meta_d, pat;            // the store
-    DBuf img, blur, score, rowcnt, rowoff, total, tpts, tscore, tdesc, old_d, res;      // one call's workspace
-    PinBuf stage, pin, down;            // the image on its way to the device; counts, a meta row, window points and old indices on theirs; a search's results on their way back
-    StageProf<KF_STAGES> prof;
-    void profile_reset() override { prof.reset(); }
-};
+// kf_match, the store (KfCtx) and the match as an enqueue: vilf_kf.hpp, shared with the second stage
 
 // ---- kf_blur -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(KF_TW * KF_TH) void kf_blur(const unsigned char *src, int W, int H, unsigned char *dst) {
@@ -273,18 +251,18 @@ __global__ __launch_bounds__(KF_NT) void kf_match(const KfMeta *meta, const unsi
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-namespace {
-KfCtx *kf_ctx(vilf_handle *h, const char *who) {
+KfCtx *vilf_kf_ctx(vilf_handle *h, const char *who) {
     KfCtx *c = vilf_stage<KfCtx>(h, ST_KF);
     if (!c) h->err = std::string(who) + ": no key-frame store (vilf_kf_create)";
     return c;
 }
-int kf_end(vilf_handle *h) {                              // a fault of the launches is reported by the call that made them
+int vilf_kf_finish(vilf_handle *h) {                      // a fault of the launches is reported by the call that made them
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipStreamSynchronize(h->stream));
     if (h->profiling) return vilf_prof_flush(h);
     return VILF_OK;
 }
+namespace {
 bool kf_points_ok(const float *pts, int n) {
     for (int i = 0; i < 2 * n; i++) if (!std::isfinite(pts[i]) || std::fabs(pts[i]) > 1.0e6f) return false;
     return true;
@@ -395,7 +373,7 @@ extern "C" int vilf_kf_create(vilf_handle *h, const vilf_kf_params *p, int cap_k
 
 extern "C" int vilf_kf_add_keyframe(vilf_handle *h, const unsigned char *img, int row_stride, const float *window_uv, int n_window, int *index_out, int *n_keypoints_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    KfCtx *c = kf_ctx(h, "vilf_kf_add_keyframe");
+    KfCtx *c = vilf_kf_ctx(h, "vilf_kf_add_keyframe");
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
     if (!img || row_stride < c->p.width) { h->err = "vilf_kf_add_keyframe: null image or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
     { const int rc = kf_check_add(h, c, "vilf_kf_add_keyframe", n_window, window_uv); if (rc != VILF_OK) return rc; }
@@ -428,7 +406,7 @@ extern "C" int vilf_kf_add_keyframe(vilf_handle *h, const unsigned char *img, in
     const KfMeta m{(int)c->used, n, n_window, 0};
     { const int rc = kf_put_meta(h, c, m); if (rc != VILF_OK) return rc; }
     prof.mark(2);
-    { const int rc = kf_end(h); if (rc != VILF_OK) return rc; }
+    { const int rc = vilf_kf_finish(h); if (rc != VILF_OK) return rc; }
     if (index_out) *index_out = c->size;
     if (n_keypoints_out) *n_keypoints_out = n;
     kf_commit(c, m);
@@ -438,7 +416,7 @@ extern "C" int vilf_kf_add_keyframe(vilf_handle *h, const unsigned char *img, in
 extern "C" int vilf_kf_add_loaded(vilf_handle *h, int n_kp, const float *keypoints, const float *keypoints_norm, const unsigned long long *descriptors,
                                   int n_window, const float *window_uv, const unsigned long long *window_descriptors, int *index_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    KfCtx *c = kf_ctx(h, "vilf_kf_add_loaded");
+    KfCtx *c = vilf_kf_ctx(h, "vilf_kf_add_loaded");
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
     if (n_kp < 0 || (n_kp > 0 && (!keypoints || !keypoints_norm || !descriptors)) || (n_window > 0 && !window_descriptors)) {
         h->err = "vilf_kf_add_loaded: n_kp >= 0 and every array whose count is positive"; return VILF_ERR_INVALID_ARGUMENT;
@@ -463,7 +441,7 @@ extern "C" int vilf_kf_add_loaded(vilf_handle *h, int n_kp, const float *keypoin
     const KfMeta m{(int)c->used, n_kp, n_window, 0};
     { const int rc = kf_put_meta(h, c, m); if (rc != VILF_OK) return rc; }
     prof.mark(0);
-    { const int rc = kf_end(h); if (rc != VILF_OK) return rc; }     // the caller's arrays are free again
+    { const int rc = vilf_kf_finish(h); if (rc != VILF_OK) return rc; }     // the caller's arrays are free again
     if (index_out) *index_out = c->size;
     kf_commit(c, m);
     return VILF_OK;
@@ -472,7 +450,7 @@ extern "C" int vilf_kf_add_loaded(vilf_handle *h, int n_kp, const float *keypoin
 extern "C" int vilf_kf_get(vilf_handle *h, int index, int cap_kp, float *keypoints, float *keypoints_norm, unsigned long long *descriptors, int *n_kp_out,
                            int cap_window, float *window_uv, unsigned long long *window_descriptors, int *n_window_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    KfCtx *c = kf_ctx(h, "vilf_kf_get");
+    KfCtx *c = vilf_kf_ctx(h, "vilf_kf_get");
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
     if (index < 0 || index >= c->size) { h->err = "vilf_kf_get: index out of range"; return VILF_ERR_INVALID_ARGUMENT; }
     const KfMeta m = c->meta[index];
@@ -489,7 +467,7 @@ extern "C" int vilf_kf_get(vilf_handle *h, int index, int cap_kp, float *keypoin
     if (nw && window_uv) HIPCHECK(h, hipMemcpyAsync(window_uv, c->win_pt.as<float2>() + k * KF_WIN_CAP, nw * 8, hipMemcpyDeviceToHost, h->stream));
     if (nw && window_descriptors) HIPCHECK(h, hipMemcpyAsync(window_descriptors, c->win_desc.as<unsigned long long>() + k * KF_WIN_CAP * KF_WORDS, nw * 32, hipMemcpyDeviceToHost, h->stream));
     prof.mark(4);
-    { const int rc = kf_end(h); if (rc != VILF_OK) return rc; }
+    { const int rc = vilf_kf_finish(h); if (rc != VILF_OK) return rc; }
     if (n_kp_out) *n_kp_out = m.n_kp;
     if (n_window_out) *n_window_out = m.n_win;
     return VILF_OK;
@@ -502,15 +480,32 @@ extern "C" int vilf_kf_size(vilf_handle *h, int *n_out) {
     return VILF_OK;
 }
 
+int vilf_kf_match_check(vilf_handle *h, KfCtx *c, const char *who, int cur, int n_old, const int *old_index) {
+    if (cur < 0 || cur >= c->size || n_old < 1 || n_old > VILF_KF_MAX_CANDIDATES || !old_index) {
+        h->err = std::string(who) + ": cur inside the store, 1 <= n_old <= VILF_KF_MAX_CANDIDATES and their indices"; return VILF_ERR_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < n_old; i++) if (old_index[i] < 0 || old_index[i] >= c->size) { h->err = std::string(who) + ": an old index outside the store"; return VILF_ERR_INVALID_ARGUMENT; }
+    return VILF_OK;
+}
+
+int vilf_kf_match_enqueue(vilf_handle *h, KfCtx *c, int cur, int n_old, const int *old_index, const KfMatchOut &out) {
+    const int nw = c->meta[cur].n_win;
+    int *po = (int *)((char *)c->pin.p + KF_PIN_DATA);
+    std::memcpy(po, old_index, (size_t)n_old * 4);
+    HIPCHECK(h, hipMemcpyAsync(c->old_d.p, po, (size_t)n_old * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, hipMemsetAsync(out.nmatched, 0, (size_t)n_old * 4, h->stream));
+    if (nw > 0) hipLaunchKernelGGL(kf_match, dim3((nw + 63) / 64, n_old), dim3(KF_NT), 0, h->stream, c->meta_d.as<KfMeta>(), c->kp_desc.as<unsigned long long>(), c->kp_pt.as<float2>(),
+                                   c->kp_norm.as<float2>(), c->win_desc.as<unsigned long long>(), cur, c->old_d.as<int>(), c->p.match_max_dist, c->p.match_accept_dist, out);
+    HIPCHECK(h, hipGetLastError());
+    return VILF_OK;
+}
+
 extern "C" int vilf_kf_match(vilf_handle *h, int cur, int n_old, const int *old_index, unsigned char *status, float *pt_old, float *pt_old_norm, int *best_index,
                              int *best_dist, int *n_matched) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    KfCtx *c = kf_ctx(h, "vilf_kf_match");
+    KfCtx *c = vilf_kf_ctx(h, "vilf_kf_match");
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
-    if (cur < 0 || cur >= c->size || n_old < 1 || n_old > VILF_KF_MAX_CANDIDATES || !old_index) {
-        h->err = "vilf_kf_match: cur inside the store, 1 <= n_old <= VILF_KF_MAX_CANDIDATES and their indices"; return VILF_ERR_INVALID_ARGUMENT;
-    }
-    for (int i = 0; i < n_old; i++) if (old_index[i] < 0 || old_index[i] >= c->size) { h->err = "vilf_kf_match: an old index outside the store"; return VILF_ERR_INVALID_ARGUMENT; }
+    { const int rc = vilf_kf_match_check(h, c, "vilf_kf_match", cur, n_old, old_index); if (rc != VILF_OK) return rc; }
     HIPCHECK(h, hipSetDevice(h->device));
     const int nw = c->meta[cur].n_win;
     const size_t rows = (size_t)n_old * nw;
@@ -521,18 +516,12 @@ extern "C" int vilf_kf_match(vilf_handle *h, int cur, int n_old, const int *old_
     if (!c->res.ensure(bytes) || !c->down.ensure(bytes)) { h->err = "allocation failed (key-frame match)"; return VILF_ERR_DEVICE; }
     char *b = c->res.as<char>();
     const KfMatchOut out{(unsigned char *)(b + o_st), (float2 *)(b + o_pt), (float2 *)(b + o_ptn), (int *)(b + o_idx), (int *)(b + o_dist), (int *)(b + o_cnt)};
-    int *po = (int *)((char *)c->pin.p + KF_PIN_DATA);
-    std::memcpy(po, old_index, (size_t)n_old * 4);
     ProfMarks prof(h, c->prof);
-    HIPCHECK(h, hipMemcpyAsync(c->old_d.p, po, (size_t)n_old * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(h, hipMemsetAsync(out.nmatched, 0, (size_t)n_old * 4, h->stream));
-    if (nw > 0) hipLaunchKernelGGL(kf_match, dim3((nw + 63) / 64, n_old), dim3(KF_NT), 0, h->stream, c->meta_d.as<KfMeta>(), c->kp_desc.as<unsigned long long>(), c->kp_pt.as<float2>(),
-                                   c->kp_norm.as<float2>(), c->win_desc.as<unsigned long long>(), cur, c->old_d.as<int>(), c->p.match_max_dist, c->p.match_accept_dist, out);
-    HIPCHECK(h, hipGetLastError());
+    { const int rc = vilf_kf_match_enqueue(h, c, cur, n_old, old_index, out); if (rc != VILF_OK) return rc; }
     prof.mark(3);
     HIPCHECK(h, hipMemcpyAsync(c->down.p, b, bytes, hipMemcpyDeviceToHost, h->stream));      // one copy of the whole record, then the caller's arrays from the pinned image
     prof.mark(4);
-    { const int rc = kf_end(h); if (rc != VILF_OK) return rc; }
+    { const int rc = vilf_kf_finish(h); if (rc != VILF_OK) return rc; }
     const char *d = (const char *)c->down.p;
     if (rows && status) std::memcpy(status, d + o_st, rows);
     if (rows && pt_old) std::memcpy(pt_old, d + o_pt, rows * 8);
@@ -545,7 +534,7 @@ extern "C" int vilf_kf_match(vilf_handle *h, int cur, int n_old, const int *old_
 
 extern "C" int vilf_kf_blur(vilf_handle *h, const unsigned char *img, int row_stride, unsigned char *out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    KfCtx *c = kf_ctx(h, "vilf_kf_blur");
+    KfCtx *c = vilf_kf_ctx(h, "vilf_kf_blur");
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
     if (!img || !out || row_stride < c->p.width) { h->err = "vilf_kf_blur: null pointer or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
     HIPCHECK(h, hipSetDevice(h->device));
@@ -555,12 +544,12 @@ extern "C" int vilf_kf_blur(vilf_handle *h, const unsigned char *img, int row_st
     prof.mark(0);
     HIPCHECK(h, hipMemcpyAsync(out, c->blur.p, c->ncell, hipMemcpyDeviceToHost, h->stream));
     prof.mark(4);
-    return kf_end(h);
+    return vilf_kf_finish(h);
 }
 
 extern "C" int vilf_kf_fast(vilf_handle *h, const unsigned char *img, int row_stride, int cap, float *pts_out, unsigned char *score_out, int *n_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    KfCtx *c = kf_ctx(h, "vilf_kf_fast");
+    KfCtx *c = vilf_kf_ctx(h, "vilf_kf_fast");
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
     if (!img || !pts_out || !n_out || cap < 0 || row_stride < c->p.width) { h->err = "vilf_kf_fast: null pointer, cap < 0 or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT; }
     HIPCHECK(h, hipSetDevice(h->device));
@@ -581,14 +570,14 @@ extern "C" int vilf_kf_fast(vilf_handle *h, const unsigned char *img, int row_st
     if (n > 0) HIPCHECK(h, hipMemcpyAsync(pts_out, c->tpts.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
     if (n > 0 && score_out) HIPCHECK(h, hipMemcpyAsync(score_out, c->tscore.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
     prof.mark(4);
-    { const int rc = kf_end(h); if (rc != VILF_OK) return rc; }
+    { const int rc = vilf_kf_finish(h); if (rc != VILF_OK) return rc; }
     *n_out = n;
     return VILF_OK;
 }
 
 extern "C" int vilf_kf_brief(vilf_handle *h, const unsigned char *img, int row_stride, const float *pts, int n, unsigned long long *desc_out) {
     if (!h) return VILF_ERR_INVALID_ARGUMENT;
-    KfCtx *c = kf_ctx(h, "vilf_kf_brief");
+    KfCtx *c = vilf_kf_ctx(h, "vilf_kf_brief");
     if (!c) return VILF_ERR_INVALID_ARGUMENT;
     if (!img || n < 0 || n > KF_MAX_POINTS || (n > 0 && (!pts || !desc_out)) || row_stride < c->p.width) {
         h->err = "vilf_kf_brief: null pointer, n outside 0 .. 2^20 or row_stride < width"; return VILF_ERR_INVALID_ARGUMENT;
@@ -606,7 +595,7 @@ extern "C" int vilf_kf_brief(vilf_handle *h, const unsigned char *img, int row_s
     prof.mark(2);
     HIPCHECK(h, hipMemcpyAsync(desc_out, c->tdesc.p, (size_t)n * 32, hipMemcpyDeviceToHost, h->stream));
     prof.mark(4);
-    return kf_end(h);
+    return vilf_kf_finish(h);
 }
 
 extern "C" int vilf_kf_profile(vilf_handle *h, double ms_out[5], long launches_out[5]) { return vilf_stage_profile(h, ST_KF, &KfCtx::prof, ms_out, launches_out); }

@@ -823,6 +823,29 @@ class ScanContext:
 
 
 KF_STAGES = ("upload_blur", "fast", "brief_lift", "match", "download")
+KFL_STAGES = ("gather", "hypotheses", "score", "refine", "download")
+
+
+def kf_default_loop_params(qic=None, tic=None, **over):
+    """vilf_kf_loop_params with the reference's constants (keyframe.cpp:226-232, 406, 480); qic (3, 3) and tic (3,) are the camera-IMU extrinsic (identity and 0
+    if not given); keyword arguments replace fields (n_hypotheses=256, seed=0, hyp_iterations=5, refine_iterations=10, min_loop_num=25, ...)"""
+    p = abi.KfLoopParams()
+    lib().vilf_kf_default_loop_params(C.byref(p))
+    if qic is not None:
+        p.qic = (C.c_double * 9)(*np.asarray(qic, dtype=np.float64).reshape(9))
+    if tic is not None:
+        p.tic = (C.c_double * 3)(*np.asarray(tic, dtype=np.float64).reshape(3))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"vilf_kf_loop_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def kf_loop_row_dict(r):
+    return dict(n_matched=r.n_matched, n_inliers=r.n_inliers, best_k=r.best_k, flags=r.flags, has_loop=bool(r.has_loop), accepted=r.accepted,
+                R=np.array(r.R).reshape(3, 3), t=np.array(r.t), PnP_R_old=np.array(r.PnP_R_old).reshape(3, 3), PnP_T_old=np.array(r.PnP_T_old),
+                relative_t=np.array(r.relative_t), relative_q=np.array(r.relative_q), relative_yaw=r.relative_yaw, cost0=r.cost0, cost1=r.cost1)
 
 
 def kf_default_params(width, height, camera, pattern, **over):
@@ -846,7 +869,8 @@ def kf_default_params(width, height, camera, pattern, **over):
 class KeyFrameStore:
     """Host mirror of what pose_graph's KeyFrame computes from an image (keyframe.cpp:75-118) and of searchByBRIEFDes (:121-171), over the device store of a
     BackendSolver handle (vilf_kf_*). Images are (height, width) uint8 arrays, points (n, 2) float32 pixels, descriptors (n, 4) uint64 (bit i in word i // 64 at
-    position i % 64). The arithmetic is the contract in include/vilfusion.h. Candidate retrieval (DBoW2) is not here: the caller names the old key frames."""
+    position i % 64). With a geometry (set_geometry) findConnection adds PnPRANSAC and the loop decision (:200-256, 401-520). The arithmetic is the contract in
+    include/vilfusion.h. Candidate retrieval (DBoW2) is not here: the caller names the old key frames."""
 
     def __init__(self, solver, width, height, camera, pattern, cap_keyframes=1024, cap_keypoints=1 << 20, params=None, **over):
         self.s, self._L = solver, solver._L
@@ -927,6 +951,49 @@ class KeyFrameStore:
         self.s._check(self._L.vilf_kf_match(self.s._h, int(cur), k, self._ip(old), self._u8(st), self._fp(pt), self._fp(ptn), self._ip(bi), self._ip(bd), self._ip(nm)), "vilf_kf_match")
         return dict(status=st[:n * k].reshape(k, n), pt_old=pt[:n * k].reshape(k, n, 2), pt_old_norm=ptn[:n * k].reshape(k, n, 2), best_index=bi[:n * k].reshape(k, n),
                     best_dist=bd[:n * k].reshape(k, n), n_matched=nm[:k])
+
+    def set_geometry(self, index, point_3d, vio_R, vio_T):
+        """the geometry of a stored key frame: point_3d (n_window, 3) float32 (the world points of its window features), origin_vio_R (3, 3), origin_vio_T (3,).
+        A second call replaces it."""
+        X = np.ascontiguousarray(point_3d, dtype=np.float32).reshape(-1, 3)
+        R, T = np.ascontiguousarray(vio_R, dtype=np.float64).reshape(9), np.ascontiguousarray(vio_T, dtype=np.float64).reshape(3)
+        nw = C.c_int(0)
+        self.s._check(self._L.vilf_kf_get(self.s._h, int(index), 0, None, None, None, None, 0, None, None, C.byref(nw)), "vilf_kf_get")
+        if len(X) != nw.value:
+            raise ValueError(f"{len(X)} world points for {nw.value} window points")
+        self.s._check(self._L.vilf_kf_set_geometry(self.s._h, int(index), self._fp(X), abi.dptr(R), abi.dptr(T)), "vilf_kf_set_geometry")
+
+    def findConnection(self, cur, olds, qic, tic, point_id=None, params=None, **over):
+        """PnPRANSAC and the loop decision of findConnection (:401-520) for key frame cur against every old key frame of `olds`, in one chain of launches -> one
+        dict per old key frame: the fields of vilf_kf_loop_result, loop_info (the 8-vector relative_t, relative_q (w, x, y, z), relative_yaw of :485-487, or None
+        without a loop), status (n,) uint8 (the inlier mask over the window points of cur) and, with point_id (n,) given, match_points (k, 3) float32: the
+        (x, y, id) rows of the fast-relocalisation message (:492-499) for the inliers (the reference publishes them only with a loop)."""
+        old = np.ascontiguousarray(olds, dtype=np.int32).reshape(-1)
+        p = params if params is not None else kf_default_loop_params(qic, tic, **over)
+        nw = C.c_int(0)
+        self.s._check(self._L.vilf_kf_get(self.s._h, int(cur), 0, None, None, None, None, 0, None, None, C.byref(nw)), "vilf_kf_get")
+        n, k = nw.value, len(old)
+        rows = (abi.KfLoopResult * max(k, 1))()
+        st, ptn = np.zeros(max(n * k, 1), dtype=np.uint8), np.zeros((max(n * k, 1), 2), dtype=np.float32)
+        self.s._check(self._L.vilf_kf_find_connection(self.s._h, C.byref(p), int(cur), k, self._ip(old), rows, self._u8(st), self._fp(ptn)), "vilf_kf_find_connection")
+        st, ptn = st[:n * k].reshape(k, n), ptn[:n * k].reshape(k, n, 2)
+        ids = None if point_id is None else np.asarray(point_id).reshape(n)
+        out = []
+        for i in range(k):
+            r = kf_loop_row_dict(rows[i])
+            r["loop_info"] = np.concatenate([r["relative_t"], r["relative_q"], [r["relative_yaw"]]]) if r["has_loop"] else None
+            r["status"] = st[i].copy()
+            if ids is not None:
+                on = st[i] != 0
+                r["match_points"] = np.concatenate([ptn[i][on], ids[on].astype(np.float32).reshape(-1, 1)], axis=1).astype(np.float32).reshape(-1, 3)
+            out.append(r)
+        return out
+
+    def loop_profile(self):
+        """ms and spans of gather, hypotheses, score, refine, download of the findConnection calls since vilf_set_profiling was switched on"""
+        ms, cnt = (C.c_double * 5)(), (C.c_long * 5)()
+        self.s._check(self._L.vilf_kf_loop_profile(self.s._h, ms, cnt), "vilf_kf_loop_profile")
+        return dict(zip(KFL_STAGES, ((ms[i], cnt[i]) for i in range(5))))
 
     def blur(self, img):
         """the blurred image BRIEF reads (stateless)"""

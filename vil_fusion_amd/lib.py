@@ -34,6 +34,7 @@ EXPORTED = [
     "vilf_exrot_default_params", "vilf_exrot_reset", "vilf_exrot_push", "vilf_exrot_get_history", "vilf_exrot_profile",
     "vilf_kf_default_params", "vilf_kf_create", "vilf_kf_add_keyframe", "vilf_kf_add_loaded", "vilf_kf_get", "vilf_kf_size", "vilf_kf_match",
     "vilf_kf_blur", "vilf_kf_fast", "vilf_kf_brief", "vilf_kf_profile",
+    "vilf_kf_default_loop_params", "vilf_kf_set_geometry", "vilf_kf_find_connection", "vilf_kf_loop_profile",
 ]
 
 
@@ -207,6 +208,11 @@ def lib():
     L.vilf_kf_fast.argtypes = [vp, u8p, C.c_int, C.c_int, fpp, u8p, ip]
     L.vilf_kf_brief.argtypes = [vp, u8p, C.c_int, fpp, C.c_int, u64p]
     L.vilf_kf_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_kf_default_loop_params.argtypes = [C.POINTER(abi.KfLoopParams)]
+    L.vilf_kf_default_loop_params.restype = None
+    L.vilf_kf_set_geometry.argtypes = [vp, C.c_int, fpp, abi.c_double_p, abi.c_double_p]
+    L.vilf_kf_find_connection.argtypes = [vp, C.POINTER(abi.KfLoopParams), C.c_int, C.c_int, ip, C.POINTER(abi.KfLoopResult), u8p, fpp]
+    L.vilf_kf_loop_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 
