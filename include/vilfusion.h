@@ -379,7 +379,8 @@ typedef struct vilf_sc_params {
     int num_exclude_recent;          /* NUM_EXCLUDE_RECENT 30 (:316) */
     int num_candidates;              /* NUM_CANDIDATES_FROM_TREE 3 (:317), at most 16; 0 = every snapshot entry */
     double search_ratio;             /* SEARCH_RATIO 0.1 (:320); 1 = all shifts */
-    double dist_thres;               /* SC_DIST_THRES 0.2 (:322, setSCdistThres :296) */
+    double dist_thres;               /* SC_DIST_THRES 0.2 (:322, setSCdistThres :296). +inf is accepted and accepts everything, also a search in which no candidate had
+                                      * a distance: min_dist stays 10000000 < inf, so loop_id = nearest = 0, nn_idx's initial value, as in the reference */
     int tree_making_period;          /* TREE_MAKING_PERIOD_ 30 (:325) */
     int pad_;
 } vilf_sc_params;

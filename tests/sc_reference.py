@@ -127,36 +127,73 @@ def ring_key_distances(q, keys):
 
 
 class SCManager:
-    def __init__(self, params=None):
+    def __init__(self, params=None, memo=None):
         self.p = params or Params()
         self.descs, self.rkeys = [], []
         self.calls = 0
         self.snapshot = 0             # entries [0, snapshot) are searchable
+        self.memo = memo              # optional dict shared between managers: distance() of a descriptor pair is computed once (see _distance)
 
     def add(self, cloud):
-        d = make_descriptor(cloud, self.p)
+        return self.add_descriptor(make_descriptor(cloud, self.p))
+
+    def add_descriptor(self, d):
+        """a key frame whose descriptor is known (tests/sc_cases.py: make_descriptor(cloud_from_heights(h)) == h)"""
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        assert d.shape == (RINGS, SECTORS)
         self.descs.append(d)
         self.rkeys.append(ring_key(d))
         return len(self.descs) - 1
 
+    def _distance(self, a, b, every):
+        if self.memo is None:
+            return distance(a, b, self.p, every)
+        key = (a.tobytes(), b.tobytes(), self.p.search_ratio)
+        if key not in self.memo:
+            ev = []
+            self.memo[key] = distance(a, b, self.p, ev) + (ev,)
+        dist, sh, ev = self.memo[key]
+        every.extend(ev)
+        return dist, sh
+
     def detect(self):
         """detectLoopClosureID for the newest key frame: the record vilf_sc_result holds, plus what the tests' preconditions need
         (ring_gap_rel: (d4 - d3) / d4 of the ring-key distances when a fourth entry exists; runner_up_gap: second smallest minus smallest distance over every
-        searched (candidate, shift))"""
+        searched (candidate, shift); distinct_gap: the next DISTINCT distance minus the smallest, for cases with planted exact ties)"""
         p = self.p
         n = len(self.descs)
-        none = dict(loop_id=-1, nearest=-1, shift=0, n_candidates=0, min_dist=NO_DIST, yaw_diff_rad=0.0, candidates=[], ring_gap_rel=np.inf, runner_up_gap=np.inf, snapshot=0)
         if n < p.num_exclude_recent + 1:
-            return none
+            return self._none()
         if self.calls % p.tree_making_period == 0:
             self.snapshot = n - p.num_exclude_recent
         self.calls += 1
-        S = self.snapshot
+        return self._search(n - 1, self.snapshot)
+
+    def detect_at(self, k):
+        """the record of key frame k under the replay rule of vilf_sc_detect_range: what detect() returned right after key frame k was added, had it been called once
+        per key frame from an empty manager. Needs key frames 0..k only and leaves the call counter alone."""
+        p = self.p
+        assert 0 <= k < len(self.descs)
+        if k < p.num_exclude_recent:
+            return self._none()
+        return self._search(k, p.tree_making_period * ((k - p.num_exclude_recent) // p.tree_making_period) + 1)
+
+    def detect_range(self, first, n):
+        return [self.detect_at(k) for k in range(first, first + n)]
+
+    @staticmethod
+    def _none():
+        return dict(loop_id=-1, nearest=-1, shift=0, n_candidates=0, min_dist=NO_DIST, yaw_diff_rad=0.0, candidates=[], ring_gap_rel=np.inf, runner_up_gap=np.inf,
+                    distinct_gap=np.inf, snapshot=0)
+
+    def _search(self, q, S):
+        """key frame q against the snapshot [0, S)"""
+        p = self.p
         ring_gap = np.inf
         if p.num_candidates == 0:
             cand = list(range(S))
         else:
-            d = ring_key_distances(self.rkeys[-1], np.array(self.rkeys[:S]))
+            d = ring_key_distances(self.rkeys[q], np.array(self.rkeys[:S]))
             order = np.argsort(d, kind="stable")                       # ties: the lower index first
             cand = [int(v) for v in order[:min(p.num_candidates, S)]]
             if S > p.num_candidates:
@@ -165,13 +202,14 @@ class SCManager:
         min_dist, nn_align, nn_idx = NO_DIST, 0, 0
         every = []
         for ci in cand:
-            dist, sh = distance(self.descs[-1], self.descs[ci], p, every)
+            dist, sh = self._distance(self.descs[q], self.descs[ci], every)
             if dist < min_dist:
                 min_dist, nn_align, nn_idx = dist, sh, ci
         every.sort()
+        above = [v for v in every if v > every[0]] if every else []
         return dict(loop_id=nn_idx if min_dist < p.dist_thres else -1, nearest=nn_idx, shift=nn_align, n_candidates=len(cand), min_dist=min_dist,
                     yaw_diff_rad=float(np.float32(nn_align * (360.0 / SECTORS) * math.pi / 180.0)), candidates=cand[:16], ring_gap_rel=ring_gap,
-                    runner_up_gap=every[1] - every[0] if len(every) > 1 else np.inf, snapshot=S)
+                    runner_up_gap=every[1] - every[0] if len(every) > 1 else np.inf, distinct_gap=above[0] - every[0] if above else np.inf, snapshot=S)
 
 
 def replay(clouds, params=None):

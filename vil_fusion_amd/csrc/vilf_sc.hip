@@ -105,7 +105,9 @@ __global__ __launch_bounds__(SC_DESC_NT) void sc_descriptor(const float4 *pts, c
         const float4 v = pts[p];
         if (!(isfinite(v.x) && isfinite(v.y) && isfinite(v.z)) || (v.x == 0.f && v.y == 0.f)) continue;
         const float z = (float)__dadd_rn((double)v.z, height);
-        const float range = __fsqrt_rn(__fadd_rn(__fmul_rn(v.x, v.x), __fmul_rn(v.y, v.y)));
+        // sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the header maps that one to the native v_sqrt_f32 (1 ulp), which put a point one float above a
+        // ring boundary into the ring below (range 60.000004 came out as 60); the plain square root is the correctly rounded one
+        const float range = __builtin_sqrtf(__fadd_rn(__fmul_rn(v.x, v.x), __fmul_rn(v.y, v.y)));
         if ((double)range > radius) continue;
         const float theta = sc_theta(v.x, v.y);
         const double fr = ceil(__dmul_rn(__ddiv_rn((double)range, radius), (double)SC_RINGS)), fs = ceil(__dmul_rn(__ddiv_rn((double)theta, 360.0), (double)SC_SECTORS));
