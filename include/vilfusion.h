@@ -1343,6 +1343,89 @@ int vilf_kf_find_connection(vilf_handle *h, const vilf_kf_loop_params *p, int cu
 /* vilf_set_profiling: gather, hypotheses, score, refine, download of the vilf_kf_find_connection calls since the switch was set (their match is booked in
  * vilf_kf_profile's slot) */
 int vilf_kf_loop_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
+
+/* ---- Visual loop closure, third stage: the 4-DoF pose graph (≙ PoseGraph::optimize4DoF, pose_graph/pose_graph.cpp:406-582, with FourDOFError, FourDOFWeightError
+ * and AngleLocalParameterization, pose_graph/pose_graph.h:101-250; device, the drift on the host) ----
+ * What consumes the second stage's loop_info: yaw and translation of the key frames between the earliest looped key frame and the newest one are re-estimated from
+ * the VIO's own relative motion (sequential edges) and the verified loops. A pure function of its arguments: it is not tied to the key-frame store. The reference
+ * hands the problem to Ceres, which cannot be built here, so this text fixes the arithmetic itself: the residuals and the graph are the reference's, the minimiser is
+ * Ceres's Levenberg-Marquardt as its documentation states it. tests/pg4_reference.py restates this text in numpy; tests/pg4_exact.py is the 40-digit yardstick both
+ * are measured against. Agreement with Ceres itself is neither measured nor claimed. The relocalisation factors, candidate retrieval and saving the
+ * graph are not part of this stage.
+ *   nodes        n key frames in order (the reference's local_index). Unknowns of node k: yaw_k in degrees and t_k [3], starting at yaw(vio_R_k) and vio_T_k. pitch_k
+ *                and roll_k come from R2ypr(vio_R_k) (Utility::R2ypr, degrees, on the device) and stay constant. fixed[k] != 0 stands for SetParameterBlockConstant
+ *                (:476-480: the first node and every node of sequence 0); fixed[0] must be set. Columns of fixed nodes carry no unknowns.
+ *   angles       NormalizeAngle(a) = a - 360 for a > 180, a + 360 for a < -180, else a (pose_graph.h:88-99: one turn at the most).
+ *                R(y, p, r) = ypr2R(y, p, r) = Rz(y) Ry(p) Rx(r), degrees (YawPitchRollToRotationMatrix).
+ *   sequential   (:483-498) for node i and j = 1 .. VILF_PG4_BAND, if i - j >= 0 and sequence[i] == sequence[i - j]: an edge (from, to) = (i - j, i) with
+ *                rel_t = vio_R_(i-j)^T (vio_T_i - vio_T_(i-j)) (the matrix as given, not rebuilt from its angles), rel_yaw = yaw_i - yaw_(i-j) at the start, not
+ *                normalised, weight w = 1, no loss.
+ *   loops        (:502-517) loops[l] = {from, to, rel_t, rel_yaw}, 0 <= from < to < n; several may share an endpoint or repeat, and a loop may lie inside the band.
+ *                w = loop_yaw_scale (0.1: the / T(10.0) of FourDOFWeightError), loss Huber(a = huber).
+ *   residual     of an edge (i, j) = (from, to), pitch and roll those of i: r[0..2] = R(yaw_i, pitch_i, roll_i)^T (t_j - t_i) - rel_t,
+ *                r[3] = w NormalizeAngle(yaw_j - yaw_i - rel_yaw).
+ *   Jacobian     analytic. d r[0..2] / d yaw_i = (pi / 180) (d R / d y)^T (t_j - t_i) (the yaw is in degrees), d r[0..2] / d t_i = -R^T, d r[0..2] / d t_j = R^T,
+ *                d r[3] / d yaw_i = -w, d r[3] / d yaw_j = w (NormalizeAngle has derivative 1). Columns of fixed nodes are zero.
+ *   loss         s = |r|^2 of the block. No loss: rho = s. Huber: rho = s, rho' = 1 for s <= a^2, else rho = 2 a sqrt(s) - a^2, rho' = a / sqrt(s); the block's residual
+ *                and Jacobian rows are scaled by sqrt(rho'), with no second-order correction (Ceres applies none when rho'' <= 0). cost = 1/2 sum rho.
+ *   step         with J, r the robustified rows over the free columns: H = J^T J, g = J^T r; (H + diag(H) / mu) delta = -g. Ceres's Jacobi scaling and its clamp of the
+ *                scaled diagonal to 1e-6 are left out; the two coincide where no column norm is below about 1e-3, which holds whenever a free node has an edge (the
+ *                yaw row alone gives a column norm of 1 for a sequential edge and loop_yaw_scale for a loop). Candidate: yaw <- NormalizeAngle(yaw + delta),
+ *                t <- t + delta. model = -(delta^T g + 1/2 |J delta|^2), rho = (cost - cost') / model.
+ *   rule         mu = initial_radius, factor = 2. At the start: max |g| <= gradient_tolerance ends the run before any attempt (VILF_PG4_GRADIENT). Otherwise, while no
+ *                flag is set: if iterations == max_iterations, VILF_PG4_MAX_ITERATIONS; else one attempt (every attempt counts as an iteration). A non-positive
+ *                pivot anywhere in the solve, or a candidate cost that is not finite, rejects the attempt (pivot_rejections; history: cost' = cost, rho = 0,
+ *                accepted = -1). Otherwise the step is accepted iff rho > min_relative_decrease. Accepted: mu = min(mu / max(1/3, 1 - (2 rho - 1)^3), max_radius),
+ *                factor = 2, the candidate becomes the state, and the run ends on any of cost - cost' <= function_tolerance cost (VILF_PG4_FUNCTION), max |g| of the
+ *                new state <= gradient_tolerance (VILF_PG4_GRADIENT), |delta| <= parameter_tolerance (|x| + parameter_tolerance) (VILF_PG4_PARAMETER; |x| the 2-norm
+ *                of the free unknowns before the step, yaw in degrees). Rejected: mu /= factor, factor *= 2, and mu < min_radius ends the run (VILF_PG4_RADIUS).
+ *   result       iterations, accepted, pivot_rejections, flags (the rules that ended the run, and VILF_PG4_FINITE iff every output is finite), cost0, cost1, the last
+ *                radius. ypr_out = (yaw, pitch, roll), R_out = ypr2R of it, on the device. The drift of the last node (:552-560), on the host in fp64 after the
+ *                download: yaw_drift = yaw(R_out[n-1]) - yaw(vio_R[n-1]) with yaw(R) = atan2(R_10, R_00) 180 / pi, r_drift = ypr2R(yaw_drift, 0, 0),
+ *                t_drift = t_out[n-1] - r_drift vio_T[n-1]. history_out [max_iterations][5], row it = {cost, cost', rho, mu before the attempt, accepted} of attempt
+ *                it; rows from `iterations` on are not written.
+ *   solver       nodes in groups of four: with VILF_PG4_BAND = 4 the sequential part of H is block tridiagonal in 16 x 16 blocks. The chain (sequential edges, and
+ *                diag(H) / mu with the loops' share of the diagonal) is factorised block by block; the loop edges enter as a rank 4 n_loops update (Woodbury) whose
+ *                4 n_loops x 4 n_loops capacitance block goes through the dense Cholesky of the large-window path. Sums run in a fixed order: no float atomics, a
+ *                result does not depend on the schedule. The host waits once per attempt. */
+#define VILF_PG4_BAND 4
+#define VILF_PG4_MAX_ITERATIONS_LIMIT 64
+#define VILF_PG4_MAX_ITERATIONS 1    /* flags: iterations reached max_iterations */
+#define VILF_PG4_FUNCTION 2
+#define VILF_PG4_GRADIENT 4
+#define VILF_PG4_PARAMETER 8
+#define VILF_PG4_RADIUS 16
+#define VILF_PG4_FINITE 32
+typedef struct vilf_pg4_params {
+    int max_iterations;              /* 0 .. 64; 5 (options.max_num_iterations). 0 evaluates the cost and returns the start */
+    int pad_;
+    double initial_radius;           /* 1e4 */
+    double max_radius, min_radius;   /* 1e16, 1e-32 */
+    double min_relative_decrease;    /* 1e-3 */
+    double function_tolerance, gradient_tolerance, parameter_tolerance;   /* 1e-6, 1e-10, 1e-8 */
+    double huber;                    /* 0.1 (ceres::HuberLoss(0.1)) */
+    double loop_yaw_scale;           /* 0.1 */
+} vilf_pg4_params;
+typedef struct vilf_pg4_loop {
+    int from, to;                    /* 0 <= from < to < n: the old key frame and the one that found it */
+    double rel_t[3], rel_yaw;        /* loop_info's relative_t and relative_yaw (degrees) */
+} vilf_pg4_loop;
+typedef struct vilf_pg4_result {
+    int iterations, accepted, pivot_rejections, flags;
+    double cost0, cost1, radius;
+    double yaw_drift, r_drift[9], t_drift[3];
+} vilf_pg4_result;
+void vilf_pg4_default_params(vilf_pg4_params *p);
+/* vio_R [n][9] (row-major), vio_T [n][3], sequence [n], fixed [n], loops [n_loops] (may be NULL with n_loops == 0) -> t_out [n][3], ypr_out [n][3], R_out [n][9],
+ * *result; history_out [max_iterations][5] may be NULL. Invalid argument, nothing written and the handle good for the next call: a null pointer among the required
+ * arguments, n < 1, fixed[0] == 0, n_loops < 0, an input that is not finite, a loop with from >= to or an index out of range, max_iterations outside 0 .. 64, a
+ * radius, huber or loop_yaw_scale that is not positive and finite, a tolerance or min_relative_decrease that is negative or not finite. Unsupported, before anything
+ * is enqueued: 4 n_loops above what the dense Cholesky takes (12288). */
+int vilf_pg4_optimize(vilf_handle *h, const vilf_pg4_params *p, int n, const double *vio_R, const double *vio_T, const int *sequence, const int *fixed,
+                      int n_loops, const vilf_pg4_loop *loops, double *t_out, double *ypr_out, double *R_out, vilf_pg4_result *result, double *history_out);
+/* vilf_set_profiling: upload + first linearisation, chain factor + chain solve, capacitance + dense solve, step + candidate linearisation + decision, download,
+ * summed over the calls since the switch was set */
+int vilf_pg4_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
 #ifdef __cplusplus
 }
 #endif

@@ -336,6 +336,27 @@ class KfLoopResult(C.Structure):
 # the mirrors of the second stage, for the layout check of tests/test_keyframe_loop_reference.py
 KFL_LAYOUTS = {"vilf_kf_loop_params": KfLoopParams, "vilf_kf_loop_result": KfLoopResult}
 
+VILF_PG4_BAND = 4
+VILF_PG4_MAX_ITERATIONS, VILF_PG4_FUNCTION, VILF_PG4_GRADIENT, VILF_PG4_PARAMETER, VILF_PG4_RADIUS, VILF_PG4_FINITE = 1, 2, 4, 8, 16, 32
+
+
+class Pg4Params(C.Structure):
+    """vilf_pg4_params: the Levenberg-Marquardt rule, the Huber width and the loops' yaw scale of a vilf_pg4_optimize"""
+    _fields_ = [("max_iterations", C.c_int), ("pad_", C.c_int), ("initial_radius", C.c_double), ("max_radius", C.c_double), ("min_radius", C.c_double),
+                ("min_relative_decrease", C.c_double), ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+                ("huber", C.c_double), ("loop_yaw_scale", C.c_double)]
+
+
+class Pg4Loop(C.Structure):
+    """vilf_pg4_loop: one verified loop, from the old key frame to the one that found it"""
+    _fields_ = [("from_", C.c_int), ("to", C.c_int), ("rel_t", C.c_double * 3), ("rel_yaw", C.c_double)]
+
+
+class Pg4Result(C.Structure):
+    """vilf_pg4_result: how a vilf_pg4_optimize ended, and the drift of its last node"""
+    _fields_ = [("iterations", C.c_int), ("accepted", C.c_int), ("pivot_rejections", C.c_int), ("flags", C.c_int), ("cost0", C.c_double), ("cost1", C.c_double),
+                ("radius", C.c_double), ("yaw_drift", C.c_double), ("r_drift", C.c_double * 9), ("t_drift", C.c_double * 3)]
+
 
 def dptr(a):
     """pointer to a C-contiguous float64 numpy array (None -> NULL)."""

@@ -83,6 +83,7 @@ enum {
     ST_TRI,              // feature triangulation: the packed candidates, the cameras and the depths (TriCtx, vilf_tri.hip)
     ST_EXROT,            // camera-IMU rotation calibration: the slots' frame counts, ric and histories (ExrotCtx, vilf_exrot.hip)
     ST_KF,               // visual loop closure: the key-frame store and its workspace (KfCtx, vilf_kf.hip)
+    ST_PG4,              // visual loop closure, third stage: the 4-DoF pose graph's workspace (Pg4Ctx, vilf_pg4.hip)
     VILF_STAGE_COUNT
 };
 

@@ -291,6 +291,55 @@ class BackendSolver:
             self._tri = BackendSolver(self.options, self._device)
         self._tri.set_profiling(on)
 
+    # ---- visual loop closure, third stage -------------------------------------------------------------------------
+    def optimize4dof(self, vio_R, vio_T, sequence, fixed, loops, params=None):
+        """≙ PoseGraph::optimize4DoF (pose_graph.cpp:406-582) on the device (vilf_pg4_optimize; the contract is in include/vilfusion.h). vio_R (n, 3, 3), vio_T (n, 3),
+        sequence and fixed (n,), loops: iterable of (from, to, rel_t[3], rel_yaw); params: a dict of vilf_pg4_params fields that replace the defaults.
+        Returns dict(t (n, 3), ypr (n, 3), R (n, 3, 3), result: dict of vilf_pg4_result, history (iterations, 5))."""
+        R = np.ascontiguousarray(vio_R, dtype=np.float64).reshape(-1, 9)
+        T = np.ascontiguousarray(vio_T, dtype=np.float64).reshape(-1, 3)
+        seq = np.ascontiguousarray(sequence, dtype=np.int32).reshape(-1)
+        fx = np.ascontiguousarray(np.asarray(fixed) != 0, dtype=np.int32).reshape(-1)
+        n = len(T)
+        if not (len(R) == n and len(seq) == n and len(fx) == n):
+            raise ValueError("optimize4dof: vio_R, vio_T, sequence and fixed differ in length")
+        p = pg4_default_params(**(params or {}))
+        loops = list(loops)
+        arr = (abi.Pg4Loop * max(len(loops), 1))()
+        for k, (a, b, rel_t, rel_yaw) in enumerate(loops):
+            arr[k].from_, arr[k].to, arr[k].rel_yaw = int(a), int(b), float(rel_yaw)
+            arr[k].rel_t[:] = [float(v) for v in rel_t]
+        t_out, ypr_out, R_out = np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 9))
+        hist = np.zeros((max(p.max_iterations, 1), 5))
+        res = abi.Pg4Result()
+        ip = C.POINTER(C.c_int)
+        self._check(self._L.vilf_pg4_optimize(self._h, C.byref(p), n, abi.dptr(R), abi.dptr(T), seq.ctypes.data_as(ip), fx.ctypes.data_as(ip), len(loops), arr,
+                                              abi.dptr(t_out), abi.dptr(ypr_out), abi.dptr(R_out), C.byref(res), abi.dptr(hist)), "vilf_pg4_optimize")
+        result = dict(iterations=res.iterations, accepted=res.accepted, pivot_rejections=res.pivot_rejections, flags=res.flags, cost0=res.cost0, cost1=res.cost1,
+                      radius=res.radius, yaw_drift=res.yaw_drift, r_drift=np.array(res.r_drift).reshape(3, 3), t_drift=np.array(res.t_drift))
+        return dict(t=t_out[:n], ypr=ypr_out[:n], R=R_out[:n].reshape(-1, 3, 3), result=result, history=hist[:res.iterations].copy())
+
+    def pg4_profile(self):
+        """ms and spans of upload + first linearisation, chain, capacitance + dense solve, step + decision, download of the optimize4dof calls since set_profiling"""
+        ms, cnt = (C.c_double * 5)(), (C.c_long * 5)()
+        self._check(self._L.vilf_pg4_profile(self._h, ms, cnt), "vilf_pg4_profile")
+        return dict(zip(PG4_STAGES, ((ms[i], cnt[i]) for i in range(5))))
+
+
+PG4_STAGES = ("upload_linearize", "chain", "capacitance_solve", "step_decide", "download")
+
+
+def pg4_default_params(**over):
+    """vilf_pg4_params with the reference's constants (max_num_iterations = 5, HuberLoss(0.1), the / 10 of FourDOFWeightError) and Ceres's defaults for the
+    trust region; keyword arguments replace fields"""
+    p = abi.Pg4Params()
+    lib().vilf_pg4_default_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"vilf_pg4_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
 
 def imu_preintegrate(noise, acc_0, gyr_0, ba, bg, dt, acc, gyr):
     """≙ IntegrationBase (host): returns an abi.ImuPreint."""

@@ -35,6 +35,7 @@ EXPORTED = [
     "vilf_kf_default_params", "vilf_kf_create", "vilf_kf_add_keyframe", "vilf_kf_add_loaded", "vilf_kf_get", "vilf_kf_size", "vilf_kf_match",
     "vilf_kf_blur", "vilf_kf_fast", "vilf_kf_brief", "vilf_kf_profile",
     "vilf_kf_default_loop_params", "vilf_kf_set_geometry", "vilf_kf_find_connection", "vilf_kf_loop_profile",
+    "vilf_pg4_default_params", "vilf_pg4_optimize", "vilf_pg4_profile",
 ]
 
 
@@ -213,6 +214,11 @@ def lib():
     L.vilf_kf_set_geometry.argtypes = [vp, C.c_int, fpp, abi.c_double_p, abi.c_double_p]
     L.vilf_kf_find_connection.argtypes = [vp, C.POINTER(abi.KfLoopParams), C.c_int, C.c_int, ip, C.POINTER(abi.KfLoopResult), u8p, fpp]
     L.vilf_kf_loop_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_pg4_default_params.argtypes = [C.POINTER(abi.Pg4Params)]
+    L.vilf_pg4_default_params.restype = None
+    L.vilf_pg4_optimize.argtypes = [vp, C.POINTER(abi.Pg4Params), C.c_int, abi.c_double_p, abi.c_double_p, ip, ip, C.c_int, C.POINTER(abi.Pg4Loop),
+                                    abi.c_double_p, abi.c_double_p, abi.c_double_p, C.POINTER(abi.Pg4Result), abi.c_double_p]
+    L.vilf_pg4_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 
