@@ -715,6 +715,19 @@ extern "C" int vilf_debug_w_row_map(int F, int cap, const unsigned char *feature
     if (F < 0 || cap < ((F + 3) & ~3) || !f_wrow || !row_feat || (F && !feature_const)) return VILF_ERR_INVALID_ARGUMENT;
     return w_row_map(F, cap, feature_const, f_wrow, row_feat);
 }
+// the class plan of a window's visual factors as the upload makes it (class_plan), from the two track tables alone: per frame pair its class, its start inside the
+// class list and its factor count; returns the window's factor slots (whole chunks of VB_CHUNK). The tracks must satisfy check_window's rule. A test hook (no handle,
+// no device); not part of include/vilfusion.h.
+extern "C" int vilf_debug_class_plan(int n_features, const int *feature_start_frame, const int *feature_obs_offset, int *cls, int *cstart, int *ccount) {
+    if (n_features < 0 || n_features > VILF_MAX_FEATURES || !cls || !cstart || !ccount || (n_features && (!feature_start_frame || !feature_obs_offset))) return VILF_ERR_INVALID_ARGUMENT;
+    for (int f = 0; f < n_features; f++) {
+        const int s = feature_start_frame[f], n = feature_obs_offset[f + 1] - feature_obs_offset[f];
+        if (s < 0 || n < 2 || s + n > VB_NF) return VILF_ERR_INVALID_ARGUMENT;
+    }
+    vilf_window_in in{};
+    in.n_features = n_features; in.feature_start_frame = feature_start_frame; in.feature_obs_offset = feature_obs_offset;
+    return class_plan(in, cls, cstart, ccount);
+}
 // the library's radix sort (vilf_sort.hip) through host buffers — a test hook (tests/test_scan2map.py compares it with a stable host sort); not part of include/vilfusion.h.
 // keys: n values of 4 (key64 == 0) or 8 bytes; the low `bits` bits are sorted, equal keys keep their order.
 extern "C" int vilf_debug_sort_pairs(vilf_handle *h, const void *keys, const int *vals, size_t n, int bits, int key64, void *keys_out, int *vals_out) {
