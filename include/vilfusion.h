@@ -1189,7 +1189,7 @@ int vilf_exrot_profile(vilf_handle *h, double ms_out[3], long launches_out[3]);
  * not available, so this text fixes the arithmetic itself, as the tracker's text does; tests/kf_reference.py restates it in numpy and the kernels agree with that
  * on every integer and every float bit. Agreement with OpenCV's own rasters (GaussianBlur's fixed-point rounding, FAST's pixel order) is neither measured nor
  * claimed. Candidate retrieval (detectLoop's DBoW2 query), PnP-RANSAC, the 4-DoF graph and the relocalisation factors are not part of this stage:
- * the caller names the old key frames.
+ * the caller names the old key frames, or asks vilf_kf_bow_detect for one (the paragraph "Visual loop closure, candidate retrieval" below).
  *   conventions  images are 8-bit, row-major, W x H, both sides > 21. R(i, n) is the tracker's reflect-101. Points are float32 (x, y) pixel coordinates, finite and
  *                within 1e6 pixels of the origin (anything else is an invalid argument). >> is arithmetic. No floating point in blur, FAST or the search.
  *   pattern      VILF_KF_BITS = 256 tests (x1_i, y1_i, x2_i, y2_i), int, given by the caller in the parameters (the reference reads config/brief_pattern.yml
@@ -1272,7 +1272,8 @@ int vilf_kf_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
  * What findConnection does after searchByBRIEFDes: the pose of the old key frame from the current key frame's world points and the old key frame's matched lifted
  * points, and the decision whether the two close a loop. cv::solvePnPRansac draws random samples and OpenCV is not available, so the search is a design of this
  * project, as rejectWithF's is; tests/kfloop_reference.py restates this text in numpy and the kernels agree with it on every integer and every float bit up to the
- * pose out (deviations from OpenCV: DESIGN.md §3t). Candidate retrieval, optimize4DoF and the relocalisation factors are not part of this stage.
+ * pose out (deviations from OpenCV: DESIGN.md §3t). Candidate retrieval (vilf_kf_bow_*, below), optimize4DoF and the relocalisation factors are not part of this
+ * stage.
  *   geometry     of a key frame: point_3d [n_window][3], the world points of its window features rounded to float32 (cv::Point3f), and origin_vio_R [9] (row-major),
  *                origin_vio_T [3] in fp64; all finite. The extrinsic qic [9], tic [3] is a parameter of the call. Only the current key frame needs a geometry.
  *   gate         for an old key frame: S = the window points of cur with match status 1 (first stage, paragraph match), in window order, m = |S|. m <= min_loop_num
@@ -1350,8 +1351,8 @@ int vilf_kf_loop_profile(vilf_handle *h, double ms_out[5], long launches_out[5])
  * the VIO's own relative motion (sequential edges) and the verified loops. A pure function of its arguments: it is not tied to the key-frame store. The reference
  * hands the problem to Ceres, which cannot be built here, so this text fixes the arithmetic itself: the residuals and the graph are the reference's, the minimiser is
  * Ceres's Levenberg-Marquardt as its documentation states it. tests/pg4_reference.py restates this text in numpy; tests/pg4_exact.py is the 40-digit yardstick both
- * are measured against. Agreement with Ceres itself is neither measured nor claimed. The relocalisation factors, candidate retrieval and saving the
- * graph are not part of this stage.
+ * are measured against. Agreement with Ceres itself is neither measured nor claimed. The relocalisation factors, candidate retrieval (vilf_kf_bow_*,
+ * below) and saving the graph are not part of this stage.
  *   nodes        n key frames in order (the reference's local_index). Unknowns of node k: yaw_k in degrees and t_k [3], starting at yaw(vio_R_k) and vio_T_k. pitch_k
  *                and roll_k come from R2ypr(vio_R_k) (Utility::R2ypr, degrees, on the device) and stay constant. fixed[k] != 0 stands for SetParameterBlockConstant
  *                (:476-480: the first node and every node of sequence 0); fixed[0] must be set. Columns of fixed nodes carry no unknowns.
@@ -1426,6 +1427,98 @@ int vilf_pg4_optimize(vilf_handle *h, const vilf_pg4_params *p, int n, const dou
 /* vilf_set_profiling: upload + first linearisation, chain factor + chain solve, capacitance + dense solve, step + candidate linearisation + decision, download,
  * summed over the calls since the switch was set */
 int vilf_pg4_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
+
+/* ---- Visual loop closure, candidate retrieval: the DBoW2 query of detectLoop (≙ PoseGraph::detectLoop and addKeyFrameIntoVoc, pose_graph/pose_graph.cpp:307-404,
+ * with TemplatedVocabulary::transform, ThirdParty/DBoW/TemplatedVocabulary.h:1065-1121 and :1217-1258, BowVector::addWeight, addIfNotExist and normalize,
+ * BowVector.cpp:34-84, and TemplatedDatabase::queryL1, TemplatedDatabase.h:656-723; device, the decision on the host) ----
+ * The stage that names the old key frame which the other three verify and use. It reads the key-point descriptors of the key-frame store, which lie on the device in
+ * the layout DBoW2 uses (boost::dynamic_bitset from the four blocks, TemplatedVocabulary.h:1541). Everything is integer Hamming distances and fp64 additions,
+ * subtractions and one division in a fixed order; tests/bow_reference.py restates this text in plain Python and the kernels agree with it on every integer and every
+ * float bit.
+ *   vocabulary   the caller's file (estimator.load_vocabulary reads the VINS binary layout): k, L, scoringType, weightingType, nNodes node records (nodeId, parentId,
+ *                weight, descriptor[4]) and nWords word records (nodeId, wordId), as VINSLoop::Vocabulary holds them (ThirdParty/VocabularyBinary.hpp). The root is
+ *                node 0 and has no record. A node's children are ordered by their position in the node array (loadBin, TemplatedVocabulary.h:1529-1538:
+ *                children.push_back in file order); this order decides ties. A leaf is a node without children (isLeaf); the tree may be unbalanced, and a node may
+ *                have any number of children >= 1: k and L are not used. Invalid argument, the store untouched: nNodes or nWords < 1, node ids that are not a
+ *                permutation of 1 .. nNodes, a parent that does not exist (or is the node itself), a node that the root does not reach, a leaf without a word, a
+ *                word on an inner node, a word id outside 0 .. nWords - 1 or used twice, a leaf named by two words, a weight that is negative or not finite, a
+ *                leaf deeper than VILF_BOW_MAX_DEPTH (the root's children have depth 1), a weightingType outside 0 .. 3 or a scoringType outside 0 .. 5.
+ *                scoringType other than L1_NORM (0) is VILF_ERR_UNSUPPORTED. The four weightings TF_IDF (0), TF (1), IDF (2), BINARY (3) are served; the weights
+ *                are the file's, as loadBin leaves them. On upload the host renumbers the nodes breadth-first: the children of a node lie side by side on the
+ *                device in their order, with descriptors, word id and weight in arrays of their own. The caller's ids never reach a kernel.
+ *   transform    of one descriptor f (:1217-1258): start at the root; among the node's children c_0 .. c_(m-1) in their order take the lexicographic minimum of
+ *                (popcount(f ^ D_(c_j)), j): the reference's strict < with the first child as the start. Repeat from that child until it is a leaf: the result is
+ *                (word_id, weight) of the leaf.
+ *   vector       of a key frame (:1065-1121), over its key-point descriptors in their order. TF_IDF and TF: every descriptor whose weight is > 0 adds its weight to
+ *                its word's value (addWeight): a word seen c times holds ((w + w) + w) ..., c - 1 rounded additions, not c w. IDF and BINARY: the value is w once
+ *                (addIfNotExist). The vector is sorted by word id. norm = the sum of |value| in ascending word order from 0.0, one rounding per addition; if
+ *                norm > 0 every value is divided by norm (normalize, BowVector.cpp:62-84). A key frame without key points, or with stopped words only (weight 0),
+ *                has an empty vector and is an entry all the same.
+ *   database     entry e is key frame e of the store; entries are added in key-frame order: adding or detecting key frame cur while the database holds a number of
+ *                entries other than cur is an invalid argument (the reference's EntryId is its own counter; tying it to the key-frame index is this project's
+ *                constraint). The vector of key frame e occupies rows kp_off .. kp_off + n_bow - 1 of two store-sized arrays (word id, value), n_bow <= n_kp.
+ *                use_di is false in the reference (pose_graph.cpp:41): no direct index, no feature vectors.
+ *   query        (queryL1) of vector v against n_entries entries with max_id: entry e is eligible iff e < max_id or max_id == -1 or e == n_entries - 1 (:679: the
+ *                strict < despite the header's comment, the all-pass value -1 which frame_index - 50 takes at frame 49, and the newest entry always, which is why
+ *                ret[0] is "the neighbour" in detectLoop). For an eligible entry s_e = the sum over the words common to v and the entry, in ascending word id, from
+ *                the first term, of (fabs(q - d) - fabs(q)) - fabs(d). An entry without a common word is no result. The results are ordered by (s_e ascending, e
+ *                ascending): std::sort leaves equal scores in no defined order, sending them to the lower id is this project's choice. The list is cut to
+ *                max_results, then Score = -s_e / 2.0.
+ *   decision     (pose_graph.cpp:351-387) on the host after the download. max_id = frame_index - min_gap. find_loop iff ret[0].Score > neighbour_score and some
+ *                ret[i].Score > loop_score with i >= 1. If find_loop and frame_index > min_gap: min_index = -1; for i = 0 ..: if min_index == -1 or (ret[i].Id <
+ *                min_index and ret[i].Score > loop_score) then min_index = ret[i].Id; the loop index is min_index (ret[0] seeds it whatever its score). Otherwise -1. */
+#define VILF_BOW_MAX_DEPTH 16        /* deepest leaf of a vocabulary */
+#define VILF_BOW_MAX_RESULTS 16      /* largest max_results */
+#define VILF_BOW_LDS_WORDS 2048      /* bow_score: a query vector of up to this many words is kept in LDS (24 KB), a longer one is read from global memory */
+#define VILF_BOW_L1_NORM 0
+#define VILF_BOW_TF_IDF 0
+#define VILF_BOW_TF 1
+#define VILF_BOW_IDF 2
+#define VILF_BOW_BINARY 3
+typedef struct vilf_bow_node { int nodeId, parentId; double weight; unsigned long long descriptor[4]; } vilf_bow_node;     /* VINSLoop::Node, 48 bytes */
+typedef struct vilf_bow_word { int nodeId, wordId; } vilf_bow_word;                                                        /* VINSLoop::Word */
+typedef struct vilf_bow_vocabulary {
+    int k, L, scoringType, weightingType, nNodes, nWords;
+    const vilf_bow_node *nodes;      /* [nNodes], in file order */
+    const vilf_bow_word *words;      /* [nWords] */
+} vilf_bow_vocabulary;
+typedef struct vilf_bow_params {
+    int max_results;                 /* 1 .. VILF_BOW_MAX_RESULTS; 4 (pose_graph.cpp:322) */
+    int min_gap;                     /* >= 0; 50 (:322, :376) */
+    double neighbour_score;          /* 0.05 (:351); not NaN */
+    double loop_score;               /* 0.015 (:355, :381); not NaN */
+} vilf_bow_params;
+typedef struct vilf_bow_result {
+    int loop_index;                  /* detectLoop's return value */
+    int find_loop;
+    int n_results;                   /* ret.size() */
+    int n_words;                     /* size of the query vector */
+    int id[VILF_BOW_MAX_RESULTS];    /* ret[i].Id, the rest -1 */
+    double score[VILF_BOW_MAX_RESULTS];      /* ret[i].Score, the rest 0 */
+} vilf_bow_result;
+void vilf_kf_bow_default_params(vilf_bow_params *p);
+/* the vocabulary of the store's database: validated on the host, renumbered and uploaded. It needs a store, drops an existing database (size 0) and replaces an
+ * existing vocabulary; vilf_kf_create drops both with the store, vilf_reset leaves both alone. Every call below is an invalid argument with nothing written without
+ * a store or without a vocabulary. */
+int vilf_kf_bow_set_vocabulary(vilf_handle *h, const vilf_bow_vocabulary *v);
+/* addKeyFrameIntoVoc (:391-404): the vector of stored key frame `index`, which must be the database's size, becomes its entry */
+int vilf_kf_bow_add(vilf_handle *h, int index);
+/* the same for key frames first .. first + n - 1 (first = the database's size, n >= 0, all in the store): ONE chain of launches over all their descriptors
+ * (transform, sort, compact), one wait. Entry for entry equal to n single adds, to the bit. */
+int vilf_kf_bow_add_range(vilf_handle *h, int first, int n);
+/* detectLoop (:307-389) of stored key frame cur = the database's size: its vector, the query against the cur entries before it, the entry added, then the decision.
+ * Invalid argument, nothing written, the database as it was: a null p or out, cur other than the size or outside the store, a parameter outside its range. */
+int vilf_kf_bow_detect(vilf_handle *h, const vilf_bow_params *p, int cur, vilf_bow_result *out);
+/* the replay over a database that holds key frames 0 .. first + n - 1 already: out[i] is what vilf_kf_bow_detect returned, or would have returned, for key frame
+ * first + i on its arrival (n_entries = first + i). All queries go in one chain of launches; the database is not touched. */
+int vilf_kf_bow_detect_range(vilf_handle *h, const vilf_bow_params *p, int first, int n, vilf_bow_result *out);
+/* the stored vector of entry `index`: *n_out words, word_out and value_out [cap] (either may be NULL). cap < its words with an array asked for: invalid argument. */
+int vilf_kf_bow_get(vilf_handle *h, int index, int cap, int *word_out, double *value_out, int *n_out);
+/* stateless: (word_id, weight) of n descriptors [n][4] (0 .. 2^24); it needs the vocabulary and leaves the database alone */
+int vilf_kf_bow_transform(vilf_handle *h, const unsigned long long *desc, int n, int *word_out, double *weight_out);
+int vilf_kf_bow_size(vilf_handle *h, int *n_out);
+/* vilf_set_profiling: transform, sort + compact, score, select, download, summed over the calls since the switch was set */
+int vilf_kf_bow_profile(vilf_handle *h, double ms_out[5], long launches_out[5]);
 #ifdef __cplusplus
 }
 #endif

@@ -336,6 +336,44 @@ class KfLoopResult(C.Structure):
 # the mirrors of the second stage, for the layout check of tests/test_keyframe_loop_reference.py
 KFL_LAYOUTS = {"vilf_kf_loop_params": KfLoopParams, "vilf_kf_loop_result": KfLoopResult}
 
+VILF_BOW_MAX_DEPTH, VILF_BOW_MAX_RESULTS, VILF_BOW_LDS_WORDS = 16, 16, 2048
+VILF_BOW_L1_NORM = 0
+VILF_BOW_TF_IDF, VILF_BOW_TF, VILF_BOW_IDF, VILF_BOW_BINARY = 0, 1, 2, 3
+
+
+class BowNode(C.Structure):
+    """vilf_bow_node: VINSLoop::Node, a record of the vocabulary file"""
+    _fields_ = [("nodeId", C.c_int), ("parentId", C.c_int), ("weight", C.c_double), ("descriptor", C.c_uint64 * 4)]
+
+
+class BowWord(C.Structure):
+    """vilf_bow_word: VINSLoop::Word"""
+    _fields_ = [("nodeId", C.c_int), ("wordId", C.c_int)]
+
+
+class BowVocabulary(C.Structure):
+    """vilf_bow_vocabulary: the header of the vocabulary file and pointers to its two record arrays"""
+    _fields_ = [("k", C.c_int), ("L", C.c_int), ("scoringType", C.c_int), ("weightingType", C.c_int), ("nNodes", C.c_int), ("nWords", C.c_int),
+                ("nodes", C.POINTER(BowNode)), ("words", C.POINTER(BowWord))]
+
+
+class BowParams(C.Structure):
+    """vilf_bow_params: the constants of detectLoop (pose_graph.cpp:322, :351, :355, :376)"""
+    _fields_ = [("max_results", C.c_int), ("min_gap", C.c_int), ("neighbour_score", C.c_double), ("loop_score", C.c_double)]
+
+
+class BowResult(C.Structure):
+    """vilf_bow_result: detectLoop's return value and the query results it was taken from"""
+    _fields_ = [("loop_index", C.c_int), ("find_loop", C.c_int), ("n_results", C.c_int), ("n_words", C.c_int),
+                ("id", C.c_int * VILF_BOW_MAX_RESULTS), ("score", C.c_double * VILF_BOW_MAX_RESULTS)]
+
+
+# the mirrors of candidate retrieval, for the layout check of tests/test_bow_reference.py
+BOW_LAYOUTS = {"vilf_bow_node": BowNode, "vilf_bow_word": BowWord, "vilf_bow_vocabulary": BowVocabulary, "vilf_bow_params": BowParams, "vilf_bow_result": BowResult}
+# the records of the VINS binary vocabulary file (ThirdParty/VocabularyBinary.hpp) as numpy sees them; BowNode and BowWord have the same layouts
+BOW_NODE_DTYPE = np.dtype([("nodeId", "<i4"), ("parentId", "<i4"), ("weight", "<f8"), ("descriptor", "<u8", (4,))])
+BOW_WORD_DTYPE = np.dtype([("nodeId", "<i4"), ("wordId", "<i4")])
+
 VILF_PG4_BAND = 4
 VILF_PG4_MAX_ITERATIONS, VILF_PG4_FUNCTION, VILF_PG4_GRADIENT, VILF_PG4_PARAMETER, VILF_PG4_RADIUS, VILF_PG4_FINITE = 1, 2, 4, 8, 16, 32
 

@@ -1,5 +1,6 @@
 // vilf_kf.hpp — what the two stages of the visual loop closure share on the host: the key-frame store (vilf_kf.hip owns it, vilf_kfloop.hip reads it and hangs a
-//   key frame's geometry on it) and the match as an enqueue, whose results stay on the device for the second stage.
+//   key frame's geometry on it) and the match as an enqueue, whose results stay on the device for the second stage. Candidate retrieval (vilf_bow.hip) hangs its
+//   vocabulary and its database of BoW vectors on the same store: it reads the store's key-point descriptors.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -7,6 +8,7 @@
 
 #define KF_STAGES 5                     // upload + blur, FAST, descriptors + lift, match, download
 #define KFL_STAGES 5                    // gather, hypotheses, score, refine, download
+#define BOW_STAGES 5                    // transform, sort + compact, score, select, download
 #define KF_WORDS VILF_KF_WORDS
 #define KF_WIN_CAP VILF_MAX_FEATURES    // window points of a key frame: slot k of the window arrays starts at k * KF_WIN_CAP
 #define KF_NT 256                       // every 1-D kernel; kf_nms_count, kf_nms_place, kf_brief: four waves = four rows / points per workgroup
@@ -37,7 +39,17 @@ struct KfCtx : VilfStage {
     DBuf loop_d;                        // one vilf_kf_find_connection's workspace
     PinBuf loop_down;
     StageProf<KFL_STAGES> loop_prof;
-    void profile_reset() override { prof.reset(); loop_prof.reset(); }
+    // candidate retrieval (vilf_bow.hip): the vocabulary, breadth-first (node 0 = the root, a node's children side by side), and the database of BoW vectors
+    bool voc_set = false;
+    int voc_nodes = 0, voc_words = 0, voc_weighting = 0, voc_wbits = 0;      // nodes with the root; voc_wbits: the bits of a sort key's word field (voc_words is the "stopped" key)
+    DBuf voc_kids, voc_desc, voc_word, voc_weight, voc_wweight;              // int2 (first child, children) [nodes]; uint64 [nodes][4]; int [nodes] (-1: inner); double [nodes]; double [words]
+    int bow_size = 0;                   // entries of the database: key frames 0 .. bow_size - 1
+    std::vector<int> bow_n;             // [capK] host mirror of bow_n_d
+    DBuf bow_word, bow_val, bow_n_d;    // [capP] int, [capP] double: the vector of key frame e in rows kp_off .. kp_off + bow_n[e] - 1; [capK] int
+    DBuf bow_k1, bow_k2, bow_v1, bow_v2, bow_temp, bow_tw, bow_twt, bow_tdesc, bow_score_d, bow_rows;     // one call's workspace
+    PinBuf bow_down;
+    StageProf<BOW_STAGES> bow_prof;
+    void profile_reset() override { prof.reset(); loop_prof.reset(); bow_prof.reset(); }
 };
 
 KfCtx *vilf_kf_ctx(vilf_handle *h, const char *who);       // the store, or null with the handle's error set

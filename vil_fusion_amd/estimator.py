@@ -897,6 +897,45 @@ def kf_loop_row_dict(r):
                 relative_t=np.array(r.relative_t), relative_q=np.array(r.relative_q), relative_yaw=r.relative_yaw, cost0=r.cost0, cost1=r.cost1)
 
 
+BOW_STAGES = ("transform", "sort_compact", "score", "select", "download")
+
+
+def load_vocabulary(path):
+    """the VINS binary vocabulary (ThirdParty/VocabularyBinary.hpp; the reference's brief_k10L6.bin) -> dict of k, L, scoringType, weightingType, nodes (structured
+    array abi.BOW_NODE_DTYPE: nodeId, parentId, weight, descriptor[4]) and words (abi.BOW_WORD_DTYPE: nodeId, wordId). The layout: six int32, then nNodes records
+    of 48 bytes, then nWords records of 8 bytes. A file that ends early, or a negative count, raises ValueError."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 24:
+        raise ValueError(f"{path}: {len(raw)} bytes, the header has 24")
+    k, L, scoring, weighting, n_nodes, n_words = (int(v) for v in np.frombuffer(raw, dtype="<i4", count=6))
+    if n_nodes < 0 or n_words < 0:
+        raise ValueError(f"{path}: nNodes {n_nodes}, nWords {n_words}")
+    need = 24 + n_nodes * abi.BOW_NODE_DTYPE.itemsize + n_words * abi.BOW_WORD_DTYPE.itemsize
+    if len(raw) < need:
+        raise ValueError(f"{path}: {len(raw)} bytes, {n_nodes} nodes and {n_words} words need {need}")
+    nodes = np.frombuffer(raw, dtype=abi.BOW_NODE_DTYPE, count=n_nodes, offset=24).copy()
+    words = np.frombuffer(raw, dtype=abi.BOW_WORD_DTYPE, count=n_words, offset=24 + n_nodes * abi.BOW_NODE_DTYPE.itemsize).copy()
+    return dict(k=k, L=L, scoringType=scoring, weightingType=weighting, nodes=nodes, words=words)
+
+
+def bow_default_params(**over):
+    """vilf_bow_params with detectLoop's constants; keyword arguments replace fields (max_results=4, min_gap=50, neighbour_score=0.05, loop_score=0.015)"""
+    p = abi.BowParams()
+    lib().vilf_kf_bow_default_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"vilf_bow_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def bow_result_dict(r):
+    n = r.n_results
+    return dict(loop_index=r.loop_index, find_loop=bool(r.find_loop), n_results=n, n_words=r.n_words, id=np.array(r.id[:], dtype=np.int32), score=np.array(r.score[:], dtype=np.float64),
+                ret=[(r.id[i], r.score[i]) for i in range(min(max(n, 0), abi.VILF_BOW_MAX_RESULTS))])
+
+
 def kf_default_params(width, height, camera, pattern, **over):
     """vilf_kf_params: camera = (fx, fy, cx, cy, k1, k2, p1, p2); pattern = (x1, y1, x2, y2), 256 integers each (the reference reads them from
     config/brief_pattern.yml); keyword arguments replace fields (fast_threshold=20, match_max_dist=128, match_accept_dist=80)"""
@@ -919,13 +958,15 @@ class KeyFrameStore:
     """Host mirror of what pose_graph's KeyFrame computes from an image (keyframe.cpp:75-118) and of searchByBRIEFDes (:121-171), over the device store of a
     BackendSolver handle (vilf_kf_*). Images are (height, width) uint8 arrays, points (n, 2) float32 pixels, descriptors (n, 4) uint64 (bit i in word i // 64 at
     position i % 64). With a geometry (set_geometry) findConnection adds PnPRANSAC and the loop decision (:200-256, 401-520). The arithmetic is the contract in
-    include/vilfusion.h. Candidate retrieval (DBoW2) is not here: the caller names the old key frames."""
+    include/vilfusion.h. With a vocabulary (set_vocabulary; load_vocabulary reads the file) detectLoop names the old key frame: the DBoW2 query of
+    pose_graph.cpp:307-389 over the stored key-point descriptors."""
 
     def __init__(self, solver, width, height, camera, pattern, cap_keyframes=1024, cap_keypoints=1 << 20, params=None, **over):
         self.s, self._L = solver, solver._L
         self.params = params if params is not None else kf_default_params(width, height, camera, pattern, **over)
         self.width, self.height = self.params.width, self.params.height
         self.s._check(self._L.vilf_kf_create(self.s._h, C.byref(self.params), int(cap_keyframes), int(cap_keypoints)), "vilf_kf_create")
+        self.has_vocabulary = False
 
     def _img(self, img):
         a = np.asarray(img)
@@ -1043,6 +1084,70 @@ class KeyFrameStore:
         ms, cnt = (C.c_double * 5)(), (C.c_long * 5)()
         self.s._check(self._L.vilf_kf_loop_profile(self.s._h, ms, cnt), "vilf_kf_loop_profile")
         return dict(zip(KFL_STAGES, ((ms[i], cnt[i]) for i in range(5))))
+
+    # ---- candidate retrieval (vilf_kf_bow_*): detectLoop's DBoW2 query over the stored key-point descriptors ----
+    def set_vocabulary(self, voc):
+        """voc: what load_vocabulary returns (k, L, scoringType, weightingType, nodes, words). Validated, renumbered breadth-first and uploaded; drops the database."""
+        nodes = np.ascontiguousarray(voc["nodes"], dtype=abi.BOW_NODE_DTYPE).reshape(-1)
+        words = np.ascontiguousarray(voc["words"], dtype=abi.BOW_WORD_DTYPE).reshape(-1)
+        v = abi.BowVocabulary(int(voc["k"]), int(voc["L"]), int(voc["scoringType"]), int(voc["weightingType"]), len(nodes), len(words),
+                              nodes.ctypes.data_as(C.POINTER(abi.BowNode)), words.ctypes.data_as(C.POINTER(abi.BowWord)))
+        self.s._check(self._L.vilf_kf_bow_set_vocabulary(self.s._h, C.byref(v)), "vilf_kf_bow_set_vocabulary")
+        self.has_vocabulary = True
+
+    def bow_size(self):
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_kf_bow_size(self.s._h, C.byref(n)), "vilf_kf_bow_size")
+        return n.value
+
+    def bow_add(self, index):
+        """addKeyFrameIntoVoc (pose_graph.cpp:391-404): key frame `index` (= the database's size) becomes an entry"""
+        self.s._check(self._L.vilf_kf_bow_add(self.s._h, int(index)), "vilf_kf_bow_add")
+
+    def bow_add_range(self, first, n):
+        """the same for n key frames in one chain of launches"""
+        self.s._check(self._L.vilf_kf_bow_add_range(self.s._h, int(first), int(n)), "vilf_kf_bow_add_range")
+
+    def detect_loop(self, index, params=None, **over):
+        """detectLoop (:307-389) for key frame `index` (= the database's size): query, add, decision -> dict of loop_index, find_loop, n_results, n_words, id, score
+        (16 each, the rest -1 / 0) and ret, the (Id, Score) pairs"""
+        p = params if params is not None else bow_default_params(**over)
+        r = abi.BowResult()
+        self.s._check(self._L.vilf_kf_bow_detect(self.s._h, C.byref(p), int(index), C.byref(r)), "vilf_kf_bow_detect")
+        return bow_result_dict(r)
+
+    def detectLoop(self, index, params=None, **over):
+        """the reference's signature: the loop index or -1"""
+        return self.detect_loop(index, params, **over)["loop_index"]
+
+    def detect_loop_range(self, first, n, params=None, **over):
+        """the replay: what detect_loop returned, or would have returned, for key frames first .. first + n - 1 on their arrival, over a database that holds them
+        already; one chain of launches, the database is not touched -> list of dicts"""
+        p = params if params is not None else bow_default_params(**over)
+        rows = (abi.BowResult * max(int(n), 1))()
+        self.s._check(self._L.vilf_kf_bow_detect_range(self.s._h, C.byref(p), int(first), int(n), rows), "vilf_kf_bow_detect_range")
+        return [bow_result_dict(rows[i]) for i in range(int(n))]
+
+    def bow_vector(self, index):
+        """the stored vector of entry `index` -> (word ids (n,) int32 ascending, values (n,) float64)"""
+        n = C.c_int(0)
+        self.s._check(self._L.vilf_kf_bow_get(self.s._h, int(index), 0, None, None, C.byref(n)), "vilf_kf_bow_get")
+        w, v = np.zeros(max(n.value, 1), dtype=np.int32), np.zeros(max(n.value, 1), dtype=np.float64)
+        self.s._check(self._L.vilf_kf_bow_get(self.s._h, int(index), n.value, self._ip(w), abi.dptr(v), None), "vilf_kf_bow_get")
+        return w[:n.value], v[:n.value]
+
+    def bow_transform(self, desc):
+        """(word id, weight) of each descriptor (n, 4) uint64 (stateless) -> ((n,) int32, (n,) float64)"""
+        d = self._desc(desc)
+        w, wt = np.zeros(max(len(d), 1), dtype=np.int32), np.zeros(max(len(d), 1), dtype=np.float64)
+        self.s._check(self._L.vilf_kf_bow_transform(self.s._h, self._u64(d), len(d), self._ip(w), abi.dptr(wt)), "vilf_kf_bow_transform")
+        return w[:len(d)], wt[:len(d)]
+
+    def bow_profile(self):
+        """ms and spans of transform, sort + compact, score, select, download since vilf_set_profiling was switched on"""
+        ms, cnt = (C.c_double * 5)(), (C.c_long * 5)()
+        self.s._check(self._L.vilf_kf_bow_profile(self.s._h, ms, cnt), "vilf_kf_bow_profile")
+        return dict(zip(BOW_STAGES, ((ms[i], cnt[i]) for i in range(5))))
 
     def blur(self, img):
         """the blurred image BRIEF reads (stateless)"""

@@ -36,6 +36,8 @@ EXPORTED = [
     "vilf_kf_blur", "vilf_kf_fast", "vilf_kf_brief", "vilf_kf_profile",
     "vilf_kf_default_loop_params", "vilf_kf_set_geometry", "vilf_kf_find_connection", "vilf_kf_loop_profile",
     "vilf_pg4_default_params", "vilf_pg4_optimize", "vilf_pg4_profile",
+    "vilf_kf_bow_default_params", "vilf_kf_bow_set_vocabulary", "vilf_kf_bow_add", "vilf_kf_bow_add_range", "vilf_kf_bow_detect", "vilf_kf_bow_detect_range", "vilf_kf_bow_get",
+    "vilf_kf_bow_transform", "vilf_kf_bow_size", "vilf_kf_bow_profile",
 ]
 
 
@@ -219,6 +221,17 @@ def lib():
     L.vilf_pg4_optimize.argtypes = [vp, C.POINTER(abi.Pg4Params), C.c_int, abi.c_double_p, abi.c_double_p, ip, ip, C.c_int, C.POINTER(abi.Pg4Loop),
                                     abi.c_double_p, abi.c_double_p, abi.c_double_p, C.POINTER(abi.Pg4Result), abi.c_double_p]
     L.vilf_pg4_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    L.vilf_kf_bow_default_params.argtypes = [C.POINTER(abi.BowParams)]
+    L.vilf_kf_bow_default_params.restype = None
+    L.vilf_kf_bow_set_vocabulary.argtypes = [vp, C.POINTER(abi.BowVocabulary)]
+    L.vilf_kf_bow_add.argtypes = [vp, C.c_int]
+    L.vilf_kf_bow_add_range.argtypes = [vp, C.c_int, C.c_int]
+    L.vilf_kf_bow_detect.argtypes = [vp, C.POINTER(abi.BowParams), C.c_int, C.POINTER(abi.BowResult)]
+    L.vilf_kf_bow_detect_range.argtypes = [vp, C.POINTER(abi.BowParams), C.c_int, C.c_int, C.POINTER(abi.BowResult)]
+    L.vilf_kf_bow_get.argtypes = [vp, C.c_int, C.c_int, ip, abi.c_double_p, ip]
+    L.vilf_kf_bow_transform.argtypes = [vp, u64p, C.c_int, ip, abi.c_double_p]
+    L.vilf_kf_bow_size.argtypes = [vp, ip]
+    L.vilf_kf_bow_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
     _lib = L
     return L
 

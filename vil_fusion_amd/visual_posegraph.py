@@ -4,8 +4,8 @@
   stage three         BackendSolver.optimize4dof (vilf_pg4_optimize): the 4-DoF graph over the key frames from the earliest looped one on, and the drift
 
 What stays here is the bookkeeping of PoseGraph::addKeyFrame (:44-213) and the write-back of optimize4DoF (:535-575): sequences, the shift of a sequence into the
-world frame on its first loop into another sequence, the drift applied to every new key frame. Candidate retrieval (detectLoop's DBoW2 query) is not here: the caller
-names the candidates, as in stage two. optimize4DoF runs when it is called, not on a thread that wakes every 2 s. Saving and loading the graph is not served."""
+world frame on its first loop into another sequence, the drift applied to every new key frame. The caller names the candidates, as in stage two, or lets the store's
+detectLoop name one (addKeyFrame(detect_loop=True): the DBoW2 query, vilf_kf_bow_detect). optimize4DoF runs when it is called, not on a thread that wakes every 2 s. Saving and loading the graph is not served."""
 import numpy as np
 
 from . import synth
@@ -29,10 +29,12 @@ class VisualPoseGraph:
         self.r_drift, self.t_drift, self.yaw_drift = np.eye(3), np.zeros(3), 0.0
         self.optimize_buf = []
 
-    def addKeyFrame(self, index, sequence, vio_R, vio_T, candidates=(), time_stamp=0.0, point_3d=None):
+    def addKeyFrame(self, index, sequence, vio_R, vio_T, candidates=(), time_stamp=0.0, point_3d=None, detect_loop=False):
         """:44-213 for the stored key frame `index` (the caller has added it to the store). candidates: the old key frames to verify, in the caller's order; among
         those whose findConnection reports has_loop the first is the loop (the reference has one candidate). point_3d, if given, is handed to the store with the
-        pose as the VIO gave it (origin_vio_R, origin_vio_T). Returns the loop's old index, or -1."""
+        pose as the VIO gave it (origin_vio_R, origin_vio_T). detect_loop (:59-69): with it set and no candidates given, the candidate is store.detectLoop(index)
+        if that is not -1; with it unset the key frame still goes into the store's database if a vocabulary is set there (addKeyFrameIntoVoc) and `index` is the
+        database's next entry. Returns the loop's old index, or -1."""
         if index in self.keyframes:
             raise ValueError(f"key frame {index} is in the graph already")
         sequence = int(sequence)
@@ -50,6 +52,11 @@ class VisualPoseGraph:
                   vio_T=self.w_r_vio @ T0 + self.w_t_vio, vio_R=self.w_r_vio @ R0)
         loop_index = -1
         old = [int(c) for c in candidates]
+        if detect_loop and not old:
+            found = self.store.detectLoop(index)
+            old = [found] if found != -1 else []
+        elif getattr(self.store, "has_vocabulary", False) and self.store.bow_size() == index:
+            self.store.bow_add(index)
         if old:
             unknown = [c for c in old if c not in self.keyframes]
             if unknown:
