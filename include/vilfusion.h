@@ -303,6 +303,9 @@ int vilf_eval_imu_raw(vilf_handle *h, const double *const *parameters, const vil
                       double *residuals, double **jacobians, double *sqrt_info225);
 int vilf_eval_lidar_between(vilf_handle *h, const double *const *parameters,
                             const vilf_lidar_constraint *c, double *residuals, double **jacobians); /* lidar_factor.h:19 */
+/* prior must be valid with 1 <= n <= VILF_PRIOR_MAX_DIM and 1 <= n_blocks <= VILF_PRIOR_MAX_BLOCKS, and its block table is checked as vilf_prior_import checks
+ * it: every block_size 7, 9 or 1, block_id >= 0, block_idx >= 0 and block_idx + local size (6 for a pose) <= n. Anything else returns
+ * VILF_ERR_INVALID_ARGUMENT before anything is copied or launched. */
 int vilf_eval_prior(vilf_handle *h, const vilf_prior *prior, const double *const *parameters,
                     double *residuals, double **jacobians);                                 /* marginalization_factor.cpp:333 */
 int vilf_eval_edge(vilf_handle *h, const double pose_qt[7], const double curr_point[3], const double point_a[3],

@@ -1086,15 +1086,20 @@ extern "C" int vilf_window_solve(vilf_handle *h, const vilf_window_in *in, vilf_
     return (out->summary.termination == VILF_TERM_FAILURE) ? VILF_SOLVER_ABNORMAL : VILF_OK;
 }
 
+// block table of a prior whose n and n_blocks are in range: global sizes 7 (pose), 9 (speed-bias) or 1 (td), local columns inside [0, n) — the kernels index
+// LDS vectors with it
+static bool prior_block_table_ok(const vilf_prior *prior) {
+    for (int i = 0; i < prior->n_blocks; i++) {
+        const int gs = prior->block_size[i], ls = gs == 7 ? 6 : gs, idx = prior->block_idx[i];
+        if ((gs != 7 && gs != 9 && gs != 1) || prior->block_id[i] < 0 || idx < 0 || idx + ls > prior->n) return false;
+    }
+    return true;
+}
+
 extern "C" int vilf_prior_import(vilf_handle *h, int slot, const vilf_prior *prior) {
     if (!h || slot < 0 || !prior) return VILF_ERR_INVALID_ARGUMENT;
     if (prior->valid && (prior->n <= 0 || prior->n > VILF_PRIOR_MAX_DIM || prior->n_blocks <= 0 || prior->n_blocks > VILF_PRIOR_MAX_BLOCKS)) return VILF_ERR_INVALID_ARGUMENT;
-    if (prior->valid) {          // block table: global sizes 7 (pose), 9 (speed-bias) or 1 (td), local columns inside [0, n) — the kernels index LDS vectors with it
-        for (int i = 0; i < prior->n_blocks; i++) {
-            const int gs = prior->block_size[i], ls = gs == 7 ? 6 : gs, idx = prior->block_idx[i];
-            if ((gs != 7 && gs != 9 && gs != 1) || prior->block_id[i] < 0 || idx < 0 || idx + ls > prior->n) { h->err = "prior block table out of range"; return VILF_ERR_INVALID_ARGUMENT; }
-        }
-    }
+    if (prior->valid && !prior_block_table_ok(prior)) { h->err = "prior block table out of range"; return VILF_ERR_INVALID_ARGUMENT; }
     if ((int)h->priors.size() <= slot) { vilf_prior z; std::memset(&z, 0, sizeof(z)); h->priors.resize(slot + 1, z); h->prior_dirty.resize(slot + 1, 1); }
     h->priors[slot] = *prior;
     h->prior_dirty[slot] = 1;
@@ -1430,7 +1435,9 @@ extern "C" int vilf_se3_plus(vilf_handle *h, const double x[7], const double d[6
 
 extern "C" int vilf_eval_prior(vilf_handle *h, const vilf_prior *p, const double *const *params, double *residuals, double **jac) {
     if (!h || !p || !params || !residuals || !p->valid || p->n < 1 || p->n > VILF_PRIOR_MAX_DIM || p->n_blocks < 1 || p->n_blocks > VILF_PRIOR_MAX_BLOCKS) return VILF_ERR_INVALID_ARGUMENT;
+    if (!prior_block_table_ok(p)) { h->err = "prior block table out of range"; return VILF_ERR_INVALID_ARGUMENT; }      // k_hook_prior indexes its LDS vector with the table
     const int n = p->n, nb = p->n_blocks;
+    for (int i = 0; i < nb; i++) if (!params[i]) return VILF_ERR_INVALID_ARGUMENT;
     const size_t doubles = 32 + 2 * 24 * 9 + (size_t)n * n + 2 * (size_t)n + 16;
     if (hook_buf(h, doubles) != VILF_OK) return VILF_ERR_DEVICE;
     std::vector<double> in(32 + 2 * 24 * 9 + (size_t)n * n + n, 0.0);
